@@ -15,8 +15,13 @@ read RANK / LOCAL_RANK / WORLD_SIZE from the environment as usual.
 
 `python bench.py --group N` is the one-process variant: N devices behind simon_group_* (what a Go host does).
 
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) is lean: it sets up, warms up, times the N steps and prints the
+headline record (`metric`, `value`, `unit`, `ms_per_step`, `dtype`, `config`, ...).  `--dump-outputs DIR` then writes what the timed
+path computed in its last step as DIR/<name>.npy (float32 / float64; see dump_outputs()).  Everything below that goes beyond the
+headline figure -- roofline, CPU baseline, parity sample, end-to-end leg, the other workloads -- runs only with `--full`.
+
 Output on rank 0: the LAST stdout line is ONE compact JSON record (<= 3 KB: the driver keeps the last ~8 KB of stdout and parses
-the last line; round 3's 24.8 KB line lost its head) -- the headline record (config 3) with `roofline` + `cpu_baseline` +
+the last line; round 3's 24.8 KB line lost its head) -- the headline record (config 3), with `--full` also `roofline` + `cpu_baseline` +
 `parity_sample` and a `digest` with one short row per other workload.  Everything else -- notes, peaks, instruction mixes, the
 `end_to_end` leg from host buffers, `other_workloads` in full (config 2, 200 signatures, the Service workloads, config 5 at 256
 scenarios and at the saturating batch size, the all-feature kernel's random mix; each with its OWN live-PMC roofline, CPU
@@ -372,6 +377,35 @@ def time_steps(ctx, steps, warmup, placement, fence, after_step=None):
     return time.perf_counter() - t0, float(np.mean(k_ms))
 
 
+DUMP_BUDGET_BYTES = 60_000_000    # --dump-outputs: all arrays together (under 64 MB with the .npy headers)
+DUMP_SEED = 20240607               # fixed: the same placement rows are sampled in every run with the same arguments
+
+
+def dump_outputs(out_dir, res, plan, n_pods, fetch_row=None):
+    """--dump-outputs: what a caller of the timed path receives after its last step, one DIR/<name>.npy per array -- the batch
+    results (simon_fetch_results: unscheduled, used_cpu, used_mem, used_vg per scenario, float64: the int64 quantities stay exact
+    below 2^53), the plan of simon_min_plan (`plan`: its fields in Plan._fields_ order, float64) and, when the placement matrix is
+    stored, placement rows as float32 (node indices, exact below 2^24): every row when the [S][P] matrix fits the budget, else a
+    fixed seeded sample of rows (`placement_rows` names them).  At most DUMP_BUDGET_BYTES in all.  Returns {name: bytes}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"unscheduled": np.asarray(res.unscheduled, np.float64), "used_cpu": np.asarray(res.used_cpu, np.float64),
+              "used_mem": np.asarray(res.used_mem, np.float64), "plan": np.array([float(getattr(plan, k)) for k, _ in plan._fields_])}
+    if res.used_vg is not None:
+        arrays["used_vg"] = np.asarray(res.used_vg, np.float64)
+    S = len(arrays["unscheduled"])
+    if fetch_row is not None and S and n_pods:
+        room = DUMP_BUDGET_BYTES - sum(a.nbytes for a in arrays.values()) - 8 * S
+        k = min(S, max(room, 0) // (4 * n_pods))
+        rows = np.arange(S) if k == S else np.sort(np.random.default_rng(DUMP_SEED).choice(S, size=k, replace=False))
+        if len(rows):
+            arrays["placement_rows"] = rows.astype(np.float64)
+            arrays["placement"] = np.stack([fetch_row(int(r)).astype(np.float32) for r in rows.tolist()])
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: a.nbytes for name, a in arrays.items()}
+
+
 def kernel_of(st):
     return "simon::table_kernel" if getattr(st, "kernel_generation", 0) in (4, 5, 6) else KERNEL_NAME.get(st.kernel_variant)
 
@@ -713,8 +747,10 @@ def run_group(args, capi, synth, torch):
             torch.cuda.synchronize(d)
         dt = time.perf_counter() - t0
         sts = [g.member_stats(i) for i in range(n)]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, g.fetch(False), g.min_plan()[0], prob.n_pods, g.fetch_placement)
         par = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             pick, refs, _ = oracle_sample(prob, scen, orders, budget_s=4.0, max_k=48)
             res = g.fetch(False)
             bad = [int(i) for i, ref in zip(pick.tolist(), refs)
@@ -792,7 +828,13 @@ def main():
                                                           "split over the N ranks instead of a batch that grows with N (the default, weak: config 4 at N = 8)")
     ap.add_argument("--group", type=int, default=0, help="N > 0: ONE process driving N devices through simon_group_* (the Go-host shape) "
                                                           "instead of one rank per GPU")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure: roofline (PMC), CPU "
+                                                        "baseline, parity sample, end-to-end leg and the other workloads (off: a lean run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in "
+                                                                        "its last step as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     spawning = args.group <= 0 and "WORLD_SIZE" not in os.environ and args.gpus > 1 and not args.pmc_child
     if not spawning:                                          # (the self-spawning parent leaves fd 1 to its ranks)
@@ -872,9 +914,9 @@ def main():
     rc = 0
     if rank == 0:
         st = ctx.stats()
-        wl = "config5" if args.workload in ("config5", "config5service") else "config3"
-        alg = algorithmic_bytes(scen, prob.n_pods, wl)
-        kname = kernel_of(st)
+        if args.dump_outputs:                                  # the last timed step's results, before anything below re-runs the batch
+            dump_outputs(args.dump_outputs, ctx.fetch(want_placement=False), ctx.min_plan(), prob.n_pods,
+                         ctx.fetch_placement if placement else None)
         value = S_total * args.steps / dt
         out = {
             "metric": "capacity-plan scenarios/sec (10k pods x ~1k nodes)", "value": round(value, 3),
@@ -894,62 +936,10 @@ def main():
                       "launched_by": "bench.py --gpus N (self-spawned torch.distributed.run)" if os.environ.get("SIMON_BENCH_SELF_SPAWNED") else "external launcher"} if use_dist else
                      {"world_size": 1, "backend": None},
         }
-        # ---- roofline of the dominant kernel ---------------------------------------------------------------------
-        pmc, source = None, None
-        mode = args.pmc
-        if mode in ("auto", "live") and world == 1:
-            child = ["--workload", args.workload, "--steps", "1", "--warmup", "0", "--counts", str(args.counts), "--pods", str(args.pods),
-                     "--orders-per-gpu", str(args.orders_per_gpu), "--sigs", str(args.sigs), "--classes", str(args.classes), "--placement", str(args.placement),
-                     "--c5-scenarios", str(c5_scenarios(args))]
-            ctx.close()                                        # free the device for the profiled children
-            t0 = time.perf_counter()
-            pmc = pmc_live(kname, child, budget_s=float(os.environ.get("SIMON_BENCH_PMC_BUDGET_S", "240")))
-            if pmc:
-                source = (f"measured live in this run: rocprofv3 --kernel-trace --pmc, {len(PMC_GROUPS)} separate passes over a 1-step child run "
-                          f"of the same workload ({time.perf_counter() - t0:.0f} s); per-dispatch averages x launches per step")
-            ctx = capi.Context(local_rank)                     # the parity legs below need the batch's results again
-            ctx.load_problem(prob)
-            ctx.load_scenarios(scen, orders)
-            ctx.run_loaded(want_placement=placement)
-        if pmc is None and mode != "off":
-            pmc, src = pmc_replayed(kname, S_local, prob.n_pods)
-            if pmc:
-                source = f"replayed from the committed profile ({src}), not measured in this run"
-        out["roofline"] = roofline_record(kname, st.kernel_variant, k_ms, st.n_launches, alg, pmc, source, wl,
-                                          lds_bytes=st.lds_bytes if st.kernel_variant == 4 else None, scenarios=S_local)
-        # ---- the oracle: CPU baseline (N = 1) and parity of the timed batch ---------------------------------------
-        if not args.no_cpu_baseline:
-            if world == 1:
-                pick, refs, tm = oracle_sample(prob, scen, orders, budget_s=float(os.environ.get("SIMON_BENCH_CPU_BUDGET_S", "12")))
-                out["cpu_baseline"] = cpu_baseline_record(tm, S_local, "this rank's batch")
-            else:
-                pick, refs, tm = oracle_sample(prob, scen, orders, budget_s=4.0, max_k=64)
-            out["parity_sample"] = parity_check(ctx, pick, refs, placement)
-            if out["parity_sample"]["mismatches"]:
-                rc = 3
-        ctx.close()
-        # ---- driver-timed records of the other single-GPU configurations, each a measurement of its own --------------
-        if world == 1 and args.workload == "config3" and not args.no_sub:
-            out["end_to_end"] = end_to_end(capi, torch, prob, scen, orders, local_rank)
-            subs = []
-            nchk5 = int(os.environ.get("SIMON_BENCH_C5_CHECK", "32"))
-            sub_steps = int(os.environ.get("SIMON_BENCH_SUB_STEPS", "5"))       # every sub-record times >= 5 steps after a warm-up
-            for name, steps, warm, nchk, c5s in (("config2", 20, 2, 1, 0), ("config3sig", sub_steps, 1, 64, 0), ("service", sub_steps, 1, 64, 0),
-                                                 ("service_anti", sub_steps, 1, 48, 0), ("service_pref", sub_steps, 1, 48, 0),
-                                                 ("config5", sub_steps, 1, nchk5, c5_scenarios(args)), ("config5", sub_steps, 1, nchk5, C5_SATURATING),
-                                                 ("service_small", sub_steps, 1, 16, 0), ("service_gpu", sub_steps, 1, 16, 0), ("service_shapes", sub_steps, 1, 16, 0), ("config5_service", sub_steps, 1, 16, c5_scenarios(args)), ("config5_asdrawn", sub_steps, 1, 16, c5_scenarios(args)), ("typical", sub_steps, 1, 2, 0), ("widemix", sub_steps, 1, 2, 0),
-                                                 ("config3sig_cliff", sub_steps, 1, 16, 0), ("config3_classes", sub_steps, 1, 16, 0), ("config3_classes_cliff", sub_steps, 1, 16, 0),
-                                                 ("config3_small", sub_steps, 1, 16, 0)):
-                try:
-                    cliff = name in ("config3sig_cliff", "config3_classes", "config3_classes_cliff", "config5_service", "config5_asdrawn")   # the cliff rows and config 5 behind Services: a shorter CPU sample; since round 5 they carry their live-PMC roofline like every other row
-                    subs.append(sub_record(name, capi, synth, torch, steps, warm, 0 if args.no_cpu_baseline else nchk, mode, c5s,
-                                           cpu_budget_s=3.0 if cliff else 6.0))
-                    if subs[-1].get("parity_sample", {}).get("mismatches"):
-                        rc = 3
-                except Exception as e:                         # noqa: BLE001
-                    subs.append({"workload": name, "error": repr(e)})
-                    rc = rc or 4
-            out["other_workloads"] = subs
+        if args.full:
+            rc = full_records(args, out, ctx, st, capi, synth, torch, prob, scen, orders, S_local, world, local_rank, placement, k_ms)
+        else:
+            ctx.close()
         emit(out)
     else:
         ctx.close()
@@ -958,6 +948,73 @@ def main():
         dist.destroy_process_group()
     if rc:
         raise SystemExit(rc)
+
+
+def full_records(args, out, ctx, st, capi, synth, torch, prob, scen, orders, S_local, world, local_rank, placement, k_ms):
+    """--full (rank 0): roofline of the dominant kernel, the oracle's CPU baseline and parity sample of the timed batch, and at N = 1
+    the end-to-end leg and the other workloads' records, added to `out`.  Closes `ctx`; returns the exit code (3 = parity mismatch,
+    4 = a sub-record broke)."""
+    rc = 0
+    wl = "config5" if args.workload in ("config5", "config5service") else "config3"
+    alg = algorithmic_bytes(scen, prob.n_pods, wl)
+    kname = kernel_of(st)
+    # ---- roofline of the dominant kernel ---------------------------------------------------------------------
+    pmc, source = None, None
+    mode = args.pmc
+    if mode in ("auto", "live") and world == 1:
+        child = ["--workload", args.workload, "--steps", "1", "--warmup", "0", "--counts", str(args.counts), "--pods", str(args.pods),
+                 "--orders-per-gpu", str(args.orders_per_gpu), "--sigs", str(args.sigs), "--classes", str(args.classes), "--placement", str(args.placement),
+                 "--c5-scenarios", str(c5_scenarios(args))]
+        ctx.close()                                        # free the device for the profiled children
+        t0 = time.perf_counter()
+        pmc = pmc_live(kname, child, budget_s=float(os.environ.get("SIMON_BENCH_PMC_BUDGET_S", "240")))
+        if pmc:
+            source = (f"measured live in this run: rocprofv3 --kernel-trace --pmc, {len(PMC_GROUPS)} separate passes over a 1-step child run "
+                      f"of the same workload ({time.perf_counter() - t0:.0f} s); per-dispatch averages x launches per step")
+        ctx = capi.Context(local_rank)                     # the parity legs below need the batch's results again
+        ctx.load_problem(prob)
+        ctx.load_scenarios(scen, orders)
+        ctx.run_loaded(want_placement=placement)
+    if pmc is None and mode != "off":
+        pmc, src = pmc_replayed(kname, S_local, prob.n_pods)
+        if pmc:
+            source = f"replayed from the committed profile ({src}), not measured in this run"
+    out["roofline"] = roofline_record(kname, st.kernel_variant, k_ms, st.n_launches, alg, pmc, source, wl,
+                                      lds_bytes=st.lds_bytes if st.kernel_variant == 4 else None, scenarios=S_local)
+    # ---- the oracle: CPU baseline (N = 1) and parity of the timed batch ---------------------------------------
+    if not args.no_cpu_baseline:
+        if world == 1:
+            pick, refs, tm = oracle_sample(prob, scen, orders, budget_s=float(os.environ.get("SIMON_BENCH_CPU_BUDGET_S", "12")))
+            out["cpu_baseline"] = cpu_baseline_record(tm, S_local, "this rank's batch")
+        else:
+            pick, refs, tm = oracle_sample(prob, scen, orders, budget_s=4.0, max_k=64)
+        out["parity_sample"] = parity_check(ctx, pick, refs, placement)
+        if out["parity_sample"]["mismatches"]:
+            rc = 3
+    ctx.close()
+    # ---- driver-timed records of the other single-GPU configurations, each a measurement of its own --------------
+    if world == 1 and args.workload == "config3" and not args.no_sub:
+        out["end_to_end"] = end_to_end(capi, torch, prob, scen, orders, local_rank)
+        subs = []
+        nchk5 = int(os.environ.get("SIMON_BENCH_C5_CHECK", "32"))
+        sub_steps = int(os.environ.get("SIMON_BENCH_SUB_STEPS", "5"))       # every sub-record times >= 5 steps after a warm-up
+        for name, steps, warm, nchk, c5s in (("config2", 20, 2, 1, 0), ("config3sig", sub_steps, 1, 64, 0), ("service", sub_steps, 1, 64, 0),
+                                             ("service_anti", sub_steps, 1, 48, 0), ("service_pref", sub_steps, 1, 48, 0),
+                                             ("config5", sub_steps, 1, nchk5, c5_scenarios(args)), ("config5", sub_steps, 1, nchk5, C5_SATURATING),
+                                             ("service_small", sub_steps, 1, 16, 0), ("service_gpu", sub_steps, 1, 16, 0), ("service_shapes", sub_steps, 1, 16, 0), ("config5_service", sub_steps, 1, 16, c5_scenarios(args)), ("config5_asdrawn", sub_steps, 1, 16, c5_scenarios(args)), ("typical", sub_steps, 1, 2, 0), ("widemix", sub_steps, 1, 2, 0),
+                                             ("config3sig_cliff", sub_steps, 1, 16, 0), ("config3_classes", sub_steps, 1, 16, 0), ("config3_classes_cliff", sub_steps, 1, 16, 0),
+                                             ("config3_small", sub_steps, 1, 16, 0)):
+            try:
+                cliff = name in ("config3sig_cliff", "config3_classes", "config3_classes_cliff", "config5_service", "config5_asdrawn")   # the cliff rows and config 5 behind Services: a shorter CPU sample; since round 5 they carry their live-PMC roofline like every other row
+                subs.append(sub_record(name, capi, synth, torch, steps, warm, 0 if args.no_cpu_baseline else nchk, mode, c5s,
+                                       cpu_budget_s=3.0 if cliff else 6.0))
+                if subs[-1].get("parity_sample", {}).get("mismatches"):
+                    rc = 3
+            except Exception as e:                         # noqa: BLE001
+                subs.append({"workload": name, "error": repr(e)})
+                rc = rc or 4
+        out["other_workloads"] = subs
+    return rc
 
 
 if __name__ == "__main__":

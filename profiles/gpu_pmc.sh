@@ -8,7 +8,7 @@ cd /tmp
 i=0
 for grp in "$@"; do
   i=$((i+1))
-  timeout 900 rocprofv3 --kernel-trace --pmc $grp -d "$OUT/pmc_$i" -o pmc -- python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline $ARGS > "$OUT/pmc_$i.log" 2>&1
+  timeout 900 rocprofv3 --kernel-trace --pmc $grp -d "$OUT/pmc_$i" -o pmc -- python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline $ARGS > "$OUT/pmc_$i.log" 2>&1
 done
 cd "$ROOT"
 python profiles/summarize.py "$OUT" 2>&1 | grep -v "plan_kernel\|unpermute" > "$OUT/summary.txt"

@@ -7,7 +7,7 @@ OUT=$PWD/gpurun_out/$TAG; mkdir -p "$OUT"
 i=0
 for E in "$@"; do
   i=$((i+1))
-  env $E timeout 600 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-sub --pmc live > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err"
+  env $E timeout 600 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-sub --pmc live > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err"
   python - "$OUT/bench_$i.json" "$E" <<'PY'
 import json,sys
 try:

@@ -26,7 +26,7 @@ for STAGE in "$@"; do
       ( timeout 2400 python -m pytest tests -m gpu -q 2>&1 | tail -8 ) > "$OUT/pytest_gpu.log"; tail -2 "$OUT/pytest_gpu.log"
       ( timeout 300 python __graft_entry__.py smoke 2>&1 | tail -2 ) > "$OUT/smoke.log"; tail -1 "$OUT/smoke.log" ;;
     bench)
-      SIMON_BENCH_DETAIL=$OUT/bench_detail.json timeout 1500 python bench.py > "$OUT/bench_default.out" 2> "$OUT/bench_default.err"; echo "bench rc=$?"
+      SIMON_BENCH_DETAIL=$OUT/bench_detail.json timeout 1500 python bench.py --full > "$OUT/bench_default.out" 2> "$OUT/bench_default.err"; echo "bench rc=$?"
       tail -1 "$OUT/bench_default.out" > "$OUT/bench_default.json"; wc -c "$OUT/bench_default.json"; cat "$OUT/bench_default.json" ;;
     rocprof)
       ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d "$OUT/rocprof" -o bench -- python $OLDPWD/bench.py --no-sub --pmc off --no-cpu-baseline --steps 5 > "$OUT/rocprof_bench.out" 2>&1 ); ls "$OUT/rocprof" | head ;;
@@ -49,7 +49,7 @@ for STAGE in "$@"; do
         IFS=';' read -ra WL <<< "${WORKLOADS:-config3;service;service --pref 60;config3sig --sigs 200;config5 --c5-scenarios 256;config5 --c5-scenarios 2048}"
         for W in "${WL[@]}"; do
           for REP in 1 2; do
-            echo "$L [$W] $( SIMON_HIP_LIB=$LIB SIMON_BENCH_DETAIL=/tmp/d.json timeout 600 python bench.py --workload $W --pmc off --no-cpu-baseline --no-sub --steps 5 2>/dev/null | tail -1 | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["roofline"]["kernel_ms"], d["config"]["kernel_generation"])' )" | tee -a "$OUT/regress.txt"
+            echo "$L [$W] $( SIMON_HIP_LIB=$LIB SIMON_BENCH_DETAIL=/tmp/d.json timeout 600 python bench.py --full --workload $W --pmc off --no-cpu-baseline --no-sub --steps 5 2>/dev/null | tail -1 | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["roofline"]["kernel_ms"], d["config"]["kernel_generation"])' )" | tee -a "$OUT/regress.txt"
           done
         done
       done ;;
@@ -57,10 +57,10 @@ for STAGE in "$@"; do
       ( timeout 1500 python -m pytest tests/test_gpu_round4.py -m gpu -q -x -k "${KEXPR:-local or wrap or abi_v3 or hundreds}" 2>&1 | tail -15 ) > "$OUT/pytest_new.log"; tail -3 "$OUT/pytest_new.log" ;;
     wide_exp)    # the all-feature kernel on the random mix x 64 sizes: workgroup shapes (env SIMON_WG) and its phase profile (prof build)
       for WG in ${WGS:-512 1024}; do
-        echo "WG=$WG $( SIMON_WG=$WG SIMON_BENCH_DETAIL=/tmp/d.json timeout 600 python bench.py --workload widemix --pmc off --no-cpu-baseline --no-sub --steps 2 --warmup 1 2>/dev/null | tail -1 | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["roofline"]["kernel_ms"], d["config"].get("workgroup"))' )" | tee -a "$OUT/wide_exp.txt"
+        echo "WG=$WG $( SIMON_WG=$WG SIMON_BENCH_DETAIL=/tmp/d.json timeout 600 python bench.py --full --workload widemix --pmc off --no-cpu-baseline --no-sub --steps 2 --warmup 1 2>/dev/null | tail -1 | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["roofline"]["kernel_ms"], d["config"].get("workgroup"))' )" | tee -a "$OUT/wide_exp.txt"
       done
       if [ -f open-simulator_amd/csrc/libsimon_hip_prof.so ]; then
-        ( SIMON_WIDE_PROF=1 SIMON_HIP_LIB=$PWD/open-simulator_amd/csrc/libsimon_hip_prof.so SIMON_BENCH_DETAIL=/tmp/d.json timeout 600 python bench.py --workload widemix --pmc off --no-cpu-baseline --no-sub --steps 1 --warmup 0 2>&1 | grep SIMON_WIDE_PROF | tail -2 ) > "$OUT/wide_phase_profile.txt"; cut -c1-900 "$OUT/wide_phase_profile.txt"
+        ( SIMON_WIDE_PROF=1 SIMON_HIP_LIB=$PWD/open-simulator_amd/csrc/libsimon_hip_prof.so SIMON_BENCH_DETAIL=/tmp/d.json timeout 600 python bench.py --full --workload widemix --pmc off --no-cpu-baseline --no-sub --steps 1 --warmup 0 2>&1 | grep SIMON_WIDE_PROF | tail -2 ) > "$OUT/wide_phase_profile.txt"; cut -c1-900 "$OUT/wide_phase_profile.txt"
       fi ;;
     wide_pmc)    # instruction-cache and wave-state counters of the all-feature kernel on the random mix (separate passes, kernel-trace only)
       ( timeout 900 python profiles/pmc_pass.py "--workload widemix --steps 1 --warmup 0" "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_IFETCH SQ_INSTS_VALU SQ_INSTS_SALU" 2>&1 | tail -6 ) > "$OUT/wide_pmc.txt"; cut -c1-1200 "$OUT/wide_pmc.txt" ;;

@@ -24,7 +24,7 @@ for STAGE in "$@"; do
         IFS=';' read -ra WL <<< "${WORKLOADS:-config3;config5 --c5-scenarios 256}"
         for W in "${WL[@]}"; do
           for REP in $(seq 1 ${REPS:-2}); do
-            echo "$L [$W] ${ENVS:-} $( env ${ENVS:-} SIMON_HIP_LIB=$LIB SIMON_BENCH_DETAIL=/tmp/d.json timeout 600 python bench.py --workload $W --pmc off --no-cpu-baseline --no-sub --steps ${STEPS:-5} 2>/dev/null | tail -1 | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["roofline"]["kernel_ms"], d["config"]["kernel_generation"], d["config"].get("workgroup"))' )" | tee -a "$OUT/regress.txt"
+            echo "$L [$W] ${ENVS:-} $( env ${ENVS:-} SIMON_HIP_LIB=$LIB SIMON_BENCH_DETAIL=/tmp/d.json timeout 600 python bench.py --full --workload $W --pmc off --no-cpu-baseline --no-sub --steps ${STEPS:-5} 2>/dev/null | tail -1 | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["roofline"]["kernel_ms"], d["config"]["kernel_generation"], d["config"].get("workgroup"))' )" | tee -a "$OUT/regress.txt"
           done
         done
       done ;;
@@ -35,7 +35,7 @@ for STAGE in "$@"; do
       ( timeout 300 python tests/fuzz_gpu.py ${FG_N:-100} ${FG_SEED:-55000} 2>&1 | tail -4 ) >> "$OUT/fuzzers.txt"
       grep -v amdgpu.ids "$OUT/fuzzers.txt" ;;
     bench)
-      SIMON_BENCH_DETAIL=$OUT/bench_detail.json timeout 1500 python bench.py > "$OUT/bench_default.out" 2> "$OUT/bench_default.err"; echo "bench rc=$?"
+      SIMON_BENCH_DETAIL=$OUT/bench_detail.json timeout 1500 python bench.py --full > "$OUT/bench_default.out" 2> "$OUT/bench_default.err"; echo "bench rc=$?"
       tail -1 "$OUT/bench_default.out" > "$OUT/bench_default.json"; wc -c "$OUT/bench_default.json"; cat "$OUT/bench_default.json" ;;
     rocprof)
       ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d "$OUT/rocprof" -o bench -- python $OLDPWD/bench.py --no-sub --pmc off --no-cpu-baseline --steps 5 > "$OUT/rocprof_bench.out" 2>&1 ); ls "$OUT/rocprof" | head

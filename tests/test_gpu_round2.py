@@ -265,7 +265,7 @@ def test_bench_gpus_flag_spawns_the_ranks_itself():
     env["SIMON_BENCH_SHARE_DEVICE"] = "1"
     env["SIMON_BENCH_DETAIL"] = os.path.join(tempfile.mkdtemp(prefix="simon_bench_"), "bench_detail.json")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--counts", "32",
-                          "--pods", "2000"], env=env, capture_output=True, text=True, timeout=900)
+                          "--pods", "2000", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["ranks"]["world_size"] == 2 and line["ranks"]["backend"] == "gloo" and line["ranks"]["one_device_test_hook"] is True
@@ -293,7 +293,7 @@ def test_bench_line_is_self_verifying():
     """One reduced single-GPU bench line: roofline fractions are fractions, the parity sample covers placements, the end-to-end leg
     ran, and every sub-record (config 2, config 5 at the small and at the saturating batch size) is a measurement of its own:
     roofline record, CPU baseline, parity sample."""
-    out, d = _bench(["--steps", "2", "--warmup", "1", "--counts", "64", "--pmc", "replay"],
+    out, d = _bench(["--steps", "2", "--warmup", "1", "--counts", "64", "--pmc", "replay", "--full"],
                     env={"SIMON_BENCH_CPU_BUDGET_S": "2", "SIMON_BENCH_C5_SCEN": "16", "SIMON_BENCH_C5_CHECK": "3"})
     assert out.returncode == 0, out.stderr[-3000:]
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["config"]["kernel"] == "score_table"
@@ -348,7 +348,7 @@ def test_bench_line_is_self_verifying():
 
 def test_bench_group_mode_one_process_two_members():
     """`bench.py --group 2`: ONE process, simon_group over two members (both on device 0 under the test hook): the Go-host shape."""
-    out, d = _bench(["--group", "2", "--steps", "2", "--warmup", "1", "--counts", "32", "--pods", "2000"],
+    out, d = _bench(["--group", "2", "--steps", "2", "--warmup", "1", "--counts", "32", "--pods", "2000", "--full"],
                     env={"SIMON_BENCH_SHARE_DEVICE": "1", "SIMON_BENCH_CPU_BUDGET_S": "2"})
     assert out.returncode == 0, out.stderr[-3000:]
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["ranks"]["devices"] == [0, 0] and "simon_group" in d["ranks"]["mode"]
@@ -358,6 +358,40 @@ def test_bench_group_mode_one_process_two_members():
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--group", "2", "--steps", "1"], capture_output=True, text=True,
                              timeout=300, env={k: v for k, v in os.environ.items() if k != "SIMON_BENCH_SHARE_DEVICE"})
         assert out.returncode != 0 and "only 1 GPU" in (out.stderr + out.stdout)
+
+
+def test_bench_plain_run_is_lean_and_dumps_what_it_computed(tmp_path):
+    """Without --full the line holds the headline figure only (no roofline, CPU baseline, parity sample, digest); --steps is the
+    number of timed steps; --dump-outputs writes the last step's results, which equal the same batch run through the library."""
+    import argparse
+    import bench
+    detail = str(tmp_path / "bench_detail.json")
+    args = ["--steps", "3", "--warmup", "1", "--counts", "32", "--pods", "2000"]
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args, "--dump-outputs", str(tmp_path / "dump")],
+                         env=dict(os.environ, SIMON_BENCH_DETAIL=detail), capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["value"] == pytest.approx(line["config"]["scenarios_per_gpu"] / (line["ms_per_step"] / 1e3), rel=2e-2)
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert k in line, k
+    for k in ("roofline", "cpu_baseline", "parity_sample", "digest", "end_to_end"):
+        assert k not in line, k
+    dump = {f[:-4]: np.load(tmp_path / "dump" / f) for f in os.listdir(tmp_path / "dump")}
+    assert {"unscheduled", "used_cpu", "used_mem", "plan", "placement", "placement_rows"} <= set(dump)
+    assert all(a.dtype in (np.float32, np.float64) for a in dump.values())
+    assert sum(os.path.getsize(tmp_path / "dump" / f) for f in os.listdir(tmp_path / "dump")) <= 64 * 10 ** 6
+    ns = argparse.Namespace(workload="config3", orders_per_gpu=4, counts=32, pods=2000, c5_scenarios=0, strong=False)
+    (prob, scen, orders), _ = bench.build_workload(ns, synth, 1)
+    with capi.Context(0) as ctx:
+        ctx.load_problem(prob)
+        res = ctx.run_batch(scen, orders)
+        plan = ctx.min_plan()
+    assert dump["unscheduled"].tolist() == res.unscheduled.tolist() and dump["used_cpu"].tolist() == res.used_cpu.tolist()
+    assert dump["used_mem"].tolist() == res.used_mem.tolist()
+    assert dump["plan"].tolist() == [float(v) for v in plan.as_dict().values()]
+    rows = dump["placement_rows"].astype(int)
+    assert len(rows) == len(scen) and (dump["placement"] == res.placement[rows]).all()   # 128 x 2 000 placements fit the budget whole
 
 
 # ---- a non-Python consumer of the C-ABI -------------------------------------------------------------------------

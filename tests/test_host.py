@@ -264,6 +264,37 @@ def test_bench_strong_mode_keeps_the_batch_fixed():
     assert (n_w, n_s, n_1) == (16, 4, 4) and len(scen_w) == 4 * len(scen_s) and (scen_s == scen_1).all()
 
 
+def test_bench_dump_outputs_stays_in_budget_and_samples_the_same_rows(tmp_path):
+    """bench.dump_outputs at BASELINE config 3's shape (4 096 scenarios x 10 000 pods: the [S][P] placement matrix is 164 MB): float
+    arrays only, at most 64 MB in all, a seeded sample of placement rows that is the same in every run, rows as the library returned them."""
+    import bench
+    from open_simulator_amd import capi
+    S, P = 4096, 10000
+    rng = np.random.default_rng(1)
+    res = capi.BatchResult.alloc(S, P, want_placement=False)
+    res.unscheduled[:] = rng.integers(0, 50, S)
+    res.used_cpu[:] = rng.integers(0, 1 << 40, S)
+    res.used_mem[:] = rng.integers(0, 1 << 50, S)
+    plan = capi.Plan(found=1, scenario=7, n_nodes=900, order_id=2, cpu_pct=63, mem_pct=65, used_cpu=504100, used_mem=1364188987392)
+
+    def row(s):
+        return (np.arange(P, dtype=np.int32) * 7 + s) % 1511
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), res, plan, P, row)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["placement.npy", "placement_rows.npy", "plan.npy", "unscheduled.npy", "used_cpu.npy", "used_mem.npy", "used_vg.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 10 ** 6
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["used_mem"].tolist() == res.used_mem.tolist() and a["plan"].tolist() == [1, 7, 900, 2, 63, 65, 504100, 1364188987392]
+    rows = a["placement_rows"].astype(int)
+    assert 1000 < len(rows) < S and (np.diff(rows) > 0).all()
+    assert all((a["placement"][i] == row(r)).all() for i, r in enumerate(rows.tolist()))
+    assert all((np.load(tmp_path / "b" / f) == a[f[:-4]]).all() for f in files)      # same arguments, same files
+    bench.dump_outputs(str(tmp_path / "c"), res, plan, P)                             # no placement matrix stored: no placement files
+    assert "placement.npy" not in os.listdir(tmp_path / "c")
+
+
 def test_spill_scan_flags_a_spill_ahead_of_the_exec_restore(tmp_path):
     """profiles/spill_scan.py (run by build() over every unit's ISA): the one pattern that cost a wrong `used_vg` in an experimental build -- a VGPR
     spill in a join block's prologue, BEFORE the block's `s_or_b64 exec, exec, ...` -- is reported; the same store after the restore, or behind

@@ -16,7 +16,7 @@ import randk8s
 from open_simulator_amd import capi, fiterror, flatten as fl, k8s, simulate as sim, workloads as wl
 
 K8S_FIXTURES = sorted(f[:-5] for f in os.listdir(G.GOLDEN) if f.startswith("k8s_") and f.endswith(".json"))
-REF_EXAMPLE = "/root/reference/example"
+REF_EXAMPLE = os.path.join(G.GOLDEN, "example")   # the reference's example/ inputs these tests use, stored as fixtures (tests/golden/README.md)
 
 
 class OracleEngine:
@@ -89,7 +89,6 @@ def test_flatten_plus_oracle_equals_object_level_scheduler(seed):
     assert got == ref
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EXAMPLE), reason="reference tree not present (GPU box)")
 def test_committed_example_fixtures_match_the_reference_inputs():
     """The committed k8s_example_* fixtures are what flatten() produces from the reference's example/ YAML today."""
     cluster = k8s.group_resources(k8s.load_objects(os.path.join(REF_EXAMPLE, "cluster/demo_1")))
@@ -110,7 +109,6 @@ def test_committed_example_fixtures_match_the_reference_inputs():
     assert sum(kinds.values()) == len(pods) == 37
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EXAMPLE), reason="reference tree not present (GPU box)")
 def test_reference_gpushare_config_end_to_end():
     """`simon apply -f example/simon-gpushare-config.yaml` through the mirror: the cluster alone holds every pod (the
     expectation the reference documents for this config), so the add-nodes search answers 0 new nodes."""
@@ -132,7 +130,6 @@ def test_reference_gpushare_config_end_to_end():
     assert len(gpu_pods) == 2
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EXAMPLE), reason="reference tree not present (GPU box)")
 def test_reference_open_local_example_end_to_end():
     """example/application/open_local on example/cluster/demo_1 with example/newnode/demo_1: each nginx-lvm pod needs
     10Gi + 40Gi of LVM and one 100Gi HDD device; worker-1 and the new-node template own ONE hdd device each, the
