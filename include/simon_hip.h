@@ -39,8 +39,9 @@
 extern "C" {
 #endif
 
-#define SIMON_HIP_ABI_VERSION 6   /* v6 (round 6): + simon_set_scalar_entries, simon_set_pod_priorities, simon_fetch_preempt_risk -- additive, every v5 struct unchanged
-                                     (v5, round 4: + simon_min_plan_device, simon_group_collective, simon_explain_local_detail) */
+#define SIMON_HIP_ABI_VERSION 7   /* v7: + simon_image_locality, simon_set_image_locality, simon_group_set_image_locality -- additive, every v6 struct unchanged
+                                     (v6, round 6: + simon_set_scalar_entries, simon_set_pod_priorities, simon_fetch_preempt_risk;
+                                     v5, round 4: + simon_min_plan_device, simon_group_collective, simon_explain_local_detail) */
 
 #define SIMON_MAX_GPU_DEV 8 /* devices per GPU-share node (pkg/type/open-gpu-share/cache/gpunodeinfo.go:34-56) */
 #define SIMON_MAX_SCALAR 4  /* extended ("scalar") resources tracked per node (V/framework/types.go:291) */
@@ -363,6 +364,27 @@ int simon_load_class_tables(simon_ctx* ctx, const simon_class_tables* tables);
 int simon_load_scenarios(simon_ctx* ctx, const simon_scenario* scen, int32_t S,
                          const int32_t* orders, int32_t n_orders);
 
+/* ABI v7.  ImageLocality (vendor/k8s.io/kubernetes/pkg/scheduler/framework/plugins/imagelocality/image_locality.go:53-125) for
+ * batches of several cluster sizes.  Its score depends on the scenario through totalNumNodes = n_nodes only:
+ *   score(c, j, n) = 100 * (clamp(sum, 23 MB, 1000 MB x containers) - 23 MB) / (1000 MB x containers - 23 MB)   (int64)
+ *   sum = over the containers of class c whose image node j lists: int64(float64(size[i]) * (float64(node_count) / float64(n)))
+ * The engine adds score(c, j, scen.n_nodes) to every scenario's score, next to simon_class_tables.static_add, which then leaves
+ * ImageLocality out.  node_count is ImageStateSummary.NumNodes as schedulerCache.addNodeImageStates leaves it (cache.go:675-698):
+ * the nodes that listed the image up to and including node j in the caller's arrival order; size is the first lister's sizeBytes.
+ * Image ids need only be consistent within the call.  Weight 1, no NormalizeScore. */
+typedef struct simon_image_locality {
+    int32_t n_images;            /* I: images that some pod class runs AND some pool node lists */
+    const int64_t* size;         /* [I] ImageStateSummary.Size, >= 0 */
+    const int32_t* node_off;     /* [N+1] CSR over pool nodes, node_off[0] = 0 */
+    const int32_t* node_image;   /* [nnz] image id, each at most once per node */
+    const int32_t* node_count;   /* [nnz] ImageStateSummary.NumNodes, in [1, N] */
+    const int32_t* class_off;    /* [Cp+1] CSR over pod classes: one entry per container (pod.Spec.Containers; init containers do not count) */
+    const int32_t* class_image;  /* [class_off[Cp]] image id per container, -1 = listed nowhere (still counts in numContainers) */
+} simon_image_locality;
+/* Call after simon_load_nodes and simon_load_class_tables (either clears it); NULL detaches.  SIMON_EINVAL for ids and offsets,
+ * SIMON_ERANGE for sizes and counts, with a message. */
+int simon_set_image_locality(simon_ctx* ctx, const simon_image_locality* img);
+
 /* Canonical (nodeTree) order per scenario.  By default the canonical order of a scenario's nodes is their pool order.  With
  * nodes in several zones the nodeTree order of a larger cluster does not extend a smaller one's (zones are visited round
  * robin, V/internal/cache/node_tree.go:119-143), so the host may supply rank[s][j] = position of pool node j in scenario
@@ -497,6 +519,8 @@ int simon_group_fetch_gpu_slices(simon_group* g, int32_t scenario, uint64_t* sli
 int simon_group_set_scalar_entries(simon_group* g, const uint8_t* entries /* [P] */);
 int simon_group_set_pod_priorities(simon_group* g, const int32_t* priority /* [P] */, int32_t init_min_priority);
 int simon_group_fetch_preempt_risk(simon_group* g, uint8_t* risk /* [S] */);
+/* ABI v7: simon_set_image_locality on every member */
+int simon_group_set_image_locality(simon_group* g, const simon_image_locality* img);
 
 /* The add-nodes search over every device: minimum n_nodes among the scenarios of the last run that schedule every pod
  * within the caps (satisfyResourceSetting, pkg/apply/apply.go:689-775); ties go to the lowest scenario index, exactly

@@ -256,7 +256,14 @@ func (c *Ctx) Load(f *Flat) error {
 			return err
 		}
 	}
-	return c.check(C.simon_load_class_tables(c.h, &t), "simon_load_class_tables")
+	if err := c.check(C.simon_load_class_tables(c.h, &t), "simon_load_class_tables"); err != nil {
+		return err
+	}
+	// ABI v7: ImageLocality's inputs; the library scores every cluster size of the batch itself
+	if im := f.cImage(&a); im != nil {
+		return c.check(C.simon_set_image_locality(c.h, im), "simon_set_image_locality")
+	}
+	return nil
 }
 
 // FetchPreemptRisk: per scenario of the last run, 1 = some pod failed while a pod of lower priority was placed -- DefaultPreemption
@@ -456,7 +463,13 @@ func (g *Group) Load(f *Flat) error {
 			return err
 		}
 	}
-	return g.check(C.simon_group_load_class_tables(g.h, &t), "simon_group_load_class_tables")
+	if err := g.check(C.simon_group_load_class_tables(g.h, &t), "simon_group_load_class_tables"); err != nil {
+		return err
+	}
+	if im := f.cImage(&a); im != nil { // ABI v7: on every member
+		return g.check(C.simon_group_set_image_locality(g.h, im), "simon_group_set_image_locality")
+	}
+	return nil
 }
 
 // FetchPreemptRisk: Ctx.FetchPreemptRisk over the group, in the caller's scenario order.

@@ -19,9 +19,10 @@ package hipengine
 // (anti-)affinity (required and preferred), topology spread constraints (explicit, and the system defaults of pods a Service /
 // ReplicaSet / StatefulSet selects), host ports, Open-Local volumes: flatten_terms.go fills those tables.  Supports() answers false
 // (the Go path runs) only for what NEITHER flattening models: scheduler configs / extra registries (pods of different priorities are
-// accepted since ABI v6: only a scenario in which DefaultPreemption could have acted comes back as ErrNeedsReference), nodes with a preferAvoidPods annotation or listed images (NodePreferAvoidPods / ImageLocality
-// would not be constants; flatten.py takes them for one cluster size), more extended resources / spread constraints / volumes
-// than the ABI's fixed widths.  Whether a supported input then runs on the score-table kernel or the all-feature kernel is the
+// accepted since ABI v6: only a scenario in which DefaultPreemption could have acted comes back as ErrNeedsReference), nodes with a preferAvoidPods annotation (NodePreferAvoidPods
+// would not be a constant; flatten.py takes it for one cluster size), more extended resources / spread constraints / volumes
+// than the ABI's fixed widths.  Nodes that list container images are accepted since ABI v7: fillImages hands the library
+// ImageLocality's inputs and the library scores every cluster size of the batch (simon_set_image_locality).  Whether a supported input then runs on the score-table kernel or the all-feature kernel is the
 // library's decision (simon_get_stats), never visible in a result.
 
 import (
@@ -100,11 +101,70 @@ func Supports(cluster simulator.ResourceTypes, apps []simulator.AppResource, o O
 		if _, ok := n.Annotations["scheduler.alpha.kubernetes.io/preferAvoidPods"]; ok {
 			return false
 		}
-		if len(n.Status.Images) > 0 { // ImageLocality would not be constant
-			return false
-		}
 	}
 	return true
+}
+
+// normalizedImageName (imagelocality/image_locality.go:120-125): a name without a tag gets ":latest"
+func normalizedImageName(name string) string {
+	if strings.LastIndex(name, ":") <= strings.LastIndex(name, "/") {
+		name = name + ":latest"
+	}
+	return name
+}
+
+// fillImages: ImageLocality's inputs (simon_image_locality, ABI v7), the twin of flatten.image_locality_inputs.  The scheduler cache meets
+// the nodes in pool order -- cluster nodes, then the clones (pkg/simulator/core.go:85-95, utils.NewFakeNodes) -- and
+// addNodeImageStates (V/internal/cache/cache.go:675-698) leaves on each node, per image name, the first lister's SizeBytes and the number
+// of nodes that listed the name up to and including this one.  Every scenario is a prefix of the pool, so those counts hold in every
+// scenario that has the node; only totalNumNodes differs, and the library takes it from the scenario.
+func fillImages(f *Flat, pool []*corev1.Node, classPods []*corev1.Pod, wanted map[string]bool) {
+	size := map[string]int64{}
+	count := map[string]int32{}
+	ids := map[string]int32{}
+	f.ImgNodeOff = []int32{0}
+	for _, n := range pool {
+		mine := map[string]bool{}
+		var names []string
+		for _, img := range n.Status.Images {
+			for _, name := range img.Names {
+				if _, ok := size[name]; !ok {
+					size[name], count[name] = img.SizeBytes, 0
+				}
+				if !mine[name] {
+					mine[name] = true
+					count[name]++
+					names = append(names, name)
+				}
+			}
+		}
+		sort.Strings(names)
+		for _, name := range names {
+			if !wanted[name] {
+				continue
+			}
+			id, ok := ids[name]
+			if !ok {
+				id = int32(len(f.ImgSize))
+				ids[name] = id
+				f.ImgSize = append(f.ImgSize, size[name])
+			}
+			f.ImgNodeImage = append(f.ImgNodeImage, id)
+			f.ImgNodeCount = append(f.ImgNodeCount, count[name])
+		}
+		f.ImgNodeOff = append(f.ImgNodeOff, int32(len(f.ImgNodeImage)))
+	}
+	f.ImgClassOff = []int32{0}
+	for _, p := range classPods { // pod.Spec.Containers only: init containers take no part (image_locality.go:96-113)
+		for _, ct := range p.Spec.Containers {
+			id, ok := ids[normalizedImageName(ct.Image)]
+			if !ok {
+				id = -1
+			}
+			f.ImgClassImage = append(f.ImgClassImage, id)
+		}
+		f.ImgClassOff = append(f.ImgClassOff, int32(len(f.ImgClassImage)))
+	}
 }
 
 // usesTermTables: does the pod need anything fillTerms (flatten_terms.go) produces -- pod (anti-)affinity, spread constraints of its
@@ -196,6 +256,23 @@ func flatten(pool []*corev1.Node, nCluster int, pods []*corev1.Pod, cluster simu
 		"node(s) didn't match Pod's node affinity"} // id 3 = SIMON_REASON_NODE_AFFINITY; taint messages are appended below
 	taintReason := map[string]uint8{}
 	anyIndex := false
+	// ImageLocality (imagelocality/image_locality.go:53-125) scores 0 everywhere unless a node lists an image some pod runs; then a pod's
+	// container images are part of its class (two pods that differ only in their images are two classes) and the library gets the
+	// plugin's inputs (fillImages, ABI v7)
+	wanted := map[string]bool{}
+	for _, p := range pods {
+		for _, ct := range p.Spec.Containers {
+			wanted[normalizedImageName(ct.Image)] = true
+		}
+	}
+	listed := false
+	for _, n := range pool {
+		for _, img := range n.Status.Images {
+			for _, name := range img.Names {
+				listed = listed || wanted[name]
+			}
+		}
+	}
 	for pi, p := range pods {
 		req := podRequest(p)
 		for k, name := range names {
@@ -268,6 +345,13 @@ func flatten(pool []*corev1.Node, nCluster int, pods []*corev1.Pod, cluster simu
 		key := classKey(fmt.Sprintf("%v|%v|%v|%s|%s|%s|%v|%v|%v|%s", classPod.Spec.Tolerations, classPod.Spec.NodeSelector, classPod.Spec.Affinity,
 			classPod.Spec.NodeName, resourceListKey(requestList(p)), p.Namespace, p.Labels, p.Spec.TopologySpreadConstraints, hostPortsOf(p),
 			p.Annotations[simontype.AnnoPodLocalStorage]))
+		if listed {
+			imgs := make([]string, 0, len(p.Spec.Containers))
+			for _, ct := range p.Spec.Containers {
+				imgs = append(imgs, normalizedImageName(ct.Image))
+			}
+			key += classKey(fmt.Sprintf("|%q", imgs))
+		}
 		c, ok := classOf[key]
 		if !ok {
 			c = int32(len(classPods))
@@ -369,6 +453,9 @@ func flatten(pool []*corev1.Node, nCluster int, pods []*corev1.Pod, cluster simu
 		if f.TaintPreferRaw == nil {
 			f.ConstScore[c] += 100
 		}
+	}
+	if listed {
+		fillImages(f, pool, classPods, wanted)
 	}
 	if err := fillTerms(f, pool, classPods, cluster); err != nil {
 		return nil, err

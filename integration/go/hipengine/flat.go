@@ -71,6 +71,10 @@ type Flat struct {
 	LocalSpecs                                        []LocalSpec
 	TopoIsHostname                                    []uint8
 	SpreadLog                                         []float64 // [N+1]: math.Log(float64(i+2)), Go's own math.Log
+	// ---- simon_image_locality (ABI v7): ImageLocality per cluster size; ImgNodeOff nil = no node lists an image a pod runs ----
+	ImgSize                                           []int64 // [I] ImageStateSummary.Size: the first lister's SizeBytes
+	ImgNodeOff, ImgNodeImage, ImgNodeCount            []int32 // [N+1] CSR over pool nodes: image id, NumNodes at the node's arrival
+	ImgClassOff, ImgClassImage                        []int32 // [Cp+1] CSR over pod classes: one image id per container, -1 = listed nowhere
 	// ---- bookkeeping for the way back (not part of the ABI) ----
 	NodeNames     []string
 	StaticReasons []string // reason id -> FitError text
@@ -137,6 +141,17 @@ func (f *Flat) cTables(a *cArena) C.simon_class_tables {
 		}
 	}
 	return t
+}
+
+// cImage: the simon_image_locality view of the ImageLocality inputs, nil when there are none (simon_set_image_locality is not called).
+func (f *Flat) cImage(a *cArena) *C.simon_image_locality {
+	if f.ImgNodeOff == nil {
+		return nil
+	}
+	im := C.simon_image_locality{n_images: C.int32_t(len(f.ImgSize))}
+	im.size, im.node_off, im.node_image, im.node_count = a.i64(f.ImgSize), a.i32(f.ImgNodeOff), a.i32(f.ImgNodeImage), a.i32(f.ImgNodeCount)
+	im.class_off, im.class_image = a.i32(f.ImgClassOff), a.i32(f.ImgClassImage)
+	return &im
 }
 
 // fillTermTables attaches the topology-term tables (InterPodAffinity, PodTopologySpread, NodePorts role lists).

@@ -16,7 +16,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 MAX_GPU_DEV = 8
 MAX_SCALAR = 4
 
@@ -107,6 +107,53 @@ class ClassTables(C.Structure):
         ("local_spec_of", _p32), ("n_local_specs", C.c_int32), ("local_specs", C.POINTER(LocalSpec)),
         ("topo_is_hostname", _pu8), ("spread_log", _pf64),
     ]
+
+
+class ImageLocalityC(C.Structure):
+    _fields_ = [
+        ("n_images", C.c_int32), ("size", _p64), ("node_off", _p32), ("node_image", _p32), ("node_count", _p32),
+        ("class_off", _p32), ("class_image", _p32),
+    ]
+
+
+@dataclass
+class ImageLocality:
+    """ABI v7 (simon_image_locality): the inputs of ImageLocality.Score for a batch of cluster sizes.  Image ids are the caller's own.
+    size[i] = ImageStateSummary.Size (the first lister's sizeBytes); per pool node a CSR of (image id, NumNodes as the arrival order leaves
+    it); per pod class one image id per container (-1: no node lists it; it still counts in numContainers)."""
+    size: np.ndarray          # [I] int64
+    node_off: np.ndarray      # [N+1] int32
+    node_image: np.ndarray    # [nnz] int32
+    node_count: np.ndarray    # [nnz] int32
+    class_off: np.ndarray     # [Cp+1] int32
+    class_image: np.ndarray   # [class_off[-1]] int32
+
+    def normalise(self):
+        self.size = np.ascontiguousarray(self.size, dtype=np.int64).reshape(-1)
+        for name in ("node_off", "node_image", "node_count", "class_off", "class_image"):
+            setattr(self, name, np.ascontiguousarray(getattr(self, name), dtype=np.int32).reshape(-1))
+        return self
+
+    def c_struct(self) -> "ImageLocalityC":
+        self.normalise()
+        return ImageLocalityC(len(self.size), _ptr(self.size, C.c_int64), _ptr(self.node_off, C.c_int32), _ptr(self.node_image, C.c_int32),
+                              _ptr(self.node_count, C.c_int32), _ptr(self.class_off, C.c_int32), _ptr(self.class_image, C.c_int32))
+
+    def score(self, c: int, j: int, n: int) -> int:
+        """The engine's formula (include/simon_hip.h, simon_image_locality) for pod class c on pool node j in a cluster of n nodes."""
+        e0, e1 = int(self.class_off[c]), int(self.class_off[c + 1])
+        if e1 == e0 or n <= 0:
+            return 0
+        mine = {int(self.node_image[q]): int(self.node_count[q]) for q in range(int(self.node_off[j]), int(self.node_off[j + 1]))}
+        total = 0
+        for e in range(e0, e1):
+            i = int(self.class_image[e])
+            if i >= 0 and i in mine:
+                total += int(float(int(self.size[i])) * (float(mine[i]) / float(n)))
+        mb = 1024 * 1024
+        hi = 1000 * mb * (e1 - e0)
+        total = min(max(total, 23 * mb), hi)
+        return 100 * (total - 23 * mb) // (hi - 23 * mb)
 
 
 class Scenario(C.Structure):
@@ -205,6 +252,7 @@ class Problem:
     scalar_entries: Optional[np.ndarray] = None    # [P] uint8, ABI v6: bit k = the request holds an ENTRY for extended resource k (bit 7: one no node tracks), a zero quantity included
     priority: Optional[np.ndarray] = None          # [P] int32, ABI v6: spec.priority (None: all equal)
     init_min_priority: int = 0x7fffffff            # lowest priority among the pods bound before the stream (behind init_*)
+    image_locality: Optional[ImageLocality] = None  # ABI v7: ImageLocality per cluster size, on the device (static_add then leaves it out)
     # class tables
     n_pod_classes: int = 1
     n_node_classes: int = 1
@@ -485,6 +533,7 @@ EXPORTS = [
     "simon_get_stats", "simon_device_results", "simon_explain_loaded", "simon_explain_local_detail",
     "simon_set_scalar_entries", "simon_set_pod_priorities", "simon_fetch_preempt_risk",
     "simon_group_set_scalar_entries", "simon_group_set_pod_priorities", "simon_group_fetch_preempt_risk",
+    "simon_set_image_locality", "simon_group_set_image_locality",
     "simon_group_create", "simon_group_destroy", "simon_group_last_error", "simon_group_size", "simon_group_member",
     "simon_group_load_nodes", "simon_group_load_pods", "simon_group_load_class_tables", "simon_group_load_scenarios",
     "simon_group_run_loaded", "simon_group_fetch_results", "simon_group_run_batch", "simon_group_fetch_placement", "simon_group_fetch_gpu_slices",
@@ -535,6 +584,8 @@ def load_library(path: Optional[str] = None):
         getattr(lib, pre + "set_pod_priorities").restype = C.c_int
         getattr(lib, pre + "fetch_preempt_risk").argtypes = [vp, _pu8]
         getattr(lib, pre + "fetch_preempt_risk").restype = C.c_int
+        getattr(lib, pre + "set_image_locality").argtypes = [vp, C.POINTER(ImageLocalityC)]
+        getattr(lib, pre + "set_image_locality").restype = C.c_int
     lib.simon_group_create.restype = vp
     lib.simon_group_create.argtypes = [_p32, C.c_int32]
     lib.simon_group_destroy.argtypes = [vp]
@@ -622,6 +673,9 @@ class Context:
         if prob.priority is not None:
             self._check(self.lib.simon_set_pod_priorities(self.h, _ptr(prob.priority, C.c_int32), int(prob.init_min_priority)), "simon_set_pod_priorities")
         self._check(self.lib.simon_load_class_tables(self.h, C.byref(t)), "simon_load_class_tables")
+        if prob.image_locality is not None:
+            im = prob.image_locality.c_struct()
+            self._check(self.lib.simon_set_image_locality(self.h, C.byref(im)), "simon_set_image_locality")
         self.problem = prob
 
     def load_scenarios(self, scen, orders: np.ndarray):
@@ -793,6 +847,9 @@ class Group:
         if prob.priority is not None:
             self._check(self.lib.simon_group_set_pod_priorities(self.h, _ptr(prob.priority, C.c_int32), int(prob.init_min_priority)), "simon_group_set_pod_priorities")
         self._check(self.lib.simon_group_load_class_tables(self.h, C.byref(t)), "simon_group_load_class_tables")
+        if prob.image_locality is not None:
+            im = prob.image_locality.c_struct()
+            self._check(self.lib.simon_group_set_image_locality(self.h, C.byref(im)), "simon_group_set_image_locality")
         self.problem = prob
 
     def load_scenarios(self, scen, orders: np.ndarray):

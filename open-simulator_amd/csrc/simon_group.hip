@@ -209,6 +209,12 @@ int simon_group_set_scalar_entries(simon_group* g, const uint8_t* entries) {
     return on_all(g, "set_scalar_entries", [&](int i) { return simon_set_scalar_entries(g->ctx[i], entries); });
 }
 
+int simon_group_set_image_locality(simon_group* g, const simon_image_locality* img) {
+    if (!g) return SIMON_EINVAL;
+    g->have_results = false;
+    return on_all(g, "set_image_locality", [&](int i) { return simon_set_image_locality(g->ctx[i], img); });
+}
+
 int simon_group_set_pod_priorities(simon_group* g, const int32_t* priority, int32_t init_min_priority) {
     if (!g) return SIMON_EINVAL;
     return on_all(g, "set_pod_priorities", [&](int i) { return simon_set_pod_priorities(g->ctx[i], priority, init_min_priority); });

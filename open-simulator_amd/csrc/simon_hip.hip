@@ -189,6 +189,16 @@ struct simon_ctx : simon::HostInputs {
     DevBuf<unsigned long long> d_plan;
     bool have_results = false, have_placement = false, have_slices = false;
     DevBuf<uint64_t> d_gpu_slices;      // [S][P] devices Reserve booked (simon_batch_out.gpu_slices), recorded on request
+    // ABI v7 ImageLocality: the caller's node classes and (pod class, node class) tables before the image split (img_refine)
+    bool img_refined = false;
+    int img_base_Cn = 0;
+    std::vector<int32_t> img_base_ncls;
+    std::vector<int64_t> img_base_raw, img_base_na, img_base_tt, img_base_add;
+    DevBuf<unsigned char> d_t_img, d_img_explain;   // score table: [slot][table class][internal node class]; explain: [1][img_R][Cn]
+    DevBuf<int32_t> d_img_slot;                     // [S] size slot of every loaded scenario
+    int img_stride_t = 0;                           // table classes x internal node classes (TableCold::img_stride)
+    std::vector<int32_t> h_img_slot;                // host sources of d_img_slot / d_img_explain: they outlive the asynchronous uploads
+    std::vector<unsigned char> h_img_explain;
     simon_stats stats{};
 };
 
@@ -224,6 +234,106 @@ uint64_t gcd_of(std::initializer_list<const std::vector<int64_t>*> vs) {
     uint64_t g = 0;
     for (auto* v : vs) for (int64_t x : *v) { if (x < 0) return 0; g = gcd_u64(g, (uint64_t)x); if (g == 1) return 1; }
     return g ? g : 1;
+}
+
+// ---- ImageLocality (ABI v7: simon_set_image_locality) -----------------------------------------------------------------------------------
+// ImageLocality.Score of pod class cp on pool node j in a cluster of n nodes (imagelocality/image_locality.go:53-125): plain IEEE fp64
+// as Go evaluates it (-ffp-contract=off), int64 arithmetic for the rest
+int img_score(const simon_ctx* c, int cp, int j, int n) {
+    const int e0 = c->img_class_off[cp], e1 = c->img_class_off[cp + 1];
+    if (e1 == e0 || n <= 0 || j < 0) return 0;
+    const int64_t mb = 1024 * 1024, lo = 23 * mb, hi = 1000 * mb * (int64_t)(e1 - e0);
+    int64_t sum = 0;
+    for (int e = e0; e < e1; ++e) {
+        const int im = c->img_class_image[e];
+        if (im < 0) continue;
+        for (int q = c->img_node_off[j]; q < c->img_node_off[j + 1]; ++q)
+            if (c->img_node_image[q] == im) {
+                sum += (int64_t)((double)c->img_size[im] * ((double)c->img_node_count[q] / (double)n));
+                break;
+            }
+        if (sum > hi) sum = hi + 1;                  // (saturates: the clamp below takes it to hi whatever follows)
+    }
+    if (sum < lo) sum = lo; else if (sum > hi) sum = hi;
+    return (int)(100 * (sum - lo) / (hi - lo));
+}
+
+// the caller's node classes and tables back (before a reload or a new image input)
+void img_unrefine(simon_ctx* c) {
+    if (!c->img_refined) return;
+    c->Cn = c->img_base_Cn; c->node_class.swap(c->img_base_ncls);
+    c->simon_raw.swap(c->img_base_raw); c->na_raw.swap(c->img_base_na); c->tt_raw.swap(c->img_base_tt); c->static_add.swap(c->img_base_add);
+    c->img_base_ncls.clear(); c->img_base_raw.clear(); c->img_base_na.clear(); c->img_base_tt.clear(); c->img_base_add.clear();
+    c->img_refined = false;
+}
+
+// One slot's scores: out[row][Cn] for a cluster of n nodes, from a node of every class (every node of a class scores alike)
+void img_slot_scores(const simon_ctx* c, int n, uint8_t* out) {
+    for (int cp = 0; cp < c->Cp; ++cp) {
+        const int r = c->img_row_of[cp];
+        if (r < 0) continue;
+        for (int k = 0; k < c->Cn; ++k) out[(size_t)r * c->Cn + k] = (uint8_t)img_score(c, cp, c->img_rep[k], n);
+    }
+}
+
+// Split the caller's node classes by image CONTENT -- (image, NumNodes) of every entry of the node -- so that the nodes of a class score
+// alike for EVERY cluster size (simon_explain of a size outside the batch included), and derive the per-slot tables of the batch
+// (img_sizes).  Classes of nodes without entries keep their ids: a problem whose nodes list nothing stages exactly as without images.
+void img_refine(simon_ctx* c) {
+    img_unrefine(c);
+    c->img_row_of.assign(c->Cp, -1);
+    c->img_R = 0; c->img_cls.clear(); c->img_rep.clear();
+    if (!c->has_img) return;
+    for (int cp = 0; cp < c->Cp; ++cp)
+        for (int e = c->img_class_off[cp]; e < c->img_class_off[cp + 1]; ++e)
+            if (c->img_class_image[e] >= 0) { c->img_row_of[cp] = c->img_R++; break; }
+    if (c->img_R == 0) return;
+    const int N = c->N, Cn0 = c->Cn;
+    std::map<std::vector<int32_t>, int> ids;
+    for (int k = 0; k < Cn0; ++k) ids.emplace(std::vector<int32_t>{k}, k);
+    std::vector<int32_t> ncls(N), rep(Cn0, -1);
+    for (int j = 0; j < N; ++j) {
+        std::vector<std::pair<int32_t, int32_t>> ent;
+        for (int q = c->img_node_off[j]; q < c->img_node_off[j + 1]; ++q) ent.emplace_back(c->img_node_image[q], c->img_node_count[q]);
+        std::sort(ent.begin(), ent.end());
+        std::vector<int32_t> key{c->node_class[j]};
+        for (auto& e : ent) { key.push_back(e.first); key.push_back(e.second); }
+        auto it = ids.emplace(std::move(key), (int)ids.size());
+        if (it.second) rep.push_back(-1);
+        ncls[j] = it.first->second;
+        if (rep[ncls[j]] < 0) rep[ncls[j]] = j;
+    }
+    const int Cn1 = (int)ids.size();
+    if (Cn1 != Cn0) {
+        c->img_base_Cn = Cn0;
+        c->img_base_ncls = c->node_class; c->img_base_raw = c->simon_raw; c->img_base_na = c->na_raw; c->img_base_tt = c->tt_raw; c->img_base_add = c->static_add;
+        std::vector<int32_t> orig(Cn1);
+        for (int k = 0; k < Cn1; ++k) orig[k] = k < Cn0 ? k : c->img_base_ncls[rep[k]];
+        for (std::vector<int64_t>* tab : {&c->simon_raw, &c->na_raw, &c->tt_raw, &c->static_add}) {
+            if (tab->empty()) continue;
+            std::vector<int64_t> t((size_t)c->Cp * Cn1);
+            for (int cp = 0; cp < c->Cp; ++cp)
+                for (int k = 0; k < Cn1; ++k) t[(size_t)cp * Cn1 + k] = (*tab)[(size_t)cp * Cn0 + orig[k]];
+            tab->swap(t);
+        }
+        c->node_class = ncls;
+        c->Cn = Cn1;
+        c->img_refined = true;
+    }
+    c->img_rep = rep;
+    const size_t slot = (size_t)c->img_R * c->Cn;
+    c->img_cls.assign(c->img_sizes.size() * slot, 0);
+    for (size_t t = 0; t < c->img_sizes.size(); ++t) img_slot_scores(c, c->img_sizes[t], c->img_cls.data() + t * slot);
+}
+
+// every slot's image scores of pod class cp, appended to a content key (nothing for a class that scores 0 everywhere)
+template <class T>
+void img_row_append(const simon_ctx* c, int cp, std::vector<T>& key) {
+    if (c->img_R == 0 || c->img_row_of[cp] < 0) return;
+    const size_t slot = (size_t)c->img_R * c->Cn, off = (size_t)c->img_row_of[cp] * c->Cn;
+    key.push_back((T)-1);                            // (a separator: rows of different lengths never alias)
+    for (size_t t = 0; t < c->img_sizes.size(); ++t)
+        for (int k = 0; k < c->Cn; ++k) key.push_back((T)c->img_cls[t * slot + off + k]);
 }
 
 // Can the score-table kernel's REST path take this problem's GPU-share / topology-term features?  Terms: only required
@@ -373,6 +483,7 @@ bool gfold_supported(simon_ctx* c) {
             std::vector<int64_t> rrow;
             for (const std::vector<int64_t>* tab : {&c->simon_raw, &c->na_raw, &c->tt_raw, &c->static_add})
                 if (!tab->empty()) rrow.insert(rrow.end(), tab->begin() + (size_t)cp * c->Cn, tab->begin() + (size_t)(cp + 1) * c->Cn);
+            img_row_append(c, cp, rrow);
             content_of[cp] = ids.emplace(std::make_pair(std::move(mrow), std::move(rrow)), (int)ids.size()).first->second;
         }
     }
@@ -698,6 +809,7 @@ bool fold_supported(simon_ctx* c) {
             std::vector<int64_t> rrow;
             for (const std::vector<int64_t>* tab : {&c->simon_raw, &c->na_raw, &c->tt_raw, &c->static_add})
                 if (!tab->empty()) rrow.insert(rrow.end(), tab->begin() + (size_t)cp * c->Cn, tab->begin() + (size_t)(cp + 1) * c->Cn);
+            img_row_append(c, cp, rrow);
             content_of[cp] = ids.emplace(std::make_pair(std::move(mrow), std::move(rrow)), (int)ids.size()).first->second;
         }
     }
@@ -726,7 +838,7 @@ void choose_variant(simon_ctx* c) {
     if (c->force_wide) return;
     c->rest = false;
     c->spread = false;
-    c->has_static = c->has_na || c->has_tt || c->has_add;
+    c->has_static = c->has_na || c->has_tt || c->has_add || c->img_R > 0;
     c->fold = fold_supported(c);
     c->gfold = gfold_supported(c);
     if (c->fold && c->has_gpu && !c->gfold) c->fold = false;        // GPU share on position masks (generation 6) takes the terms along
@@ -753,7 +865,7 @@ void choose_variant(simon_ctx* c) {
         for (int64_t x : c->na_raw) if (x < 0 || x >= (1ll << 30)) return;
         for (int64_t x : c->tt_raw) if (x < 0 || x >= (1ll << 30)) return;
         for (int64_t x : c->static_add) { if (x < 0) return; add_max = std::max(add_max, x); }
-        if (201 + 200 + (c->has_na ? 100 : 0) + (c->has_tt ? 100 : 0) + add_max > 1023) return;
+        if (201 + 200 + (c->has_na ? 100 : 0) + (c->has_tt ? 100 : 0) + add_max + (c->img_R > 0 ? 100 : 0) > 1023) return;   // (+ ImageLocality <= 100)
     }
     // Ephemeral storage and extended resources take part only when somebody requests them: with no request and nothing requested at
     // the start, fitsRequest's `Allocatable < request + Requested` (fit.go:264-299) is 0-false on every node whatever the allocatable.
@@ -868,6 +980,7 @@ int stage_narrow(simon_ctx* c) {
             std::vector<int32_t> rrow(raw32.begin() + (size_t)cp * c->Cn, raw32.begin() + (size_t)(cp + 1) * c->Cn);
             for (const std::vector<int64_t>* tab : {&c->na_raw, &c->tt_raw, &c->static_add})       // static score rows are content too
                 if (!tab->empty()) rrow.insert(rrow.end(), tab->begin() + (size_t)cp * c->Cn, tab->begin() + (size_t)(cp + 1) * c->Cn);
+            img_row_append(c, cp, rrow);                               // ... and so are the image score rows of every size of the batch
             auto it = tc_id.emplace(std::make_pair(std::move(mrow), std::move(rrow)), (int)tc_rep.size());
             if (it.second) tc_rep.push_back(cp);
             tc_of[cp] = it.first->second;
@@ -1111,6 +1224,9 @@ int stage_narrow(simon_ctx* c) {
                     col.push_back(raw32[(size_t)tc_rep[tc] * c->Cn + nc]);
                     for (const std::vector<int64_t>* tab : {&c->na_raw, &c->tt_raw, &c->static_add})
                         if (!tab->empty()) col.push_back((int32_t)(*tab)[(size_t)tc_rep[tc] * c->Cn + nc]);
+                    const int ir = c->img_R ? c->img_row_of[tc_rep[tc]] : -1;   // ImageLocality: the class's score column for every size of the batch
+                    for (size_t t = 0; ir >= 0 && t < c->img_sizes.size(); ++t)
+                        col.push_back(c->img_cls[(t * c->img_R + ir) * c->Cn + nc]);
                 }
                 content_of[nc] = col_id.emplace(std::move(col), (int)col_id.size()).first->second;
             }
@@ -1163,6 +1279,19 @@ int stage_narrow(simon_ctx* c) {
                 for (int tc = 0; tc < Ctc; ++tc)
                     for (int d = 0; d < Ct; ++d) t[(size_t)tc * Ct + d] = (int32_t)(*tab)[(size_t)tc_rep[tc] * c->Cn + orig_of[d]];
                 HIP_TRY(c, buf->upload(t, st));
+            }
+            if (c->img_R > 0) {                                       // ImageLocality: [slot][table class][internal node class]
+                const size_t nslot = std::max<size_t>(c->img_sizes.size(), 1);
+                std::vector<unsigned char> img_t(nslot * Ctc * Ct, 0);
+                for (size_t t = 0; t < c->img_sizes.size(); ++t)
+                    for (int tc = 0; tc < Ctc; ++tc) {
+                        const int ir = c->img_row_of[tc_rep[tc]];
+                        if (ir < 0) continue;
+                        for (int d = 0; d < Ct; ++d) img_t[(t * Ctc + tc) * Ct + d] = c->img_cls[(t * c->img_R + ir) * c->Cn + orig_of[d]];
+                    }
+                HIP_TRY(c, c->d_t_img.upload(img_t, st));
+                HIP_TRY(c, hipStreamSynchronize(st));                  // (img_t dies at the end of this block)
+                c->img_stride_t = Ctc * Ct;
             }
             if (c->has_mask) {
                 std::vector<uint64_t> mask_t((size_t)Ctc * words);
@@ -1294,6 +1423,10 @@ int stage(simon_ctx* c) {
     c->has_gpu = c->has_gpu_nodes;
     if (!c->has_gpu)
         for (int p = 0; p < c->P; ++p) if (c->p_gpu_mem[p] > 0) { c->has_gpu = true; break; }
+    img_refine(c);                                                  // (ABI v7: node classes split by image content, the batch's size slots)
+    if (c->debug_route && c->img_R > 0)
+        fprintf(stderr, "[route] image split: %d node classes (caller %d), %d image-scoring pod classes, %zu sizes\n", c->Cn,
+                c->img_refined ? c->img_base_Cn : c->Cn, c->img_R, c->img_sizes.size());
     choose_variant(c);
     if (c->variant != SIMON_KERNEL_NARROW) c->spread = false;         // (a later precondition sent the problem to the all-feature kernel)
     // prefix sums of allocatable for the occupancy caps (satisfyResourceSetting, apply.go:737-760)
@@ -1472,6 +1605,8 @@ int simon_load_nodes(simon_ctx* c, const simon_nodes_soa* nd) {
     if (nd->n_scalar < 0 || nd->n_scalar > SIMON_MAX_SCALAR) return fail(c, SIMON_EINVAL, "n_scalar out of range");
     if (nd->n_scalar > 0 && !nd->scalar_alloc) return fail(c, SIMON_EINVAL, "scalar_alloc missing");
     if (nd->n_topo_keys < 0 || (nd->n_topo_keys > 0 && (!nd->topo_dom || !nd->topo_n_dom))) return fail(c, SIMON_EINVAL, "topology arrays missing");
+    img_unrefine(c);                     // (a new pool: the image input no longer describes it)
+    c->has_img = false; c->img_sizes.clear();
     c->N = N; c->K = nd->n_scalar; c->Kt = nd->n_topo_keys;
     copy_opt(c->alloc_cpu, nd->alloc_cpu, N); copy_opt(c->alloc_mem, nd->alloc_mem, N);
     copy_opt(c->alloc_eph, nd->alloc_eph, N); copy_opt(c->alloc_pods, nd->alloc_pods, N);
@@ -1579,11 +1714,59 @@ int simon_set_pod_priorities(simon_ctx* c, const int32_t* priority, int32_t init
     return SIMON_OK;
 }
 
+int simon_set_image_locality(simon_ctx* c, const simon_image_locality* im) {
+    if (!c) return SIMON_EINVAL;
+    if (!c->have_nodes || !c->have_tables) return fail(c, SIMON_ESTATE, "set_image_locality: load nodes and class tables first");
+    img_unrefine(c);
+    c->staged = false; c->wide_staged = false; c->have_results = false;
+    c->has_img = false; c->img_sizes.clear();
+    c->img_size.clear(); c->img_node_off.clear(); c->img_node_image.clear(); c->img_node_count.clear(); c->img_class_off.clear(); c->img_class_image.clear();
+    if (!im) return SIMON_OK;
+    const int N = c->N, Cp = c->Cp, I = im->n_images;
+    if (I < 0) return fail(c, SIMON_EINVAL, "image locality: n_images %d < 0", I);
+    if (!im->node_off || !im->class_off || (I > 0 && !im->size)) return fail(c, SIMON_EINVAL, "image locality: size / node_off / class_off missing");
+    if (im->node_off[0] != 0) return fail(c, SIMON_EINVAL, "image locality: node_off[0] != 0");
+    for (int j = 0; j < N; ++j)
+        if (im->node_off[j + 1] < im->node_off[j] || im->node_off[j + 1] - im->node_off[j] > I)
+            return fail(c, SIMON_EINVAL, "image locality: node %d: node_off not ascending or more entries than images", j);
+    if (im->class_off[0] != 0) return fail(c, SIMON_EINVAL, "image locality: class_off[0] != 0");
+    for (int k = 0; k < Cp; ++k)
+        if (im->class_off[k + 1] < im->class_off[k] || im->class_off[k + 1] - im->class_off[k] > (1 << 20))
+            return fail(c, SIMON_EINVAL, "image locality: pod class %d: class_off not ascending or more than 2^20 containers", k);
+    const size_t nnz = (size_t)im->node_off[N], ncont = (size_t)im->class_off[Cp];
+    if ((nnz > 0 && (!im->node_image || !im->node_count)) || (ncont > 0 && !im->class_image))
+        return fail(c, SIMON_EINVAL, "image locality: node_image / node_count / class_image missing");
+    copy_opt(c->img_size, im->size, (size_t)I);
+    copy_opt(c->img_node_off, im->node_off, (size_t)N + 1);
+    copy_opt(c->img_node_image, im->node_image, nnz);
+    copy_opt(c->img_node_count, im->node_count, nnz);
+    copy_opt(c->img_class_off, im->class_off, (size_t)Cp + 1);
+    copy_opt(c->img_class_image, im->class_image, ncont);
+    for (int i = 0; i < I; ++i)
+        if (c->img_size[i] < 0 || c->img_size[i] >= (1ll << 53)) return fail(c, SIMON_ERANGE, "image locality: image %d: size %lld outside [0, 2^53)", i, (long long)c->img_size[i]);
+    std::vector<int32_t> seen(std::max(I, 1), -1);
+    for (int j = 0; j < N; ++j)
+        for (int q = c->img_node_off[j]; q < c->img_node_off[j + 1]; ++q) {
+            const int32_t i = c->img_node_image[q];
+            if (i < 0 || i >= I) return fail(c, SIMON_EINVAL, "image locality: node %d lists image id %d outside [0,%d)", j, i, I);
+            if (seen[i] == j) return fail(c, SIMON_EINVAL, "image locality: node %d lists image %d twice", j, i);
+            seen[i] = j;
+            if (c->img_node_count[q] < 1 || c->img_node_count[q] > N)
+                return fail(c, SIMON_ERANGE, "image locality: node %d: NumNodes %d of image %d outside [1,%d]", j, c->img_node_count[q], i, N);
+        }
+    for (size_t e = 0; e < ncont; ++e)
+        if (c->img_class_image[e] < -1 || c->img_class_image[e] >= I) return fail(c, SIMON_EINVAL, "image locality: class_image[%zu] = %d outside [-1,%d)", e, c->img_class_image[e], I);
+    c->has_img = true;
+    return SIMON_OK;
+}
+
 int simon_load_class_tables(simon_ctx* c, const simon_class_tables* tb) {
     if (!c || !tb) return SIMON_EINVAL;
     if (tb->struct_size != sizeof(simon_class_tables)) return fail(c, SIMON_EINVAL, "simon_class_tables size mismatch");
     if (!c->have_nodes) return fail(c, SIMON_ESTATE, "load nodes before class tables");
     if (tb->n_pod_classes <= 0 || tb->n_node_classes <= 0 || !tb->simon_raw) return fail(c, SIMON_EINVAL, "class tables: bad sizes");
+    img_unrefine(c);                     // (new class tables: the image input no longer describes them)
+    c->has_img = false; c->img_sizes.clear();
     c->Cp = tb->n_pod_classes; c->Cn = tb->n_node_classes;
     const size_t words = (size_t)(c->N + 63) / 64;
     c->has_mask = tb->static_mask != nullptr;
@@ -1697,6 +1880,13 @@ int simon_load_class_tables(simon_ctx* c, const simon_class_tables* tb) {
 
 int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, const int32_t* orders, int32_t n_orders) {
     if (!c || !scen || S <= 0 || !orders || n_orders <= 0) return c ? fail(c, SIMON_EINVAL, "load_scenarios: bad arguments") : SIMON_EINVAL;
+    if (c->has_img) {                    // ImageLocality: one slot per distinct cluster size; another set of sizes re-stages the tables
+        std::vector<int32_t> sizes(S);
+        for (int s = 0; s < S; ++s) sizes[s] = scen[s].n_nodes;
+        std::sort(sizes.begin(), sizes.end());
+        sizes.erase(std::unique(sizes.begin(), sizes.end()), sizes.end());
+        if (sizes != c->img_sizes) { c->img_sizes = sizes; c->staged = false; }
+    }
     int rc = stage(c);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1731,6 +1921,13 @@ int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, co
     HIP_TRY(c, c->d_used_mem.ensure(S));
     HIP_TRY(c, c->d_used_vg.ensure(S));
     HIP_TRY(c, c->d_plan.ensure(1));
+    if (c->img_R > 0) {
+        std::vector<int32_t>& slot = c->h_img_slot;
+        slot.resize(S);
+        for (int s = 0; s < S; ++s) slot[s] = (int32_t)(std::lower_bound(c->img_sizes.begin(), c->img_sizes.end(), scen[s].n_nodes) - c->img_sizes.begin());
+        HIP_TRY(c, c->d_img_slot.upload(slot, c->stream));
+    }
+    c->wide.img_slot_ext = c->img_R > 0 ? c->d_img_slot.p : nullptr;
     c->h_perm = perm;
     c->scen_ni.assign(S, 0);
     c->h_orders.assign(orders, orders + (size_t)n_orders * P);
@@ -1953,6 +2150,7 @@ int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
             cold.gpu_slices = want_slices ? reinterpret_cast<unsigned long long*>(c->d_gpu_slices.p) : nullptr;
             cold.na_raw = c->has_na ? c->d_t_na.p : nullptr; cold.tt_raw = c->has_tt ? c->d_t_tt.p : nullptr; cold.add_raw = c->has_add ? c->d_t_add.p : nullptr;
             if (c->has_ranks) { cold.rk_pos = c->d_rk_pos.p; cold.rk_rank = c->d_node_rank.p; }
+            if (c->img_R > 0) { cold.img = c->d_t_img.p; cold.img_slot = c->d_img_slot.p; cold.img_stride = c->img_stride_t; }
             if (c->rest) {
                 cold.xrows = c->d_xrows.p; cold.zdom = c->d_zdom.p; cold.xsig = c->d_xsig.p; cold.xalloc = c->d_xalloc.p; cold.i_xused = c->d_i_xused.p;
                 cold.gsig = c->d_gsig.p; cold.gpu_cnt = c->d_gpu_cnt.p; cold.gpu_devtot = c->d_gpu_devtot.p; cold.i_gused = c->d_i_gused.p;
@@ -1973,7 +2171,7 @@ int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
             f.cls_list = c->has_ranks ? c->d_rk_ids.p : c->d_cls_list.p; f.pods = c->d_podsC.p; f.orders = c->d_orders.p; f.perm = c->d_perm.p;
             f.ws_off = c->d_ws_off.p; f.ws = c->d_ws.p; f.coarse = c->table_coarse; f.rest = c->rest; f.spread = c->spread; f.aff = c->rest && !c->aff_idx.empty(); f.team = team; f.lds_ws = lds_ws; f.lds_x = lds_x;
             f.place_step = want_placement ? c->d_place_step.p : nullptr;
-            f.sc = TableScalars{(c->N + 63) / 64, c->Cn_t, c->Cp, P, S, c->n_sigs, c->has_ranks ? c->N : 0, (c->has_na ? 1 : 0) | (c->has_tt ? 2 : 0) | (c->has_add ? 4 : 0) | (want_slices ? 8 : 0) | (c->sig_twins ? 16 : 0) | (c->fold ? 32 : 0) | ((c->spread && (c->ipa_fold || c->hard_fold)) ? 64 : 0) | (c->gfold ? 128 : 0), c->rest ? (int)c->zone_keys.size() : 0, c->rest ? c->rest_M : 0, c->rest ? c->rest_G : 0, c->rest ? c->rest_X : 0, c->spread ? c->sp_TH : 0, c->spread ? c->sp_TZ : 0, c->spread ? (int)c->sp_zkeys.size() : 0, ni_top, c->g_cpu, c->g_mem};
+            f.sc = TableScalars{(c->N + 63) / 64, c->Cn_t, c->Cp, P, S, c->n_sigs, c->has_ranks ? c->N : 0, (c->has_na ? 1 : 0) | (c->has_tt ? 2 : 0) | (c->has_add ? 4 : 0) | (want_slices ? 8 : 0) | (c->sig_twins ? 16 : 0) | (c->fold ? 32 : 0) | ((c->spread && (c->ipa_fold || c->hard_fold)) ? 64 : 0) | (c->gfold ? 128 : 0) | (c->img_R > 0 ? 256 : 0), c->rest ? (int)c->zone_keys.size() : 0, c->rest ? c->rest_M : 0, c->rest ? c->rest_G : 0, c->rest ? c->rest_X : 0, c->spread ? c->sp_TH : 0, c->spread ? c->sp_TZ : 0, c->spread ? (int)c->sp_zkeys.size() : 0, ni_top, c->g_cpu, c->g_mem};
             HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
             HIP_TRY(c, launch_table(f, S, c->has_mask, c->nzeq, c->has_pin, table_lds, c->stream));
             if (want_placement)
@@ -2252,6 +2450,14 @@ static int explain_impl(simon_ctx* c, int n_nodes, const int32_t* order, int ran
     if (ranked_scenario >= 0) {
         rk = c->d_node_rank.p + (size_t)ranked_scenario * c->N;
         iv = c->d_node_inv.p + (size_t)ranked_scenario * c->N;
+    }
+    if (c->img_R > 0) {                  // ImageLocality of THIS size, whether or not the batch has it
+        std::vector<unsigned char>& one = c->h_img_explain;
+        one.assign((size_t)c->img_R * c->Cn, 0);
+        img_slot_scores(c, n_nodes, one.data());
+        HIP_TRY(c, c->d_img_explain.upload(one, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->wide.img_explain_ext = c->d_img_explain.p;
     }
     c->explain_nodes = n_nodes;
     c->explain_ran = true;

@@ -800,6 +800,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     //   + TaintToleration PreferNoSchedule (DefaultNormalizeScore(100, true): 100 - 100 raw / max, 100 everywhere when max = 0)
     //   + already weighted static scores (NodePreferAvoidPods), small ones only (simon_hip.hip: static_tables_fit).
     // floor(100 x / m) = (int)fma(100 x, 1/m, 0.5/m) for 0 <= x <= m < 2^30 (the la_term argument, simon_device.h).
+    // ImageLocality (static_tables & 256): the first entry of this scenario's size slot -- wave-uniform, a scalar load on the rare path
+    auto img_base = [&](GPtr<const TableCold> cc) -> size_t {
+        return (size_t)__builtin_amdgcn_readfirstlane(gp(cc->img_slot)[s]) * (size_t)cc->img_stride;
+    };
     auto class_term = [&](bool inb, int rawc, int c, int dd) -> int {
         const int lo = wave_min_i32(inb ? rawc : 0x7fffffff);
         const int hi = wave_max_i32(inb ? rawc : (int)0x80000000);
@@ -821,6 +825,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
             term += inb ? (mx ? 100 - (int)__builtin_fma((double)v * 100.0, r, 0.5 * r) : 100) : 0;
         }
         if (sc.static_tables & 4) term += inb ? gp(cc->add_raw)[c * Cn + dd] : 0;
+        if (sc.static_tables & 256) term += inb ? (int)gp(cc->img)[img_base(cc) + c * Cn + dd] : 0;
         return term;
     };
     // class_term for two classes per lane (CN2: lane l holds classes d0 = l and d1 = 64 + l): the same formulas with the extremes and
@@ -848,6 +853,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
             t1 += in1 ? (mx ? 100 - (int)__builtin_fma((double)a1 * 100.0, r, 0.5 * r) : 100) : 0;
         }
         if (sc.static_tables & 4) { t0 += in0 ? gp(cc->add_raw)[c * Cn + d0] : 0; t1 += in1 ? gp(cc->add_raw)[c * Cn + d1] : 0; }
+        if (sc.static_tables & 256) {
+            const size_t ib = img_base(cc);
+            t0 += in0 ? (int)gp(cc->img)[ib + c * Cn + d0] : 0; t1 += in1 ? (int)gp(cc->img)[ib + c * Cn + d1] : 0;
+        }
     };
     // Re-base summary row k after the set of node classes with a feasible node changed.
     auto renormalise = [&](int k, int c) {
@@ -902,6 +911,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
 #pragma unroll
                 for (int g = 0; g < 4; ++g) tq[g] += inq[g] ? gp(cc->add_raw)[c * Cn + dq[g]] : 0;
             }
+            if (sc.static_tables & 256) {
+                const size_t ib = img_base(cc);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) tq[g] += inq[g] ? (int)gp(cc->img)[ib + c * Cn + dq[g]] : 0;
+            }
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 if (g * 64 + lane < Cn) {
@@ -938,6 +952,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
                 t1 += in1 ? (mx ? 100 - (int)__builtin_fma((double)a1 * 100.0, r, 0.5 * r) : 100) : 0;
             }
             if (sc.static_tables & 4) { t0 += in0 ? gp(cc->add_raw)[c * Cn + d0] : 0; t1 += in1 ? gp(cc->add_raw)[c * Cn + d1] : 0; }
+            if (sc.static_tables & 256) {
+                const size_t ib = img_base(cc);
+                t0 += in0 ? (int)gp(cc->img)[ib + c * Cn + d0] : 0; t1 += in1 ? (int)gp(cc->img)[ib + c * Cn + d1] : 0;
+            }
             s_tmp[d0] = t0 - (int)s_sn[k * Cn + d0];
             s_sn[k * Cn + d0] = (unsigned short)t0;
             if (v1) { s_tmp[d1] = t1 - (int)s_sn[k * Cn + d1]; s_sn[k * Cn + d1] = (unsigned short)t1; }
@@ -2209,7 +2227,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
                         // of their own: with them every leave re-bases.
                         bool rebase = left == 0;
                         if constexpr (kCls4) {
-                            if (rebase && !(sc.static_tables & 7)) {
+                            if (rebase && !(sc.static_tables & (7 | 256))) {
                                 const int raw = simon_raw[((KQ > 1 && dirty_bit == KQ - 1) ? my_tc[KQ - 1] : my_tc[0]) * Cn + dstar];
                                 const int2 e = s_ext[k];
                                 rebase = !(e.x < raw && raw < e.y);

@@ -36,6 +36,17 @@ struct HostInputs {
     // ABI v2: static (pod class, node class) score inputs
     std::vector<int64_t> na_raw, tt_raw, static_add;
     bool has_na = false, has_tt = false, has_add = false;
+    // ABI v7 ImageLocality (simon_set_image_locality): the caller's arrays, and what staging derives from them.  With images the node
+    // classes the kernels see are the caller's classes split by image content (img_entries), so that every node of a class scores alike
+    // for every cluster size; img_cls[slot][row][Cn] = score of (image-scoring pod class of row `row`, node class) at img_sizes[slot].
+    bool has_img = false;
+    std::vector<int64_t> img_size;
+    std::vector<int32_t> img_node_off, img_node_image, img_node_count, img_class_off, img_class_image;
+    std::vector<int32_t> img_row_of;     // [Cp] row of an image-scoring class, -1 = scores 0 everywhere
+    int32_t img_R = 0;
+    std::vector<int32_t> img_sizes;      // distinct n_nodes of the loaded batch, ascending (one slot each)
+    std::vector<uint8_t> img_cls;        // [slots][img_R][Cn]
+    std::vector<int32_t> img_rep;        // [Cn] a node of every (split) node class
     // topology terms (InterPodAffinity + PodTopologySpread)
     std::vector<int32_t> term_key, term_set;
     std::vector<uint64_t> node_sets;
@@ -53,7 +64,7 @@ struct HostInputs {
     bool has_ipa_score = false;   // any pref_* or own_* entry exists
     // everything of v2_features() but NodePorts (port terms are node-level by construction: the score-table kernel's REST path takes them)
     bool v2_features_but_ports() const {
-        return has_na || has_tt || has_add || !aff_idx.empty() || has_ipa_score || !sh_idx.empty() || !ss_idx.empty() || has_local;
+        return has_na || has_tt || has_add || has_img || !aff_idx.empty() || has_ipa_score || !sh_idx.empty() || !ss_idx.empty() || has_local;
     }
     // ... and but the static score tables (NodeAffinity preferred, TaintToleration PreferNoSchedule, weighted additions), which the
     // score-table kernel folds into its class term
@@ -61,7 +72,7 @@ struct HostInputs {
         return has_ipa_score || !sh_idx.empty() || !ss_idx.empty() || has_local;
     }
     bool v2_features() const {
-        return has_na || has_tt || has_add || !aff_idx.empty() || has_ipa_score || !sh_idx.empty() || !ss_idx.empty() || !port_idx.empty() || has_local;
+        return has_na || has_tt || has_add || has_img || !aff_idx.empty() || has_ipa_score || !sh_idx.empty() || !ss_idx.empty() || !port_idx.empty() || has_local;
     }
 };
 
@@ -124,6 +135,8 @@ struct WideCold {
     // tables
     const uint8_t* static_reason;
     const int64_t* na_raw; const int64_t* tt_raw; const int64_t* static_add;   // [Cp][Cn] or null
+    // kArgImage: img[(slot * img_R + img_row_of[class]) * Cn + node class], slot = img_slot[scenario] (explain: a one-slot table)
+    const uint8_t* img; const int32_t* img_row_of; const int32_t* img_slot; int32_t img_R;
     const int32_t* term_key; const int32_t* term_dom_off /*[Tm] offset of term t's counters*/;
     const int32_t* term_set /*[Tm] row of node_sets or -1*/; const uint64_t* node_sets;
     const int32_t* anti_off; const int32_t* anti_idx; const int32_t* match_off; const int32_t* match_idx;
@@ -197,7 +210,9 @@ constexpr uint32_t kArgGpu = 1u, kArgMask = 2u, kArgEph = 4u, kArgNzeq = 8u, kAr
                    kArgIpaCache = 2048u, kArgPtsCache = 4096u, kArgPtsSlotsShift = 13u /*3 bits: soft constraints per class, at most*/,
                    // more than 64 node classes (no class mode): the pod class's rows of the four (pod class, node class) tables are
                    // staged in LDS all the same when they fit (round 6: per feasible node they were up to seven dependent FLAT loads)
-                   kArgRowsLds = 65536u;
+                   kArgRowsLds = 65536u,
+                   // ABI v7: ImageLocality scores per (size slot of the scenario, pod class, node class), added to the class term
+                   kArgImage = 131072u;
 
 // tuning / experiment knobs: environment variables read ONCE, when the context is created (simon_ctx_create)
 struct WideKnobs {
@@ -213,7 +228,7 @@ struct WideKnobs {
 
 struct WideDevice {
     WideKnobs knobs;
-    void* blobs[96] = {};
+    void* blobs[112] = {};
     int n_blobs = 0;
     int state_chunk = 0;   // scenarios whose state is allocated
     int total_dom = 0, seen_stride = 0;
@@ -227,6 +242,10 @@ struct WideDevice {
     int32_t* i_npods = nullptr;
     uint64_t* static_mask = nullptr; uint8_t* static_reason = nullptr; int64_t* simon_raw = nullptr;
     int64_t *na_raw = nullptr, *tt_raw = nullptr, *static_add = nullptr;
+    uint8_t* img = nullptr;                  // [slots][img_R][Cn] of the batch
+    int32_t *img_row_of = nullptr, *img_zero = nullptr;
+    const int32_t* img_slot_ext = nullptr;   // [S] slot of every loaded scenario (owned by the context)
+    const uint8_t* img_explain_ext = nullptr;   // [1][img_R][Cn] of the scenario being explained (owned by the context)
     int32_t *term_key = nullptr, *term_dom_off = nullptr, *term_set = nullptr, *anti_off = nullptr, *anti_idx = nullptr,
             *match_off = nullptr, *match_idx = nullptr, *manti_off = nullptr, *manti_idx = nullptr, *mown_off = nullptr, *mown_idx = nullptr, *aff_off = nullptr, *aff_idx = nullptr, *port_off = nullptr, *port_idx = nullptr, *pref_off = nullptr,
             *pref_idx = nullptr, *pref_w = nullptr, *own_off = nullptr, *own_idx = nullptr, *own_w = nullptr,

@@ -781,6 +781,12 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
             const int64_t* na_row = COLD(A)->na_raw ? COLD(A)->na_raw + crow : nullptr;
             const int64_t* tt_row = COLD(A)->tt_raw ? COLD(A)->tt_raw + crow : nullptr;
             const int64_t* add_row = COLD(A)->static_add ? COLD(A)->static_add + crow : nullptr;
+            // ImageLocality (ABI v7): this scenario's size slot, a row per image-scoring class; folded into the staged rows below
+            const uint8_t* img_row = nullptr;
+            if ((A.flags & kArgImage) != 0u) {
+                const int ir = COLD(A)->img_row_of[p.cls];
+                if (ir >= 0) img_row = COLD(A)->img + ((size_t)COLD(A)->img_slot[A.scen_base + s] * COLD(A)->img_R + ir) * Cn;
+            }
             bool refill = false;
             int64_t* s_rows = nullptr;
             long long rv0 = 0, rv1 = 0, rv2 = 0, rv3 = 0;
@@ -797,7 +803,7 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
                         dst[c] = raw_row[c];
                         dst[Cn + c] = na_row ? na_row[c] : 0;
                         dst[2 * Cn + c] = tt_row ? tt_row[c] : 0;
-                        dst[3 * Cn + c] = add_row ? add_row[c] : 0;
+                        dst[3 * Cn + c] = (add_row ? add_row[c] : 0) + (img_row ? (int64_t)img_row[c] : 0);
                     }
                     rows_cls = p.cls;
                     __syncthreads();
@@ -806,7 +812,8 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
                 raw_row = s_rows;
                 if (na_row) na_row = s_rows + Cn;
                 if (tt_row) tt_row = s_rows + 2 * Cn;
-                if (add_row) add_row = s_rows + 3 * Cn;
+                if (add_row || img_row) add_row = s_rows + 3 * Cn;
+                img_row = nullptr;
             }
             if (class_mode) {
                 // Refills alternate between two LDS copies: a lane still reading the previous class's rows (e.g. in a
@@ -820,13 +827,14 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
                     rv0 = raw_row[tid];
                     rv1 = na_row ? na_row[tid] : 0;
                     rv2 = tt_row ? tt_row[tid] : 0;
-                    rv3 = add_row ? add_row[tid] : 0;
+                    rv3 = (add_row ? add_row[tid] : 0) + (img_row ? (long long)img_row[tid] : 0);
                 }
                 rows_cls = p.cls;
                 raw_row = s_rows;
                 if (na_row) na_row = s_rows + Cn;
                 if (tt_row) tt_row = s_rows + 2 * Cn;
-                if (add_row) add_row = s_rows + 3 * Cn;
+                if (add_row || img_row) add_row = s_rows + 3 * Cn;
+                img_row = nullptr;
             }
             // ---------------- stage 0: PodTopologySpread.PreFilter minimum per hard constraint -----------
             Hard4 hard_min{0, 0, 0, 0};
@@ -1336,9 +1344,10 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
                     if (na_row && na_max != 0) t += divq(100 * na_row[nc], na_max);
                     if (tt_row) t += tt_max == 0 ? 100 : 100 - divq(100 * tt_row[nc], tt_max);
                     if (add_row) t += add_row[nc];
+                    if (img_row) t += img_row[nc];       // (global-row path only: the LDS rows carry it)
                     return t;
                 };
-                const bool need_term = range != 0 || na_row || tt_row || add_row;
+                const bool need_term = range != 0 || na_row || tt_row || add_row || img_row;
                 // class mode: lane c of every wave evaluates class c once, the nodes fetch it with a wave shuffle
                 int my_term = 0;
                 if (class_mode && need_term && lane < Cn && ((cmask >> lane) & 1ull)) my_term = (int)class_term(lane);
@@ -1676,6 +1685,10 @@ void fill_args(const WideDevice& w, const HostInputs& in, WideArgs& a, WideCold&
     c.static_reason = in.static_reason.empty() ? nullptr : w.static_reason;
     c.na_raw = in.has_na ? w.na_raw : nullptr; c.tt_raw = in.has_tt ? w.tt_raw : nullptr;
     c.static_add = in.has_add ? w.static_add : nullptr;
+    if (in.has_img && in.img_R > 0) {               // (the scenario's table: wide_run / wide_explain)
+        a.flags = (a.flags | kArgImage) & ~kArgKey32;
+        c.img_row_of = w.img_row_of; c.img_R = in.img_R;
+    }
     c.term_key = w.term_key; c.term_dom_off = w.term_dom_off; c.term_set = w.term_set; c.node_sets = w.node_sets;
     c.anti_off = w.anti_off; c.anti_idx = w.anti_idx; c.match_off = w.match_off; c.match_idx = w.match_idx;
     c.manti_off = w.manti_off; c.manti_idx = w.manti_idx; c.mown_off = w.mown_off; c.mown_idx = w.mown_idx;
@@ -1919,6 +1932,7 @@ int wide_stage(WideDevice& w, const HostInputs& in, hipStream_t st, std::string&
     PUT(i_scalar_req, in.i_scalar_req, 1); PUT(i_gpu_used, in.i_gpu_used, N * SIMON_MAX_GPU_DEV);
     PUT(static_mask, in.static_mask, 1); PUT(static_reason, in.static_reason, 1); PUT(simon_raw, in.simon_raw, 1);
     PUT(na_raw, in.na_raw, 1); PUT(tt_raw, in.tt_raw, 1); PUT(static_add, in.static_add, 1);
+    PUT(img, in.img_cls, 1); PUT(img_row_of, in.img_row_of, 1); PUT(img_zero, std::vector<int32_t>(), 1);   // (no host source: put() zero-fills the one element)
     PUT(term_key, in.term_key, 1); PUT(term_dom_off, dom_off, 1); PUT(term_set, term_set, 1); PUT(node_sets, in.node_sets, 1);
     PUT(anti_off, anti_off, 1); PUT(anti_idx, anti_sorted, 1); PUT(match_off, match_off, 1); PUT(match_idx, in.match_idx, 1);
     PUT(manti_off, manti_off, 1); PUT(manti_idx, manti_idx, 1); PUT(mown_off, mown_off, 1); PUT(mown_idx, mown_idx, 1);
@@ -1964,6 +1978,10 @@ int wide_run(WideDevice& w, const HostInputs& in, const WideScenario* d_scen, co
     a.mask_lanes = w.mask_lanes;
     c.node_rank = d_node_rank; c.node_inv = d_node_inv;
     c.gpu_slices = d_gpu_slices;
+    if (a.flags & kArgImage) {
+        if (!w.img_slot_ext || in.img_sizes.empty()) { err = "wide kernel: image scores of the batch are not staged"; return SIMON_ESTATE; }
+        c.img = w.img; c.img_slot = w.img_slot_ext;
+    }
     if (d_node_rank && d_node_inv) a.flags |= kArgRanked;
     a.orders = d_orders;
     a.bc_words = (std::max(max_n, 1) + 3) & ~3;
@@ -2078,6 +2096,10 @@ int wide_explain(WideDevice& w, const HostInputs& in, int n_nodes, const int32_t
     a.mask_lanes = w.mask_lanes;
     c.node_rank = d_rank_row; c.node_inv = d_inv_row;
     if (d_rank_row && d_inv_row) a.flags |= kArgRanked;
+    if (a.flags & kArgImage) {                   // the image scores of THIS n_nodes, whether or not the batch has the size
+        if (!w.img_explain_ext) { err = "wide explain: image scores of the scenario are not staged"; cleanup(); return SIMON_ESTATE; }
+        c.img = w.img_explain_ext; c.img_slot = w.img_zero;
+    }
     a.S = 1; a.scen = (const WideScenario*)d_scen; a.orders = (const int32_t*)d_order;
     a.bc_words = (std::max(n_nodes, 1) + 3) & ~3;
     a.n_sigs = 0;   // failure codes come from the full per-node evaluation

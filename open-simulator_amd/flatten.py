@@ -344,6 +344,42 @@ def image_states(nodes_in_arrival_order: List[dict]) -> Dict[str, Dict[str, Tupl
     return out
 
 
+def normalized_image_names(pod: dict) -> List[str]:
+    """normalizedImageName (imagelocality/image_locality.go:120-125) of every container in pod.Spec.Containers order (init containers
+    take no part in the score)."""
+    out = []
+    for c in pod["spec"].get("containers") or []:
+        name = str(c.get("image") or "")
+        out.append(name if name.rfind(":") > name.rfind("/") else name + ":latest")
+    return out
+
+
+def image_locality_inputs(nodes: List[dict], class_rep: List[dict], wanted, img_states) -> "capi.ImageLocality":
+    """The engine's ImageLocality inputs (ABI v7, capi.ImageLocality) for the pool `nodes` (pool order) and the pod classes: the images
+    some class runs AND some node lists, per node its (image, NumNodes) entries as the arrival order leaves them (image_states), per
+    class one image per container (-1 where no node lists it)."""
+    ids: Dict[str, int] = {}
+    size: List[int] = []
+    node_off, node_image, node_count = [0], [], []
+    for n in nodes:
+        st = img_states[n["metadata"]["name"]]
+        for name in sorted(st):
+            if name not in wanted:
+                continue
+            if name not in ids:
+                ids[name] = len(ids)
+                size.append(st[name][0])
+            node_image.append(ids[name])
+            node_count.append(st[name][1])
+        node_off.append(len(node_image))
+    class_off, class_image = [0], []
+    for p in class_rep:
+        class_image += [ids.get(name, -1) for name in normalized_image_names(p)]
+        class_off.append(len(class_image))
+    return capi.ImageLocality(np.array(size, np.int64), np.array(node_off, np.int32), np.array(node_image, np.int32),
+                              np.array(node_count, np.int32), np.array(class_off, np.int32), np.array(class_image, np.int32)).normalise()
+
+
 def image_locality_score(pod: dict, states: Dict[str, Tuple[int, int]], total_nodes: int) -> int:
     """ImageLocality.Score (imagelocality/image_locality.go:53-113): sum over the containers of
     int64(float64(size) * (float64(NumNodes) / float64(totalNumNodes))), clamped to [23 MB, 1000 MB x containers], scaled to 0..100."""
@@ -352,9 +388,7 @@ def image_locality_score(pod: dict, states: Dict[str, Tuple[int, int]], total_no
     if not conts:
         return 0
     ssum = 0
-    for c in conts:
-        name = str(c.get("image") or "")
-        name = name if name.rfind(":") > name.rfind("/") else name + ":latest"          # normalizedImageName (:120-125)
+    for name in normalized_image_names(pod):
         if name in states:
             sz, cnt = states[name]
             ssum += int(float(sz) * (float(cnt) / float(total_nodes)))
@@ -365,10 +399,13 @@ def image_locality_score(pod: dict, states: Dict[str, Tuple[int, int]], total_no
 
 def flatten(nodes: List[dict], pods: List[dict], services=(), replicasets=(), statefulsets=(),
             gates: Optional[List[int]] = None, storage_classes=(), image_total: Optional[int] = None,
-            node_arrival_order: Optional[List[str]] = None) -> Flat:
+            node_arrival_order: Optional[List[str]] = None, image_batch: bool = False) -> Flat:
     """nodes: the pool in canonical order (cluster nodes, then new-node clones).  pods: the stream in scheduling order;
     a pod with spec.nodeName is bound without filtering (V/eventhandlers.go:223-236).  gates[p] = node index the pod
-    depends on (DaemonSet pods of new nodes, pkg/simulator/core.go:85-95) or -1."""
+    depends on (DaemonSet pods of new nodes, pkg/simulator/core.go:85-95) or -1.
+    image_batch: ImageLocality travels as its inputs (capi.ImageLocality, ABI v7) and the engine scores it per scenario size, for
+    batches of several sizes; static_add then carries NodePreferAvoidPods only.  Without it a node that lists an image the pods run
+    needs image_total (one size) and raises Unsupported otherwise."""
     N, P = len(nodes), len(pods)
     node_names = [n["metadata"]["name"] for n in nodes]
     node_index = {name: j for j, name in enumerate(node_names)}
@@ -456,6 +493,24 @@ def flatten(nodes: List[dict], pods: List[dict], services=(), replicasets=(), st
         if "_class_affinity" in p and (pin[i] < 0 or preset[i] >= 0):
             raise Unsupported(f"DaemonSet pod {p['metadata']['name']}: node {p.get('_daemon_node')} is not in the pool")
 
+    # ---- ImageLocality (imagelocality/image_locality.go:53-113) is a constant 0 as long as no node lists an image a pod runs.
+    # Otherwise a pod's score depends on its container images, which then join the pod-class key (two pods that differ only in their
+    # images are two classes), and on the cluster size (spread = NumNodes / totalNumNodes): with ONE size (image_total = the scenario's
+    # node count, simulate()) it is a static per (class, node) score that joins static_add; a batch of sizes hands the engine its inputs
+    # (image_batch, ABI v7); anything else is left to the Go path.
+    wanted = set()
+    for p in tpods:
+        wanted.update(normalized_image_names(p))
+    img_nodes = [j for j, n in enumerate(nodes)
+                 if any(wanted.intersection(img.get("names") or []) for img in (n.get("status") or {}).get("images") or [])]
+    img_states = None
+    if img_nodes:
+        if image_total is None and not image_batch:
+            raise Unsupported(f"node {node_names[img_nodes[0]]} lists image(s) the pods run: ImageLocality depends on the cluster size")
+        by_name = {n["metadata"]["name"]: n for n in nodes}
+        arrival = [by_name[x] for x in node_arrival_order] if node_arrival_order is not None else nodes
+        img_states = image_states(arrival)
+
     class_ids: Dict[str, int] = {}
     class_rep: List[dict] = []
     rq_of_class: List[Dict[str, Quantity]] = []
@@ -467,7 +522,7 @@ def flatten(nodes: List[dict], pods: List[dict], services=(), replicasets=(), st
         key = json.dumps([md.get("namespace"), md.get("labels") or {}, spec.get("nodeSelector"), spec.get("affinity"),
                           spec.get("tolerations"), spec.get("topologySpreadConstraints"), owner,
                           {k: str(v) for k, v in rq.items()}, spec.get("overhead"), host_ports(p),
-                          pod_local_volumes(p, storage_classes)], sort_keys=True)
+                          pod_local_volumes(p, storage_classes)] + ([normalized_image_names(p)] if img_nodes else []), sort_keys=True)
         if key not in class_ids:
             class_ids[key] = len(class_rep)
             class_rep.append(p)
@@ -483,24 +538,9 @@ def flatten(nodes: List[dict], pods: List[dict], services=(), replicasets=(), st
     prio_t = np.array([int(p["spec"].get("priority") or 0) for p in tpods], np.int32)
     priority = prio_t[tmpl_of] if len(set(prio_t.tolist())) > 1 else None
 
-    # ---- ImageLocality (imagelocality/image_locality.go:53-113) is a constant 0 as long as no node lists an image a pod
-    # runs.  Otherwise its score depends on the cluster size (spread = NumNodes / totalNumNodes): with ONE size
-    # (image_total = the scenario's node count, simulate()) it is a static per (class, node) score that joins static_add;
-    # a batch of different sizes is left to the Go path.
-    wanted = set()
-    for p in class_rep:
-        for c in p["spec"].get("containers") or []:
-            name = str(c.get("image") or "")
-            wanted.add(name if name.rfind(":") > name.rfind("/") else name + ":latest")          # normalizedImageName (:120-125)
-    img_nodes = [j for j, n in enumerate(nodes)
-                 if any(wanted.intersection(img.get("names") or []) for img in (n.get("status") or {}).get("images") or [])]
-    img_states = None
-    if img_nodes:
-        if image_total is None:
-            raise Unsupported(f"node {node_names[img_nodes[0]]} lists image(s) the pods run: ImageLocality depends on the cluster size")
-        by_name = {n["metadata"]["name"]: n for n in nodes}
-        arrival = [by_name[x] for x in node_arrival_order] if node_arrival_order is not None else nodes
-        img_states = image_states(arrival)
+    image_locality = None
+    if img_states is not None and image_batch:
+        image_locality = image_locality_inputs(nodes, class_rep, wanted, img_states)
 
     # ---- static filters per (pod class, node): first failing plugin in registry order --------------------------
     # A class looks at a node only through the label keys its nodeSelector / node affinity name, the node's taints,
@@ -620,7 +660,7 @@ def flatten(nodes: List[dict], pods: List[dict], services=(), replicasets=(), st
         trip = intern_col(zip(na_u.tolist(), tt_u.tolist(), npa_u.tolist()))
         _, part = np.unique(part * (int(trip.max()) + 1) + trip[inv], return_inverse=True)
     img_cols: Dict[int, np.ndarray] = {}            # class -> ImageLocality score per node (only classes that score somewhere)
-    if img_states is not None:
+    if img_states is not None and not image_batch:
         for c, p in enumerate(class_rep):
             col = np.zeros(N, np.int64)
             for j in img_nodes:
@@ -956,7 +996,7 @@ def flatten(nodes: List[dict], pods: List[dict], services=(), replicasets=(), st
         gpu_mem=gpu_mem if gpu_mem.any() else None, pod_gpu_cnt=gpu_cnt if gpu_mem.any() else None,
         gpu_index=gpu_index if gpu_index.any() else None,
         n_pod_classes=Cp, n_node_classes=Cn, static_mask=None if static_ok.all() else static_mask,
-        static_reason=None if static_ok.all() else static_reason, simon_raw=simon_raw, const_score=const, **prob_kw).normalise()
+        static_reason=None if static_ok.all() else static_reason, simon_raw=simon_raw, const_score=const, image_locality=image_locality, **prob_kw).normalise()
     return Flat(problem=prob, node_names=node_names,
                 pod_refs=[(p["metadata"]["namespace"], p["metadata"]["name"]) for p in pods], pods=pods,
                 static_reasons={v: k for k, v in reason_ids.items()}, scalar_names=scalar_names,

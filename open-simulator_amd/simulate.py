@@ -23,6 +23,8 @@ from . import capi, fiterror, flatten as fl, k8s, workloads as wl
 class HipEngine:
     """The product engine: libsimon_hip.so on one device."""
 
+    supports_image_locality = True            # ImageLocality per scenario size on the device (ABI v7): sweep() batches image clusters
+
     def __init__(self, device_id: int = 0):
         self.device_id = device_id
 
@@ -327,9 +329,11 @@ class SweepBatch:
 
 @_gc_paused
 def sweep_batch(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node: Optional[dict], counts: Sequence[int],
-                ranks_ok: bool = True) -> SweepBatch:
+                ranks_ok: bool = True, image_batch: bool = False) -> SweepBatch:
     """cluster + up to max(counts) clones of new_node -> ONE problem and len(counts) scenarios (what `sweep` hands to the engine; also
-    used by bench.py and profiles/e2e_sweep.py to time the engine on Kubernetes-object workloads)."""
+    used by bench.py and profiles/e2e_sweep.py to time the engine on Kubernetes-object workloads).  image_batch: nodes that list the
+    pods' images hand the engine ImageLocality's inputs (flatten's image_batch; arrival order = pool order, cluster nodes then clones)
+    instead of raising Unsupported."""
     counts = list(counts)
     base = list(cluster.get("Node", []))
     if max(counts) > 0 and new_node is None:
@@ -350,7 +354,7 @@ def sweep_batch(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new
             node_ranks[s, order] = np.arange(len(order), dtype=np.int32)
     pods, gates = build_stream(cluster, apps, pool, len(base))
     flat = fl.flatten(pool, pods, cluster.get("Service", []), cluster.get("ReplicaSet", []), cluster.get("StatefulSet", []), gates,
-                      storage_classes=_storage_classes(cluster, apps))
+                      storage_classes=_storage_classes(cluster, apps), image_batch=image_batch)
     scen = np.array([[len(base) + k, 0] for k in counts], np.int32)
     orders = np.arange(len(pods), dtype=np.int32)[None, :]
     return SweepBatch(flat, scen, orders, node_ranks, pool, base)
@@ -369,12 +373,13 @@ def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node:
     if max_mem > 100 or max_mem < 0:
         max_mem = 100
     try:
-        batch = sweep_batch(cluster, apps, new_node, counts, ranks_ok=getattr(engine, "supports_node_ranks", True))
+        batch = sweep_batch(cluster, apps, new_node, counts, ranks_ok=getattr(engine, "supports_node_ranks", True),
+                            image_batch=getattr(engine, "supports_image_locality", False))
     except fl.Unsupported as e:
         if "ImageLocality" not in str(e) and "node ranks" not in str(e):
             raise
-        # ImageLocality scores depend on the cluster size: every size is its own problem with its own static scores (and an engine
-        # without per-scenario node ranks runs a pool of several zones size by size)
+        # ImageLocality scores depend on the cluster size: an engine without the per-size image scores runs every size as its own
+        # problem with its own static scores (and an engine without per-scenario node ranks runs a pool of several zones size by size)
         return _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg)
     flat, scen, orders, node_ranks, pool, base = batch.flat, batch.scen, batch.orders, batch.node_ranks, batch.pool, batch.base
     want_gpu = flat.problem.gpu_mem is not None
