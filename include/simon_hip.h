@@ -392,6 +392,22 @@ int simon_set_image_locality(simon_ctx* ctx, const simon_image_locality* img);
  * maximum in canonical order) reads it.  Call after simon_load_scenarios; NULL returns to pool order. */
 int simon_set_node_ranks(simon_ctx* ctx, const int32_t* rank /* [S][N] */);
 
+/* Pool segments: batches over mixes of several new-node types (pkg/apply/apply.go:155-166 clones ONE template; a mix (c_1 .. c_T) is
+ * Simulate(cluster + NewFakeNodes(type_1, c_1) + ... + NewFakeNodes(type_T, c_T))).  Pool = fixed nodes [0, seg_start[0]) that every
+ * scenario holds, then n_seg segments, segment g = [seg_start[g], seg_start[g+1]), seg_start[n_seg] = N.  Scenario s holds the fixed
+ * nodes and the first count[s][g] nodes of every segment g; scen[s].n_nodes must equal seg_start[0] + sum_g count[s][g].  Its canonical
+ * order is pool order restricted to its nodes; simon_set_node_ranks called afterwards supplies rank rows over the scenario's own nodes
+ * (entries of the nodes it lacks are ignored).  A gated pod exists in scenario s iff s holds gate_node; a pinned pod whose node s lacks
+ * is unschedulable there.  simon_min_plan* keep their key and use each scenario's own allocatable / VG totals.
+ * Call after simon_load_scenarios (which clears it); n_seg = 0 returns to prefix scenarios.  SIMON_EINVAL: n_seg < 0, missing
+ * arrays, starts not ascending, a count beyond its segment, an n_nodes mismatch, n_seg > SIMON_MAX_SEGMENTS, a segment node with pods bound before the
+ * stream (init_*) or the target of a preset pod.  SIMON_ESTATE: ImageLocality in effect (simon_set_image_locality).  A segmented batch
+ * runs on the score-table kernel only: simon_run_loaded refuses (SIMON_ESTATE) a problem that needs the all-feature kernel, and
+ * simon_explain / simon_explain_loaded refuse while one is loaded -- replay the scenario's own problem instead.  A call that fails
+ * leaves the batch a prefix batch. */
+#define SIMON_MAX_SEGMENTS 8
+int simon_set_scenario_segments(simon_ctx* ctx, int32_t n_seg, const int32_t* seg_start, const int32_t* count /* [S][n_seg] */);
+
 /* ABI v6.  Which extended resources the pod's computed request holds an ENTRY for, whatever the quantity: bit k of entries[p] =
  * resource k of simon_nodes_soa.scalar_alloc, bit 7 = an entry for a resource no node of the pool advertises.
  * computePodResourceRequest builds the request with Resource.Add / SetMaxResource (V/framework/plugins/noderesources/fit.go:148-165,

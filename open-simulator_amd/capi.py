@@ -22,6 +22,9 @@ MAX_SCALAR = 4
 
 UNSCHEDULED = -1
 GATED = -2
+ESTATE = -1      # SIMON_ESTATE (SimonError.code)
+EINVAL = -22     # SIMON_EINVAL
+MAX_SEGMENTS = 8 # SIMON_MAX_SEGMENTS
 
 FAIL_STATIC = 0x8000
 REASON_NODE_AFFINITY = 3
@@ -534,6 +537,7 @@ EXPORTS = [
     "simon_set_scalar_entries", "simon_set_pod_priorities", "simon_fetch_preempt_risk",
     "simon_group_set_scalar_entries", "simon_group_set_pod_priorities", "simon_group_fetch_preempt_risk",
     "simon_set_image_locality", "simon_group_set_image_locality",
+    "simon_set_scenario_segments",
     "simon_group_create", "simon_group_destroy", "simon_group_last_error", "simon_group_size", "simon_group_member",
     "simon_group_load_nodes", "simon_group_load_pods", "simon_group_load_class_tables", "simon_group_load_scenarios",
     "simon_group_run_loaded", "simon_group_fetch_results", "simon_group_run_batch", "simon_group_fetch_placement", "simon_group_fetch_gpu_slices",
@@ -571,6 +575,7 @@ def load_library(path: Optional[str] = None):
     lib.simon_fetch_gpu_slices.argtypes = [vp, C.c_int32, _pu64]
     lib.simon_run_batch.argtypes = [vp, C.POINTER(Scenario), C.c_int32, _p32, C.c_int32, C.POINTER(BatchOut)]
     lib.simon_set_node_ranks.argtypes = [vp, _p32]
+    lib.simon_set_scenario_segments.argtypes = [vp, C.c_int32, _p32, _p32]
     lib.simon_min_plan.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(Plan)]
     lib.simon_min_plan_vg.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Plan), C.POINTER(C.c_int32)]
     lib.simon_explain.argtypes = [vp, Scenario, _p32, _p32, _pu16, C.c_int32]
@@ -660,7 +665,9 @@ class Context:
     def _check(self, rc: int, what: str):
         if rc < 0:
             msg = self.lib.simon_last_error(self.h)
-            raise SimonError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+            err = SimonError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+            err.code = rc
+            raise err
         return rc
 
     def load_problem(self, prob: Problem):
@@ -733,6 +740,18 @@ class Context:
             return
         r = np.ascontiguousarray(ranks, dtype=np.int32)
         self._check(self.lib.simon_set_node_ranks(self.h, _ptr(r, C.c_int32)), "simon_set_node_ranks")
+
+    def set_scenario_segments(self, seg_start, counts) -> None:
+        """Pool segments (node-type mixes): fixed nodes [0, seg_start[0]), segment g = [seg_start[g], seg_start[g+1]); scenario s holds
+        the fixed nodes and the first counts[s][g] nodes of every segment (include/simon_hip.h: simon_set_scenario_segments).
+        seg_start None: back to prefix scenarios."""
+        if seg_start is None or len(seg_start) == 0:
+            self._check(self.lib.simon_set_scenario_segments(self.h, 0, None, None), "simon_set_scenario_segments")
+            return
+        st = np.ascontiguousarray(seg_start, dtype=np.int32)
+        cn = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1, len(st))
+        self._check(self.lib.simon_set_scenario_segments(self.h, len(st), _ptr(st, C.c_int32), _ptr(cn, C.c_int32)),
+                    "simon_set_scenario_segments")
 
     def min_plan(self, max_cpu_pct: int = 100, max_mem_pct: int = 100) -> Plan:
         plan = Plan()

@@ -173,6 +173,16 @@ struct simon_ctx : simon::HostInputs {
     DevBuf<int64_t> d_prefix_cpu, d_prefix_mem, d_prefix_vg;
     DevBuf<int32_t> d_node_rank, d_node_inv;      // [S][N] per-scenario nodeTree ranks (simon_set_node_ranks)
     bool has_ranks = false;
+    // segmented batch (simon_set_scenario_segments): fixed nodes [0, seg_start[0]) + the first seg_count[s][g] nodes of every segment g.
+    // Implies per-scenario ranks (absent nodes rank N) and per-scenario class lists; h_scls [S][Cn_t] = nodes of class d scenario s holds;
+    // seg_tot [3][S] = its allocatable cpu / memory and VG capacity (satisfyResourceSetting over its own nodes)
+    int seg_n = 0;
+    std::vector<int32_t> seg_start, seg_count, seg_of, h_scls;
+    std::vector<int64_t> seg_tot;
+    DevBuf<int32_t> d_scls;
+    DevBuf<int64_t> d_seg_tot;
+    bool orders_perm = false;                     // every loaded order is a permutation of [0, P) (the score-table kernel's placement gather)
+    std::vector<int64_t> prefix_cpu, prefix_mem;   // [N+1] allocatable of the first n nodes
     std::vector<int64_t> prefix_vg;   // [N+1] Open-Local VG capacity of the first n nodes (0 without local storage)
     WideDevice wide;
     // scenarios
@@ -1439,6 +1449,7 @@ int stage(simon_ctx* c) {
             for (int q = 0; q < c->l_vg_cnt[j]; ++q) cap += c->l_vg_cap[(size_t)j * SIMON_MAX_VG + q];
         c->prefix_vg[j + 1] = c->prefix_vg[j] + cap;
     }
+    c->prefix_cpu = pc; c->prefix_mem = pm;
     HIP_TRY(c, c->d_prefix_cpu.upload(pc, c->stream));
     HIP_TRY(c, c->d_prefix_mem.upload(pm, c->stream));
     HIP_TRY(c, c->d_prefix_vg.upload(c->prefix_vg, c->stream));
@@ -1497,17 +1508,19 @@ __global__ void plan_kernel(const ScenarioDesc* __restrict__ scen, int S, const 
                             const int64_t* __restrict__ used_cpu, const int64_t* __restrict__ used_mem,
                             const int64_t* __restrict__ prefix_cpu, const int64_t* __restrict__ prefix_mem, int max_cpu,
                             int max_mem, const int64_t* __restrict__ used_vg, const int64_t* __restrict__ prefix_vg, int max_vg,
-                            unsigned long long* __restrict__ out) {
+                            const int64_t* __restrict__ seg_tot, unsigned long long* __restrict__ out) {
     unsigned long long best = ~0ull;
     for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < S; s += gridDim.x * blockDim.x) {
         if (unsched[s] != 0) continue;
         const int n = scen[s].n_nodes;
         // int(float64(used.MilliValue()) / float64(alloc.MilliValue()) * 100), apply.go:759-760
-        const int cpu = (int)((double)used_cpu[s] / (double)prefix_cpu[n] * 100.0);
-        const int mem = (int)((double)(used_mem[s] * 1000) / (double)(prefix_mem[n] * 1000) * 100.0);
+        // segmented batch (seg_tot = [3][S]): the totals of the scenario's own nodes
+        const int64_t ac = seg_tot ? seg_tot[s] : prefix_cpu[n], am = seg_tot ? seg_tot[S + s] : prefix_mem[n], av = seg_tot ? seg_tot[2 * S + s] : prefix_vg[n];
+        const int cpu = (int)((double)used_cpu[s] / (double)ac * 100.0);
+        const int mem = (int)((double)(used_mem[s] * 1000) / (double)(am * 1000) * 100.0);
         if (cpu > max_cpu || mem > max_mem) continue;
-        if (used_vg && prefix_vg[n] != 0 &&                      // MaxVG, apply.go:767-771
-            (int)((double)used_vg[s] / (double)prefix_vg[n] * 100.0) > max_vg) continue;
+        if (used_vg && av != 0 &&                                // MaxVG, apply.go:767-771
+            (int)((double)used_vg[s] / (double)av * 100.0) > max_vg) continue;
         const unsigned long long key = ((unsigned long long)(unsigned)n << 32) | (unsigned)s;
         best = key < best ? key : best;
     }
@@ -1878,8 +1891,71 @@ int simon_load_class_tables(simon_ctx* c, const simon_class_tables* tb) {
     return SIMON_OK;
 }
 
+// padded sizes, summary layout and workspace slices of the loaded batch for the score-table kernel (simon_load_scenarios; again
+// after simon_set_scenario_segments, whose scenarios have their own class counts)
+static int table_layout(simon_ctx* c) {
+    const int S = (int)c->scen.size(), max_n = c->max_n;
+    const std::vector<int32_t>& perm = c->h_perm;
+    {
+        // padded class-major size of every scenario; workspace slice of every workgroup (launch order = perm)
+        const int Ct = c->Cn_t;
+        std::vector<int> ni16(S), ni64(S);
+        int top16 = 16, top64 = 64;
+        for (int s = 0; s < S; ++s) {
+            int a = 0, b = 0;
+            for (int d = 0; d < Ct; ++d) {
+                const int cnt = c->seg_n ? c->h_scls[(size_t)s * Ct + d] : c->h_clsprefix[(size_t)c->scen[s].n_nodes * Ct + d];   // (segmented: the scenario's own count)
+                a += (cnt + 15) & ~15; b += (cnt + 63) & ~63;
+            }
+            ni16[s] = std::max(a, 16); ni64[s] = std::max(b, 64);
+            top16 = std::max(top16, ni16[s]); top64 = std::max(top64, ni64[s]);
+        }
+        {
+            // One-level or two-level summary (simon_table.hip: tcarve)?  The LDS of a workgroup decides how many scenario waves a CU
+            // holds (allocation granularity 1 280 B, 160 KB, at most 32 single-wave workgroups: profiles/micro/occupancy_probe.hip),
+            // and a batch that offers more runs in rounds.  The two-level form needs a quarter of the LDS but costs an 8-byte load and
+            // ~15 VALU per signature and cycle more (+19 % per wave, measured).  Cost model fitted to profiles/README.md (config 3:
+            // 256 scenarios 7.7 ms, 4 096 14.0 ms, 8 192 27.5 ms one-level / 32.3 ms two-level; 100 signatures 39.5 / 32.1 ms):
+            // a round of w waves per CU takes 1 + 0.055 (w - 1) units up to 16 waves and 0.11 per wave beyond.
+            auto fit = [](size_t lds) { const size_t g = (lds + 1279) / 1280 * 1280; return g ? (int)std::min<size_t>(32, kTableLdsPerCU / g) : 32; };
+            const int nzk = c->spread ? ((int)c->sp_zkeys.size() | ((c->ipa_fold || c->hard_fold) ? 0x100 : 0) | (Ct > kTableMaxClasses ? 0x400 : 0)) : -1;   // (| 0x100: the second score table of spread_select; | 0x400: CN2's larger one)
+            const size_t lds16 = table_lds_bytes(c->n_sigs, top16, Ct, false, false) + c->lds_pad, lds64 = table_lds_bytes(c->n_sigs, top64, Ct, true, c->rest, nzk) + c->lds_pad;
+            const bool fine_ok = max_n <= kTableMaxNodes && top16 <= kTableMaxPadded && lds16 <= 64 * 1024, coarse_ok = top64 <= kTableMaxPaddedCoarse && lds64 <= kTableLdsMaxWG && Ct <= 128;   // (129 .. 256 classes: one-level only, simon_table_cls4.hip)
+            const int per_cu = (S + c->n_cus - 1) / std::max(c->n_cus, 1);
+            auto cost = [&](int fits, double factor) {
+                auto round_cost = [](int w) { return 1.0 + 0.055 * (std::min(w, 16) - 1) + 0.11 * std::max(w - 16, 0); };
+                double t = 0;
+                for (int left = per_cu; left > 0; left -= fits) t += round_cost(std::min(left, fits));
+                return t * factor;
+            };
+            bool coarse = coarse_ok && (!fine_ok || cost(std::max(fit(lds64), 1), 1.2) < 0.95 * cost(std::max(fit(lds16), 1), 1.0));
+            if (c->force_coarse >= 0) coarse = c->force_coarse ? coarse_ok : !fine_ok && coarse_ok;
+            if (c->rest) coarse = coarse_ok;                        // the REST path is built on the two-level layout
+            if (c->n_sigs > 128) coarse = coarse_ok;                // ... and so are the signature groups beyond 128 (simon_table.hip: MANY)
+            if (c->spread) coarse = coarse_ok;                      // ... and the SPREAD path (generation 7)
+            if (c->fold || c->gfold) coarse = coarse_ok;            // ... and the folded exclusions / GPU share (carried by the two-level instantiations)
+            c->table_coarse = coarse;
+            for (int s = 0; s < S; ++s) c->scen_ni[s] = coarse ? ni64[s] : ni16[s];
+            const int ni_top = coarse ? top64 : top16;
+            c->table_ni_top = ni_top;
+            std::vector<unsigned long long> ws_off(S);
+            size_t off = 0;
+            for (int b = 0; b < S; ++b) { ws_off[b] = off; off += table_ws_bytes(c->n_sigs, c->scen_ni[perm[b]], c->nzeq, coarse, Ct, c->rest ? c->rest_M : 0, c->rest ? (int)c->zone_keys.size() : 0, c->spread ? c->sp_TH : 0, c->spread ? c->sp_TZ : 0)
+                                                                    + (c->gfold ? (((size_t)c->scen_ni[perm[b]] * 40 + 127) & ~(size_t)127) : 0); }   // + GPU fold: devices by position
+            c->ws_total = off;
+            HIP_TRY(c, c->d_ws_off.upload(ws_off, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            // more than 128 signatures: two-level layout without the REST path (simon_table.hip: MANY; since round 4 also under generation 7's
+            // walks); else generation 2 / all-feature kernel
+            c->table_perm_ok = (!c->rest || coarse) && (c->n_sigs <= 128 || coarse) && (!c->spread || coarse) && (!c->fold || coarse) && (!c->gfold || coarse);
+        }
+    }
+    return SIMON_OK;
+}
+
 int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, const int32_t* orders, int32_t n_orders) {
     if (!c || !scen || S <= 0 || !orders || n_orders <= 0) return c ? fail(c, SIMON_EINVAL, "load_scenarios: bad arguments") : SIMON_EINVAL;
+    c->seg_n = 0;                                        // (segments belong to the batch they were set for)
     if (c->has_img) {                    // ImageLocality: one slot per distinct cluster size; another set of sizes re-stages the tables
         std::vector<int32_t> sizes(S);
         for (int s = 0; s < S; ++s) sizes[s] = scen[s].n_nodes;
@@ -1930,6 +2006,7 @@ int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, co
     c->wide.img_slot_ext = c->img_R > 0 ? c->d_img_slot.p : nullptr;
     c->h_perm = perm;
     c->scen_ni.assign(S, 0);
+    c->orders_perm = false;
     c->h_orders.assign(orders, orders + (size_t)n_orders * P);
     c->table_perm_ok = false;
     if (c->variant == SIMON_KERNEL_NARROW && c->table_ok) {
@@ -1943,58 +2020,12 @@ int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, co
                 if (slot >= 0) { is_perm = false; break; }
                 slot = i;
             }
-        // padded class-major size of every scenario; workspace slice of every workgroup (launch order = perm)
-        const int Ct = c->Cn_t;
-        std::vector<int> ni16(S), ni64(S);
-        int top16 = 16, top64 = 64;
-        for (int s = 0; s < S; ++s) {
-            int a = 0, b = 0;
-            for (int d = 0; d < Ct; ++d) {
-                const int cnt = c->h_clsprefix[(size_t)scen[s].n_nodes * Ct + d];
-                a += (cnt + 15) & ~15; b += (cnt + 63) & ~63;
-            }
-            ni16[s] = std::max(a, 16); ni64[s] = std::max(b, 64);
-            top16 = std::max(top16, ni16[s]); top64 = std::max(top64, ni64[s]);
-        }
+        c->orders_perm = is_perm;
+        c->S = S; c->max_n = max_n;
         if (is_perm) {
-            // One-level or two-level summary (simon_table.hip: tcarve)?  The LDS of a workgroup decides how many scenario waves a CU
-            // holds (allocation granularity 1 280 B, 160 KB, at most 32 single-wave workgroups: profiles/micro/occupancy_probe.hip),
-            // and a batch that offers more runs in rounds.  The two-level form needs a quarter of the LDS but costs an 8-byte load and
-            // ~15 VALU per signature and cycle more (+19 % per wave, measured).  Cost model fitted to profiles/README.md (config 3:
-            // 256 scenarios 7.7 ms, 4 096 14.0 ms, 8 192 27.5 ms one-level / 32.3 ms two-level; 100 signatures 39.5 / 32.1 ms):
-            // a round of w waves per CU takes 1 + 0.055 (w - 1) units up to 16 waves and 0.11 per wave beyond.
-            auto fit = [](size_t lds) { const size_t g = (lds + 1279) / 1280 * 1280; return g ? (int)std::min<size_t>(32, kTableLdsPerCU / g) : 32; };
-            const int nzk = c->spread ? ((int)c->sp_zkeys.size() | ((c->ipa_fold || c->hard_fold) ? 0x100 : 0) | (Ct > kTableMaxClasses ? 0x400 : 0)) : -1;   // (| 0x100: the second score table of spread_select; | 0x400: CN2's larger one)
-            const size_t lds16 = table_lds_bytes(c->n_sigs, top16, Ct, false, false) + c->lds_pad, lds64 = table_lds_bytes(c->n_sigs, top64, Ct, true, c->rest, nzk) + c->lds_pad;
-            const bool fine_ok = max_n <= kTableMaxNodes && top16 <= kTableMaxPadded && lds16 <= 64 * 1024, coarse_ok = top64 <= kTableMaxPaddedCoarse && lds64 <= kTableLdsMaxWG && Ct <= 128;   // (129 .. 256 classes: one-level only, simon_table_cls4.hip)
-            const int per_cu = (S + c->n_cus - 1) / std::max(c->n_cus, 1);
-            auto cost = [&](int fits, double factor) {
-                auto round_cost = [](int w) { return 1.0 + 0.055 * (std::min(w, 16) - 1) + 0.11 * std::max(w - 16, 0); };
-                double t = 0;
-                for (int left = per_cu; left > 0; left -= fits) t += round_cost(std::min(left, fits));
-                return t * factor;
-            };
-            bool coarse = coarse_ok && (!fine_ok || cost(std::max(fit(lds64), 1), 1.2) < 0.95 * cost(std::max(fit(lds16), 1), 1.0));
-            if (c->force_coarse >= 0) coarse = c->force_coarse ? coarse_ok : !fine_ok && coarse_ok;
-            if (c->rest) coarse = coarse_ok;                        // the REST path is built on the two-level layout
-            if (c->n_sigs > 128) coarse = coarse_ok;                // ... and so are the signature groups beyond 128 (simon_table.hip: MANY)
-            if (c->spread) coarse = coarse_ok;                      // ... and the SPREAD path (generation 7)
-            if (c->fold || c->gfold) coarse = coarse_ok;            // ... and the folded exclusions / GPU share (carried by the two-level instantiations)
-            c->table_coarse = coarse;
-            for (int s = 0; s < S; ++s) c->scen_ni[s] = coarse ? ni64[s] : ni16[s];
-            const int ni_top = coarse ? top64 : top16;
-            c->table_ni_top = ni_top;
-            std::vector<unsigned long long> ws_off(S);
-            size_t off = 0;
-            for (int b = 0; b < S; ++b) { ws_off[b] = off; off += table_ws_bytes(c->n_sigs, c->scen_ni[perm[b]], c->nzeq, coarse, Ct, c->rest ? c->rest_M : 0, c->rest ? (int)c->zone_keys.size() : 0, c->spread ? c->sp_TH : 0, c->spread ? c->sp_TZ : 0)
-                                                                    + (c->gfold ? (((size_t)c->scen_ni[perm[b]] * 40 + 127) & ~(size_t)127) : 0); }   // + GPU fold: devices by position
-            c->ws_total = off;
-            HIP_TRY(c, c->d_ws_off.upload(ws_off, c->stream));
             HIP_TRY(c, c->d_inv_orders.upload(inv, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            // more than 128 signatures: two-level layout without the REST path (simon_table.hip: MANY; since round 4 also under generation 7's
-            // walks); else generation 2 / all-feature kernel
-            c->table_perm_ok = (!c->rest || coarse) && (c->n_sigs <= 128 || coarse) && (!c->spread || coarse) && (!c->fold || coarse) && (!c->gfold || coarse);
+            rc = table_layout(c);
+            if (rc) return rc;
         }
     }
     HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
@@ -2008,28 +2039,40 @@ int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, co
     return SIMON_OK;
 }
 
-int simon_set_node_ranks(simon_ctx* c, const int32_t* rank) {
-    if (!c) return SIMON_EINVAL;
-    if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "set_node_ranks: load scenarios first");
-    if (!rank) { c->has_ranks = false; return SIMON_OK; }
+// is pool node j part of loaded scenario s?  Prefix batches: j < n_nodes; segmented ones: a fixed node or within its segment's count
+static inline bool node_in(const simon_ctx* c, size_t s, int j) {
+    if (!c->seg_n) return j < c->scen[s].n_nodes;
+    const int g = c->seg_of[j];
+    return g < 0 || j - c->seg_start[g] < c->seg_count[s * c->seg_n + g];
+}
+
+// rank rows of the loaded batch: the caller's (validated over each scenario's own nodes) or, rank == NULL on a segmented batch, pool
+// order restricted to the scenario.  Nodes outside a scenario get rank N (the score-table kernel tests presence by it).
+static int load_ranks(simon_ctx* c, const int32_t* rank) {
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t S = c->S, N = c->N;
     std::vector<int32_t> inv(S * N, 0);
+    std::vector<int32_t> rk = c->seg_n ? std::vector<int32_t>(S * N, (int32_t)N) : std::vector<int32_t>(rank, rank + S * N);
+    std::vector<char> seen;
     for (size_t s = 0; s < S; ++s) {
         const int n = c->scen[s].n_nodes;
-        std::vector<char> seen(n, 0);
-        for (int j = 0; j < n; ++j) {
-            const int r = rank[s * N + j];
-            if (r < 0 || r >= n || seen[r]) return fail(c, SIMON_EINVAL, "set_node_ranks: scenario %d: not a permutation of 0..%d", (int)s, n - 1);
+        seen.assign(n, 0);
+        int next = 0;
+        const int hi = c->seg_n ? (int)N : n;
+        for (int j = 0; j < hi; ++j) {
+            if (c->seg_n && !node_in(c, s, j)) continue;
+            const int r = rank ? rank[s * N + j] : next++;
+            if (r < 0 || r >= n || seen[r]) return fail(c, SIMON_EINVAL, "set_node_ranks: scenario %d: not a permutation of 0..%d over its nodes", (int)s, n - 1);
             seen[r] = 1;
             inv[s * N + r] = j;
+            if (c->seg_n) rk[s * N + j] = r;
         }
     }
-    std::vector<int32_t> rk(rank, rank + S * N);
     HIP_TRY(c, c->d_node_rank.upload(rk, c->stream));
     HIP_TRY(c, c->d_node_inv.upload(inv, c->stream));
     // the score-table kernel's view of a scenario's own node order: per-class node lists in rank order (class segments at the
-    // pool's class offsets; a scenario fills the first clsprefix[n][d] entries of segment d) and a node's index inside its class
+    // pool's class offsets; a scenario fills the first clsprefix[n][d] entries of segment d -- segmented: h_scls[s][d]) and a node's
+    // index inside its class
     c->table_ranks_ok = false;
     if (c->variant == SIMON_KERNEL_NARROW && c->table_ok && c->table_perm_ok) {
         const int Ct = c->Cn_t;
@@ -2051,6 +2094,98 @@ int simon_set_node_ranks(simon_ctx* c, const int32_t* rank) {
     c->has_ranks = true;
     c->have_results = false;
     return SIMON_OK;
+}
+
+int simon_set_node_ranks(simon_ctx* c, const int32_t* rank) {
+    if (!c) return SIMON_EINVAL;
+    if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "set_node_ranks: load scenarios first");
+    if (!rank) {
+        if (c->seg_n) return load_ranks(c, nullptr);          // a segmented batch keeps its own rows: pool order over its nodes
+        c->has_ranks = false; return SIMON_OK;
+    }
+    return load_ranks(c, rank);
+}
+
+// a failed simon_set_scenario_segments leaves the batch as a prefix batch: its own layout again, no ranks
+static int seg_abandon(simon_ctx* c, int rc) {
+    c->seg_n = 0;
+    c->has_ranks = false; c->table_ranks_ok = false; c->have_results = false;
+    if (c->variant == SIMON_KERNEL_NARROW && c->table_ok && c->orders_perm) (void)table_layout(c);
+    return rc;
+}
+
+int simon_set_scenario_segments(simon_ctx* c, int32_t n_seg, const int32_t* seg_start, const int32_t* count) {
+    if (!c) return SIMON_EINVAL;
+    if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "set_scenario_segments: load scenarios first");
+    if (c->has_img) return fail(c, SIMON_ESTATE, "set_scenario_segments: ImageLocality is in effect (its image counts depend on the node set)");
+    const int S = c->S, N = c->N;
+    if (n_seg < 0 || n_seg > SIMON_MAX_SEGMENTS) return fail(c, SIMON_EINVAL, "set_scenario_segments: n_seg %d outside [0,%d]", n_seg, SIMON_MAX_SEGMENTS);
+    if (n_seg > 0 && (!seg_start || !count)) return fail(c, SIMON_EINVAL, "set_scenario_segments: %d segments without starts / counts", n_seg);
+    if (n_seg == 0) {                                        // back to prefix scenarios
+        if (!c->seg_n) return SIMON_OK;
+        c->seg_n = 0;
+        c->has_ranks = false; c->table_ranks_ok = false; c->have_results = false;
+        return (c->variant == SIMON_KERNEL_NARROW && c->table_ok && c->orders_perm) ? table_layout(c) : SIMON_OK;
+    }
+    for (int g = 0; g < n_seg; ++g) {
+        const int end = g + 1 < n_seg ? seg_start[g + 1] : N;
+        if (seg_start[g] < 0 || seg_start[g] > end || end > N) return fail(c, SIMON_EINVAL, "set_scenario_segments: segment %d [%d,%d) is not ascending inside [0,%d]", g, seg_start[g], end, N);
+    }
+    const int fixed = seg_start[0];
+    for (int s = 0; s < S; ++s) {
+        long long tot = fixed;
+        for (int g = 0; g < n_seg; ++g) {
+            const int cnt = count[(size_t)s * n_seg + g], len = (g + 1 < n_seg ? seg_start[g + 1] : N) - seg_start[g];
+            if (cnt < 0 || cnt > len) return fail(c, SIMON_EINVAL, "set_scenario_segments: scenario %d: count %d of segment %d outside [0,%d]", s, cnt, g, len);
+            tot += cnt;
+        }
+        if (tot != c->scen[s].n_nodes) return fail(c, SIMON_EINVAL, "set_scenario_segments: scenario %d: n_nodes %d, but its fixed nodes and counts make %lld", s, c->scen[s].n_nodes, tot);
+    }
+    // a segment node starts empty: pods bound before the stream or by Spec.NodeName would need it in every scenario
+    auto nz = [](const auto& v, size_t i) { return i < v.size() && v[i] != 0; };
+    for (int j = fixed; j < N; ++j) {
+        bool busy = nz(c->i_npods, j) || nz(c->i_req_cpu, j) || nz(c->i_req_mem, j) || nz(c->i_req_eph, j) || nz(c->i_nz_cpu, j) || nz(c->i_nz_mem, j) || nz(c->l_dev_alloc, j);
+        for (int k = 0; k < SIMON_MAX_GPU_DEV; ++k) busy = busy || nz(c->i_gpu_used, (size_t)j * SIMON_MAX_GPU_DEV + k);
+        for (int k = 0; k < SIMON_MAX_VG; ++k) busy = busy || nz(c->l_vg_req, (size_t)j * SIMON_MAX_VG + k);
+        for (size_t k = 0; k < c->i_scalar_req.size() / std::max(N, 1); ++k) busy = busy || nz(c->i_scalar_req, k * N + j);
+        if (busy) return fail(c, SIMON_EINVAL, "set_scenario_segments: segment node %d carries pods bound before the stream", j);
+    }
+    for (int p = 0; p < c->P; ++p)
+        if (c->p_preset[p] >= fixed) return fail(c, SIMON_EINVAL, "set_scenario_segments: pod %d is preset to segment node %d", p, c->p_preset[p]);
+    c->seg_n = n_seg;
+    c->seg_start.assign(seg_start, seg_start + n_seg);
+    c->seg_count.assign(count, count + (size_t)S * n_seg);
+    c->seg_of.assign(N, -1);
+    for (int g = 0; g < n_seg; ++g)
+        for (int j = seg_start[g]; j < (g + 1 < n_seg ? seg_start[g + 1] : N); ++j) c->seg_of[j] = g;
+    // satisfyResourceSetting's denominators over each scenario's own nodes: prefix differences per segment
+    const std::vector<int64_t>* pf[3] = {&c->prefix_cpu, &c->prefix_mem, &c->prefix_vg};
+    c->seg_tot.assign((size_t)3 * S, 0);
+    for (int q = 0; q < 3; ++q) {
+        const std::vector<int64_t>& v = *pf[q];
+        if (v.size() < (size_t)N + 1) continue;
+        for (int s = 0; s < S; ++s) {
+            int64_t t = v[fixed];
+            for (int g = 0; g < n_seg; ++g) t += v[seg_start[g] + c->seg_count[(size_t)s * n_seg + g]] - v[seg_start[g]];
+            c->seg_tot[(size_t)q * S + s] = t;
+        }
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, c->d_seg_tot.upload(c->seg_tot, c->stream));
+    if (c->variant == SIMON_KERNEL_NARROW && c->table_ok) {    // per-class counts of every scenario: the score-table kernel's prologue and layout
+        const int Ct = c->Cn_t;
+        c->h_scls.assign((size_t)S * Ct, 0);
+        for (int s = 0; s < S; ++s)
+            for (int j = 0; j < N; ++j)
+                if (node_in(c, s, j)) ++c->h_scls[(size_t)s * Ct + c->h_ncls_t[j]];
+        HIP_TRY(c, c->d_scls.upload(c->h_scls, c->stream));
+        if (c->orders_perm) {
+            const int rc = table_layout(c);
+            if (rc) return seg_abandon(c, rc);
+        }
+    }
+    const int rc = load_ranks(c, nullptr);
+    return rc ? seg_abandon(c, rc) : SIMON_OK;
 }
 
 int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
@@ -2123,9 +2258,9 @@ int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
                                ni_top <= (c->table_coarse ? kTableMaxPaddedCoarse : kTableMaxPadded) && table_lds <= ((c->table_coarse || lds_ws) ? kTableLdsMaxWG : (size_t)64 * 1024);
         // pinned pods (pin_node) are known to the score-table kernel and the all-feature kernel only
         if (c->debug_route)
-            fprintf(stderr, "[route] variant %d rest %d spread %d fold %d gfold %d table_ok %d perm_ok %d coarse %d n_sigs %d Cn_t %d ni_top %d lds %zu max_n %d M %d NZ %d TH %d TZ %d\n", c->variant, (int)c->rest,
+            fprintf(stderr, "[route] variant %d rest %d spread %d fold %d gfold %d table_ok %d perm_ok %d coarse %d n_sigs %d Cn_t %d ni_top %d lds %zu max_n %d M %d NZ %d TH %d TZ %d segments %d\n", c->variant, (int)c->rest,
                     (int)c->spread, (int)c->fold, (int)c->gfold, (int)c->table_ok, (int)c->table_perm_ok, (int)c->table_coarse, c->n_sigs, c->Cn_t, ni_top, table_lds, c->max_n,
-                    c->rest_M, (int)c->zone_keys.size(), c->sp_TH, c->sp_TZ);
+                    c->rest_M, (int)c->zone_keys.size(), c->sp_TH, c->sp_TZ, c->seg_n);
         const bool needs_table_or_wide = c->has_pin || too_big || c->rest || c->spread || c->fold || c->gfold || !c->raw_fits_lds || c->has_ranks || c->has_static;
         // Beyond 256 signatures generation 2 (register-resident state, every node re-evaluated per cycle: its time does not depend on
         // the signature count) overtakes the score table (measured, profiles/r03: 300 signatures 124 ms against 119 ms, 384: 169 ms) --
@@ -2150,6 +2285,7 @@ int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
             cold.gpu_slices = want_slices ? reinterpret_cast<unsigned long long*>(c->d_gpu_slices.p) : nullptr;
             cold.na_raw = c->has_na ? c->d_t_na.p : nullptr; cold.tt_raw = c->has_tt ? c->d_t_tt.p : nullptr; cold.add_raw = c->has_add ? c->d_t_add.p : nullptr;
             if (c->has_ranks) { cold.rk_pos = c->d_rk_pos.p; cold.rk_rank = c->d_node_rank.p; }
+            if (c->seg_n) cold.scls = c->d_scls.p;
             if (c->img_R > 0) { cold.img = c->d_t_img.p; cold.img_slot = c->d_img_slot.p; cold.img_stride = c->img_stride_t; }
             if (c->rest) {
                 cold.xrows = c->d_xrows.p; cold.zdom = c->d_zdom.p; cold.xsig = c->d_xsig.p; cold.xalloc = c->d_xalloc.p; cold.i_xused = c->d_i_xused.p;
@@ -2171,7 +2307,7 @@ int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
             f.cls_list = c->has_ranks ? c->d_rk_ids.p : c->d_cls_list.p; f.pods = c->d_podsC.p; f.orders = c->d_orders.p; f.perm = c->d_perm.p;
             f.ws_off = c->d_ws_off.p; f.ws = c->d_ws.p; f.coarse = c->table_coarse; f.rest = c->rest; f.spread = c->spread; f.aff = c->rest && !c->aff_idx.empty(); f.team = team; f.lds_ws = lds_ws; f.lds_x = lds_x;
             f.place_step = want_placement ? c->d_place_step.p : nullptr;
-            f.sc = TableScalars{(c->N + 63) / 64, c->Cn_t, c->Cp, P, S, c->n_sigs, c->has_ranks ? c->N : 0, (c->has_na ? 1 : 0) | (c->has_tt ? 2 : 0) | (c->has_add ? 4 : 0) | (want_slices ? 8 : 0) | (c->sig_twins ? 16 : 0) | (c->fold ? 32 : 0) | ((c->spread && (c->ipa_fold || c->hard_fold)) ? 64 : 0) | (c->gfold ? 128 : 0) | (c->img_R > 0 ? 256 : 0), c->rest ? (int)c->zone_keys.size() : 0, c->rest ? c->rest_M : 0, c->rest ? c->rest_G : 0, c->rest ? c->rest_X : 0, c->spread ? c->sp_TH : 0, c->spread ? c->sp_TZ : 0, c->spread ? (int)c->sp_zkeys.size() : 0, ni_top, c->g_cpu, c->g_mem};
+            f.sc = TableScalars{(c->N + 63) / 64, c->Cn_t, c->Cp, P, S, c->n_sigs, c->has_ranks ? c->N : 0, (c->has_na ? 1 : 0) | (c->has_tt ? 2 : 0) | (c->has_add ? 4 : 0) | (want_slices ? 8 : 0) | (c->sig_twins ? 16 : 0) | (c->fold ? 32 : 0) | ((c->spread && (c->ipa_fold || c->hard_fold)) ? 64 : 0) | (c->gfold ? 128 : 0) | (c->img_R > 0 ? 256 : 0) | (c->seg_n ? 512 : 0), c->rest ? (int)c->zone_keys.size() : 0, c->rest ? c->rest_M : 0, c->rest ? c->rest_G : 0, c->rest ? c->rest_X : 0, c->spread ? c->sp_TH : 0, c->spread ? c->sp_TZ : 0, c->spread ? (int)c->sp_zkeys.size() : 0, ni_top, c->g_cpu, c->g_mem};
             HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
             HIP_TRY(c, launch_table(f, S, c->has_mask, c->nzeq, c->has_pin, table_lds, c->stream));
             if (want_placement)
@@ -2228,6 +2364,11 @@ int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
             HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
         }
     }
+    if (c->debug_route && c->seg_n)
+        fprintf(stderr, "[route] segmented batch (%d segments, %d fixed nodes): %s\n", c->seg_n, c->seg_start[0],
+                run_wide ? "all-feature kernel -- refused" : table_used ? "score-table kernel, ranked instantiation" : "refused");
+    if (run_wide && c->seg_n)     // the all-feature kernel takes prefix scenarios only
+        return fail(c, SIMON_ESTATE, "run_loaded: segmented batch on a problem the score-table kernel does not take; run each scenario's own problem");
     if (run_wide) {
         if (!c->wide_staged) {   // a NARROW problem whose batch cannot use the cache kernel but has pinned pods
             int rcw = wide_stage(c->wide, *c, c->stream, c->err);
@@ -2386,7 +2527,7 @@ static int launch_plan(simon_ctx* c, int32_t max_cpu_pct, int32_t max_mem_pct, i
     const int blocks = std::min(64, (c->S + 255) / 256);
     hipLaunchKernelGGL(plan_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_scen.p, c->S, c->d_unsched.p,
                        c->d_used_cpu.p, c->d_used_mem.p, c->d_prefix_cpu.p, c->d_prefix_mem.p, max_cpu_pct, max_mem_pct,
-                       c->has_local ? c->d_used_vg.p : nullptr, c->d_prefix_vg.p, max_vg_pct, c->d_plan.p);
+                       c->has_local ? c->d_used_vg.p : nullptr, c->d_prefix_vg.p, max_vg_pct, c->seg_n ? c->d_seg_tot.p : nullptr, c->d_plan.p);
     HIP_TRY(c, hipGetLastError());
     return SIMON_OK;
 }
@@ -2418,15 +2559,17 @@ int simon_min_plan_vg(simon_ctx* c, int32_t max_cpu_pct, int32_t max_mem_pct, in
     HIP_TRY(c, hipMemcpy(&um, c->d_used_mem.p + s, 8, hipMemcpyDeviceToHost));
     const int n = c->scen[s].n_nodes;
     int64_t ac = 0, am = 0;
-    for (int j = 0; j < n; ++j) { ac += c->alloc_cpu[j]; am += c->alloc_mem[j]; }
+    for (int j = 0; j < c->N; ++j)
+        if (node_in(c, s, j)) { ac += c->alloc_cpu[j]; am += c->alloc_mem[j]; }
     best->found = 1; best->scenario = s; best->n_nodes = n; best->order_id = c->scen[s].order_id;
     best->cpu_pct = (int)((double)uc / (double)ac * 100.0);
     best->mem_pct = (int)((double)(um * 1000) / (double)(am * 1000) * 100.0);
     best->used_cpu = uc; best->used_mem = um;
-    if (vg_pct && c->has_local && c->prefix_vg[n] != 0) {
+    const int64_t av = c->seg_n ? c->seg_tot[(size_t)2 * c->S + s] : c->prefix_vg[n];
+    if (vg_pct && c->has_local && av != 0) {
         int64_t uv = 0;
         HIP_TRY(c, hipMemcpy(&uv, c->d_used_vg.p + s, 8, hipMemcpyDeviceToHost));
-        *vg_pct = (int)((double)uv / (double)c->prefix_vg[n] * 100.0);
+        *vg_pct = (int)((double)uv / (double)av * 100.0);
     }
     return SIMON_OK;
 }
@@ -2435,6 +2578,7 @@ static int explain_impl(simon_ctx* c, int n_nodes, const int32_t* order, int ran
                         uint16_t* fail_codes, int32_t max_failed) {
     int rc = stage(c);
     if (rc) return rc;
+    if (c->seg_n) return fail(c, SIMON_ESTATE, "explain: segmented batch loaded");
     if (n_nodes < 0 || n_nodes > c->N) return fail(c, SIMON_EINVAL, "explain: n_nodes out of range");
     for (int i = 0; i < c->P; ++i) if (order[i] < 0 || order[i] >= c->P) return fail(c, SIMON_EINVAL, "explain: bad order");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2476,6 +2620,8 @@ int simon_explain_loaded(simon_ctx* c, int32_t scenario, int32_t* failed_pods, u
     if (!c || !failed_pods || !fail_codes || max_failed <= 0) return c ? fail(c, SIMON_EINVAL, "explain_loaded: bad arguments") : SIMON_EINVAL;
     if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "explain_loaded: no scenarios loaded");
     if (scenario < 0 || scenario >= c->S) return fail(c, SIMON_EINVAL, "explain_loaded: scenario %d outside [0,%d)", scenario, c->S);
+    if (c->seg_n)        // the replay runs on the all-feature kernel, which takes prefix scenarios only
+        return fail(c, SIMON_ESTATE, "explain_loaded: segmented batch; explain the scenario's own problem (its nodes alone)");
     const ScenarioDesc& sd = c->scen[scenario];
     return explain_impl(c, sd.n_nodes, c->h_orders.data() + (size_t)sd.order_id * c->P, c->has_ranks ? scenario : -1,
                         failed_pods, fail_codes, max_failed);

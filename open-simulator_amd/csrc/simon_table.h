@@ -33,7 +33,7 @@ struct PodRowC { int32_t sigcls, preset, gate, rest; };
 struct TableScalars {
     int32_t mask_words, Cn, Cp, P, S, K;
     int32_t rk_stride;   // 0: cls_list = the pool's per-class node lists; N: per-scenario lists in rank order (simon_set_node_ranks)
-    int32_t static_tables;   // bit 0 / 1 / 2: TableCold::na_raw / tt_raw / add_raw present; bit 3: record TableCold::gpu_slices; bit 4: signature k + 64 is a twin of k (same request); bit 5: TableCold::foldx present; bit 6: SPREAD && AFF instantiations; bit 7: Open-Gpu-Share folded into the table (SigRow::pad = GPU request, devices per position behind the workspace); bit 8: TableCold::img present
+    int32_t static_tables;   // bit 0 / 1 / 2: TableCold::na_raw / tt_raw / add_raw present; bit 3: record TableCold::gpu_slices; bit 4: signature k + 64 is a twin of k (same request); bit 5: TableCold::foldx present; bit 6: SPREAD && AFF instantiations; bit 7: Open-Gpu-Share folded into the table (SigRow::pad = GPU request, devices per position behind the workspace); bit 8: TableCold::img present; bit 9: segmented batch (TableCold::scls, ranked instantiations only)
     int32_t NZ;          // REST: topology keys that are NOT node-level (a term on one marks every position of the pod's domain)
     int32_t M, G, X;     // REST: rows of the per-block position masks (G GPU requests + X extra-resource requests + 2 x terms)
     int32_t TH, TZ, NZK; // SPREAD: hostname-key term rows, zone-key term rows, zone-like topology keys (class split)
@@ -83,6 +83,8 @@ struct TableCold {
     const unsigned char* img;
     const int32_t* img_slot;        // [S] size slot of a scenario
     int32_t img_stride;             // table classes x internal node classes
+    // segmented batch (simon_set_scenario_segments, TableScalars::static_tables & 512): [S][Cn] nodes of class d that scenario s holds
+    const int32_t* scls;
 };
 
 struct TableLaunch {

@@ -471,13 +471,21 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     static_assert(!LDSX || (REST && NW == 1 && !LDSWS), "LDS-resident mask rows serve generation 6");
     unsigned char* const wsb = LDSWS ? smem + ((cv.total + 127) & ~127) : ws + ws_off[blockIdx.x];
     const int32_t* __restrict__ order = orders + (size_t)__builtin_amdgcn_readfirstlane(scen[s].order_id) * P;
+    // Segmented batch (simon_set_scenario_segments; static_tables & 512, ranked instantiations only): the scenario holds fixed nodes and a
+    // prefix of every pool segment, not a prefix of the pool.  Its per-class lists hold its own nodes alone, so the class counts come from
+    // its own row (TableCold::scls) and a node is in the scenario iff its rank is below n (the host gives absent nodes rank N).
+    const bool segd = RANKED && (sc.static_tables & 512) != 0;
+    auto cnt_at = [&](int d) -> int {                                 // nodes of class d in this scenario (the instantiations without ranks: as before)
+        if constexpr (RANKED) { if (segd) return gp(cold->scls)[(size_t)s * Cn + d]; }
+        return clsprefix[(size_t)n * Cn + d];
+    };
 
     // ---- prologue 1: clear, tables -> LDS, class segments --------------------------------------
     for (int i = tid; i < K * Cn; i += TT) { if (CNT_LDS) s_cnt[i] = 0; s_sn[i] = 0; }
     if constexpr (kCls4) { for (int i = tid; i < Cn * 8; i += TT) ((int*)(smem + cv.shape))[i] = ((const int*)shapes)[(i >> 3) * 12 + (i & 7)]; }
     else for (int i = tid; i < Cn * 12; i += TT) ((int*)(smem + cv.shape))[i] = ((const int*)shapes)[i];
     // count of class-d nodes among the first n canonical nodes, padded to 16 (COARSE: to 64, one class per summary entry)
-    const int cnt_d = (lane < Cn) ? clsprefix[(size_t)n * Cn + lane] : 0;
+    const int cnt_d = (lane < Cn) ? cnt_at(lane) : 0;
     const int pad_d = (cnt_d + (UNIT - 1)) & ~(UNIT - 1);
     int incl = pad_d;
 #pragma unroll
@@ -492,7 +500,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     // index already; what is lane-shaped is this prefix scan, the count lookup of the prologue and the class terms' re-base.
     int cnt_d2 = 0;
     if (Cn > 64) {
-        cnt_d2 = (64 + lane < Cn) ? clsprefix[(size_t)n * Cn + 64 + lane] : 0;
+        cnt_d2 = (64 + lane < Cn) ? cnt_at(64 + lane) : 0;
         const int pad2 = (cnt_d2 + (UNIT - 1)) & ~(UNIT - 1);
         int incl2 = pad2;
 #pragma unroll
@@ -507,7 +515,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         if constexpr (kCls4) {
 #pragma nounroll
         for (int g = 2; g * 64 < Cn; ++g) {
-            const int cg = (g * 64 + lane < Cn) ? clsprefix[(size_t)n * Cn + g * 64 + lane] : 0;
+            const int cg = (g * 64 + lane < Cn) ? cnt_at(g * 64 + lane) : 0;
             const int padg = (cg + (UNIT - 1)) & ~(UNIT - 1);
             int inclg = padg;
 #pragma unroll
@@ -526,7 +534,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         if (Cn <= 64) return lo;
         const int hi = __shfl(cnt_d2, d & 63, 64);
         int r = d < 64 ? lo : hi;
-        if (kCls4 && d >= 128) r = clsprefix[(size_t)n * Cn + (d < Cn ? d : 0)];   // (classes 128 ..: from the prefix table)
+        if (kCls4 && d >= 128) r = cnt_at(d < Cn ? d : 0);   // (classes 128 ..: from the prefix table)
         return r;
     };
     const int nblk = ni >> 4, nun = ni >> UB;                         // table blocks (16 positions); summary entries
@@ -1882,7 +1890,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         const int idx = i0 + lane;
         if (idx >= P) return make_int4((int)0x80000000, -1, 0x7fffffff, 0);
         const PodRowC r = pods[order[idx]];
-        const bool special = r.gate >= n || r.preset != -1;
+        // (segmented: the gate node is absent iff its rank is N -- one gather per chunk, only for gated pods of a segmented batch)
+        const bool gated_out = segd ? (r.gate >= 0 && gp(cold->rk_rank)[(size_t)s * (size_t)cold->N + r.gate] >= n) : r.gate >= n;
+        const bool special = gated_out || r.preset != -1;
         return make_int4(r.sigcls | (special ? (int)0x80000000 : 0), r.preset, r.gate, r.rest);
     };
     int4 nxt = load_chunk(0);
@@ -1932,7 +1942,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
             const int r_preset = __builtin_amdgcn_readlane(cur.y, il), r_gate = __builtin_amdgcn_readlane(cur.z, il);
             GPtr<const TableCold> cc = cold;
             asm volatile("" : "+s"(cc));                               // rare paths: fetch their pointers here, not in loop-long SGPRs
-            if (r_gate >= n) {
+            if (segd ? (r_gate >= 0 && __builtin_amdgcn_readfirstlane(gp(cc->rk_rank)[(size_t)s * (size_t)cc->N + r_gate]) >= n) : r_gate >= n) {
                 res = -2;                                              // pod not part of this scenario
             } else if (r_preset >= 0) {                                // addPodToCache path (V/eventhandlers.go:223-236)
                 bound = true;
@@ -1943,7 +1953,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
             } else {                                                   // pinned pod (simon_pods_soa.pin_node, stored as -2 - node):
                 const int pin = -2 - r_preset;                         // its node affinity admits ONE node; the table byte of
                 res = -1;                                              // (signature, node) holds static filters + fit
-                if (HAS_PIN && pin < n) {
+                if (HAS_PIN && (segd ? __builtin_amdgcn_readfirstlane(gp(cc->rk_rank)[(size_t)s * (size_t)cc->N + pin]) < n : pin < n)) {
                     const int dp = __builtin_amdgcn_readfirstlane(gp(cc->ncls)[pin]);
                     const int rk = __builtin_amdgcn_readfirstlane(ranked ? gp(cc->rk_pos)[(size_t)s * (size_t)cc->N + pin] : gp(cc->rank)[pin]);
                     const int pp = __builtin_amdgcn_readfirstlane(s_seg[dp]) + rk;

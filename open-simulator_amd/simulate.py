@@ -24,18 +24,25 @@ class HipEngine:
     """The product engine: libsimon_hip.so on one device."""
 
     supports_image_locality = True            # ImageLocality per scenario size on the device (ABI v7): sweep() batches image clusters
+    supports_scenario_segments = True         # pool segments (simon_set_scenario_segments): sweep_mix() batches node-type mixes
 
     def __init__(self, device_id: int = 0):
         self.device_id = device_id
 
-    def run(self, prob: capi.Problem, scen, orders, want_placement=True, node_ranks=None, want_gpu_slices=False) -> capi.BatchResult:
+    def run(self, prob: capi.Problem, scen, orders, want_placement=True, node_ranks=None, want_gpu_slices=False,
+            segments=None) -> capi.BatchResult:
+        """segments: (seg_start [G], counts [S][G]) -- scenario s holds the pool nodes before seg_start[0] and the first counts[s][g] of every
+        segment g (sweep_mix); None = every scenario is a prefix of the pool."""
         with capi.Context(self.device_id) as ctx:
             ctx.load_problem(prob)
-            if node_ranks is None:
+            if node_ranks is None and segments is None:
                 res = ctx.run_batch(scen, orders, want_placement, want_gpu_slices)
             else:
                 ctx.load_scenarios(scen, orders)
-                ctx.set_node_ranks(node_ranks)        # per-scenario nodeTree order (clusters with several zones)
+                if segments is not None:
+                    ctx.set_scenario_segments(*segments)
+                if node_ranks is not None:
+                    ctx.set_node_ranks(node_ranks)    # per-scenario nodeTree order (clusters with several zones)
                 ctx.run_loaded(want_placement, want_gpu_slices)
                 res = ctx.fetch(want_placement, want_gpu_slices)
             self.last_stats = ctx.stats()             # which kernel ran (simon_get_stats)
@@ -443,6 +450,211 @@ def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, m
         res.node_status = [{"node": _gpu_node_status(n, per_dev[j]) if j in per_dev else _node_out(n), "pods": per_node[j]} for j, n in enumerate(nodes)]
         result = res
     return SweepResult(list(counts), uns, cpu_pct, mem_pct, None if best is None else counts[best], result, vg_pct, risks)
+
+
+@dataclass
+class MixSweepResult:
+    """sweep_mix over the grid of node-type mixes: per mix its counts (one per type), unscheduled pods and occupancies."""
+    counts: List[tuple]                  # per mix: new nodes of every type
+    unscheduled: List[int]
+    cpu_pct: List[int]
+    mem_pct: List[int]
+    vg_pct: List[int]
+    needs_reference: List[bool]
+    best: Optional[tuple]                # the feasible mix of least cost (ties: fewer new nodes, then the smallest count vector)
+    cost: Optional[float]
+    result: Optional[SimulateResult]     # SimulateResult of that mix (node_status over its own nodes)
+    batched: bool = True                 # one segmented engine batch (False: every mix ran as its own problem)
+    fallback: Optional[str] = None       # why the mixes ran one by one (None when batched); sweep_mix also warns (MixFallbackWarning)
+
+
+class MixFallbackWarning(UserWarning):
+    """sweep_mix could not batch the grid and runs every mix as its own problem: one engine context, flatten and launch per mix
+    (a 64 x 64 grid is 4 096 of them).  The reason names what refused: an engine without pool segments, nodes that list the pods'
+    images (ImageLocality over a node set), or a problem the segmented score-table kernel does not take (the all-feature kernel
+    runs prefix scenarios only: Open-Local, hard hostname spread, pools beyond the table's limits)."""
+
+
+def mix_fake_nodes(new_nodes: Sequence[dict], counts: Sequence[int]) -> List[List[dict]]:
+    """NewFakeNodes per type (pkg/utils/utils.go:885-901).  Type 0 keeps new_fake_nodes' names (one type = sweep()'s pool); the clones
+    of type t > 0 are named simon-t<t>-<index>, unique across types."""
+    out = []
+    for t, (tmpl, k) in enumerate(zip(new_nodes, counts)):
+        nodes = wl.new_fake_nodes(tmpl, k) if k > 0 else []
+        if t > 0:
+            renamed = []
+            for i, n in enumerate(nodes):
+                name = f"{wl.NEW_NODE_NAME_PREFIX}-t{t}-{i:05d}"
+                labels = dict(n["metadata"]["labels"])
+                if labels.get(k8s.LABEL_HOSTNAME) == n["metadata"]["name"]:
+                    labels[k8s.LABEL_HOSTNAME] = name
+                renamed.append(dict(n, metadata=dict(n["metadata"], name=name, labels=labels)))
+            nodes = renamed
+        out.append(nodes)
+    return out
+
+
+def mix_node_ranks(pool: List[dict], present: np.ndarray) -> np.ndarray:
+    """rank[s][j] = position of pool node j in nodeTree.list() of scenario s's own nodes (present[s] = its pool nodes, inserted in pool
+    order; V/internal/cache/node_tree.go:119-143: zones in first-appearance order, one node per zone per round), -1 where absent.
+    Vectorised over the scenarios: no per-mix loop over the nodes."""
+    zid: Dict[str, int] = {}
+    z = np.array([zid.setdefault(k8s.zone_key(n), len(zid)) for n in pool], np.int64)
+    S, N = present.shape
+    Z = len(zid)
+    onehot = (z[None, :] == np.arange(Z)[:, None])                                   # [Z][N]
+    big = np.int64(N + 1)
+    # index of a node inside its zone among the scenario's nodes; zone order = first appearance among them
+    inzone = np.zeros((S, N), np.int64)
+    first = np.full((S, Z), big, np.int64)
+    for q in range(Z):                                                               # (zones: a handful)
+        m = present & onehot[q][None, :]
+        inzone[m] = (np.cumsum(m, axis=1) - 1)[m]
+        any_q = m.any(axis=1)
+        first[any_q, q] = m[any_q].argmax(axis=1)
+    zorder = np.argsort(np.argsort(first, axis=1, kind="stable"), axis=1, kind="stable")   # rank of every zone by first appearance
+    key = np.where(present, inzone * Z + np.take_along_axis(zorder, np.broadcast_to(z, (S, N)), axis=1), np.iinfo(np.int64).max)
+    order = np.argsort(key, axis=1, kind="stable")
+    rank = np.empty((S, N), np.int64)
+    np.put_along_axis(rank, order, np.broadcast_to(np.arange(N), (S, N)), axis=1)
+    return np.where(present, rank, -1).astype(np.int32)
+
+
+def _best_mix(mixes, ok, costs):
+    if not ok:
+        return None
+    return min(ok, key=lambda s: (sum(c * k for c, k in zip(costs, mixes[s])), sum(mixes[s]), tuple(mixes[s])))
+
+
+def _caps(max_cpu, max_mem, max_vg):
+    return tuple(100 if v > 100 or v < 0 else v for v in (max_cpu, max_mem, max_vg))
+
+
+@_gc_paused
+def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_nodes: Sequence[dict], counts: Sequence[Sequence[int]],
+              costs: Optional[Sequence[float]] = None, engine=None, max_cpu: int = 100, max_mem: int = 100, max_vg: int = 100) -> MixSweepResult:
+    """The add-nodes search over mixes of several new-node types (Applier.Run clones ONE template, pkg/apply/apply.go:155-166): mix
+    (c_1 .. c_T) = Simulate(cluster + NewFakeNodes(type_1, c_1) + ... + NewFakeNodes(type_T, c_T)), the grid = the Cartesian product of
+    counts (one iterable per type).  The answer is the mix of least total cost sum_t costs[t] * c_t (default 1 per node) with no
+    unscheduled pod and the MaxCPU / MaxMemory / MaxVG caps of satisfyResourceSetting over its own nodes; ties go to fewer new nodes,
+    then to the smallest count vector.  One engine batch over the pool cluster + every type's clones up to its largest count, one
+    segment per type (simon_set_scenario_segments); engines without segments, clusters whose nodes list the pods' images and problems
+    the segmented kernel does not take run every mix as its own problem."""
+    import itertools
+    engine = engine or HipEngine()
+    new_nodes = list(new_nodes)
+    counts = [list(c) for c in counts]
+    if not new_nodes or len(counts) != len(new_nodes):
+        raise ValueError("sweep_mix: one count list per new-node type")
+    if len(new_nodes) > capi.MAX_SEGMENTS:
+        raise ValueError(f"sweep_mix: at most {capi.MAX_SEGMENTS} node types")
+    if any(not c for c in counts):
+        raise ValueError("sweep_mix: every node type needs at least one count")
+    if any(k < 0 for c in counts for k in c):
+        raise ValueError("sweep_mix: counts must be >= 0")
+    costs = [1] * len(new_nodes) if costs is None else list(costs)
+    if len(costs) != len(new_nodes):
+        raise ValueError(f"sweep_mix: {len(costs)} costs for {len(new_nodes)} node types")
+    mixes = [tuple(int(k) for k in m) for m in itertools.product(*counts)]
+    caps = _caps(max_cpu, max_mem, max_vg)
+    if not getattr(engine, "supports_scenario_segments", False):
+        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, "the engine has no pool segments")
+    base = list(cluster.get("Node", []))
+    top = [max(c, default=0) for c in counts]
+    typed = mix_fake_nodes(new_nodes, top)
+    pool = base + [n for nodes in typed for n in nodes]
+    seg_start = np.cumsum([len(base)] + top[:-1]).astype(np.int32)
+    cnt = np.array(mixes, np.int32).reshape(len(mixes), len(new_nodes))
+    present = np.ones((len(mixes), len(pool)), bool)
+    for g, st in enumerate(seg_start.tolist()):
+        present[:, st:st + top[g]] = np.arange(top[g])[None, :] < cnt[:, g:g + 1]
+    node_ranks = mix_node_ranks(pool, present) if len({k8s.zone_key(n) for n in pool}) > 1 else None
+    pods, gates = build_stream(cluster, apps, pool, len(base))
+    try:
+        flat = fl.flatten(pool, pods, cluster.get("Service", []), cluster.get("ReplicaSet", []), cluster.get("StatefulSet", []), gates,
+                          storage_classes=_storage_classes(cluster, apps))
+    except fl.Unsupported as e:
+        if "ImageLocality" not in str(e):
+            raise
+        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps,
+                                  "nodes list the pods' images: ImageLocality depends on the node set")
+    scen = np.stack([len(base) + cnt.sum(1), np.zeros(len(mixes), np.int64)], 1).astype(np.int32)
+    orders = np.arange(len(pods), dtype=np.int32)[None, :]
+    want_gpu = flat.problem.gpu_mem is not None
+    kw = {"want_gpu_slices": True} if want_gpu else {}
+    if node_ranks is not None:
+        kw["node_ranks"] = node_ranks
+    try:
+        out = engine.run(flat.problem, scen, orders, segments=(seg_start, cnt), **kw)
+    except capi.SimonError as e:
+        if getattr(e, "code", None) != capi.ESTATE:
+            raise
+        # a problem on the all-feature kernel (prefix scenarios only): every mix as its own problem
+        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, f"the engine refused the segmented batch: {e}")
+    # satisfyResourceSetting over each mix's own nodes: the fixed nodes + a prefix of every segment
+    pr = flat.problem
+    vg_cap = None
+    if pr.local_flags is not None and out.used_vg is not None:
+        vg_cap = (pr.local_vg_cap * (np.arange(capi.MAX_VG)[None, :] < pr.local_vg_cnt[:, None])).sum(1)
+    def totals(v):
+        c = np.concatenate([[0], np.cumsum(np.asarray(v, np.int64))])
+        t = np.full(len(mixes), c[len(base)], np.int64)
+        for g, st in enumerate(seg_start.tolist()):
+            t += c[st + cnt[:, g]] - c[st]
+        return t
+    ac, am = totals(pr.alloc_cpu), totals(pr.alloc_mem)
+    av = totals(vg_cap) if vg_cap is not None else None
+    cpu_pct = [occupancy_pct(int(out.used_cpu[s]), int(ac[s])) for s in range(len(mixes))]
+    mem_pct = [occupancy_pct(int(out.used_mem[s]) * 1000, int(am[s]) * 1000) for s in range(len(mixes))]
+    vg_pct = [occupancy_pct(int(out.used_vg[s]), int(av[s])) for s in range(len(mixes))] if av is not None else [0] * len(mixes)
+    ok = [s for s in range(len(mixes)) if out.unscheduled[s] == 0 and cpu_pct[s] <= caps[0] and mem_pct[s] <= caps[1] and vg_pct[s] <= caps[2]]
+    best = _best_mix(mixes, ok, costs)
+    result = None
+    if best is not None:
+        res, per_node, per_dev = _unflatten(flat, out.placement[best], len(pool), {}, out.gpu_slices[best] if want_gpu and out.gpu_slices is not None else None)
+        res.node_status = [{"node": _gpu_node_status(pool[j], per_dev[j]) if j in per_dev else _node_out(pool[j]), "pods": per_node[j]}
+                           for j in np.flatnonzero(present[best]).tolist()]
+        result = res
+    return MixSweepResult(mixes, out.unscheduled.tolist(), cpu_pct, mem_pct, vg_pct, [_risk(out, s) for s in range(len(mixes))],
+                          None if best is None else mixes[best], None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result)
+
+
+def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why: str) -> MixSweepResult:
+    """Every mix as its own Simulate(): cluster + each type's clones in type order, canonical nodeTree order."""
+    import warnings
+    warnings.warn(f"sweep_mix runs {len(mixes)} mixes one by one ({why})", MixFallbackWarning, stacklevel=3)
+    base = list(cluster.get("Node", []))
+    uns, cpu_pct, mem_pct, vg_pct, risks, kept = [], [], [], [], [], {}
+    for s, mix in enumerate(mixes):
+        nodes = base + [n for nodes in mix_fake_nodes(new_nodes, mix) for n in nodes]
+        pods, _ = build_stream(cluster, apps, nodes, len(nodes))
+        arrival = [n["metadata"]["name"] for n in nodes]
+        nodes = [nodes[j] for j in k8s.canonical_node_order(nodes)]
+        flat = fl.flatten(nodes, pods, cluster.get("Service", []), cluster.get("ReplicaSet", []), cluster.get("StatefulSet", []),
+                          storage_classes=_storage_classes(cluster, apps), image_total=len(nodes), node_arrival_order=arrival)
+        want_gpu = flat.problem.gpu_mem is not None
+        out = engine.run(flat.problem, np.array([[len(nodes), 0]], np.int32), np.arange(len(pods), dtype=np.int32)[None, :],
+                         **({"want_gpu_slices": True} if want_gpu else {}))
+        uns.append(int(out.unscheduled[0]))
+        risks.append(_risk(out, 0))
+        cpu_pct.append(occupancy_pct(int(out.used_cpu[0]), int(flat.problem.alloc_cpu.sum())))
+        mem_pct.append(occupancy_pct(int(out.used_mem[0]) * 1000, int(flat.problem.alloc_mem.sum()) * 1000))
+        vg = 0
+        if flat.problem.local_flags is not None and out.used_vg is not None:
+            cap = int((flat.problem.local_vg_cap * (np.arange(capi.MAX_VG)[None, :] < flat.problem.local_vg_cnt[:, None])).sum())
+            vg = occupancy_pct(int(out.used_vg[0]), cap)
+        vg_pct.append(vg)
+        if uns[-1] == 0 and cpu_pct[-1] <= caps[0] and mem_pct[-1] <= caps[1] and vg <= caps[2]:
+            kept[s] = (flat, out, nodes)
+    best = _best_mix(mixes, list(kept), costs)
+    result = None
+    if best is not None:
+        flat, out, nodes = kept[best]
+        res, per_node, per_dev = _unflatten(flat, out.placement[0], len(nodes), {}, out.gpu_slices[0] if out.gpu_slices is not None else None)
+        res.node_status = [{"node": _gpu_node_status(n, per_dev[j]) if j in per_dev else _node_out(n), "pods": per_node[j]} for j, n in enumerate(nodes)]
+        result = res
+    return MixSweepResult(mixes, uns, cpu_pct, mem_pct, vg_pct, risks, None if best is None else mixes[best],
+                          None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result, batched=False, fallback=why)
 
 
 def load_config(path: str, base_dir: str = ".") -> dict:
