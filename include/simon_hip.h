@@ -400,7 +400,8 @@ int simon_set_node_ranks(simon_ctx* ctx, const int32_t* rank /* [S][N] */);
  * (entries of the nodes it lacks are ignored).  A gated pod exists in scenario s iff s holds gate_node; a pinned pod whose node s lacks
  * is unschedulable there.  simon_min_plan* keep their key and use each scenario's own allocatable / VG totals.
  * Call after simon_load_scenarios (which clears it); n_seg = 0 returns to prefix scenarios.  SIMON_EINVAL: n_seg < 0, missing
- * arrays, starts not ascending, a count beyond its segment, an n_nodes mismatch, n_seg > SIMON_MAX_SEGMENTS, a segment node with pods bound before the
+ * arrays, starts not ascending, a count beyond its segment, an n_nodes mismatch, a scenario of no nodes at all
+ * (no fixed nodes, every count 0), n_seg > SIMON_MAX_SEGMENTS, a segment node with pods bound before the
  * stream (init_*) or the target of a preset pod.  SIMON_ESTATE: ImageLocality in effect (simon_set_image_locality).  A segmented batch
  * runs on the score-table kernel only: simon_run_loaded refuses (SIMON_ESTATE) a problem that needs the all-feature kernel, and
  * simon_explain / simon_explain_loaded refuse while one is loaded -- replay the scenario's own problem instead.  A call that fails

@@ -2140,6 +2140,7 @@ int simon_set_scenario_segments(simon_ctx* c, int32_t n_seg, const int32_t* seg_
             tot += cnt;
         }
         if (tot != c->scen[s].n_nodes) return fail(c, SIMON_EINVAL, "set_scenario_segments: scenario %d: n_nodes %d, but its fixed nodes and counts make %lld", s, c->scen[s].n_nodes, tot);
+        if (tot == 0) return fail(c, SIMON_EINVAL, "set_scenario_segments: scenario %d holds no node at all (no fixed nodes, every count 0)", s);   // (the ranked instantiations have never run an empty scenario)
     }
     // a segment node starts empty: pods bound before the stream or by Spec.NodeName would need it in every scenario
     auto nz = [](const auto& v, size_t i) { return i < v.size() && v[i] != 0; };

@@ -560,6 +560,8 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
     if not getattr(engine, "supports_scenario_segments", False):
         return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, "the engine has no pool segments")
     base = list(cluster.get("Node", []))
+    if not base and any(sum(m) == 0 for m in mixes):   # (a scenario holds one node at least: simon_set_scenario_segments, and flatten)
+        raise ValueError("sweep_mix: a cluster without nodes needs at least one new node in every mix")
     top = [max(c, default=0) for c in counts]
     typed = mix_fake_nodes(new_nodes, top)
     pool = base + [n for nodes in typed for n in nodes]

@@ -1,6 +1,7 @@
 """Node-type mixes on the device (simon_set_scenario_segments): one segment reproducing prefix sizes is bit-identical to the plain batch
 on every score-table route; two and three segments match the CPU oracle on each mix's own problem, by object names; refusals leave a
-usable context.  Run with -m gpu on an MI355X."""
+usable context; a slice of the fuzz regime (fuzz_mix.py) with the route of every case pinned; the setter's state machine on one
+context; degenerate segment shapes; 4 096 mixes in one launch; preempt-risk flags of a segmented batch.  Run with -m gpu on an MI355X."""
 import itertools
 
 import numpy as np
@@ -40,29 +41,7 @@ def _run(prob, scen, env, monkeypatch, segments=None, ranks=None, want_gpu=False
         return res, ctx.stats()
 
 
-def _segmentable(prob, scen):
-    """The problem with nodes from the batch's smallest size on made segment-ready: no pod bound there before the stream or by
-    Spec.NodeName (a preset pod there keeps its gate and becomes a gated pod that is neither preset nor pinned)."""
-    import dataclasses
-    F = int(scen[:, 0].min())
-    kw = {f.name: getattr(prob, f.name) for f in dataclasses.fields(prob) if not f.name.startswith("_")}
-    for name in ("init_req_cpu", "init_req_mem", "init_req_eph", "init_nz_cpu", "init_nz_mem", "init_npods", "init_gpu_used", "init_vg_req",
-                 "init_dev_alloc"):
-        if kw[name] is not None:
-            v = np.array(kw[name])
-            v[F:] = 0
-            kw[name] = v
-    if kw["init_scalar_req"] is not None:
-        v = np.array(kw["init_scalar_req"])
-        v[:, F:] = 0
-        kw["init_scalar_req"] = v
-    if kw["preset_node"] is not None:
-        pr = np.array(kw["preset_node"])
-        if kw["gate_node"] is None:
-            kw["gate_node"] = np.full(len(pr), -1, np.int32)
-        kw["gate_node"] = np.where(pr >= F, np.maximum(kw["gate_node"], pr), kw["gate_node"]).astype(np.int32)
-        kw["preset_node"] = np.where(pr >= F, -1, pr).astype(np.int32)
-    return capi.Problem(**kw).normalise(), F
+_segmentable = MU.segmentable
 
 
 def _route_case(name):
@@ -317,3 +296,220 @@ def test_open_local_mixes_fall_back_visibly_and_match_the_oracle():
         ref = sim.sweep_mix(cluster, apps, types, grid, engine=MU.OracleEngine())
     assert hip.counts == ref.counts and hip.unscheduled == ref.unscheduled and hip.vg_pct == ref.vg_pct
     assert hip.cpu_pct == ref.cpu_pct and hip.mem_pct == ref.mem_pct and hip.best == ref.best
+
+
+# ---- the fuzz regime's slice, the state machine, degenerate shapes, the advertised batch size ---------------------------------------
+def _slice():
+    import fuzz_mix
+    return sorted(fuzz_mix.SLICE)
+
+
+@pytest.mark.parametrize("case", _slice())
+def test_fuzz_mix_slice_on_its_pinned_route(case):
+    """One case of tests/fuzz_mix.py (segments with starts anywhere, 1 ... 8 of them, caller ranks, plan caps, priorities -- see its
+    docstring) with the kernel every run of it must take: the slice cannot drift onto another route unnoticed.  Array-level cases: every
+    field of every scenario against the oracle on the scenario's own nodes; cases from 500 000 on: sweep_mix by object names against
+    Simulate() of every mix alone."""
+    import fuzz_mix
+    ok, info = fuzz_mix.one_case(case)
+    print(info)
+    routes, fams = fuzz_mix.SLICE[case]
+    assert not info["refused"], info
+    assert info.get("slice_missing", []) == [], info
+    assert [tuple(r) for r in info["routes"]] == [tuple(r) for r in routes], info
+    assert sorted(info["families"]) == sorted(fams + ["multi_segment"]), info      # what the case is in the slice for: still so
+    assert ok, info
+
+
+def _assert_segmented(res, prob, scen, orders, starts, counts, ranks=None, gpu=False):
+    for s in range(len(scen)):
+        row, ref = MU.oracle_of_scenario(prob, MU.present_mask(prob.n_nodes, starts, counts[s]), orders[scen[s, 1]], None if ranks is None else ranks[s])
+        assert res.placement[s].tolist() == row.tolist(), s
+        assert (int(res.unscheduled[s]), int(res.used_cpu[s]), int(res.used_mem[s])) == (int(ref.unscheduled[0]), int(ref.used_cpu[0]), int(ref.used_mem[0])), s
+        if gpu:
+            assert (res.gpu_slices[s] == ref.gpu_slices[0]).all(), s
+
+
+def _assert_same(a, b):
+    assert (a.placement == b.placement).all() and a.unscheduled.tolist() == b.unscheduled.tolist()
+    assert a.used_cpu.tolist() == b.used_cpu.tolist() and a.used_mem.tolist() == b.used_mem.tolist()
+
+
+STATE = {"generation4": (dict(gates=True, pins=True, n_node_classes=9, n_pod_classes=8), {"SIMON_TABLE_COARSE": "0"}, 4),
+         "generation7": (dict(spread_soft=True, gates=True, n_node_classes=4, n_pod_classes=8), {}, 7)}
+
+
+@pytest.mark.parametrize("name", sorted(STATE))
+def test_segments_ranks_and_batches_replace_each_other_on_one_context(name, monkeypatch):
+    """The state machine of one context: three segments -> two other segments with other counts (same totals) -> caller rank rows ->
+    simon_set_node_ranks(NULL) (pool order over each scenario's nodes again) -> no segments (the prefix batch) -> a new prefix batch.
+    Every segmented run against the oracle on each scenario's own nodes, every prefix run against a fresh context."""
+    kw, env, gen = STATE[name]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    N, F, S = 150, 60, 6
+    prob, _ = MU.segmentable(randprob.rand_problem(31, N=N, P=400, **kw), fixed=F)
+    rng = np.random.default_rng(7)
+    orders = np.stack([np.arange(prob.n_pods), rng.permutation(prob.n_pods), rng.permutation(prob.n_pods)]).astype(np.int32)
+    st_a, st_b = np.array([F, 97, 131], np.int32), np.array([F, 110], np.int32)
+    cnt_a = np.stack([rng.integers(0, n + 1, S) for n in (37, 34, 19)], 1).astype(np.int32)
+    tot = cnt_a.sum(1)
+    b0 = np.array([rng.integers(max(0, t - 40), min(t, 50) + 1) for t in tot])
+    cnt_b = np.stack([b0, tot - b0], 1).astype(np.int32)
+    assert (cnt_b >= 0).all() and (cnt_b <= [50, 40]).all()
+    scen = np.stack([F + tot, rng.integers(0, 3, S)], 1).astype(np.int32)
+    ranks = rng.integers(-3, N + 3, (S, N)).astype(np.int32)
+    for s in range(S):
+        own = np.flatnonzero(MU.present_mask(N, st_b, cnt_b[s]))
+        ranks[s, own] = rng.permutation(len(own))
+    scen2 = np.array([[N, 0], [90, 2], [33, 1], [120, 1]], np.int32)
+
+    def fresh(sc):
+        with capi.Context(0) as c2:
+            c2.load_problem(prob)
+            return c2.run_batch(sc, orders)
+
+    with capi.Context(0) as ctx:
+        ctx.load_problem(prob)
+        ctx.load_scenarios(scen, orders)
+
+        def run():
+            ctx.run_loaded(True)
+            st = ctx.stats()
+            assert (st.kernel_variant, st.kernel_generation) == (capi.KERNEL_NARROW_CACHE, gen)
+            return ctx.fetch(True)
+
+        ctx.set_scenario_segments(st_a, cnt_a)
+        _assert_segmented(run(), prob, scen, orders, st_a, cnt_a)
+        ctx.set_scenario_segments(st_b, cnt_b)
+        after_b = run()
+        _assert_segmented(after_b, prob, scen, orders, st_b, cnt_b)
+        ctx.set_node_ranks(ranks)
+        _assert_segmented(run(), prob, scen, orders, st_b, cnt_b, ranks)
+        ctx.set_node_ranks(None)
+        _assert_same(run(), after_b)
+        ctx.set_scenario_segments(st_a, cnt_a)                       # back to A after ranks: pool order, A's class counts
+        _assert_segmented(run(), prob, scen, orders, st_a, cnt_a)
+        ctx.set_scenario_segments(None, None)
+        _assert_same(run(), fresh(scen))
+        ctx.load_scenarios(scen2, orders)
+        _assert_same(run(), fresh(scen2))
+        ctx.load_scenarios(scen, orders)                             # and a segmented batch after a prefix batch of another size
+        ctx.set_scenario_segments(st_b, cnt_b)
+        _assert_same(run(), after_b)
+
+
+def test_degenerate_segment_shapes():
+    """What the validator admits at the edges: eight segments, an empty one among them (two equal starts, and one that starts at N), no
+    fixed nodes (seg_start[0] == 0), scenarios that hold every segment in full, nothing but the fixed nodes, or one single node.  A
+    scenario of NO nodes (all counts 0 without fixed nodes) is refused with SIMON_EINVAL and leaves a usable batch."""
+    N, P = 100, 300
+    rng = np.random.default_rng(3)
+    orders = np.stack([np.arange(P), rng.permutation(P)]).astype(np.int32)
+    for F, starts in ((0, [0, 7, 7, 30, 41, 63, 64, 100]), (13, [13, 14, 29, 29, 50, 77, 99, 100])):
+        prob, _ = MU.segmentable(randprob.rand_problem(40 + F, N=N, P=P, gates=True, pins=True, tight_pods=True, n_node_classes=9, n_pod_classes=8), fixed=F)
+        starts = np.array(starts, np.int32)
+        lens = np.append(starts[1:], N) - starts
+        assert len(starts) == capi.MAX_SEGMENTS and (lens == 0).sum() == 2
+        cnt = np.stack([rng.integers(0, n + 1, 6) for n in lens], 1).astype(np.int32)
+        cnt[0] = lens                                                 # the whole pool
+        cnt[1] = 0                                                    # nothing but the fixed nodes ...
+        if F == 0:
+            cnt[1, 3] = 1                                             # ... or one single node from the middle of the pool
+        cnt[2] = 0
+        cnt[2, 5] = lens[5]                                           # one whole segment far from the fixed nodes, nothing else
+        scen = np.stack([F + cnt.sum(1), rng.integers(0, 2, 6)], 1).astype(np.int32)
+        with capi.Context(0) as ctx:
+            ctx.load_problem(prob)
+            if F == 0:                                                # an empty scenario: refused before anything is laid out
+                none = cnt.copy()
+                none[1] = 0
+                ctx.load_scenarios(np.stack([none.sum(1), scen[:, 1]], 1).astype(np.int32), orders)
+                with pytest.raises(capi.SimonError) as e:
+                    ctx.set_scenario_segments(starts, none)
+                assert e.value.code == capi.EINVAL and "no node" in str(e.value)
+            ctx.load_scenarios(scen, orders)
+            ctx.set_scenario_segments(starts, cnt)
+            ctx.run_loaded(True)
+            res = ctx.fetch(True)
+            assert ctx.stats().kernel_variant == capi.KERNEL_NARROW_CACHE
+        _assert_segmented(res, prob, scen, orders, starts, cnt)
+        assert res.unscheduled[1] > 0 and (res.placement[0] >= F).any()
+
+
+def test_a_64_by_64_grid_of_mixes_in_one_launch():
+    """The batch size sweep_mix advertises: 4 096 mixes of two node types (0 ... 63 nodes of each) behind 30 fixed nodes, one launch.
+    Against the oracle: a fixed sample of the mixes that holds the grid's four corners and both edges (>= 256 of them); simon_min_plan_vg
+    over ALL 4 096 results, recomputed in numpy with each mix's own allocatable totals."""
+    F, K = 30, 63
+    N, P = F + 2 * K, 300
+    prob, _ = MU.segmentable(randprob.rand_problem(64, N=N, P=P, gates=True, tight_pods=True, n_node_classes=9, n_pod_classes=8), fixed=F)
+    mixes = np.array(list(itertools.product(range(K + 1), range(K + 1))), np.int32)
+    starts = np.array([F, F + K], np.int32)
+    scen = np.stack([F + mixes.sum(1), np.zeros(len(mixes), np.int32)], 1).astype(np.int32)
+    orders = np.arange(P, dtype=np.int32)[None]
+    caps = (100, 70, 45, 20)
+    with capi.Context(0) as ctx:
+        ctx.load_problem(prob)
+        ctx.load_scenarios(scen, orders)
+        ctx.set_scenario_segments(starts, mixes)
+        ctx.run_loaded(True)
+        res = ctx.fetch(True)
+        st = ctx.stats()
+        plans = [ctx.min_plan_vg(cap, cap, 100)[0] for cap in caps]
+        plans = [(int(p.found), int(p.scenario) if p.found else -1) for p in plans]
+    assert st.kernel_variant == capi.KERNEL_NARROW_CACHE and st.n_launches == 1 and len(mixes) == 4096
+    idx = lambda a, b: a * (K + 1) + b                               # noqa: E731
+    sample = sorted({idx(a, b) for a in (0, K) for b in (0, K)} | {idx(0, b) for b in range(K + 1)} | {idx(a, 0) for a in range(K + 1)} |
+                    set(range(0, 4096, 11)))
+    assert len(sample) >= 256
+    sub = sample
+    _assert_segmented(type("R", (), dict(placement=res.placement[sub], unscheduled=res.unscheduled[sub], used_cpu=res.used_cpu[sub],
+                                         used_mem=res.used_mem[sub])), prob, scen[sub], orders, starts, mixes[sub])
+    ca = np.concatenate([[0], np.cumsum(prob.alloc_cpu.astype(np.int64))])
+    cm = np.concatenate([[0], np.cumsum(prob.alloc_mem.astype(np.int64))])
+    tot = lambda c: c[F] + (c[F + mixes[:, 0]] - c[F]) + (c[F + K + mixes[:, 1]] - c[F + K])   # noqa: E731
+    ac, am = tot(ca), tot(cm)
+    cpu = np.array([sim.occupancy_pct(int(u), int(a)) for u, a in zip(res.used_cpu, ac)])
+    mem = np.array([sim.occupancy_pct(int(u) * 1000, int(a) * 1000) for u, a in zip(res.used_mem, am)])
+    assert (res.unscheduled == 0).any() and (res.unscheduled > 0).any()
+    for cap, got in zip(caps, plans):
+        ok = np.flatnonzero((res.unscheduled == 0) & (cpu <= cap) & (mem <= cap))
+        want = (1, int(min(ok, key=lambda s: (int(scen[s, 0]), s)))) if len(ok) else (0, -1)
+        assert got == want, cap
+    assert plans[0][0] == 1
+
+
+def _risk_case():
+    N, F = 47, 12
+    prob, _ = MU.segmentable(randprob.rand_problem(6101, N=N, P=160, presets=True, gates=True, tight_pods=True), fixed=F)
+    rng = np.random.default_rng(1)
+    prob.priority = rng.choice([0, 0, 0, 10, 1000, -5], prob.n_pods).astype(np.int32)
+    prob.init_min_priority = 100
+    starts = np.array([F, 25, 38], np.int32)
+    lens = np.array([13, 13, 9])
+    cnt = np.stack([rng.integers(0, n + 1, 10) for n in lens], 1).astype(np.int32)
+    cnt[0], cnt[1] = lens, 0
+    scen = np.stack([F + cnt.sum(1), rng.integers(0, 2, 10)], 1).astype(np.int32)
+    orders = np.stack([np.arange(160), rng.permutation(160)]).astype(np.int32)
+    return prob, scen, orders, starts, cnt
+
+
+def test_preempt_risk_flags_of_a_segmented_batch():
+    """simon_fetch_preempt_risk on a segmented batch of pods with unequal priorities: the oracle's flag of every scenario on its own nodes
+    (flags set and flags unset in the batch), next to placements and aggregates."""
+    prob, scen, orders, starts, cnt = _risk_case()
+    want = []
+    for s in range(len(scen)):
+        _, ref = MU.oracle_of_scenario(prob, MU.present_mask(prob.n_nodes, starts, cnt[s]), orders[scen[s, 1]])
+        want.append(int(ref.preempt_risk[0]))
+    assert 0 in want and 1 in want
+    with capi.Context(0) as ctx:
+        ctx.load_problem(prob)
+        ctx.load_scenarios(scen, orders)
+        ctx.set_scenario_segments(starts, cnt)
+        ctx.run_loaded(True)
+        res = ctx.fetch(True)
+        assert ctx.fetch_preempt_risk().tolist() == want
+        assert ctx.stats().kernel_variant == capi.KERNEL_NARROW_CACHE
+    _assert_segmented(res, prob, scen, orders, starts, cnt)
