@@ -1023,7 +1023,7 @@ int stage_narrow(simon_ctx* c) {
         }
         // 65 .. 128 signatures: the kernel keeps two per lane (k and k + 64).  When every signature of the upper half can sit 64 slots
         // above a TWIN -- the same request under another table class -- the kernel evaluates a lane's node byte once for both
-        // (TableScalars::static_tables & 16; config 5: 42 request shapes x 2 table classes).  A permutation of the ids, nothing else.
+        // (TableScalars::static_tables & kStTwins; config 5: 42 request shapes x 2 table classes).  A permutation of the ids, nothing else.
         c->sig_twins = false;
         if (c->gfold && (int)sigs.size() > kTableMaxSigs) c->table_ok = false;      // (gfold_supported counted them: cannot happen)
         if (c->table_ok && !c->no_sig_twins && !c->gfold && sigs.size() > 64 && sigs.size() <= 128) {
@@ -2306,11 +2306,12 @@ int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
             TableLaunch f{};
             f.cold = reinterpret_cast<const TableCold*>(c->d_table_cold.p);
             f.cls_list = c->has_ranks ? c->d_rk_ids.p : c->d_cls_list.p; f.pods = c->d_podsC.p; f.orders = c->d_orders.p; f.perm = c->d_perm.p;
-            f.ws_off = c->d_ws_off.p; f.ws = c->d_ws.p; f.coarse = c->table_coarse; f.rest = c->rest; f.spread = c->spread; f.aff = c->rest && !c->aff_idx.empty(); f.team = team; f.lds_ws = lds_ws; f.lds_x = lds_x;
+            f.ws_off = c->d_ws_off.p; f.ws = c->d_ws.p; f.coarse = c->table_coarse; f.rest = c->rest; f.spread = c->spread; f.aff = c->rest && !c->aff_idx.empty(); f.team = team; f.lds_ws = lds_ws; f.lds_x = lds_x; f.nzeq = c->nzeq; f.has_pin = c->has_pin;
             f.place_step = want_placement ? c->d_place_step.p : nullptr;
-            f.sc = TableScalars{(c->N + 63) / 64, c->Cn_t, c->Cp, P, S, c->n_sigs, c->has_ranks ? c->N : 0, (c->has_na ? 1 : 0) | (c->has_tt ? 2 : 0) | (c->has_add ? 4 : 0) | (want_slices ? 8 : 0) | (c->sig_twins ? 16 : 0) | (c->fold ? 32 : 0) | ((c->spread && (c->ipa_fold || c->hard_fold)) ? 64 : 0) | (c->gfold ? 128 : 0) | (c->img_R > 0 ? 256 : 0) | (c->seg_n ? 512 : 0), c->rest ? (int)c->zone_keys.size() : 0, c->rest ? c->rest_M : 0, c->rest ? c->rest_G : 0, c->rest ? c->rest_X : 0, c->spread ? c->sp_TH : 0, c->spread ? c->sp_TZ : 0, c->spread ? (int)c->sp_zkeys.size() : 0, ni_top, c->g_cpu, c->g_mem};
+            f.sc = TableScalars{(c->N + 63) / 64, c->Cn_t, c->Cp, P, S, c->n_sigs, c->has_ranks ? c->N : 0, (c->has_na ? kStNa : 0) | (c->has_tt ? kStTt : 0) | (c->has_add ? kStAdd : 0) | (want_slices ? kStGpuSlices : 0) | (c->sig_twins ? kStTwins : 0) | (c->fold ? kStFold : 0) | ((c->spread && (c->ipa_fold || c->hard_fold)) ? kStSpreadAff : 0) | (c->gfold ? kStGpuFold : 0) | (c->img_R > 0 ? kStImg : 0) | (c->seg_n ? kStSegments : 0), c->rest ? (int)c->zone_keys.size() : 0, c->rest ? c->rest_M : 0, c->rest ? c->rest_G : 0, c->rest ? c->rest_X : 0, c->spread ? c->sp_TH : 0, c->spread ? c->sp_TZ : 0, c->spread ? (int)c->sp_zkeys.size() : 0, ni_top, c->g_cpu, c->g_mem};
+            if (c->debug_route) fprintf(stderr, "[route] unit %s nzeq %d team %d\n", table_unit_name(f), (int)f.nzeq, f.team);
             HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-            HIP_TRY(c, launch_table(f, S, c->has_mask, c->nzeq, c->has_pin, table_lds, c->stream));
+            HIP_TRY(c, launch_table(f, S, table_lds, c->stream));
             if (want_placement)
                 HIP_TRY(c, launch_unpermute(c->d_place_step.p, c->d_inv_orders.p, c->d_scen.p, S, P, c->d_place.p, c->stream));
             HIP_TRY(c, hipEventRecord(c->ev1, c->stream));

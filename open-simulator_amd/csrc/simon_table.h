@@ -15,7 +15,7 @@ struct SigRow {      // one pod request signature (48 B)
     double nz_c, nz_m;     // non-zero request (V/framework/types.go:601-636)
     int32_t cls;           // pod class: row of static_mask / simon_raw
     uint32_t flags;        // bit0: all-zero request (fit.go:244-249)
-    int32_t pad[2];        // GPU fold (TableScalars::static_tables & 128): gpu-mem per device in gcd units, devices requested (0: not a GPU signature; -1: a GPU request for no device)
+    int32_t pad[2];        // GPU fold (TableScalars::static_tables & kStGpuFold): gpu-mem per device in gcd units, devices requested (0: not a GPU signature; -1: a GPU request for no device)
 };
 static_assert(sizeof(SigRow) == 48, "SigRow must be 48 bytes");
 
@@ -30,10 +30,25 @@ static_assert(sizeof(ShapeRow) == 48, "ShapeRow must be 48 bytes");
 // request + 1 << 6 | entries << 12 | offset << 18 of the pod's entries in TableCold::xrows (0 = the score table alone decides the pod)
 struct PodRowC { int32_t sigcls, preset, gate, rest; };
 
+// bits of TableScalars::static_tables
+enum TableStatic : int32_t {
+    kStNa = 1,           // TableCold::na_raw present (NodeAffinity preferred terms)
+    kStTt = 2,           // TableCold::tt_raw present (TaintToleration PreferNoSchedule)
+    kStAdd = 4,          // TableCold::add_raw present (already weighted additions)
+    kStGpuSlices = 8,    // record TableCold::gpu_slices
+    kStTwins = 16,       // signature k + 64 is a twin of k (same request)
+    kStFold = 32,        // TableCold::foldx present (required anti-affinity / host ports on node-level keys folded into the table)
+    kStSpreadAff = 64,   // the SPREAD && AFF instantiations (preferred pod (anti-)affinity / hard zone constraints in spread_select)
+    kStGpuFold = 128,    // Open-Gpu-Share folded into the table (SigRow::pad = GPU request, devices per position behind the workspace)
+    kStImg = 256,        // TableCold::img present (ImageLocality)
+    kStSegments = 512,   // segmented batch (TableCold::scls, ranked instantiations only)
+    kStClassTerms = kStNa | kStTt | kStAdd | kStImg,   // any static score table next to the Simon raw scores in the class term
+};
+
 struct TableScalars {
     int32_t mask_words, Cn, Cp, P, S, K;
     int32_t rk_stride;   // 0: cls_list = the pool's per-class node lists; N: per-scenario lists in rank order (simon_set_node_ranks)
-    int32_t static_tables;   // bit 0 / 1 / 2: TableCold::na_raw / tt_raw / add_raw present; bit 3: record TableCold::gpu_slices; bit 4: signature k + 64 is a twin of k (same request); bit 5: TableCold::foldx present; bit 6: SPREAD && AFF instantiations; bit 7: Open-Gpu-Share folded into the table (SigRow::pad = GPU request, devices per position behind the workspace); bit 8: TableCold::img present; bit 9: segmented batch (TableCold::scls, ranked instantiations only)
+    int32_t static_tables;   // TableStatic bits
     int32_t NZ;          // REST: topology keys that are NOT node-level (a term on one marks every position of the pod's domain)
     int32_t M, G, X;     // REST: rows of the per-block position masks (G GPU requests + X extra-resource requests + 2 x terms)
     int32_t TH, TZ, NZK; // SPREAD: hostname-key term rows, zone-key term rows, zone-like topology keys (class split)
@@ -62,12 +77,12 @@ struct TableCold {
     // allocatable and Requested at the start [N][8] (component 0 = ephemeral storage, 1.. = extended resources)
     const uint32_t *xsig, *xalloc, *i_xused;
     const int32_t* zdom;            // [NZ][N] domain of a node under a zone-like key (-1: no label)
-    unsigned long long* gpu_slices; // [S][P] by pod id: devices Reserve booked (simon_batch_out.gpu_slices), written when TableScalars::static_tables & 8
+    unsigned long long* gpu_slices; // [S][P] by pod id: devices Reserve booked (simon_batch_out.gpu_slices), written when TableScalars::static_tables & kStGpuSlices
     // SPREAD (soft PodTopologySpread constraints, generation 7): per pod class [soft constraints..., counted terms...] in sp_ent
     // (soft: term slot | maxSkew << 16 | SIMON_SPREAD_DUP_KEY bit 30; counted: term slot | multiplicity << 16), each with its term's
     // row: kind (1 hostname-like row, 2 zone-like row) | row << 2 | zone key slot << 16 | (node set + 1) << 19; Go's math.Log table;
     // node sets; zone domain of a class
-    const uint32_t* foldx;          // [K][ceil(K / 32)] (TableScalars::static_tables & 32): bit S of row L = a pod of signature L on a node excludes signature S from it
+    const uint32_t* foldx;          // [K][ceil(K / 32)] (TableScalars::static_tables & kStFold): bit S of row L = a pod of signature L on a node excludes signature S from it
     const int2* sp_ent;             // x = the entry, y = its term's row (kind | row << 2 | zone key slot << 16 | (node set + 1) << 19)
     const double* spread_log;       // [N + 1] math.Log(float64(i + 2)) (simon_class_tables.spread_log)
     const uint64_t* node_sets;      // [R][set_words]
@@ -78,12 +93,12 @@ struct TableCold {
     // REST && SPREAD in one instantiation (round 6): PodRowC::rest keeps the REST descriptor (per pod: its GPU request is part of it), the
     // SPREAD descriptor travels here, by pod id
     const int32_t* sp_word;         // [P]
-    // ImageLocality (ABI v7, TableScalars::static_tables & 256): img[img_slot[s] * img_stride + table class * Cn + internal node class],
+    // ImageLocality (ABI v7, TableScalars::static_tables & kStImg): img[img_slot[s] * img_stride + table class * Cn + internal node class],
     // 0..100, added to the class term next to add_raw
     const unsigned char* img;
     const int32_t* img_slot;        // [S] size slot of a scenario
     int32_t img_stride;             // table classes x internal node classes
-    // segmented batch (simon_set_scenario_segments, TableScalars::static_tables & 512): [S][Cn] nodes of class d that scenario s holds
+    // segmented batch (simon_set_scenario_segments, TableScalars::static_tables & kStSegments): [S][Cn] nodes of class d that scenario s holds
     const int32_t* scls;
 };
 
@@ -98,6 +113,8 @@ struct TableLaunch {
     bool rest;           // some pods need the per-node filters of the REST path (implies coarse)
     bool coarse;         // two-level summary: LDS entries cover 64 positions, per-16 entries live in the workspace (tcarve)
     bool lds_x;          // generation 6 with its mask rows, row totals and the canonical index of every position in LDS (table_kernel: LDSX; batches resident at once)
+    bool nzeq;           // NonZero == request for every pod and node (the Z instantiations)
+    bool has_pin;        // some pod is pinned to a node (HAS_PIN; the REST, SPREAD and LDS-resident units know pinned pods anyway)
     bool lds_ws;         // generation 4 with the scenario's workspace in LDS (table_kernel: LDSWS; small batches of small problems): the dynamic LDS of the launch = summaries + the largest workspace
     TableScalars sc;
 };
@@ -132,26 +149,13 @@ constexpr int kTableMaxClassesPlain = 256;   // ... up to four per lane where on
 
 size_t table_lds_bytes(int K, int ni_max, int Cn, bool coarse, bool rest, int nzk = -1);   // LDS per workgroup for padded scenario sizes up to ni_max (nzk >= 0: SPREAD; | 0x100: second score table; | 0x200: team mode; | 0x400: CN2's larger score table)
 size_t table_ws_bytes(int K, int ni, bool nzeq, bool coarse, int Cn, int M, int NZ, int TH = 0, int TZ = 0);  // HBM workspace of ONE scenario with ni padded positions
-// launches n_blocks scenarios (one 64-thread workgroup each), scenario of block b = a.perm[b]
-hipError_t launch_table(const TableLaunch& a, int n_blocks, bool has_mask, bool nzeq, bool has_pin, size_t lds_bytes, hipStream_t st);
-// the same for a.team == kTeamWaves (64 * team threads per scenario; SPREAD problems only): simon_table_team4.hip
-hipError_t launch_table_team4(const TableLaunch& a, int n_blocks, bool has_mask, bool nzeq, size_t lds_bytes, hipStream_t st);
-// generation 4 with the workspace in LDS (simon_table_lds.hip; lds_bytes = table_lds_bytes(...) rounded up to 128 + the largest table_ws_bytes of the batch)
-hipError_t launch_table_lds(const TableLaunch& a, int n_blocks, bool nzeq, size_t lds_bytes, hipStream_t st);
-// generation 6 with the mask rows in LDS (simon_table_restlds.hip; lds_bytes = table_lds_bytes(...) rounded up to 128 + table_ldsx_bytes(...))
-hipError_t launch_table_rest_lds(const TableLaunch& a, int n_blocks, bool nzeq, size_t lds_bytes, hipStream_t st);
+// launches n_blocks scenarios (one workgroup of 64 * max(team, 1) threads each), scenario of block b = a.perm[b], on the translation unit that
+// serves the launch (simon_table.hip: table_route)
+hipError_t launch_table(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);
+const char* table_unit_name(const TableLaunch& a);   // the unit launch_table sends `a` to, by file name (SIMON_DEBUG_ROUTE)
 inline size_t table_ldsx_bytes(int ni_max, int M) {   // rows [M][ni_max / 16] u16, row totals [M] u32, canonical indices [ni_max] u16 (each rounded up to 128 bytes)
     return ((((size_t)(ni_max >> 4) * M * 2) + 127) & ~(size_t)127) + (((size_t)M * 4 + 127) & ~(size_t)127) + (((size_t)ni_max * 2 + 127) & ~(size_t)127);
 }
-// generation 6, one wave per scenario (simon_table_rest.hip: the REST instantiations, a translation unit of their own since round 5)
-hipError_t launch_table_rest(const TableLaunch& a, int n_blocks, bool nzeq, size_t lds_bytes, hipStream_t st);
-hipError_t launch_table_cls4(const TableLaunch& a, int n_blocks, bool nzeq, size_t lds_bytes, hipStream_t st);    // generation 4 for 129 .. 256 node classes (simon_table_cls4.hip)
-hipError_t launch_table_rest2(const TableLaunch& a, int n_blocks, bool nzeq, size_t lds_bytes, hipStream_t st);   // ... for 65 .. 128 node classes (simon_table_rest2.hip)
-// generation 7, one wave per scenario (simon_table_spread.hip: the SPREAD instantiations, a translation unit of their own)
-hipError_t launch_table_spread(const TableLaunch& a, int n_blocks, bool has_mask, bool nzeq, size_t lds_bytes, hipStream_t st);
-// generation 7 over the position-mask rows of generation 6 (REST && SPREAD: simon_table_rs.hip; <= 64 node classes)
-hipError_t launch_table_rs(const TableLaunch& a, int n_blocks, bool nzeq, size_t lds_bytes, hipStream_t st);
-hipError_t launch_table_spread2(const TableLaunch& a, int n_blocks, bool nzeq, size_t lds_bytes, hipStream_t st);   // ... for 65 .. 128 node classes (simon_table_spread2.hip)
 // placement[s][pod] = place_step[s][inverse order of s][pod]: the kernel records placements by scheduling STEP (coalesced)
 hipError_t launch_unpermute(const int32_t* place_step, const int32_t* inv_orders, const ScenarioDesc* scen, int S, int P,
                             int32_t* placement, hipStream_t st);

@@ -418,7 +418,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     static_assert(NW == 1 || SPREAD, "team mode exists for the SPREAD instantiations");
     static_assert(!CN2 || (SPREAD && !MANY && !REST) || (REST && !LDSX && !SPREAD) || (!REST && !SPREAD && !COARSE && !MANY && !LDSWS), "CN2 = two node classes per lane in spread_select (<= 128 signatures) or in rest_select (rows in HBM); without rows and walks: 129 .. 256 classes on the one-level layout (simon_table_cls4.hip)");
     constexpr int TABMAX = CN2 ? kSpreadTabMax2 : kSpreadTabMax;
-    const TCarve cv = tcarve(K, sc.ni_max, Cn, COARSE, REST, SPREAD ? (sc.NZK | ((sc.static_tables & 64) ? 0x100 : 0) | (NW > 1 ? 0x200 : 0) | (CN2 ? 0x400 : 0)) : -1, kCls4);
+    const TCarve cv = tcarve(K, sc.ni_max, Cn, COARSE, REST, SPREAD ? (sc.NZK | ((sc.static_tables & kStSpreadAff) ? 0x100 : 0) | (NW > 1 ? 0x200 : 0) | (CN2 ? 0x400 : 0)) : -1, kCls4);
     const int TH = SPREAD ? sc.TH : 0, TZ = SPREAD ? sc.TZ : 0, NZK = SPREAD ? sc.NZK : 0;
     signed char* s_zdom = (signed char*)(smem + cv.zdom);          // SPREAD: [NZK][Cn]
     unsigned short* s_stash = (unsigned short*)(smem + cv.stash);  // SPREAD: [positions] count | table byte << 8 of the pod being placed
@@ -471,10 +471,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     static_assert(!LDSX || (REST && NW == 1 && !LDSWS), "LDS-resident mask rows serve generation 6");
     unsigned char* const wsb = LDSWS ? smem + ((cv.total + 127) & ~127) : ws + ws_off[blockIdx.x];
     const int32_t* __restrict__ order = orders + (size_t)__builtin_amdgcn_readfirstlane(scen[s].order_id) * P;
-    // Segmented batch (simon_set_scenario_segments; static_tables & 512, ranked instantiations only): the scenario holds fixed nodes and a
+    // Segmented batch (simon_set_scenario_segments; static_tables & kStSegments, ranked instantiations only): the scenario holds fixed nodes and a
     // prefix of every pool segment, not a prefix of the pool.  Its per-class lists hold its own nodes alone, so the class counts come from
     // its own row (TableCold::scls) and a node is in the scenario iff its rank is below n (the host gives absent nodes rank N).
-    const bool segd = RANKED && (sc.static_tables & 512) != 0;
+    const bool segd = RANKED && (sc.static_tables & kStSegments) != 0;
     auto cnt_at = [&](int d) -> int {                                 // nodes of class d in this scenario (the instantiations without ranks: as before)
         if constexpr (RANKED) { if (segd) return gp(cold->scls)[(size_t)s * Cn + d]; }
         return clsprefix[(size_t)n * Cn + d];
@@ -564,10 +564,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     unsigned* g_zcnt = (unsigned*)(g_hrow + (((size_t)TH * ni + 127) & ~(size_t)127));   // [TZ][16] per domain of a zone-like key
     unsigned char* g_hmax = (unsigned char*)(g_zcnt + (((size_t)TZ * 16 + 31) & ~(size_t)31));   // [TH] largest counter of a hostname-key row
     unsigned short* g_canon = (unsigned short*)(g_hmax + (((size_t)TH + 127) & ~(size_t)127));    // [ni] RANKED: rank of the position's node in the scenario's order
-    // GPU fold (TableScalars::static_tables & 128; the two-level instantiations without REST rows): the devices of every position behind
+    // GPU fold (TableScalars::static_tables & kStGpuFold; the two-level instantiations without REST rows): the devices of every position behind
     // the scenario's workspace -- used [ni][8], per-device total [ni], device count [ni] (gcd units)
     constexpr bool kGpuFoldable = COARSE && !REST && HAS_PIN;
-    const bool gfold = kGpuFoldable && (sc.static_tables & 128);
+    const bool gfold = kGpuFoldable && (sc.static_tables & kStGpuFold);
     unsigned* g_fu = (unsigned*)(wsb + table_ws_of(K, ni, NZEQ, COARSE, Cn, M, NZ, TH, TZ, kCls4));
     unsigned* g_ft = g_fu + (size_t)ni * 8;
     int* g_fc = (int*)(g_ft + ni);
@@ -808,7 +808,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     //   + TaintToleration PreferNoSchedule (DefaultNormalizeScore(100, true): 100 - 100 raw / max, 100 everywhere when max = 0)
     //   + already weighted static scores (NodePreferAvoidPods), small ones only (simon_hip.hip: static_tables_fit).
     // floor(100 x / m) = (int)fma(100 x, 1/m, 0.5/m) for 0 <= x <= m < 2^30 (the la_term argument, simon_device.h).
-    // ImageLocality (static_tables & 256): the first entry of this scenario's size slot -- wave-uniform, a scalar load on the rare path
+    // ImageLocality (static_tables & kStImg): the first entry of this scenario's size slot -- wave-uniform, a scalar load on the rare path
     auto img_base = [&](GPtr<const TableCold> cc) -> size_t {
         return (size_t)__builtin_amdgcn_readfirstlane(gp(cc->img_slot)[s]) * (size_t)cc->img_stride;
     };
@@ -820,20 +820,20 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         int term = (inb && range) ? 2 * (int)__builtin_fma((double)(rawc - lo) * 100.0, rr, 0.5 * rr) : 0;
         GPtr<const TableCold> cc = cold;
         asm volatile("" : "+s"(cc));                                  // rare path: its pointers are fetched here, and only when present
-        if (sc.static_tables & 1) {
+        if (sc.static_tables & kStNa) {
             const int v = gp(cc->na_raw)[c * Cn + dd];
             const int mx = wave_max_i32(inb ? v : 0);
             const double r = mx ? 1.0 / (double)mx : 0.0;
             term += (inb && mx) ? (int)__builtin_fma((double)v * 100.0, r, 0.5 * r) : 0;
         }
-        if (sc.static_tables & 2) {
+        if (sc.static_tables & kStTt) {
             const int v = gp(cc->tt_raw)[c * Cn + dd];
             const int mx = wave_max_i32(inb ? v : 0);
             const double r = mx ? 1.0 / (double)mx : 0.0;
             term += inb ? (mx ? 100 - (int)__builtin_fma((double)v * 100.0, r, 0.5 * r) : 100) : 0;
         }
-        if (sc.static_tables & 4) term += inb ? gp(cc->add_raw)[c * Cn + dd] : 0;
-        if (sc.static_tables & 256) term += inb ? (int)gp(cc->img)[img_base(cc) + c * Cn + dd] : 0;
+        if (sc.static_tables & kStAdd) term += inb ? gp(cc->add_raw)[c * Cn + dd] : 0;
+        if (sc.static_tables & kStImg) term += inb ? (int)gp(cc->img)[img_base(cc) + c * Cn + dd] : 0;
         return term;
     };
     // class_term for two classes per lane (CN2: lane l holds classes d0 = l and d1 = 64 + l): the same formulas with the extremes and
@@ -846,22 +846,22 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         t0 = (in0 && range) ? 2 * (int)__builtin_fma((double)(raw0 - lo) * 100.0, rr, 0.5 * rr) : 0;
         t1 = (in1 && range) ? 2 * (int)__builtin_fma((double)(raw1 - lo) * 100.0, rr, 0.5 * rr) : 0;
         GPtr<const TableCold> cc = cold;
-        if (sc.static_tables & 1) {
+        if (sc.static_tables & kStNa) {
             const int a0 = gp(cc->na_raw)[c * Cn + d0], a1 = gp(cc->na_raw)[c * Cn + d1];
             const int mx = max(wave_max_i32(in0 ? a0 : 0), wave_max_i32(in1 ? a1 : 0));
             const double r = mx ? 1.0 / (double)mx : 0.0;
             t0 += (in0 && mx) ? (int)__builtin_fma((double)a0 * 100.0, r, 0.5 * r) : 0;
             t1 += (in1 && mx) ? (int)__builtin_fma((double)a1 * 100.0, r, 0.5 * r) : 0;
         }
-        if (sc.static_tables & 2) {
+        if (sc.static_tables & kStTt) {
             const int a0 = gp(cc->tt_raw)[c * Cn + d0], a1 = gp(cc->tt_raw)[c * Cn + d1];
             const int mx = max(wave_max_i32(in0 ? a0 : 0), wave_max_i32(in1 ? a1 : 0));
             const double r = mx ? 1.0 / (double)mx : 0.0;
             t0 += in0 ? (mx ? 100 - (int)__builtin_fma((double)a0 * 100.0, r, 0.5 * r) : 100) : 0;
             t1 += in1 ? (mx ? 100 - (int)__builtin_fma((double)a1 * 100.0, r, 0.5 * r) : 100) : 0;
         }
-        if (sc.static_tables & 4) { t0 += in0 ? gp(cc->add_raw)[c * Cn + d0] : 0; t1 += in1 ? gp(cc->add_raw)[c * Cn + d1] : 0; }
-        if (sc.static_tables & 256) {
+        if (sc.static_tables & kStAdd) { t0 += in0 ? gp(cc->add_raw)[c * Cn + d0] : 0; t1 += in1 ? gp(cc->add_raw)[c * Cn + d1] : 0; }
+        if (sc.static_tables & kStImg) {
             const size_t ib = img_base(cc);
             t0 += in0 ? (int)gp(cc->img)[ib + c * Cn + d0] : 0; t1 += in1 ? (int)gp(cc->img)[ib + c * Cn + d1] : 0;
         }
@@ -893,7 +893,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
             for (int g = 0; g < 4; ++g) tq[g] = (inq[g] && range) ? 2 * (int)__builtin_fma((double)(rawq[g] - lo) * 100.0, rr, 0.5 * rr) : 0;
             GPtr<const TableCold> cc = cold;
             asm volatile("" : "+s"(cc));                                  // rare path: its pointers are fetched here, and only when present
-            if (sc.static_tables & 1) {
+            if (sc.static_tables & kStNa) {
                 int a[4], mx = 0;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) a[g] = gp(cc->na_raw)[c * Cn + dq[g]];
@@ -904,7 +904,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
 #pragma unroll
                 for (int g = 0; g < 4; ++g) tq[g] += (inq[g] && mx) ? (int)__builtin_fma((double)a[g] * 100.0, r, 0.5 * r) : 0;
             }
-            if (sc.static_tables & 2) {
+            if (sc.static_tables & kStTt) {
                 int a[4], mx = 0;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) a[g] = gp(cc->tt_raw)[c * Cn + dq[g]];
@@ -915,11 +915,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
 #pragma unroll
                 for (int g = 0; g < 4; ++g) tq[g] += inq[g] ? (mx ? 100 - (int)__builtin_fma((double)a[g] * 100.0, r, 0.5 * r) : 100) : 0;
             }
-            if (sc.static_tables & 4) {
+            if (sc.static_tables & kStAdd) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) tq[g] += inq[g] ? gp(cc->add_raw)[c * Cn + dq[g]] : 0;
             }
-            if (sc.static_tables & 256) {
+            if (sc.static_tables & kStImg) {
                 const size_t ib = img_base(cc);
 #pragma unroll
                 for (int g = 0; g < 4; ++g) tq[g] += inq[g] ? (int)gp(cc->img)[ib + c * Cn + dq[g]] : 0;
@@ -945,22 +945,22 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
             int t0 = (in0 && range) ? 2 * (int)__builtin_fma((double)(raw0 - lo) * 100.0, rr, 0.5 * rr) : 0;
             int t1 = (in1 && range) ? 2 * (int)__builtin_fma((double)(raw1 - lo) * 100.0, rr, 0.5 * rr) : 0;
             GPtr<const TableCold> cc = cold;
-            if (sc.static_tables & 1) {
+            if (sc.static_tables & kStNa) {
                 const int a0 = gp(cc->na_raw)[c * Cn + d0], a1 = gp(cc->na_raw)[c * Cn + d1];
                 const int mx = max(wave_max_i32(in0 ? a0 : 0), wave_max_i32(in1 ? a1 : 0));
                 const double r = mx ? 1.0 / (double)mx : 0.0;
                 t0 += (in0 && mx) ? (int)__builtin_fma((double)a0 * 100.0, r, 0.5 * r) : 0;
                 t1 += (in1 && mx) ? (int)__builtin_fma((double)a1 * 100.0, r, 0.5 * r) : 0;
             }
-            if (sc.static_tables & 2) {
+            if (sc.static_tables & kStTt) {
                 const int a0 = gp(cc->tt_raw)[c * Cn + d0], a1 = gp(cc->tt_raw)[c * Cn + d1];
                 const int mx = max(wave_max_i32(in0 ? a0 : 0), wave_max_i32(in1 ? a1 : 0));
                 const double r = mx ? 1.0 / (double)mx : 0.0;
                 t0 += in0 ? (mx ? 100 - (int)__builtin_fma((double)a0 * 100.0, r, 0.5 * r) : 100) : 0;
                 t1 += in1 ? (mx ? 100 - (int)__builtin_fma((double)a1 * 100.0, r, 0.5 * r) : 100) : 0;
             }
-            if (sc.static_tables & 4) { t0 += in0 ? gp(cc->add_raw)[c * Cn + d0] : 0; t1 += in1 ? gp(cc->add_raw)[c * Cn + d1] : 0; }
-            if (sc.static_tables & 256) {
+            if (sc.static_tables & kStAdd) { t0 += in0 ? gp(cc->add_raw)[c * Cn + d0] : 0; t1 += in1 ? gp(cc->add_raw)[c * Cn + d1] : 0; }
+            if (sc.static_tables & kStImg) {
                 const size_t ib = img_base(cc);
                 t0 += in0 ? (int)gp(cc->img)[ib + c * Cn + d0] : 0; t1 += in1 ? (int)gp(cc->img)[ib + c * Cn + d1] : 0;
             }
@@ -1249,7 +1249,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
             const int gnum = __builtin_amdgcn_readlane((int)my_gsig.y, gs);
             unsigned u[8] = {L.ua.x, L.ua.y, L.ua.z, L.ua.w, L.ub.x, L.ub.y, L.ub.z, L.ub.w};
             const unsigned long long booked = gpu_commit_t(u, L.gc, L.tot, greq, gnum);   // Reserve (open-gpu-share.go:147-188), every lane alike
-            if (__builtin_expect(sc.static_tables & 8, 0)) {              // the caller wants the devices (simon_batch_out.gpu_slices), by pod id
+            if (__builtin_expect(sc.static_tables & kStGpuSlices, 0)) {              // the caller wants the devices (simon_batch_out.gpu_slices), by pod id
                 const int pid = __builtin_amdgcn_readfirstlane(order[step]);
                 if (lane == 0) gp(cold->gpu_slices)[(size_t)s * (size_t)P + (size_t)pid] = booked;
             }
@@ -2087,13 +2087,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
                 oldq[q] = rowp[q][pstar & 15];                         // this signature's byte before the cycle (same cache line as the row)
                 if (COARSE) F[q] = *(const uint2*)(g_fine + ((unsigned)(pstar >> 6) * (unsigned)K + (unsigned)kk[q]) * 4u);
             }
-            // Fold (TableScalars::static_tables & 32): required anti-affinity / host ports on node-level keys.  The landing pod's signature
+            // Fold (TableScalars::static_tables & kStFold): required anti-affinity / host ports on node-level keys.  The landing pod's signature
             // names the signatures that may not use this node any more (TableCold::foldx, one bit per signature): their bytes go to 0 with
             // the refresh below and stay there -- the table's monotone infeasibility; summaries and counters follow as for a full node.
             // Only the two-level instantiations without the REST rows that know pinned pods carry the code (the host picks them for such
             // problems): the kernels of the benchmark configurations stay as they are.
             constexpr bool kFoldable = COARSE && !REST && HAS_PIN;   // (launch_table sends a problem with the fold to the HAS_PIN instantiations)
-            const bool fold = kFoldable && (sc.static_tables & 32);
+            const bool fold = kFoldable && (sc.static_tables & kStFold);
             const unsigned KW = ((unsigned)K + 31u) >> 5;
             unsigned xfold[KQ];
             if constexpr (kFoldable) {
@@ -2237,7 +2237,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
                         // of their own: with them every leave re-bases.
                         bool rebase = left == 0;
                         if constexpr (kCls4) {
-                            if (rebase && !(sc.static_tables & (7 | 256))) {
+                            if (rebase && !(sc.static_tables & kStClassTerms)) {
                                 const int raw = simon_raw[((KQ > 1 && dirty_bit == KQ - 1) ? my_tc[KQ - 1] : my_tc[0]) * Cn + dstar];
                                 const int2 e = s_ext[k];
                                 rebase = !(e.x < raw && raw < e.y);
@@ -2252,11 +2252,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
             };
             // NodeResourcesFit + LeastAllocated + BalancedAllocation of the touched node per signature of this lane.  With 65 .. 128
             // signatures the host puts a signature's twin -- same request, another table class (static mask / Simon row) -- 64 slots up
-            // whenever every upper signature has one (TableScalars::static_tables & 16): the upper byte is the lower lane's, unmasked.
+            // whenever every upper signature has one (TableScalars::static_tables & kStTwins): the upper byte is the lower lane's, unmasked.
             unsigned nbq[KQ];
             nbq[0] = eval_node(my_req_c[0], my_req_m[0], my_nz_c[0], my_nz_m[0], my_zero[0], rq_c, rq_m, nzc, nzm, (int)st.freep, sh);
             if constexpr (KQ > 1) {
-                if (sc.static_tables & 16) nbq[KQ - 1] = nbq[0];
+                if (sc.static_tables & kStTwins) nbq[KQ - 1] = nbq[0];
                 else nbq[KQ - 1] = eval_node(my_req_c[KQ - 1], my_req_m[KQ - 1], my_nz_c[KQ - 1], my_nz_m[KQ - 1], my_zero[KQ - 1], rq_c, rq_m, nzc, nzm, (int)st.freep, sh);
             }
             if constexpr (kFoldable) {
@@ -2283,7 +2283,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
                         u[0] = gfa.x; u[1] = gfa.y; u[2] = gfa.z; u[3] = gfa.w; u[4] = gfb.x; u[5] = gfb.y; u[6] = gfb.z; u[7] = gfb.w;
                         gbooked = true;
                         const unsigned long long booked = gpu_commit_t(u, gfc, gft, greq, gnum);
-                        if (sc.static_tables & 8) {                       // the caller wants the devices (simon_batch_out.gpu_slices), by pod id
+                        if (sc.static_tables & kStGpuSlices) {                       // the caller wants the devices (simon_batch_out.gpu_slices), by pod id
                             const int pid = __builtin_amdgcn_readfirstlane(order[i0 + il]);
                             if (lane == 0) gp(cold->gpu_slices)[(size_t)s * (size_t)P + (size_t)pid] = booked;
                         }
@@ -2375,279 +2375,177 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     }
 }
 
-// launch of one instantiation of the single-wave kernel (shared by this unit and simon_table_rest.hip: a template costs nothing where it is not used)
-template <bool M, bool Z, bool PIN, int KQ, int NBQ, bool COARSE, bool REST, bool RANKED, bool AFF = false, bool MANY = false, bool SPREAD = false, bool CN2 = false>
-static hipError_t launch_t7(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    if constexpr (REST && !AFF) {
-        if (a.aff) return launch_t7<M, Z, PIN, KQ, NBQ, COARSE, REST, RANKED, true, false, false, CN2>(a, n_blocks, lds, st);
-    }
-    if (REST && !CN2 && a.sc.Cn > 64) return hipErrorInvalidValue;    // (65 .. 128 node classes under the REST select: simon_table_rest2.hip)
-    if constexpr (KQ == 2 && COARSE && !MANY && !SPREAD && !CN2) {    // more than 128 signatures: the instantiation with further groups (round 6: also with the REST rows)
-        if (a.sc.K > 128) return launch_t7<M, Z, PIN, KQ, NBQ, COARSE, REST, RANKED, AFF, true>(a, n_blocks, lds, st);
-    }
-    if (!MANY && a.sc.K > 64 * KQ) return hipErrorInvalidValue;       // simon_hip.hip keeps such batches away (two-level, no REST)
-    auto kern = table_kernel<M, Z, PIN, KQ, NBQ, COARSE, REST, RANKED, AFF, MANY, SPREAD, 1, false, false, CN2>;
+// ---- host side: from a TableLaunch to one table_kernel<...> instantiation ------------------------------------------------------------
+// Every translation unit has one entry with this signature; launch_table (the base unit, at the end of the file) picks the unit.
+hipError_t launch_table_team4(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);        // several waves per scenario: simon_table_team4.hip
+hipError_t launch_table_team_nzeq4(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);   // ... its NonZero == request half: simon_table_team4z.hip
+hipError_t launch_table_rs(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);           // generation 7 over the position-mask rows: simon_table_rs.hip
+hipError_t launch_table_rs_nzeq(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);      // ... its NonZero == request half: simon_table_rsz.hip
+hipError_t launch_table_spread2(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);      // generation 7, two node classes per lane: simon_table_spread2.hip
+hipError_t launch_table_spread(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);       // generation 7: simon_table_spread.hip
+hipError_t launch_table_lds(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);          // generation 4, workspace in LDS: simon_table_lds.hip
+hipError_t launch_table_rest2(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);        // generation 6, two node classes per lane: simon_table_rest2.hip
+hipError_t launch_table_rest_lds(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);     // generation 6, mask rows in LDS: simon_table_restlds.hip
+hipError_t launch_table_rest(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);         // generation 6: simon_table_rest.hip
+hipError_t launch_table_cls4(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);         // generation 4, 129 .. 256 node classes: simon_table_cls4.hip
+
+// The launch itself: `waves` per workgroup, one workgroup per scenario.
+template <class Kern>
+static hipError_t launch_kernel(Kern kern, const TableLaunch& a, int n_blocks, int waves, size_t lds, hipStream_t st) {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64), lds, st, a.cold, a.cls_list, a.pods, a.orders, a.perm, a.ws_off, a.place_step, a.ws, a.sc);
+    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * waves), lds, st, a.cold, a.cls_list, a.pods, a.orders, a.perm, a.ws_off, a.place_step, a.ws, a.sc);
     return hipGetLastError();
 }
-template <bool M, bool Z, bool PIN, int KQ, int NBQ, bool COARSE, bool REST = false, bool CN2 = false>
-static hipError_t launch_t6(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    return a.sc.rk_stride != 0 ? launch_t7<M, Z, PIN, KQ, NBQ, COARSE, REST, true, false, false, false, CN2>(a, n_blocks, lds, st)
-                               : launch_t7<M, Z, PIN, KQ, NBQ, COARSE, REST, false, false, false, false, CN2>(a, n_blocks, lds, st);
+
+// Run-time flags as compile-time constants: with_consts(f, flag, OneOf<1, 2>{n}, ...) calls f(std::bool_constant<flag>{},
+// std::integral_constant<int, n>{}, ...), so that f names its kernel's template arguments by its parameters.  A value outside its set is
+// refused.  f prunes the combinations that must not exist with `if constexpr`: what it does not name is not instantiated.
+template <int... Vs> struct OneOf { int v; };
+template <class F> static hipError_t with_consts(F&& f) { return f(); }
+template <class F, class... Rest> static hipError_t with_consts(F&& f, bool b, Rest... rest);
+template <class F, int V, int... Vs, class... Rest> static hipError_t with_consts(F&& f, OneOf<V, Vs...> o, Rest... rest) {
+    if (o.v == V) return with_consts([&](auto... c) -> hipError_t { return f(std::integral_constant<int, V>{}, c...); }, rest...);
+    if constexpr (sizeof...(Vs) > 0) return with_consts(f, OneOf<Vs...>{o.v}, rest...);
+    else return hipErrorInvalidValue;
 }
+template <class F, class... Rest> static hipError_t with_consts(F&& f, bool b, Rest... rest) {
+    return b ? with_consts([&](auto... c) -> hipError_t { return f(std::true_type{}, c...); }, rest...)
+             : with_consts([&](auto... c) -> hipError_t { return f(std::false_type{}, c...); }, rest...);
+}
+
+// The flags every unit derives the same way
+static OneOf<1, 2> table_kq(const TableLaunch& a) { return {a.sc.K > 64 ? 2 : 1}; }                        // signatures per lane in registers
+static OneOf<1, 2> table_nbq64(const TableLaunch& a) { return {a.sc.ni_max / 64 <= 64 ? 1 : 2}; }           // two-level: LDS entries of 64 positions per lane
+static OneOf<1, 2, 4> table_nbq16(const TableLaunch& a) { const int nblk = a.sc.ni_max / 16; return {nblk <= 64 ? 1 : nblk <= 128 ? 2 : 4}; }   // one-level: entries of 16 positions per lane
+static bool table_ranked(const TableLaunch& a) { return a.sc.rk_stride != 0; }                             // per-scenario node order (a sweep over several zones)
+static bool table_folds(const TableLaunch& a) { return (a.sc.static_tables & (kStFold | kStGpuFold)) != 0; }   // (the folds are carried by COARSE && !REST && HAS_PIN: the base unit alone)
+static bool table_spread_aff(const TableLaunch& a) { return (a.sc.static_tables & kStSpreadAff) != 0; }    // preferred pod (anti-)affinity / hard zone constraints in spread_select: SPREAD && AFF
+// More than 128 signatures on the two-level layout (MANY: two per lane in registers + further groups of 128 from memory).  Under generation 7's
+// walks one shape (KQ = 2, two entries per lane) serves every cluster size: the regime is rare.
+static bool table_many(const TableLaunch& a) { return a.sc.K > 128; }
+
+// The halves by NonZero == request of the units that compile as two hipcc processes (simon_table_team<N>z.hip, simon_table_rsz.hip define SIMON_TABLE_NZEQ_HALF)
+#ifdef SIMON_TABLE_NZEQ_HALF
+constexpr bool kHalfZ = true;
+#else
+constexpr bool kHalfZ = false;
+#endif
+
 #ifdef SIMON_TABLE_TEAM_TU
 // ---- this translation unit (simon_table_team<N>.hip) holds the team-mode instantiations only: NW = SIMON_TABLE_TEAM_TU waves per scenario ----
 constexpr int kTuWaves = SIMON_TABLE_TEAM_TU;
 #define SIMON_TEAM_CAT2(a, b) a##b
 #define SIMON_TEAM_CAT(a, b) SIMON_TEAM_CAT2(a, b)
-template <bool M, bool Z, int KQ, int NBQ, bool RANKED, bool AFF, bool CN2 = false, bool REST = false, bool MANY = false>
-static hipError_t launch_team6(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    if constexpr (!CN2 && !REST) {                                    // the walks over the position-mask rows (REST && SPREAD): <= 64 classes
-        if (a.rest) {
-            if (a.sc.Cn > 64) return hipErrorInvalidValue;
-            if constexpr (!AFF) { if (a.aff) return launch_team6<M, Z, KQ, NBQ, RANKED, true, false, true>(a, n_blocks, lds, st); }
-            return launch_team6<M, Z, KQ, NBQ, RANKED, AFF, false, true>(a, n_blocks, lds, st);
-        }
-    }
-    if (a.rest && !REST) return hipErrorInvalidValue;
-    if constexpr (!CN2 && !REST) {                                    // 65 .. 128 node classes: two per lane in the walks
-        if (a.sc.Cn > 64) return launch_team6<M, Z, KQ, NBQ, RANKED, AFF, true>(a, n_blocks, lds, st);
-    }
-    if constexpr (KQ == 2 && NBQ == 2 && !CN2 && !MANY) {             // 129 .. 1 023 signatures (round 6: the leader's refresh takes the further groups along as the single wave does)
-        if (a.sc.K > 128) return launch_team6<M, Z, KQ, NBQ, RANKED, AFF, false, REST, true>(a, n_blocks, lds, st);
-    }
-    if ((!MANY && a.sc.K > 64 * KQ) || (!CN2 && a.sc.Cn > 64)) return hipErrorInvalidValue;
-    auto kern = table_kernel<M, Z, true, KQ, NBQ, true, REST, RANKED, AFF, MANY, true, kTuWaves, false, false, CN2>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * kTuWaves), lds, st, a.cold, a.cls_list, a.pods, a.orders, a.perm, a.ws_off, a.place_step, a.ws, a.sc);
-    return hipGetLastError();
-}
-template <bool M, bool Z, int KQ, int NBQ>
-static hipError_t launch_team4(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    const bool ranked = a.sc.rk_stride != 0, ipa = (a.sc.static_tables & 64) != 0;     // (& 64: preferred pod (anti-)affinity / hard zone constraints: SPREAD && AFF)
-    if (ranked) return ipa ? launch_team6<M, Z, KQ, NBQ, true, true>(a, n_blocks, lds, st) : launch_team6<M, Z, KQ, NBQ, true, false>(a, n_blocks, lds, st);
-    return ipa ? launch_team6<M, Z, KQ, NBQ, false, true>(a, n_blocks, lds, st) : launch_team6<M, Z, KQ, NBQ, false, false>(a, n_blocks, lds, st);
-}
-template <bool M, bool Z>
-static hipError_t launch_team2(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    const bool one = a.sc.ni_max / 64 <= 64 && a.sc.K <= 128;        // (more than 128 signatures: one shape, two entries per lane)
-    if (a.sc.K > 64) return one ? launch_team4<M, Z, 2, 1>(a, n_blocks, lds, st) : launch_team4<M, Z, 2, 2>(a, n_blocks, lds, st);
-    return one ? launch_team4<M, Z, 1, 1>(a, n_blocks, lds, st) : launch_team4<M, Z, 1, 2>(a, n_blocks, lds, st);
+static hipError_t launch_team_half(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
+    const bool cn2 = a.sc.Cn > 64, many = table_many(a);             // 65 .. 128 node classes: two per lane in the walks; 129 .. 1 023 signatures: the leader's refresh takes the further groups along
+    if (cn2 && (a.rest || many)) return hipErrorInvalidValue;         // (the walks over the position-mask rows, and the further groups: <= 64 classes)
+    const OneOf<1, 2> nbq = many ? OneOf<1, 2>{2} : table_nbq64(a);
+    return with_consts([&](auto KQ, auto NBQ, auto RANKED, auto AFF, auto CN2, auto REST, auto MANY) -> hipError_t {
+        if constexpr ((CN2 && (REST || MANY)) || (MANY && (KQ != 2 || NBQ != 2))) return hipErrorInvalidValue;
+        else return launch_kernel(table_kernel<true, kHalfZ, true, KQ, NBQ, true, REST, RANKED, AFF, MANY, true, kTuWaves, false, false, CN2>, a, n_blocks, kTuWaves, lds, st);
+    }, table_kq(a), nbq, table_ranked(a), table_spread_aff(a) || (a.rest && a.aff), cn2, a.rest, many);
 }
 // The unit's instantiations in two halves by NonZero == request (Z), each a hipcc process of its own (the unit was the build's longest pole by far:
-// 4 m 37 s next to 16 others on 8 cores): simon_table_team<N>z.hip defines SIMON_TABLE_NZEQ_HALF and holds Z = true, simon_table_team<N>.hip the rest + the entry.
+// 4 m 37 s next to 16 others on 8 cores): simon_table_team<N>z.hip holds Z = true, simon_table_team<N>.hip the rest + the entry.
 #ifdef SIMON_TABLE_NZEQ_HALF
 hipError_t SIMON_TEAM_CAT(launch_table_team_nzeq, SIMON_TABLE_TEAM_TU)(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
-    return launch_team2<true, true>(a, n_blocks, lds_bytes, st);
+    return launch_team_half(a, n_blocks, lds_bytes, st);
 }
 #else
-hipError_t SIMON_TEAM_CAT(launch_table_team_nzeq, SIMON_TABLE_TEAM_TU)(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);
-hipError_t SIMON_TEAM_CAT(launch_table_team, SIMON_TABLE_TEAM_TU)(const TableLaunch& a, int n_blocks, bool has_mask, bool nzeq, size_t lds_bytes, hipStream_t st) {
+hipError_t SIMON_TEAM_CAT(launch_table_team, SIMON_TABLE_TEAM_TU)(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
     if (!a.spread || !a.coarse || a.team != kTuWaves) return hipErrorInvalidValue;
-    (void)has_mask;                                                   // (a run-time test of the prologue: TableCold::static_mask is null without one)
-    return nzeq ? SIMON_TEAM_CAT(launch_table_team_nzeq, SIMON_TABLE_TEAM_TU)(a, n_blocks, lds_bytes, st) : launch_team2<true, false>(a, n_blocks, lds_bytes, st);
+    return a.nzeq ? SIMON_TEAM_CAT(launch_table_team_nzeq, SIMON_TABLE_TEAM_TU)(a, n_blocks, lds_bytes, st) : launch_team_half(a, n_blocks, lds_bytes, st);
 }
 #endif
 #elif defined(SIMON_TABLE_SPREAD_TU)
-// ---- this translation unit (simon_table_spread.hip) holds generation 7: the single-wave SPREAD instantiations (80 of the largest kernels of
+// ---- this translation unit (simon_table_spread.hip) holds generation 7: the single-wave SPREAD instantiations (among the largest kernels of
 // the library -- next to simon_table.hip instead of inside it, build() runs one hipcc process per unit) ----
-template <bool M, bool Z, int KQ, int NBQ, bool RANKED, bool AFF, bool MANY>
-static hipError_t launch_sp7(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    if (!MANY && a.sc.K > 64 * KQ) return hipErrorInvalidValue;
-    auto kern = table_kernel<M, Z, true, KQ, NBQ, true, false, RANKED, AFF, MANY, true>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64), lds, st, a.cold, a.cls_list, a.pods, a.orders, a.perm, a.ws_off, a.place_step, a.ws, a.sc);
-    return hipGetLastError();
-}
-template <bool M, bool Z, int KQ>
-static hipError_t launch_sp4(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    const bool ranked = a.sc.rk_stride != 0, ipa = (a.sc.static_tables & 64) != 0;     // (& 64: preferred pod (anti-)affinity / hard zone constraints in spread_select: SPREAD && AFF)
-    if constexpr (KQ == 2) {
-        // 129 .. 1 023 signatures behind Services (round 4): the signature groups of MANY under generation 7's walks.  The walk reads its
-        // pod's row of the table whatever the signature's number; the refresh takes the further groups along as it does without the
-        // walks.  One shape (two entries per lane) serves every cluster size: the regime is rare.
-        if (a.sc.K > 128) {
-            if (ipa) return ranked ? launch_sp7<M, Z, KQ, 2, true, true, true>(a, n_blocks, lds, st) : launch_sp7<M, Z, KQ, 2, false, true, true>(a, n_blocks, lds, st);
-            return ranked ? launch_sp7<M, Z, KQ, 2, true, false, true>(a, n_blocks, lds, st) : launch_sp7<M, Z, KQ, 2, false, false, true>(a, n_blocks, lds, st);
-        }
-    }
-    const bool one = a.sc.ni_max / 64 <= 64;
-    if (ipa) {
-        if (ranked) return one ? launch_sp7<M, Z, KQ, 1, true, true, false>(a, n_blocks, lds, st) : launch_sp7<M, Z, KQ, 2, true, true, false>(a, n_blocks, lds, st);
-        return one ? launch_sp7<M, Z, KQ, 1, false, true, false>(a, n_blocks, lds, st) : launch_sp7<M, Z, KQ, 2, false, true, false>(a, n_blocks, lds, st);
-    }
-    if (ranked) return one ? launch_sp7<M, Z, KQ, 1, true, false, false>(a, n_blocks, lds, st) : launch_sp7<M, Z, KQ, 2, true, false, false>(a, n_blocks, lds, st);
-    return one ? launch_sp7<M, Z, KQ, 1, false, false, false>(a, n_blocks, lds, st) : launch_sp7<M, Z, KQ, 2, false, false, false>(a, n_blocks, lds, st);
-}
-template <bool M, bool Z>
-static hipError_t launch_sp2(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    return a.sc.K > 64 ? launch_sp4<M, Z, 2>(a, n_blocks, lds, st) : launch_sp4<M, Z, 1>(a, n_blocks, lds, st);
-}
-hipError_t launch_table_spread(const TableLaunch& a, int n_blocks, bool has_mask, bool nzeq, size_t lds_bytes, hipStream_t st) {
+hipError_t launch_table_spread(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
     if (!a.spread || !a.coarse || a.rest || a.team > 1) return hipErrorInvalidValue;
-    (void)has_mask;
-    return nzeq ? launch_sp2<true, true>(a, n_blocks, lds_bytes, st) : launch_sp2<true, false>(a, n_blocks, lds_bytes, st);
+    // 129 .. 1 023 signatures behind Services (round 4): the signature groups of MANY under generation 7's walks.  The walk reads its
+    // pod's row of the table whatever the signature's number; the refresh takes the further groups along as it does without the walks.
+    const bool many = table_many(a);
+    const OneOf<1, 2> nbq = many ? OneOf<1, 2>{2} : table_nbq64(a);
+    return with_consts([&](auto Z, auto KQ, auto NBQ, auto RANKED, auto AFF, auto MANY) -> hipError_t {
+        if constexpr (MANY && (KQ != 2 || NBQ != 2)) return hipErrorInvalidValue;
+        else return launch_kernel(table_kernel<true, Z, true, KQ, NBQ, true, false, RANKED, AFF, MANY, true>, a, n_blocks, 1, lds_bytes, st);
+    }, a.nzeq, table_kq(a), nbq, table_ranked(a), table_spread_aff(a), many);
 }
 #elif defined(SIMON_TABLE_SPREAD2_TU)
 // ---- this translation unit (simon_table_spread2.hip) holds generation 7 for 65 .. 128 internal node classes (CN2): <= 128 signatures,
 // one wave per scenario ----
-template <bool Z, int KQ, int NBQ, bool RANKED = false, bool AFF = false>
-static hipError_t launch_sc3(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    if constexpr (!RANKED) {
-        if (a.sc.rk_stride != 0) return launch_sc3<Z, KQ, NBQ, true, AFF>(a, n_blocks, lds, st);
-    }
-    if constexpr (!AFF) {                                             // (& 64: preferred pod (anti-)affinity / hard zone constraints in spread_select: SPREAD && AFF)
-        if (a.sc.static_tables & 64) return launch_sc3<Z, KQ, NBQ, RANKED, true>(a, n_blocks, lds, st);
-    }
-    if (a.sc.K > 64 * KQ) return hipErrorInvalidValue;
-    auto kern = table_kernel<true, Z, true, KQ, NBQ, true, false, RANKED, AFF, false, true, 1, false, false, true>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64), lds, st, a.cold, a.cls_list, a.pods, a.orders, a.perm, a.ws_off, a.place_step, a.ws, a.sc);
-    return hipGetLastError();
-}
-template <bool Z, int KQ>
-static hipError_t launch_sc2(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    return a.sc.ni_max / 64 <= 64 ? launch_sc3<Z, KQ, 1>(a, n_blocks, lds, st) : launch_sc3<Z, KQ, 2>(a, n_blocks, lds, st);
-}
-hipError_t launch_table_spread2(const TableLaunch& a, int n_blocks, bool nzeq, size_t lds_bytes, hipStream_t st) {
+hipError_t launch_table_spread2(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
     if (!a.spread || !a.coarse || a.rest || a.team > 1 || a.sc.Cn <= 64 || a.sc.K > 128) return hipErrorInvalidValue;
-    if (a.sc.K > 64) return nzeq ? launch_sc2<true, 2>(a, n_blocks, lds_bytes, st) : launch_sc2<false, 2>(a, n_blocks, lds_bytes, st);
-    return nzeq ? launch_sc2<true, 1>(a, n_blocks, lds_bytes, st) : launch_sc2<false, 1>(a, n_blocks, lds_bytes, st);
+    return with_consts([&](auto Z, auto KQ, auto NBQ, auto RANKED, auto AFF) -> hipError_t {
+        return launch_kernel(table_kernel<true, Z, true, KQ, NBQ, true, false, RANKED, AFF, false, true, 1, false, false, true>, a, n_blocks, 1, lds_bytes, st);
+    }, a.nzeq, table_kq(a), table_nbq64(a), table_ranked(a), table_spread_aff(a));
 }
 #elif defined(SIMON_TABLE_LDS_TU)
-// ---- this translation unit (simon_table_lds.hip) holds generation 4 with the scenario's workspace in LDS (LDSWS): small batches of small problems ----
-template <bool Z, int KQ, int NBQ, bool RANKED = false>
-static hipError_t launch_lds3(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    if constexpr (!RANKED) {                                          // per-scenario node order (a sweep over several zones): its own instantiation
-        if (a.sc.rk_stride != 0) return launch_lds3<Z, KQ, NBQ, true>(a, n_blocks, lds, st);
-    }
-    if (a.sc.K > 64 * KQ) return hipErrorInvalidValue;
-    auto kern = table_kernel<true, Z, true, KQ, NBQ, false, false, RANKED, false, false, false, 1, true>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64), lds, st, a.cold, a.cls_list, a.pods, a.orders, a.perm, a.ws_off, a.place_step, a.ws, a.sc);
-    return hipGetLastError();
-}
-template <bool Z, int KQ>
-static hipError_t launch_lds2(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    const int nblk = a.sc.ni_max / 16;
-    return nblk <= 64 ? launch_lds3<Z, KQ, 1>(a, n_blocks, lds, st) : nblk <= 128 ? launch_lds3<Z, KQ, 2>(a, n_blocks, lds, st) : launch_lds3<Z, KQ, 4>(a, n_blocks, lds, st);
-}
-hipError_t launch_table_lds(const TableLaunch& a, int n_blocks, bool nzeq, size_t lds_bytes, hipStream_t st) {
-    if (!a.lds_ws || a.coarse || a.rest || a.spread || a.team > 1 || a.sc.K > 128 || (a.sc.static_tables & (32 | 128))) return hipErrorInvalidValue;
-    if (a.sc.K > 64) return nzeq ? launch_lds2<true, 2>(a, n_blocks, lds_bytes, st) : launch_lds2<false, 2>(a, n_blocks, lds_bytes, st);
-    return nzeq ? launch_lds2<true, 1>(a, n_blocks, lds_bytes, st) : launch_lds2<false, 1>(a, n_blocks, lds_bytes, st);
+// ---- this translation unit (simon_table_lds.hip) holds generation 4 with the scenario's workspace in LDS (LDSWS): small batches of small problems;
+// lds_bytes = table_lds_bytes(...) rounded up to 128 + the largest table_ws_bytes of the batch ----
+hipError_t launch_table_lds(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
+    if (!a.lds_ws || a.coarse || a.rest || a.spread || a.team > 1 || a.sc.K > 128 || table_folds(a)) return hipErrorInvalidValue;
+    return with_consts([&](auto Z, auto KQ, auto NBQ, auto RANKED) -> hipError_t {
+        return launch_kernel(table_kernel<true, Z, true, KQ, NBQ, false, false, RANKED, false, false, false, 1, true>, a, n_blocks, 1, lds_bytes, st);
+    }, a.nzeq, table_kq(a), table_nbq16(a), table_ranked(a));
 }
 #elif defined(SIMON_TABLE_RESTLDS_TU)
-// ---- this translation unit (simon_table_restlds.hip) holds generation 6 with its mask rows, row totals and canonical indices in LDS (LDSX) ----
-template <bool Z, int KQ, int NBQ, bool AFF, bool RANKED = false>
-static hipError_t launch_rl4(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    if constexpr (!RANKED) {
-        if (a.sc.rk_stride != 0) return launch_rl4<Z, KQ, NBQ, AFF, true>(a, n_blocks, lds, st);
-    }
-    if (a.sc.K > 64 * KQ) return hipErrorInvalidValue;
-    auto kern = table_kernel<true, Z, true, KQ, NBQ, true, true, RANKED, AFF, false, false, 1, false, true>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64), lds, st, a.cold, a.cls_list, a.pods, a.orders, a.perm, a.ws_off, a.place_step, a.ws, a.sc);
-    return hipGetLastError();
-}
-template <bool Z, int KQ>
-static hipError_t launch_rl2(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    const bool one = a.sc.ni_max / 64 <= 64;
-    if (a.aff) return one ? launch_rl4<Z, KQ, 1, true>(a, n_blocks, lds, st) : launch_rl4<Z, KQ, 2, true>(a, n_blocks, lds, st);
-    return one ? launch_rl4<Z, KQ, 1, false>(a, n_blocks, lds, st) : launch_rl4<Z, KQ, 2, false>(a, n_blocks, lds, st);
-}
-hipError_t launch_table_rest_lds(const TableLaunch& a, int n_blocks, bool nzeq, size_t lds_bytes, hipStream_t st) {
-    if (!a.lds_x || !a.rest || !a.coarse || a.spread || a.team > 1) return hipErrorInvalidValue;
-    if (a.sc.K > 64) return nzeq ? launch_rl2<true, 2>(a, n_blocks, lds_bytes, st) : launch_rl2<false, 2>(a, n_blocks, lds_bytes, st);
-    return nzeq ? launch_rl2<true, 1>(a, n_blocks, lds_bytes, st) : launch_rl2<false, 1>(a, n_blocks, lds_bytes, st);
+// ---- this translation unit (simon_table_restlds.hip) holds generation 6 with its mask rows, row totals and canonical indices in LDS (LDSX);
+// lds_bytes = table_lds_bytes(...) rounded up to 128 + table_ldsx_bytes(...) ----
+hipError_t launch_table_rest_lds(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
+    if (!a.lds_x || !a.rest || !a.coarse || a.spread || a.team > 1 || a.sc.K > 128) return hipErrorInvalidValue;
+    return with_consts([&](auto Z, auto KQ, auto NBQ, auto RANKED, auto AFF) -> hipError_t {
+        return launch_kernel(table_kernel<true, Z, true, KQ, NBQ, true, true, RANKED, AFF, false, false, 1, false, true>, a, n_blocks, 1, lds_bytes, st);
+    }, a.nzeq, table_kq(a), table_nbq64(a), table_ranked(a), a.aff);
 }
 #elif defined(SIMON_TABLE_RS_TU)
 // ---- this translation unit (simon_table_rs.hip) holds generation 7's walks over generation 6's position-mask rows (REST && SPREAD): one wave per
 // scenario (or the team unit's four), <= 64 node classes ----
-template <bool Z, int KQ, int NBQ, bool RANKED = false, bool AFF = false>
-static hipError_t launch_rs3(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    if constexpr (!RANKED) {
-        if (a.sc.rk_stride != 0) return launch_rs3<Z, KQ, NBQ, true, AFF>(a, n_blocks, lds, st);
-    }
-    if constexpr (!AFF) {                                             // (& 64: preferred pod (anti-)affinity / hard zone constraints in the walk; a.aff: required-affinity entries)
-        if ((a.sc.static_tables & 64) || a.aff) return launch_rs3<Z, KQ, NBQ, RANKED, true>(a, n_blocks, lds, st);
-    }
-    if constexpr (KQ == 2 && NBQ == 2) {                              // 129 .. 1 023 signatures: the signature groups of MANY (one shape, as for generation 7 alone)
-        if (a.sc.K > 128) {
-            auto kern = table_kernel<true, Z, true, 2, 2, true, true, RANKED, AFF, true, true>;
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64), lds, st, a.cold, a.cls_list, a.pods, a.orders, a.perm, a.ws_off, a.place_step, a.ws, a.sc);
-            return hipGetLastError();
-        }
-    }
-    if (a.sc.K > 64 * KQ) return hipErrorInvalidValue;
-    auto kern = table_kernel<true, Z, true, KQ, NBQ, true, true, RANKED, AFF, false, true>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64), lds, st, a.cold, a.cls_list, a.pods, a.orders, a.perm, a.ws_off, a.place_step, a.ws, a.sc);
-    return hipGetLastError();
-}
-template <bool Z, int KQ>
-static hipError_t launch_rs2(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    if constexpr (KQ == 2) { if (a.sc.K > 128) return launch_rs3<Z, KQ, 2>(a, n_blocks, lds, st); }
-    return a.sc.ni_max / 64 <= 64 ? launch_rs3<Z, KQ, 1>(a, n_blocks, lds, st) : launch_rs3<Z, KQ, 2>(a, n_blocks, lds, st);
+static hipError_t launch_rs_half(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
+    const bool many = table_many(a);                                  // 129 .. 1 023 signatures: the signature groups of MANY (one shape, as for generation 7 alone)
+    const OneOf<1, 2> nbq = many ? OneOf<1, 2>{2} : table_nbq64(a);
+    return with_consts([&](auto KQ, auto NBQ, auto RANKED, auto AFF, auto MANY) -> hipError_t {
+        if constexpr (MANY && (KQ != 2 || NBQ != 2)) return hipErrorInvalidValue;
+        else return launch_kernel(table_kernel<true, kHalfZ, true, KQ, NBQ, true, true, RANKED, AFF, MANY, true>, a, n_blocks, 1, lds, st);
+    }, table_kq(a), nbq, table_ranked(a), table_spread_aff(a) || a.aff, many);   // (AFF: preferred pod (anti-)affinity / hard zone constraints in the walk, or required-affinity entries)
 }
 // (two halves by NonZero == request, as the team unit: simon_table_rsz.hip holds Z = true, simon_table_rs.hip the rest + the entry)
 #ifdef SIMON_TABLE_NZEQ_HALF
-hipError_t launch_table_rs_nzeq(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
-    return a.sc.K > 64 ? launch_rs2<true, 2>(a, n_blocks, lds_bytes, st) : launch_rs2<true, 1>(a, n_blocks, lds_bytes, st);
-}
+hipError_t launch_table_rs_nzeq(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) { return launch_rs_half(a, n_blocks, lds_bytes, st); }
 #else
-hipError_t launch_table_rs_nzeq(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);
-hipError_t launch_table_rs(const TableLaunch& a, int n_blocks, bool nzeq, size_t lds_bytes, hipStream_t st) {
-    if (!a.spread || !a.rest || !a.coarse || a.team > 1 || a.lds_x || a.sc.Cn > 64 || (a.sc.static_tables & (32 | 128))) return hipErrorInvalidValue;
-    if (nzeq) return launch_table_rs_nzeq(a, n_blocks, lds_bytes, st);
-    return a.sc.K > 64 ? launch_rs2<false, 2>(a, n_blocks, lds_bytes, st) : launch_rs2<false, 1>(a, n_blocks, lds_bytes, st);
+hipError_t launch_table_rs(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
+    if (!a.spread || !a.rest || !a.coarse || a.team > 1 || a.lds_x || a.sc.Cn > 64 || table_folds(a)) return hipErrorInvalidValue;
+    return a.nzeq ? launch_table_rs_nzeq(a, n_blocks, lds_bytes, st) : launch_rs_half(a, n_blocks, lds_bytes, st);
 }
 #endif
 #elif defined(SIMON_TABLE_CLS4_TU)
 // ---- this translation unit (simon_table_cls4.hip) holds generations 4 for 129 .. 256 internal node classes: one-level layout, > 2 048 padded positions (a class
 // segment is padded to 16), so NBQ = 4; the instantiation that knows pinned pods serves every problem ----
-template <bool Z>
-static hipError_t launch_cls4b(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    return a.sc.K > 64 ? launch_t6<true, Z, true, 2, 4, false, false, true>(a, n_blocks, lds, st) : launch_t6<true, Z, true, 1, 4, false, false, true>(a, n_blocks, lds, st);
-}
-hipError_t launch_table_cls4(const TableLaunch& a, int n_blocks, bool nzeq, size_t lds_bytes, hipStream_t st) {
-    if (a.rest || a.spread || a.coarse || a.team > 1 || a.lds_ws || a.sc.Cn <= 128 || a.sc.Cn > kTableMaxClassesPlain || a.sc.K > 128 || (a.sc.static_tables & (32 | 128))) return hipErrorInvalidValue;
-    return nzeq ? launch_cls4b<true>(a, n_blocks, lds_bytes, st) : launch_cls4b<false>(a, n_blocks, lds_bytes, st);
+hipError_t launch_table_cls4(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
+    if (a.rest || a.spread || a.coarse || a.team > 1 || a.lds_ws || a.sc.Cn <= 128 || a.sc.Cn > kTableMaxClassesPlain || a.sc.K > 128 || table_folds(a)) return hipErrorInvalidValue;
+    return with_consts([&](auto Z, auto KQ, auto RANKED) -> hipError_t {
+        return launch_kernel(table_kernel<true, Z, true, KQ, 4, false, false, RANKED, false, false, false, 1, false, false, true>, a, n_blocks, 1, lds_bytes, st);
+    }, a.nzeq, table_kq(a), table_ranked(a));
 }
 #elif defined(SIMON_TABLE_REST2_TU)
 // ---- this translation unit (simon_table_rest2.hip) holds generation 6 for 65 .. 128 internal node classes (CN2 in rest_select; rows in HBM) ----
-template <bool Z, int KQ>
-static hipError_t launch_rest2c(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    return a.sc.ni_max / 64 <= 64 ? launch_t6<true, Z, true, KQ, 1, true, true, true>(a, n_blocks, lds, st)
-                                  : launch_t6<true, Z, true, KQ, 2, true, true, true>(a, n_blocks, lds, st);
-}
-hipError_t launch_table_rest2(const TableLaunch& a, int n_blocks, bool nzeq, size_t lds_bytes, hipStream_t st) {
-    if (!a.rest || !a.coarse || a.spread || a.team > 1 || a.lds_x || a.sc.Cn <= 64) return hipErrorInvalidValue;
-    if (a.sc.K > 64) return nzeq ? launch_rest2c<true, 2>(a, n_blocks, lds_bytes, st) : launch_rest2c<false, 2>(a, n_blocks, lds_bytes, st);
-    return nzeq ? launch_rest2c<true, 1>(a, n_blocks, lds_bytes, st) : launch_rest2c<false, 1>(a, n_blocks, lds_bytes, st);
+hipError_t launch_table_rest2(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
+    if (!a.rest || !a.coarse || a.spread || a.team > 1 || a.lds_x || a.sc.Cn <= 64 || a.sc.K > 128) return hipErrorInvalidValue;
+    return with_consts([&](auto Z, auto KQ, auto NBQ, auto RANKED, auto AFF) -> hipError_t {
+        return launch_kernel(table_kernel<true, Z, true, KQ, NBQ, true, true, RANKED, AFF, false, false, 1, false, false, true>, a, n_blocks, 1, lds_bytes, st);
+    }, a.nzeq, table_kq(a), table_nbq64(a), table_ranked(a), a.aff);
 }
 #elif defined(SIMON_TABLE_REST_TU)
 // ---- this translation unit (simon_table_rest.hip) holds generation 6: the REST instantiations (position masks: Open-Gpu-Share devices,
-// required (anti-)affinity, host ports, ephemeral storage / extended resources) -- the 32 largest kernels of the single-wave family ----
-template <bool Z, int KQ>
-static hipError_t launch_rest2(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    return a.sc.ni_max / 64 <= 64 ? launch_t6<true, Z, true, KQ, 1, true, true>(a, n_blocks, lds, st)
-                                  : launch_t6<true, Z, true, KQ, 2, true, true>(a, n_blocks, lds, st);
-}
-hipError_t launch_table_rest(const TableLaunch& a, int n_blocks, bool nzeq, size_t lds_bytes, hipStream_t st) {
+// required (anti-)affinity, host ports, ephemeral storage / extended resources) -- the largest kernels of the single-wave family ----
+hipError_t launch_table_rest(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
     if (!a.rest || !a.coarse || a.spread || a.team > 1) return hipErrorInvalidValue;
-    if (a.sc.K > 64) return nzeq ? launch_rest2<true, 2>(a, n_blocks, lds_bytes, st) : launch_rest2<false, 2>(a, n_blocks, lds_bytes, st);
-    return nzeq ? launch_rest2<true, 1>(a, n_blocks, lds_bytes, st) : launch_rest2<false, 1>(a, n_blocks, lds_bytes, st);
+    if (a.sc.Cn > 64) return hipErrorInvalidValue;                    // (65 .. 128 node classes under the REST select: simon_table_rest2.hip)
+    return with_consts([&](auto Z, auto KQ, auto NBQ, auto RANKED, auto AFF, auto MANY) -> hipError_t {
+        if constexpr (MANY && KQ != 2) return hipErrorInvalidValue;
+        else return launch_kernel(table_kernel<true, Z, true, KQ, NBQ, true, true, RANKED, AFF, MANY, false>, a, n_blocks, 1, lds_bytes, st);
+    }, a.nzeq, table_kq(a), table_nbq64(a), table_ranked(a), a.aff, table_many(a));
 }
 #else
 // placement[s][pod] = place_step[s][inv_order[order_id(s)][pod]]: gather (scattered reads hit L2, stores coalesced)
@@ -2691,44 +2589,57 @@ hipError_t launch_unpermute(const int32_t* place_step, const int32_t* inv_orders
     return hipGetLastError();
 }
 
-template <bool M, bool Z, bool PIN, int KQ>
-static hipError_t launch_t4(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    if constexpr (PIN) {                                              // REST rides on the instantiation that knows pinned pods: simon_table_rest.hip
-        if (a.rest && a.sc.Cn > 64) return launch_table_rest2(a, n_blocks, Z, lds, st);   // two node classes per lane in the REST select: simon_table_rest2.hip
-        if (a.rest) return a.lds_x ? launch_table_rest_lds(a, n_blocks, Z, lds, st) : launch_table_rest(a, n_blocks, Z, lds, st);
-    }
-    if (a.spread) return hipErrorInvalidValue;                        // (generation 7 lives in simon_table_spread.hip: launch_table_spread)
-    if (a.coarse) {                                                   // entries of 64 positions: <= 8192 padded positions
-        return a.sc.ni_max / 64 <= 64 ? launch_t6<M, Z, PIN, KQ, 1, true>(a, n_blocks, lds, st) : launch_t6<M, Z, PIN, KQ, 2, true>(a, n_blocks, lds, st);
-    }
-    if (a.sc.Cn > 128) return launch_table_cls4(a, n_blocks, Z, lds, st);   // 129 .. 256 node classes: simon_table_cls4.hip
-    const int nblk = a.sc.ni_max / 16;
-    return nblk <= 64 ? launch_t6<M, Z, PIN, KQ, 1, false>(a, n_blocks, lds, st)
-           : nblk <= 128 ? launch_t6<M, Z, PIN, KQ, 2, false>(a, n_blocks, lds, st) : launch_t6<M, Z, PIN, KQ, 4, false>(a, n_blocks, lds, st);
-}
-
 size_t table_lds_bytes(int K, int ni_max, int Cn, bool coarse, bool rest, int nzk) { return (size_t)tcarve(K, ni_max, Cn, coarse, rest, nzk, !coarse && Cn > 128).total; }
 size_t table_ws_bytes(int K, int ni, bool nzeq, bool coarse, int Cn, int M, int NZ, int TH, int TZ) { return table_ws_of(K, ni, nzeq, coarse, Cn, M, NZ, TH, TZ, !coarse && Cn > 128); }
 
-template <bool M, bool Z, bool PIN>
-static hipError_t launch_t3(const TableLaunch& a, int n_blocks, size_t lds, hipStream_t st) {
-    return a.sc.K > 64 ? launch_t4<M, Z, PIN, 2>(a, n_blocks, lds, st) : launch_t4<M, Z, PIN, 1>(a, n_blocks, lds, st);
-}
-template <bool M, bool Z>
-static hipError_t launch_t2(const TableLaunch& a, int n_blocks, bool has_pin, size_t lds, hipStream_t st) {
-    return has_pin ? launch_t3<M, Z, true>(a, n_blocks, lds, st) : launch_t3<M, Z, false>(a, n_blocks, lds, st);
+// ---- this translation unit (simon_table.hip) holds generations 4 and 5 without rows and walks, and the route to every other unit ----
+static hipError_t launch_table_base(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
+    if (a.spread || a.rest || a.team > 1 || a.lds_ws || (!a.coarse && a.sc.Cn > 128)) return hipErrorInvalidValue;
+    const bool many = a.coarse && table_many(a);
+    if (!many && a.sc.K > 128) return hipErrorInvalidValue;           // simon_hip.hip keeps such batches away (more than 128 signatures: two-level only)
+    const bool pin = a.has_pin || table_folds(a);                     // HAS_PIN: pinned pods, or a fold (carried by COARSE && !REST && HAS_PIN)
+    const OneOf<1, 2, 4> nbq = a.coarse ? OneOf<1, 2, 4>{table_nbq64(a).v} : table_nbq16(a);   // entries of 64 positions: <= 8192 padded positions; of 16: <= 4096
+    return with_consts([&](auto Z, auto PIN, auto KQ, auto COARSE, auto NBQ, auto RANKED, auto MANY) -> hipError_t {
+        if constexpr ((COARSE && NBQ == 4) || (MANY && !(COARSE && KQ == 2))) return hipErrorInvalidValue;
+        else return launch_kernel(table_kernel<true, Z, PIN, KQ, NBQ, COARSE, false, RANKED, false, MANY, false>, a, n_blocks, 1, lds_bytes, st);
+    }, a.nzeq, pin, table_kq(a), a.coarse, nbq, table_ranked(a), many);
 }
 
-hipError_t launch_table(const TableLaunch& a, int n_blocks, bool has_mask, bool nzeq, bool has_pin, size_t lds_bytes, hipStream_t st) {
-    if (a.team > 1)                                                   // several waves per scenario: simon_table_team<N>.hip
-        return a.team == kTeamWaves ? launch_table_team4(a, n_blocks, has_mask, nzeq, lds_bytes, st) : hipErrorInvalidValue;
-    if (a.spread && a.rest) return launch_table_rs(a, n_blocks, nzeq, lds_bytes, st);             // generation 7 over the position-mask rows: simon_table_rs.hip
-    if (a.spread && a.sc.Cn > 64) return launch_table_spread2(a, n_blocks, nzeq, lds_bytes, st);   // generation 7, two node classes per lane: simon_table_spread2.hip
-    if (a.spread) return launch_table_spread(a, n_blocks, has_mask, nzeq, lds_bytes, st);   // generation 7: simon_table_spread.hip
-    if (a.lds_ws) return launch_table_lds(a, n_blocks, nzeq, lds_bytes, st);                // generation 4, workspace in LDS: simon_table_lds.hip
-    has_pin = has_pin || a.rest || (a.sc.static_tables & (32 | 128));   // (& 32, & 128: the folds, carried by COARSE && !REST && HAS_PIN)
-    (void)has_mask;                                                   // (HAS_MASK is a prologue-only, run-time test since round 5: one instantiation serves both)
-    return nzeq ? launch_t2<true, true>(a, n_blocks, has_pin, lds_bytes, st) : launch_t2<true, false>(a, n_blocks, has_pin, lds_bytes, st);
+// Which unit serves a launch: the first rule that holds.  Each unit's entry restates its side of this as its precondition.
+enum class TableUnit { Team, Rs, Spread2, Spread, Lds, Rest2, RestLds, Rest, Cls4, Base };
+static TableUnit table_route(const TableLaunch& a) {
+    if (a.team > 1) return TableUnit::Team;                           // several waves per scenario (SPREAD only, with or without the REST rows)
+    if (a.spread && a.rest) return TableUnit::Rs;                     // generation 7 over the position-mask rows
+    if (a.spread && a.sc.Cn > 64) return TableUnit::Spread2;          // generation 7, two node classes per lane
+    if (a.spread) return TableUnit::Spread;                           // generation 7
+    if (a.lds_ws) return TableUnit::Lds;                              // generation 4, workspace in LDS
+    if (a.rest && a.sc.Cn > 64) return TableUnit::Rest2;              // generation 6, two node classes per lane in the REST select
+    if (a.rest && a.lds_x) return TableUnit::RestLds;                 // generation 6, mask rows in LDS
+    if (a.rest) return TableUnit::Rest;                               // generation 6
+    if (!a.coarse && a.sc.Cn > 128) return TableUnit::Cls4;           // generation 4, 129 .. 256 node classes
+    return TableUnit::Base;                                           // generations 4 and 5
+}
+
+const char* table_unit_name(const TableLaunch& a) {
+    static const char* const names[] = {"simon_table_team4", "simon_table_rs", "simon_table_spread2", "simon_table_spread", "simon_table_lds",
+                                        "simon_table_rest2", "simon_table_restlds", "simon_table_rest", "simon_table_cls4", "simon_table"};
+    return names[(int)table_route(a)];
+}
+
+hipError_t launch_table(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
+    switch (table_route(a)) {
+        case TableUnit::Team: return a.team == kTeamWaves ? launch_table_team4(a, n_blocks, lds_bytes, st) : hipErrorInvalidValue;
+        case TableUnit::Rs: return launch_table_rs(a, n_blocks, lds_bytes, st);
+        case TableUnit::Spread2: return launch_table_spread2(a, n_blocks, lds_bytes, st);
+        case TableUnit::Spread: return launch_table_spread(a, n_blocks, lds_bytes, st);
+        case TableUnit::Lds: return launch_table_lds(a, n_blocks, lds_bytes, st);
+        case TableUnit::Rest2: return launch_table_rest2(a, n_blocks, lds_bytes, st);
+        case TableUnit::RestLds: return launch_table_rest_lds(a, n_blocks, lds_bytes, st);
+        case TableUnit::Rest: return launch_table_rest(a, n_blocks, lds_bytes, st);
+        case TableUnit::Cls4: return launch_table_cls4(a, n_blocks, lds_bytes, st);
+        case TableUnit::Base: return launch_table_base(a, n_blocks, lds_bytes, st);
+    }
+    return hipErrorInvalidValue;
 }
 #endif  // SIMON_TABLE_TEAM_TU
 

@@ -312,3 +312,29 @@ def test_spill_scan_flags_a_spill_ahead_of_the_exec_restore(tmp_path):
     good.write_text("kern:\n.LBB0_2:\n\ts_or_b64 exec, exec, s[0:1]\n\tscratch_store_dwordx2 off, v[12:13], off offset:796 ; 8-byte Folded Spill\n"
                     ".LBB0_3:\n\tv_add_u32_e32 v0, 1, v0\n\tscratch_store_dword off, v0, off offset:4 ; 4-byte Folded Spill\n\ts_or_b64 exec, exec, s[2:3]\n\ts_endpgm\n")
     assert mod.scan(str(good)) == (2, [])
+
+
+def test_built_kernels_match_the_manifest():
+    """profiles/kernel_manifest.txt pins the kernels of every translation unit by mangled name.  The flags of a launch become template
+    arguments in the host code at the end of simon_table.hip: a combination too many there costs build time and code size and nothing fails,
+    one too few refuses launches only a fuzzer reaches.  build() leaves every unit's assembly in build/isa/; both directions are compared."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("kernel_manifest", os.path.join(ROOT, "profiles", "kernel_manifest.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    import __graft_entry__ as g
+    want = mod.read_manifest()
+    assert sorted(want) == sorted(s[:-4] for s in g.HIP_SOURCES)
+    assert all(names == sorted(set(names)) for names in want.values())
+    table = {u: n for u, n in want.items() if u.startswith("simon_table")}
+    owner = {}
+    for unit, names in table.items():                   # (the all-feature kernel's units share their small helper kernels)
+        for n in names:
+            assert owner.setdefault(n, unit) == unit, f"{n} is listed for {owner[n]} and {unit}"
+    assert sum(sum("table_kernel" in n for n in names) for names in table.values()) == 464 and sum(len(n) for n in table.values()) == 466
+    have = mod.scan()
+    if not have:
+        pytest.skip("no build/isa/*.s: build() ran without the ISA scan")
+    assert sorted(have) == sorted(want), "build/isa/ does not hold one file per translation unit"
+    diff = mod.compare(have, want)
+    assert not diff, "; ".join(f"{u}: {len(miss)} missing {miss[:2]}, {len(extra)} unexpected {extra[:2]}" for u, miss, extra in diff)
