@@ -407,6 +407,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
 #else
     constexpr bool TIE_FIRST = REST || MANY;                          // MANY: a lost speculation would reload three groups of rows
 #endif
+    // The plain pod's cycle as straight-line code (the assume is expanded inside the branch that chose the node, see the scheduling loop): the
+    // instantiations whose select is the summary scan alone.  REST rows, SPREAD walks and the further signature groups of MANY hold too much in
+    // registers for a second copy of the assume; they keep one call behind the merge of their selects.
+    constexpr bool kStraight = !REST && !SPREAD && !MANY;
     static_assert(!MANY || (KQ == 2 && COARSE && !CN2 && !LDSX), "MANY = groups of 128 signatures on the two-level layout (since round 6 also under the REST select: its rows and counters are indexed by signature already)");
     constexpr int NG = MANY ? 2 : 0;                                  // further signature groups (K <= 128 (1 + NG))
     static_assert(!SPREAD || COARSE, "SPREAD is built on the two-level layout");
@@ -1928,10 +1932,23 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         unsigned rtv = 0;                                                  // lane e: placed pods counted on entry e's row (required affinity)
         if (REST && AFF && lane < r_nrows && ((unsigned)rowv >> 31)) rtv = g_rowtot[(unsigned)rowv & 0xFFFFu];
 
+        // -------- assume: NodeInfo.AddPod (V/framework/types.go:482-508) + table column + summary ----
+        // One body (simon_table_assume.inc) for every branch of the cycle that has chosen a node.  The instantiations without REST rows, SPREAD walks
+        // and further signature groups (kStraight) expand it twice, through this lambda: behind the summary scan with scanned = true, bound = false
+        // as constants -- the plain pod runs from its pod word to the back edge without a merge, and nothing the rare pods define differently (the
+        // summary entries, the tie check) lives outside that branch -- and once more behind the cold pk < 0 branch.  The others include it once, as
+        // plain statements where the block always stood: wrapped in a lambda the same text cost the MANY instantiations 12 .. 16 VGPRs and a wave
+        // per SIMD (179 against 167 VGPRs at KQ = NBQ = 2; config 3 with 200 signatures 83.2 -> 86.1 ms).
+        const uint4* const sel_tab = (const uint4*)kSel;               // (named in the kernel's own body: a lambda that names the table makes it an external symbol, reached through the GOT)
+        auto assume = [&](const bool scanned, const bool bound, int& pstar, int& dstar, int& res, const unsigned top, const unsigned (&m16q)[NBQ], const unsigned (&e16q)[NBQ]) __attribute__((always_inline)) {
+            if constexpr (kStraight) {
+#include "simon_table_assume.inc"
+            }
+        };
         // res: what the placement row records for this step: >= 0 an index into cls_list (turned into the canonical node index
         // 64 steps at a time, off the critical path), -1 unschedulable, -2 not part of the scenario
         int res, pstar = -1, dstar = 0;
-        unsigned top = 0, m16q[NBQ];
+        unsigned top = 0, m16q[NBQ], e16q[NBQ];                        // (e16q: the entries' totals, m16q >> UB)
         bool scanned = false, bound = false;                           // bound: a preset pod (no Reserve: the scheduler never saw it)
         // a pod with soft spread constraints / preferred pod (anti-)affinity / hard zone constraints: every node's score moves -- the one
         // select the whole team takes part in (a single call site below: helpers skip everything else of the cycle)
@@ -1962,12 +1979,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
                     if (REST && rw != 0) clear = !((__builtin_amdgcn_readfirstlane(excluded(pp >> 4, r_nrows, rowv, r_gs, r_xs, aff_escape(r_nrows, rowv, rtv))) >> (pp & 15)) & 1u);
                     if (byte != 0 && clear) { res = __builtin_amdgcn_readfirstlane(gp(cc->cls_off)[dp]) + rk; pstar = pp; dstar = dp; }
                 }
-                if (res < 0) ++unsched;
+            }
+            if constexpr (kStraight) {
+                if (pstar >= 0) assume(false, bound, pstar, dstar, res, 0u, m16q, e16q);   // (no scan: the entries are not read)
             }
         } else if (REST && __builtin_expect(rw != 0, 0) && !(RS && spread_pod)) {   // (cold for the register allocator: spills belong here)
             pstar = rest_select(r_sig, r_cls, r_nrows, rowv, r_gs, r_xs, aff_escape(r_nrows, rowv, rtv), dstar, res);
             TPROF(10);                                                 // REST pods: the whole select
-            if (pstar < 0) { ++unsched; res = -1; }
+            if (pstar < 0) res = -1;
         } else if (spread_pod) {
             const int k = r_sig;
             const unsigned dq = (unsigned)__builtin_amdgcn_readlane((int)my_dirty, k & 63);
@@ -1979,7 +1998,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
                 if constexpr (RS) pstar = spread_select(k, r_cls, sp_soft, sp_match, sp_ipa, sp_hard, spv, spt, dstar, res, r_nrows, rowv, r_gs, r_xs, aff_escape(r_nrows, rowv, rtv));
                 else pstar = spread_select(k, r_cls, sp_soft, sp_match, sp_ipa, sp_hard, spv, spt, dstar, res);
                 TPROF(18);                                             // spread: winner
-                if (pstar < 0) { ++unsched; res = -1; }
+                if (pstar < 0) res = -1;
             }
         } else {
             const int k = r_sig;
@@ -1989,7 +2008,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
                 if (lane == (k & 63)) my_dirty &= ~(1u << (k >> 6));
             }
             // -------- summary scan: one u16 per 16 (COARSE: 64) positions ------------------------------
-            const unsigned short* srow = s_sum + k * nbp;
+            // (the row's offset is computed behind the re-base, from a copy of k the compiler cannot follow: shared with the re-base's own
+            // it arrives through a merge of the two paths, and the copies on the plain pod's edge cost it two branches and a flag)
+            int ks = k;
+            asm volatile("" : "+s"(ks));
+            const unsigned short* srow = s_sum + ks * nbp;
             unsigned key = 0;
 #pragma unroll
             for (int q = 0; q < NBQ; ++q) {
@@ -2001,14 +2024,24 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
             for (int q = 0; q < NBQ; ++q) {
                 // (total + 1) << KB | (last - b) << UB | UNIT - 1 - pos  ==  (total + 1) << KB | PMASK - position; an entry of 0 (no
                 // feasible node behind it) stays below 1 << KB
+                // The total (entry >> UB) is taken out once, by an instruction the compiler cannot fold -- left to it, the shift becomes a
+                // shift-and-mask of the key, and the tie check below shifts again -- and serves both: and-or and shift-add finish the key (the
+                // fields do not overlap: the sum is the bitwise or), and the tie check compares the totals it finds.
+                // (kStraight only: two more values live through the REST / MANY selects cost their instantiations a wave per SIMD, 168 -> 170 VGPRs)
                 const unsigned m16 = m16q[q];
-                key = max(key, (((m16 << (KB - UB)) & ~PMASK) | (unsigned)cb[q]) | (m16 & UMASK));
+                if constexpr (kStraight) {
+                    unsigned e;
+                    asm("v_lshrrev_b32 %0, %2, %1" : "=v"(e) : "v"(m16), "n"(UB));
+                    e16q[q] = e;
+                    key = max(key, (e << KB) + ((m16 & UMASK) | (unsigned)cb[q]));
+                } else {
+                    key = max(key, (((m16 << (KB - UB)) & ~PMASK) | (unsigned)cb[q]) | (m16 & UMASK));
+                }
             }
             TPROF_WAIT_LDS; TPROF(1);                                  // pod row, dirty check, summary row arrived
             key = wave_max_u32(key);
             TPROF(2);                                                  // key build + wave max
             if (__builtin_expect(key <= PMASK, 0)) {                   // FitError: pod deleted, state unchanged
-                ++unsched;
                 res = -1;
             } else {
                 pstar = (int)(PMASK - (key & PMASK));                  // first maximum in POSITION order (speculative: tie check below)
@@ -2017,6 +2050,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
                 dstar = info >> 16;
                 res = (info & 0xFFFF) - 8192 + pstar;                  // index into cls_list
                 scanned = true;
+                if constexpr (kStraight) assume(true, false, pstar, dstar, res, top, m16q, e16q);
             }
         }
         if constexpr (NW > 1) {
@@ -2024,330 +2058,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
                 if constexpr (RS) pstar = spread_select(r_sig, r_cls, sp_soft, sp_match, sp_ipa, sp_hard, spv, spt, dstar, res, r_nrows, rowv, r_gs, r_xs, aff_escape(r_nrows, rowv, rtv));
                 else pstar = spread_select(r_sig, r_cls, sp_soft, sp_match, sp_ipa, sp_hard, spv, spt, dstar, res);
                 TPROF(18);                                             // spread: winner
-                if (pstar < 0) { ++unsched; res = -1; }
+                if (pstar < 0) res = -1;
             }
         }
-        // -------- assume: NodeInfo.AddPod (V/framework/types.go:482-508) + table column + summary ----
-        if (lead && pstar >= 0) {
-            TPROF(3);                                                  // winner info
-            // Position order is canonical order inside a class only: do entries of ANOTHER class reach the same total?  Then the
-            // first maximum in CANONICAL order decides (static per-class node lists, L2-hot).
-            auto tie_with_other_class = [&]() -> bool {
-                bool other = false;
-#pragma unroll
-                for (int q = 0; q < NBQ; ++q) other = other || ((m16q[q] >> UB) == top && bcls[q] != dstar);   // duplicates carry entry 0's class
-                return __ballot(other) != 0;
-            };
-            auto canonical_first = [&]() -> int {
-#ifdef SIMON_TABLE_PROFILE
-                tp_acc[7] += 1;                                        // how often the canonical tie-break runs
-#endif
-                unsigned key2 = 0;
-                int canon[NBQ];
-#pragma unroll
-                for (int q = 0; q < NBQ; ++q) {
-                    const int pq = (q * 64 + lane) * UNIT + (UNIT - 1) - (int)(m16q[q] & UMASK);
-                    const bool tied = (m16q[q] >> UB) == top && q * 64 + lane < nun;
-                    if constexpr (LDSX) canon[q] = tied ? (int)sx_canon[pq] : (int)PMASK;
-                    else {
-                    canon[q] = tied ? cls_list[rk_off + (unsigned)((binfo[q] & 0xFFFF) - 8192 + pq)] : (int)PMASK;
-                    if (ranked && tied) canon[q] = gp(cold->rk_rank)[(size_t)s * (size_t)cold->N + canon[q]];
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < NBQ; ++q) {
-                    const int pq = (q * 64 + lane) * UNIT + (UNIT - 1) - (int)(m16q[q] & UMASK);
-                    if ((m16q[q] >> UB) == top && q * 64 + lane < nun) key2 = max(key2, ((PMASK - (unsigned)canon[q]) << KB) | (unsigned)pq);
-                }
-                key2 = wave_max_u32(key2);
-                return (int)(key2 & PMASK);
-            };
-            // Generations 4 / 5 speculate: the loads of the first maximum in POSITION order go out first and the tie check runs while
-            // they are in flight (it fires on 0.2 % of the cycles of config 3).  The REST instantiation resolves the tie BEFORE it
-            // loads: its problems split node classes into nodes with / without devices -- twin classes of one shape that tie on
-            // every other cycle (config 5: 49 %), and a lost speculation costs a second round trip to the scenario's workspace.
-            if (TIE_FIRST && scanned && __builtin_expect(tie_with_other_class(), 0)) {
-                const int p2 = canonical_first();
-                if (p2 != pstar) {
-                    pstar = p2;
-                    const int info = winner_info(pstar >> UB);
-                    dstar = info >> 16;
-                    res = (info & 0xFFFF) - 8192 + pstar;
-                }
+        if constexpr (!kStraight) {
+            if (lead && pstar >= 0) {
+#include "simon_table_assume.inc"
             }
-            NodeState st = g_state[pstar];
-            unsigned char* rowp[KQ];
-            uint4 T[KQ];
-            uint2 F[KQ];                                               // COARSE: the four per-16 entries of (signature, touched 64 positions)
-            unsigned oldq[KQ];
-#pragma unroll
-            for (int q = 0; q < KQ; ++q) {
-                rowp[q] = g_tile + (tile_blk((unsigned)(pstar >> 4)) + koff[q]);   // uniform table base + 32-bit byte offset
-                T[q] = *(const uint4*)rowp[q];
-                oldq[q] = rowp[q][pstar & 15];                         // this signature's byte before the cycle (same cache line as the row)
-                if (COARSE) F[q] = *(const uint2*)(g_fine + ((unsigned)(pstar >> 6) * (unsigned)K + (unsigned)kk[q]) * 4u);
-            }
-            // Fold (TableScalars::static_tables & kStFold): required anti-affinity / host ports on node-level keys.  The landing pod's signature
-            // names the signatures that may not use this node any more (TableCold::foldx, one bit per signature): their bytes go to 0 with
-            // the refresh below and stay there -- the table's monotone infeasibility; summaries and counters follow as for a full node.
-            // Only the two-level instantiations without the REST rows that know pinned pods carry the code (the host picks them for such
-            // problems): the kernels of the benchmark configurations stay as they are.
-            constexpr bool kFoldable = COARSE && !REST && HAS_PIN;   // (launch_table sends a problem with the fold to the HAS_PIN instantiations)
-            const bool fold = kFoldable && (sc.static_tables & kStFold);
-            const unsigned KW = ((unsigned)K + 31u) >> 5;
-            unsigned xfold[KQ];
-            if constexpr (kFoldable) {
-                if (__builtin_expect(fold, 0)) {                      // (a uniform branch)
-#pragma unroll
-                    for (int q = 0; q < KQ; ++q) xfold[q] = gp(cold->foldx)[(unsigned)r_sig * KW + ((unsigned)kk[q] >> 5)];
-                }
-            }
-            // MANY: the rows of the signatures beyond the register-resident ones, same round trip (uniform group conditions)
-            unsigned xfg[NG ? NG : 1][KQ];
-            unsigned char* rowg[NG ? NG : 1][KQ];
-            uint4 Tg[NG ? NG : 1][KQ];
-            uint2 Fg[NG ? NG : 1][KQ];
-            unsigned oldg[NG ? NG : 1][KQ];
-            int kg[NG ? NG : 1][KQ];
-            if constexpr (MANY) {
-#pragma unroll
-                for (int g = 0; g < NG; ++g) {
-                    if (128 * (g + 1) < K) {
-#pragma unroll
-                        for (int q = 0; q < KQ; ++q) {
-                            const int k = 128 * (g + 1) + 64 * q + lane;
-                            kg[g][q] = k < K ? k : 0;
-                            rowg[g][q] = g_tile + (tile_blk((unsigned)(pstar >> 4)) + (unsigned)kg[g][q] * KS);
-                            Tg[g][q] = *(const uint4*)rowg[g][q];
-                            oldg[g][q] = rowg[g][q][pstar & 15];
-                            Fg[g][q] = *(const uint2*)(g_fine + ((unsigned)(pstar >> 6) * (unsigned)K + (unsigned)kg[g][q]) * 4u);
-                            if (__builtin_expect(fold, 0)) xfg[g][q] = gp(cold->foldx)[(unsigned)r_sig * KW + ((unsigned)kg[g][q] >> 5)];
-                        }
-                    }
-                }
-            }
-            uint2 z = make_uint2(0, 0);
-            if (!NZEQ) z = g_nz[pstar];
-            if (!TIE_FIRST && scanned && __builtin_expect(tie_with_other_class(), 0)) {   // rare: first maximum in CANONICAL order
-                const int p2 = canonical_first();
-                if (p2 != pstar) {                                     // the speculated winner loses the tie: load the real one
-                    pstar = p2;
-                    const int info = winner_info(pstar >> UB);
-                    dstar = info >> 16;
-                    res = (info & 0xFFFF) - 8192 + pstar;
-                    st = g_state[pstar];
-#pragma unroll
-                    for (int q = 0; q < KQ; ++q) {
-                        rowp[q] = g_tile + (tile_blk((unsigned)(pstar >> 4)) + koff[q]);
-                        T[q] = *(const uint4*)rowp[q];
-                        oldq[q] = rowp[q][pstar & 15];
-                        if (COARSE) F[q] = *(const uint2*)(g_fine + ((unsigned)(pstar >> 6) * (unsigned)K + (unsigned)kk[q]) * 4u);
-                    }
-                    if (!NZEQ) z = g_nz[pstar];
-                }
-            }
-            const int blk = pstar >> 4, pos = pstar & 15;
-            RestLoads RL{};
-            if (REST && __builtin_expect(rw != 0, 0)) RL = rest_assume_load(pstar, r_nrows, rowv, bound ? -1 : r_gs, r_xs);
-            // GPU fold: the landing position's devices travel with the assume's loads (uniform addresses)
-            uint4 gfa = make_uint4(0, 0, 0, 0), gfb = make_uint4(0, 0, 0, 0);
-            unsigned gft = 0;
-            int gfc = 0;
-            if constexpr (kGpuFoldable) {
-                if (__builtin_expect(gfold, 0)) {
-                    gfc = g_fc[pstar]; gft = g_ft[pstar];
-                    gfa = *(const uint4*)(g_fu + (size_t)pstar * 8); gfb = *(const uint4*)(g_fu + (size_t)pstar * 8 + 4);
-                }
-            }
-            SpreadLoads SPL{0u, 0u, false};
-            if (SPREAD && sp_match != 0) SPL = spread_count_load(pstar, dstar, res, spv, spt, sp_soft, sp_match);
-            const ShapeRow sh = shape_of(dstar);
-            unsigned snq[KQ];
-#pragma unroll
-            for (int q = 0; q < KQ; ++q) snq[q] = s_sn[kk[q] * Cn + dstar];
-            // byte -> u16 expansion selectors of the touched block row with the new byte already in place (kSel, above)
-            const uint4 selA = ((const uint4*)kSel)[pos * 2], selB = ((const uint4*)kSel)[pos * 2 + 1];
-            TPROF_WAIT_LDS; TPROF(4);                                  // loads issued; shape row and class term arrived (LDS)
-            TPROF_WAIT_MEM; TPROF(5);                                  // node state and table row arrived (L2 / HBM)
-            const int sl = r_sig & 63;
-            const bool hiq = KQ > 1 && (r_sig >> 6);
-            unsigned add_c, add_m, addz_c = 0, addz_m = 0;
-            if (MANY && __builtin_expect(r_sig >= 64 * KQ, 0)) {       // a signature beyond the register-resident ones (K > 128): its row
-                const SigRow rs = sigs[r_sig];                         // (uniform index: scalar loads)
-                add_c = (unsigned)rs.req_c; add_m = (unsigned)rs.req_m; addz_c = (unsigned)rs.nz_c; addz_m = (unsigned)rs.nz_m;
-            } else {
-                add_c = (unsigned)(hiq ? __builtin_amdgcn_readlane((int)my_add_c[KQ - 1], sl) : __builtin_amdgcn_readlane((int)my_add_c[0], sl));
-                add_m = (unsigned)(hiq ? __builtin_amdgcn_readlane((int)my_add_m[KQ - 1], sl) : __builtin_amdgcn_readlane((int)my_add_m[0], sl));
-                if (!NZEQ) {
-                    addz_c = (unsigned)(hiq ? __builtin_amdgcn_readlane((int)my_addz_c[KQ - 1], sl) : __builtin_amdgcn_readlane((int)my_addz_c[0], sl));
-                    addz_m = (unsigned)(hiq ? __builtin_amdgcn_readlane((int)my_addz_m[KQ - 1], sl) : __builtin_amdgcn_readlane((int)my_addz_m[0], sl));
-                }
-            }
-            st.rq_c += add_c;
-            st.rq_m += add_m;
-            st.freep -= 1u;
-            double nzc = 0.0, nzm = 0.0;
-            if (!NZEQ) {
-                z.x += addz_c;
-                z.y += addz_m;
-                if (lane == 0) g_nz[pstar] = z;
-                nzc = (double)z.x; nzm = (double)z.y;
-            }
-            if (lane == 0) g_state[pstar] = st;
-            const double rq_c = (double)st.rq_c, rq_m = (double)st.rq_m;
-            TPROF(8);                                                  // state update (readlanes of the signature's request), state store
-            // Signature k's byte of the touched node, its block key, summary entries and feasible-node counter (lane-local k).
-            auto refresh_sig = [&](int k, bool valid, unsigned nb_raw,
-                                   unsigned char* rowk, const uint4 Tk, const uint2 Fk, unsigned old, unsigned snk, int dirty_bit) {
-                const unsigned nb = old ? nb_raw : 0u;                    // static mask / monotone infeasibility
-                // One wave: its vector memory accesses are served in order, so the next cycle's loads of this row / state
-                // observe these stores; no cache maintenance, no wait.
-                if (valid && nb != old) {
-                    rowk[pos] = (unsigned char)nb;
-                    const unsigned m = block_key16_patched(Tk, nb, selA, selB);
-                    const unsigned e16 = (m >> 4) ? m + (snk << 4) : 0u;
-                    if constexpr (COARSE) {
-                        // per-16 entry to the workspace; the entry of the 64 positions = max over its four per-16 entries, each
-                        // re-keyed to total << 6 | 63 - position (a feasible entry is >= 64, the constants alone stay below)
-                        const int j = blk & 3;                            // uniform
-                        g_fine[((unsigned)(pstar >> 6) * (unsigned)K + (unsigned)k) * 4u + (unsigned)j] = (unsigned short)e16;
-                        const unsigned keep = (j & 1) ? 0x0000FFFFu : 0xFFFF0000u, ins = e16 << ((j & 1) * 16);
-                        const unsigned fx = (j & 2) ? Fk.x : ((Fk.x & keep) | ins);
-                        const unsigned fy = (j & 2) ? ((Fk.y & keep) | ins) : Fk.y;
-                        const unsigned cx = (((fx & 0xFFF0FFF0u) << 2) | (fx & 0x000F000Fu)) | 0x00200030u;
-                        const unsigned cy = (((fy & 0xFFF0FFF0u) << 2) | (fy & 0x000F000Fu)) | 0x00000010u;
-                        const unsigned mm = pkmax_t(cx, cy);
-                        const unsigned c64 = max(mm & 0xFFFFu, mm >> 16);
-                        s_sum[k * nbp + (pstar >> 6)] = (unsigned short)(c64 >= 64u ? c64 : 0u);
-                    } else {
-                        s_sum[k * nbp + blk] = (unsigned short)e16;
-                    }
-                    if (!nb) {                                            // the node stopped being feasible for this signature
-                        const int cidx = k * Cn + dstar;
-                        int left;
-                        // plain read-modify-write (lane-local: a (signature, class) counter belongs to the lane that owns the signature):
-                        // an atomic is performed in L2 and would leave the wave's later plain loads of the counter to a stale L1 line
-                        if constexpr (!CNT_LDS) { left = g_cnt[cidx] - 1; g_cnt[cidx] = left; }
-                        else { left = s_cnt[cidx] - 1; s_cnt[cidx] = left; }
-                        // The class term of row k changes: re-base before its next use -- unless (kCls4: hundreds of small classes, each leaving the
-                        // feasible set of every signature at some point) the class that left sat strictly INSIDE the extremes of the last re-base:
-                        // lo and hi are then attained by classes that stay, the min-max normalisation (simon.go:76-101) of every other class is
-                        // what it was, and the leaver's own entries are all 0 and stay 0 (bytes never come back).  While a row is dirty the stored
-                        // extremes may be stale -- it is re-based before its next use whatever this test says.  Static score tables have maxima
-                        // of their own: with them every leave re-bases.
-                        bool rebase = left == 0;
-                        if constexpr (kCls4) {
-                            if (rebase && !(sc.static_tables & kStClassTerms)) {
-                                const int raw = simon_raw[((KQ > 1 && dirty_bit == KQ - 1) ? my_tc[KQ - 1] : my_tc[0]) * Cn + dstar];
-                                const int2 e = s_ext[k];
-                                rebase = !(e.x < raw && raw < e.y);
-                            }
-                        }
-                        if (rebase) my_dirty |= 1u << dirty_bit;
-#ifdef SIMON_TABLE_DEBUG
-                        printf("DBG s=%d step=%d CNT k=%d class=%d left=%d\n", s, i0 + il, k, dstar, left);
-#endif
-                    }
-                }
-            };
-            // NodeResourcesFit + LeastAllocated + BalancedAllocation of the touched node per signature of this lane.  With 65 .. 128
-            // signatures the host puts a signature's twin -- same request, another table class (static mask / Simon row) -- 64 slots up
-            // whenever every upper signature has one (TableScalars::static_tables & kStTwins): the upper byte is the lower lane's, unmasked.
-            unsigned nbq[KQ];
-            nbq[0] = eval_node(my_req_c[0], my_req_m[0], my_nz_c[0], my_nz_m[0], my_zero[0], rq_c, rq_m, nzc, nzm, (int)st.freep, sh);
-            if constexpr (KQ > 1) {
-                if (sc.static_tables & kStTwins) nbq[KQ - 1] = nbq[0];
-                else nbq[KQ - 1] = eval_node(my_req_c[KQ - 1], my_req_m[KQ - 1], my_nz_c[KQ - 1], my_nz_m[KQ - 1], my_zero[KQ - 1], rq_c, rq_m, nzc, nzm, (int)st.freep, sh);
-            }
-            if constexpr (kFoldable) {
-                if (__builtin_expect(fold, 0)) {                      // folded exclusions: the signatures this landing rules out get byte 0
-#pragma unroll
-                    for (int q = 0; q < KQ; ++q) nbq[q] = ((xfold[q] >> (kk[q] & 31)) & 1u) ? 0u : nbq[q];
-                }
-            }
-            unsigned gu[8] = {0, 0, 0, 0, 0, 0, 0, 0};                   // GPU fold: the landing node's devices after Reserve (MANY: the further groups read them)
-            bool gbooked = false;
-            if constexpr (kGpuFoldable) {
-                if (__builtin_expect(gfold, 0)) {
-                    // Open-Gpu-Share folded into the table: a GPU pod the scheduler placed books its devices (Reserve,
-                    // open-gpu-share.go:147-188: every lane alike), and the GPU signatures whose request stopped fitting the node get
-                    // byte 0 -- for good (device memory is never released).  Pods bound by Spec.NodeName never reach Reserve.
-                    unsigned greq = (unsigned)(hiq ? __builtin_amdgcn_readlane((int)my_greq[KQ - 1], sl) : __builtin_amdgcn_readlane((int)my_greq[0], sl));
-                    int gnum = hiq ? __builtin_amdgcn_readlane(my_gnum[KQ - 1], sl) : __builtin_amdgcn_readlane(my_gnum[0], sl);
-                    if (MANY && __builtin_expect(r_sig >= 64 * KQ, 0)) {   // a signature beyond the register-resident ones: its row (uniform index)
-                        const SigRow rs = sigs[r_sig];
-                        greq = (unsigned)rs.pad[0]; gnum = rs.pad[1];
-                    }
-                    if (gnum > 0 && !bound) {
-                        unsigned (&u)[8] = gu;
-                        u[0] = gfa.x; u[1] = gfa.y; u[2] = gfa.z; u[3] = gfa.w; u[4] = gfb.x; u[5] = gfb.y; u[6] = gfb.z; u[7] = gfb.w;
-                        gbooked = true;
-                        const unsigned long long booked = gpu_commit_t(u, gfc, gft, greq, gnum);
-                        if (sc.static_tables & kStGpuSlices) {                       // the caller wants the devices (simon_batch_out.gpu_slices), by pod id
-                            const int pid = __builtin_amdgcn_readfirstlane(order[i0 + il]);
-                            if (lane == 0) gp(cold->gpu_slices)[(size_t)s * (size_t)P + (size_t)pid] = booked;
-                        }
-                        if (lane == 0) {
-                            *(uint4*)(g_fu + (size_t)pstar * 8) = make_uint4(u[0], u[1], u[2], u[3]);
-                            *(uint4*)(g_fu + (size_t)pstar * 8 + 4) = make_uint4(u[4], u[5], u[6], u[7]);
-                        }
-#pragma unroll
-                        for (int q = 0; q < KQ; ++q)
-                            if (my_gnum[q] != 0 && !gpu_fits_t(u, gfc, gft, my_greq[q], my_gnum[q])) nbq[q] = 0u;
-                    }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < KQ; ++q)
-                refresh_sig(kk[q], kvalid[q], nbq[q], rowp[q], T[q], COARSE ? F[q] : make_uint2(0u, 0u),
-                            oldq[q], snq[q], q);
-            // MANY: the further groups (their table rows arrived with group 0's; the signature rows of TableCold::sigs are L2-hot)
-            if constexpr (MANY) {
-#pragma unroll
-                for (int g = 0; g < NG; ++g) {
-                    if (128 * (g + 1) < K) {
-                        SigRow rg[KQ];
-                        unsigned sng[KQ];
-#pragma unroll
-                        for (int q = 0; q < KQ; ++q) { rg[q] = sigs[kg[g][q]]; sng[q] = s_sn[kg[g][q] * Cn + dstar]; }
-#pragma unroll
-                        for (int q = 0; q < KQ; ++q)
-                            refresh_sig(kg[g][q], 128 * (g + 1) + 64 * q + lane < K,
-                                        ((fold && ((xfg[g][q] >> (kg[g][q] & 31)) & 1u)) ||
-                                         (kGpuFoldable && gbooked && rg[q].pad[1] != 0 && !gpu_fits_t(gu, gfc, gft, (unsigned)rg[q].pad[0], rg[q].pad[1]))) ? 0u :
-                                        eval_node(rg[q].req_c, rg[q].req_m, rg[q].nz_c, rg[q].nz_m, rg[q].flags & 1u, rq_c, rq_m, nzc, nzm, (int)st.freep, sh),
-                                        rowg[g][q], Tg[g][q], Fg[g][q], oldg[g][q], sng[q], 2 * (g + 1) + q);
-                    }
-                }
-                // 385 .. 1 023 signatures (round 4): the groups beyond the two whose rows travel with group 0's take a round trip of their
-                // own each -- a problem of that many signatures that needs generation 7's walks or a fold has the all-feature kernel as
-                // its alternative, not a faster table.  (uniform trip count; a lane beyond K evaluates signature 0 and stores nothing)
-                for (int g = NG; 128 * (g + 1) < K; ++g) {
-#pragma unroll
-                    for (int q = 0; q < KQ; ++q) {
-                        const int kq = 128 * (g + 1) + 64 * q + lane;
-                        const int kx = kq < K ? kq : 0;
-                        unsigned char* rowx = g_tile + (tile_blk((unsigned)(pstar >> 4)) + (unsigned)kx * KS);
-                        const uint4 Tx = *(const uint4*)rowx;
-                        const unsigned oldx = rowx[pstar & 15];
-                        const uint2 Fx = *(const uint2*)(g_fine + ((unsigned)(pstar >> 6) * (unsigned)K + (unsigned)kx) * 4u);
-                        const unsigned xfx = fold ? gp(cold->foldx)[(unsigned)r_sig * KW + ((unsigned)kx >> 5)] : 0u;
-                        const SigRow rx = sigs[kx];
-                        const unsigned snx = s_sn[kx * Cn + dstar];
-                        refresh_sig(kx, kq < K,
-                                    ((fold && ((xfx >> (kx & 31)) & 1u)) ||
-                                     (kGpuFoldable && gbooked && rx.pad[1] != 0 && !gpu_fits_t(gu, gfc, gft, (unsigned)rx.pad[0], rx.pad[1]))) ? 0u :
-                                    eval_node(rx.req_c, rx.req_m, rx.nz_c, rx.nz_m, rx.flags & 1u, rq_c, rq_m, nzc, nzm, (int)st.freep, sh),
-                                    rowx, Tx, Fx, oldx, snx, 2 * (g + 1) + q);
-                    }
-                }
-            }
-            TPROF(9);                                                  // evaluation, patch, block key, summary / table stores
-            if (REST && __builtin_expect(rw != 0, 0)) rest_assume_store(RL, pstar, r_nrows, rowv, bound ? -1 : r_gs, r_xs, i0 + il);
-            if (SPREAD && sp_match != 0) spread_count_store(SPL, pstar, dstar, spv, spt, sp_soft, sp_match);
-            TPROF(19);                                                 // spread: counter stores
-            __builtin_amdgcn_wave_barrier();
-            TPROF(6);                                                  // REST: term rows, GPU commit and GPU rows
         }
 #ifdef SIMON_TABLE_DEBUG
         if (lane == 0) printf("DBG s=%d step=%d sig=%d cls=%d pstar=%d dstar=%d res=%d top=%u ni=%d nblk=%d\n", s, i0 + il, r_sig, r_cls, pstar, dstar, res, top, ni, nblk);
@@ -2355,6 +2072,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         // -------- placement, recorded by STEP (coalesced); simon_hip.hip permutes to pod ids ---
         plreg = (il == lane) ? res : plreg;
         }
+        // unschedulable pods: counted off the chunk's recorded results (res == -1), not carried through the cycle as a counter
+        unsched += __popcll(__ballot(lane < steps && plreg == -1));
         if (lead && place && lane < steps) place[i0 + lane] = plreg >= 0 ? cls_list[rk_off + (unsigned)plreg] : plreg;   // 64 canonical indices per gather
     }
 
