@@ -492,6 +492,33 @@ int simon_explain_loaded(simon_ctx* ctx, int32_t scenario, int32_t* failed_pods,
  * negative error (SIMON_ESTATE before any explain call).  (ABI v5) */
 int simon_explain_local_detail(simon_ctx* ctx, int64_t* detail, int32_t max_failed);
 
+/* simon_explain_loaded for MANY scenarios of the loaded batch in one launch (one workgroup per listed scenario), with every failed
+ * pod's per-node codes already reduced on the device to the histogram FitError.Error() is built from: at most SIMON_EXPLAIN_BINS
+ * (code, node count) pairs in ascending code order.  `scenarios` holds indices into the LOADED batch: any order, repeats allowed.
+ * Every listed scenario is replayed with its own node count, order, rank row (simon_set_node_ranks) and ImageLocality size slot;
+ * n_failed[k] and failed_pods[k][..] are what simon_explain_loaded returns / writes for scenarios[k] (n_failed may exceed max_failed:
+ * only the first max_failed pods are recorded); bins[k][i][0 .. min(n_bins[k][i], max_bins)) are the sorted distinct codes of pod i's
+ * row with their counts, n_bins[k][i] the number of distinct codes (it may exceed max_bins), or -1 with a zero bin row when a pod
+ * has more than SIMON_EXPLAIN_BINS distinct codes -- ask for the rows then.  fail_codes, when not NULL, receives the full rows:
+ * row (k, i) holds the codes of scenarios[k]'s nodes in its first n_nodes entries; code_stride must be at least the largest listed
+ * n_nodes.  Entries beyond what a scenario recorded are zero.
+ * Returns 0 or a negative error: SIMON_ESTATE with nothing loaded or a segmented batch loaded (as simon_explain_loaded);
+ * SIMON_EINVAL for an index outside the batch, bad sizes (n_scen < 1, max_failed < 1, max_bins outside [1, SIMON_EXPLAIN_BINS]) or a
+ * code_stride that is too small.  A failed call changes nothing; simon_run_loaded, simon_explain* and simon_explain_local_detail
+ * behave afterwards as they did before (the detail of the last SINGLE explain stays available).
+ * Not covered: no simon_group_* forward (explain on simon_group_member(i) with member-local indices, as for simon_explain_loaded);
+ * no Open-Local size details in batch (replay that scenario with simon_explain_loaded + simon_explain_local_detail); no segmented
+ * batches.  (additive to ABI v7) */
+#define SIMON_EXPLAIN_BINS 64
+typedef struct simon_fail_bin { uint16_t code, pad; int32_t count; } simon_fail_bin;
+int simon_explain_batch(simon_ctx* ctx, const int32_t* scenarios, int32_t n_scen,   /* indices into the LOADED batch: any order, repeats allowed */
+                        int32_t max_failed, int32_t max_bins,                        /* 1 <= max_bins <= SIMON_EXPLAIN_BINS */
+                        int32_t* n_failed      /* [n_scen] all unscheduled pods, may exceed max_failed */,
+                        int32_t* failed_pods   /* [n_scen][max_failed] */,
+                        int32_t* n_bins        /* [n_scen][max_failed] distinct codes (may exceed max_bins), -1 = more than SIMON_EXPLAIN_BINS */,
+                        simon_fail_bin* bins   /* [n_scen][max_failed][max_bins], ascending code */,
+                        uint16_t* fail_codes   /* NULL, or [n_scen][max_failed][code_stride] full rows */, int32_t code_stride);
+
 int simon_get_stats(simon_ctx* ctx, simon_stats* stats);
 
 /* Raw device pointers of the last run's per-scenario results (for zero-copy collectives from the

@@ -372,6 +372,39 @@ func (c *Ctx) ExplainLoaded(scenario, nNodes, maxFailed int) (total int, failed 
 	return splitCodes(int(rc), failed, flat, nNodes, maxFailed, c.check(rc, "simon_explain_loaded"))
 }
 
+// FailBin is simon_fail_bin: one (failure code, node count) pair of a failed pod's histogram.
+type FailBin struct {
+	Code, Pad uint16
+	Count     int32
+}
+
+// ExplainBatch replays the listed scenarios of the loaded batch in one launch (simon_explain_batch): nFailed[k] unscheduled pods
+// of scenarios[k] (it may exceed maxFailed), failed[k*maxFailed+i] the recorded pod ids, nBins[k*maxFailed+i] the distinct codes of
+// pod i (-1: more than SIMON_EXPLAIN_BINS, take the row) and bins[(k*maxFailed+i)*maxBins ..] its (code, count) pairs in ascending
+// code order.  codeStride > 0 asks for the full code rows too: rows[(k*maxFailed+i)*codeStride ..], scenario k's nodes first.
+func (c *Ctx) ExplainBatch(scenarios []int32, maxFailed, maxBins, codeStride int) (nFailed, failed, nBins []int32, bins []FailBin, rows []uint16, err error) {
+	n := len(scenarios)
+	if n == 0 || maxFailed <= 0 || maxBins <= 0 {
+		return nil, nil, nil, nil, nil, fmt.Errorf("simon_explain_batch: empty request")
+	}
+	nFailed = make([]int32, n)
+	failed = make([]int32, n*maxFailed)
+	nBins = make([]int32, n*maxFailed)
+	bins = make([]FailBin, n*maxFailed*maxBins) // eight bytes per pair, the layout of the C struct
+	var rowPtr *C.uint16_t
+	if codeStride > 0 {
+		rows = make([]uint16, n*maxFailed*codeStride)
+		rowPtr = (*C.uint16_t)(unsafe.Pointer(&rows[0]))
+	}
+	rc := C.simon_explain_batch(c.h, (*C.int32_t)(unsafe.Pointer(&scenarios[0])), C.int32_t(n), C.int32_t(maxFailed), C.int32_t(maxBins),
+		(*C.int32_t)(unsafe.Pointer(&nFailed[0])), (*C.int32_t)(unsafe.Pointer(&failed[0])), (*C.int32_t)(unsafe.Pointer(&nBins[0])),
+		(*C.simon_fail_bin)(unsafe.Pointer(&bins[0])), rowPtr, C.int32_t(codeStride))
+	if err = c.check(rc, "simon_explain_batch"); err != nil {
+		return nil, nil, nil, nil, nil, err
+	}
+	return nFailed, failed, nBins, bins, rows, nil
+}
+
 // LocalDetail is one row of simon_explain_local_detail: what Open-Local's error text carries for a node that failed a pod with
 // SIMON_FAIL_LOCAL_LVM / _DEV (Kind = SIMON_LOCAL_ERR_*; zero elsewhere).
 type LocalDetail struct{ Kind, A, B, C int64 }

@@ -533,7 +533,7 @@ EXPORTS = [
     "simon_hip_version", "simon_hip_device_count", "simon_ctx_create", "simon_ctx_destroy", "simon_last_error",
     "simon_load_nodes", "simon_load_pods", "simon_load_class_tables", "simon_load_scenarios", "simon_run_loaded",
     "simon_fetch_results", "simon_fetch_placement", "simon_fetch_gpu_slices", "simon_run_batch", "simon_min_plan", "simon_min_plan_vg", "simon_min_plan_device", "simon_explain", "simon_set_node_ranks",
-    "simon_get_stats", "simon_device_results", "simon_explain_loaded", "simon_explain_local_detail",
+    "simon_get_stats", "simon_device_results", "simon_explain_loaded", "simon_explain_local_detail", "simon_explain_batch",
     "simon_set_scalar_entries", "simon_set_pod_priorities", "simon_fetch_preempt_risk",
     "simon_group_set_scalar_entries", "simon_group_set_pod_priorities", "simon_group_fetch_preempt_risk",
     "simon_set_image_locality", "simon_group_set_image_locality",
@@ -581,6 +581,7 @@ def load_library(path: Optional[str] = None):
     lib.simon_explain.argtypes = [vp, Scenario, _p32, _p32, _pu16, C.c_int32]
     lib.simon_explain_loaded.argtypes = [vp, C.c_int32, _p32, _pu16, C.c_int32]
     lib.simon_explain_local_detail.argtypes = [vp, _p64, C.c_int32]
+    lib.simon_explain_batch.argtypes = [vp, _p32, C.c_int32, C.c_int32, C.c_int32, _p32, _p32, _p32, C.c_void_p, _pu16, C.c_int32]
     _pu8 = C.POINTER(C.c_uint8)
     for pre in ("simon_", "simon_group_"):
         getattr(lib, pre + "set_scalar_entries").argtypes = [vp, _pu8]
@@ -627,6 +628,33 @@ def load_library(path: Optional[str] = None):
     if path == library_path():
         _LIB = lib
     return lib
+
+
+EXPLAIN_BINS = 64     # SIMON_EXPLAIN_BINS
+FAIL_BIN_DTYPE = np.dtype([("code", np.uint16), ("pad", np.uint16), ("count", np.int32)])     # simon_fail_bin
+
+
+@dataclass
+class ExplainBatch:
+    """What simon_explain_batch returns for the listed scenarios (list position k, recorded failed pod i < min(n_failed[k], max_failed))."""
+    scenarios: np.ndarray       # [k] the indices as listed
+    n_nodes: np.ndarray         # [k] node count of every listed scenario
+    n_failed: np.ndarray        # [k] unscheduled pods (may exceed max_failed)
+    failed_pods: np.ndarray     # [k][max_failed]
+    n_bins: np.ndarray          # [k][max_failed] distinct codes (may exceed max_bins); -1: more than EXPLAIN_BINS, take the row
+    bins: np.ndarray            # [k][max_failed][max_bins] FAIL_BIN_DTYPE, ascending code
+    rows: Optional[np.ndarray]  # [k][max_failed][code_stride] uint16 with rows=True: scenario k's codes in the first n_nodes[k] entries
+
+    def recorded(self, k: int) -> int:
+        return min(int(self.n_failed[k]), self.failed_pods.shape[1])
+
+    def pod_bins(self, k: int, i: int):
+        """(code, node count) pairs of failed pod i of listed scenario k, or None when they are incomplete (n_bins -1 or beyond max_bins)."""
+        nb = int(self.n_bins[k, i])
+        if nb < 0 or nb > self.bins.shape[2]:
+            return None
+        b = self.bins[k, i, :nb]
+        return list(zip(b["code"].tolist(), b["count"].tolist()))
 
 
 class SimonError(RuntimeError):
@@ -787,6 +815,28 @@ class Context:
                                                       int(max_failed)), "simon_explain_loaded")
         k = min(n, max_failed)
         return n, failed[:k], codes[:k]
+
+    def explain_batch(self, scenarios, max_failed: int = 64, max_bins: int = 32, rows: bool = False,
+                      code_stride: Optional[int] = None) -> "ExplainBatch":
+        """simon_explain_batch: replay the listed scenarios of the loaded batch (indices in any order, repeats allowed) in one launch;
+        per failed pod the (code, node count) histogram of its per-node failure codes, and with rows=True the full code rows too
+        (row stride: the largest listed n_nodes unless code_stride says otherwise)."""
+        idx = np.ascontiguousarray(scenarios, dtype=np.int32).reshape(-1)
+        k = len(idx)
+        if rows and code_stride is None:
+            ok = self.scen is not None and k > 0 and bool(((idx >= 0) & (idx < len(self.scen))).all())
+            code_stride = max(int(self.scen[idx, 0].max()), 1) if ok else 1        # (a bad index is the library's to refuse)
+        stride = int(code_stride) if rows else 0
+        n_failed = np.zeros(k, np.int32)
+        failed = np.zeros((k, max(int(max_failed), 0)), np.int32)
+        n_bins = np.zeros((k, max(int(max_failed), 0)), np.int32)
+        bins = np.zeros((k, max(int(max_failed), 0), max(int(max_bins), 0)), FAIL_BIN_DTYPE)
+        codes = np.zeros((k, max(int(max_failed), 0), max(stride, 0)), np.uint16) if rows else None
+        self._check(self.lib.simon_explain_batch(self.h, _ptr(idx, C.c_int32), k, int(max_failed), int(max_bins), _ptr(n_failed, C.c_int32),
+                                                 _ptr(failed, C.c_int32), _ptr(n_bins, C.c_int32), bins.ctypes.data_as(C.c_void_p),
+                                                 _ptr(codes, C.c_uint16), stride), "simon_explain_batch")
+        n_nodes = self.scen[idx, 0].astype(np.int32)
+        return ExplainBatch(idx, n_nodes, n_failed, failed, n_bins, bins, codes)
 
     def explain_local_detail(self, n_failed: int, n_nodes: int) -> Optional[np.ndarray]:
         """simon_explain_local_detail after explain / explain_loaded: [n_failed][n_nodes][4] int64 {LOCAL_ERR_*, a, b, c} -- what

@@ -2629,6 +2629,37 @@ int simon_explain_loaded(simon_ctx* c, int32_t scenario, int32_t* failed_pods, u
                         failed_pods, fail_codes, max_failed);
 }
 
+int simon_explain_batch(simon_ctx* c, const int32_t* scenarios, int32_t n_scen, int32_t max_failed, int32_t max_bins, int32_t* n_failed,
+                        int32_t* failed_pods, int32_t* n_bins, simon_fail_bin* bins, uint16_t* fail_codes, int32_t code_stride) {
+    if (!c) return SIMON_EINVAL;
+    if (!scenarios || n_scen <= 0 || max_failed <= 0 || max_bins < 1 || max_bins > SIMON_EXPLAIN_BINS || !n_failed || !failed_pods || !n_bins || !bins)
+        return fail(c, SIMON_EINVAL, "explain_batch: bad arguments");
+    if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "explain_batch: no scenarios loaded");
+    if (c->seg_n)        // the replay runs on the all-feature kernel, which takes prefix scenarios only
+        return fail(c, SIMON_ESTATE, "explain_batch: segmented batch; explain each scenario's own problem (its nodes alone)");
+    std::vector<WideScenario> hs((size_t)n_scen);
+    int max_n = 0;
+    for (int k = 0; k < n_scen; ++k) {
+        if (scenarios[k] < 0 || scenarios[k] >= c->S) return fail(c, SIMON_EINVAL, "explain_batch: scenario %d outside [0,%d)", scenarios[k], c->S);
+        hs[k] = WideScenario{c->scen[scenarios[k]].n_nodes, c->scen[scenarios[k]].order_id};
+        max_n = std::max(max_n, hs[k].n_nodes);
+    }
+    if (fail_codes && code_stride < std::max(max_n, 1)) return fail(c, SIMON_EINVAL, "explain_batch: code_stride %d below the largest listed n_nodes %d", code_stride, max_n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->wide_staged) {   // the batch ran on another kernel: the failure codes still come from the all-feature kernel
+        int rc = wide_stage(c->wide, *c, c->stream, c->err);
+        if (rc) return rc;
+        c->wide_staged = true;
+    }
+    // workgroup shape as simon_run_loaded chooses it for the all-feature kernel
+    const bool two_groups = n_scen >= 2 * c->n_cus && max_n <= 8192;
+    int T = c->force_T ? c->force_T : (max_n <= 1024 || two_groups ? 256 : max_n <= 16384 ? 512 : 1024);
+    if (T == 128) T = 256;
+    return wide_explain_batch(c->wide, *c, hs.data(), scenarios, n_scen, c->d_orders.p, max_n, T, max_failed, max_bins, n_failed, failed_pods, n_bins,
+                              bins, fail_codes, code_stride, c->has_ranks ? c->d_node_rank.p : nullptr, c->has_ranks ? c->d_node_inv.p : nullptr,
+                              c->img_R > 0 ? c->h_img_slot.data() : nullptr, c->stream, c->err);
+}
+
 int simon_get_stats(simon_ctx* c, simon_stats* st) {
     if (!c || !st) return SIMON_EINVAL;
     *st = c->stats;

@@ -180,6 +180,12 @@ struct WideCold {
     const int32_t* node_rank; const int32_t* node_inv;
     // devices Reserve booked for every placed GPU pod (simon_batch_out.gpu_slices), rows of the WHOLE batch [S_total][P]; null = not recorded
     uint64_t* gpu_slices;
+    // batched explain (simon_explain_batch): the explain outputs above are indexed by the launch's scenario k = scen_base + s --
+    // failed_pods[k][max_failed], n_failed[k], fail_codes[k][max_failed][code_stride] (null: no rows wanted) -- and every recorded pod's
+    // codes are reduced to (code, node count) pairs: bins[k][max_failed][max_bins] ascending by code, n_bins[k][max_failed] = distinct
+    // codes, -1 beyond SIMON_EXPLAIN_BINS.  bins == null: no histogram.  The single-scenario replay is k = 0 with code_stride = n_nodes.
+    int32_t code_stride, max_bins;
+    simon_fail_bin* bins; int32_t* n_bins;
 };
 
 struct WideArgs {
@@ -287,5 +293,9 @@ int wide_run(WideDevice& w, const HostInputs& in, const WideScenario* d_scen, co
 int wide_explain(WideDevice& w, const HostInputs& in, int n_nodes, const int32_t* order, int32_t* failed_pods,
                  uint16_t* fail_codes, int32_t max_failed, int T, const int32_t* d_rank_row, const int32_t* d_inv_row, hipStream_t st,
                  std::string& err, std::vector<int64_t>* local_detail = nullptr);
+int wide_explain_batch(WideDevice& w, const HostInputs& in, const WideScenario* h_scen, const int32_t* h_idx, int S, const int32_t* d_orders,
+                       int max_n, int T, int32_t max_failed, int32_t max_bins, int32_t* n_failed, int32_t* failed_pods, int32_t* n_bins,
+                       simon_fail_bin* bins, uint16_t* fail_codes, int32_t code_stride, const int32_t* d_node_rank, const int32_t* d_node_inv,
+                       const int32_t* h_img_slot, hipStream_t st, std::string& err);
 
 }  // namespace simon

@@ -57,6 +57,59 @@ class HipEngine:
             nf, failed, codes = ctx.explain(n_nodes, order, max_failed)
             return nf, failed, codes, ctx.explain_local_detail(len(failed), n_nodes)
 
+    def explain_batch(self, prob: capi.Problem, scen, orders, node_ranks, ids, max_failed: int, max_bins: int = 32) -> List["ExplainedScenario"]:
+        """Why the pods of scenarios `ids` of the batch (scen, orders, node_ranks) fail, many scenarios per launch (simon_explain_batch):
+        per failed pod the (code, node count) histogram.  Scenarios with a pod whose histogram cannot be turned into text -- a code that
+        names the node (fiterror.NODE_SPECIFIC_CODES) or more distinct codes than fit -- are listed once more for their full code rows,
+        and those with Open-Local's size-carrying errors are replayed one by one for the sizes (simon_explain_local_detail).
+        The output buffers of one call hold max_failed entries for EVERY listed scenario, so the list goes to the device in groups whose
+        buffers stay within `buffer_bytes` (a group is one scenario at least: that one's buffers are explain_loaded's)."""
+        ids = [int(s) for s in ids]
+        per_bins = max_failed * (8 + 8 * max_bins)                           # failed_pods + n_bins + bins, per listed scenario
+        with capi.Context(self.device_id) as ctx:
+            ctx.load_problem(prob)
+            ctx.load_scenarios(scen, orders)
+            if node_ranks is not None:
+                ctx.set_node_ranks(node_ranks)
+            out, again = [], []
+            for group in _groups(ids, max(1, self.buffer_bytes // per_bins)):
+                eb = ctx.explain_batch(group, max_failed, max_bins)
+                for k, s in enumerate(group):
+                    rec = eb.recorded(k)
+                    bins = [eb.pod_bins(k, i) for i in range(rec)]
+                    if any(b is None or any(c in fiterror.NODE_SPECIFIC_CODES for c, _ in b) for b in bins):
+                        again.append(len(out))
+                    out.append(ExplainedScenario(s, int(eb.n_nodes[k]), int(eb.n_failed[k]), eb.failed_pods[k, :rec].copy(), bins))
+            per_rows = per_bins + 2 * max_failed * max([out[k].n_nodes for k in again], default=0)
+            for group in _groups(again, max(1, self.buffer_bytes // per_rows)):
+                er = ctx.explain_batch([out[k].scenario for k in group], max_failed, max_bins, rows=True)
+                for q, k in enumerate(group):
+                    e = out[k]
+                    e.rows = er.rows[q, :len(e.failed), :e.n_nodes].copy()
+                    if np.isin(e.rows, (capi.FAIL_LOCAL_LVM, capi.FAIL_LOCAL_DEV)).any():
+                        _, _, e.rows = ctx.explain_loaded(e.scenario, max_failed)
+                        e.detail = ctx.explain_local_detail(len(e.failed), e.n_nodes)
+            return out
+
+    supports_explain_batch = True             # sweep(..., reasons=True) explains every failing size in one launch
+    buffer_bytes = 256 << 20                  # explain_batch: host (and device) output buffers per simon_explain_batch call
+
+
+def _groups(items: list, size: int):
+    return (items[i:i + size] for i in range(0, len(items), size))
+
+
+@dataclass
+class ExplainedScenario:
+    """One scenario of HipEngine.explain_batch: its failed pods and, per pod, either the (code, node count) histogram or the code row."""
+    scenario: int
+    n_nodes: int
+    n_failed: int
+    failed: np.ndarray                      # pod ids, in scheduling order
+    bins: List[Optional[list]]              # per failed pod: [(code, node count)] or None (take the row)
+    rows: Optional[np.ndarray] = None       # [failed][n_nodes] codes, when some pod's histogram does not give the text
+    detail: Optional[np.ndarray] = None     # [failed][n_nodes][4] Open-Local error sizes, when a row holds such a code
+
 
 class NeedsReference(fl.Unsupported):
     """The scenario is one the engine does not model: a pod failed while a pod of LOWER priority was placed, so DefaultPreemption
@@ -316,6 +369,10 @@ class SweepResult:
     vg_pct: Optional[List[int]] = None   # Open-Local volume-group occupancy per scenario (0 without local storage)
     needs_reference: Optional[List[bool]] = None   # per scenario: a pod failed while a lower-priority pod was placed (DefaultPreemption could have
                                                    # acted: its unscheduled count is the engine's, not necessarily the reference's); never a scenario the plan accepts
+    # sweep(..., reasons=True): per count the pods that stay unscheduled, [{"pod": ..., "reason": str}] exactly as simulate() of that size fills
+    # SimulateResult.unscheduled_pods ("show results" of the add-nodes loop, pkg/apply/apply.go:229-232); empty without reasons.  With an
+    # app DaemonSet a size may be listed from its own simulate() run (_same_stream): len(unscheduled_pods[s]) may then differ from unscheduled[s]
+    unscheduled_pods: List[List[dict]] = field(default_factory=list)
 
 
 def occupancy_pct(used: int, alloc: int) -> int:
@@ -367,12 +424,67 @@ def sweep_batch(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new
     return SweepBatch(flat, scen, orders, node_ranks, pool, base)
 
 
+def _reason_texts(flat: fl.Flat, failed, rows, detail, bins=None) -> Dict[int, str]:
+    """UnscheduledPod.Reason by pod id, from the pods' code rows (as simulate() does) or, where a pod has one, its histogram."""
+    reasons = {}
+    for i, pid in enumerate(np.asarray(failed).tolist()):
+        ns, name = flat.pod_refs[pid]
+        if rows is None:
+            reasons[pid] = fiterror.unscheduled_reason_bins(ns, name, bins[i][0], bins[i][1], static_reasons=flat.static_reasons,
+                                                            scalar_names=flat.scalar_names)
+        else:
+            reasons[pid] = fiterror.unscheduled_reason(ns, name, rows[i], node_names=flat.node_names, static_reasons=flat.static_reasons,
+                                                       scalar_names=flat.scalar_names, local_detail=None if detail is None else detail[i],
+                                                       vg_names=flat.info.get("vg_names", ()))
+    return reasons
+
+
+def _unscheduled_list(flat: fl.Flat, placement: np.ndarray, reasons: Dict[int, str]) -> List[dict]:
+    return [{"pod": _public(flat.pods[pid]), "reason": reasons.get(pid, "")} for pid, j in enumerate(placement.tolist()) if j == capi.UNSCHEDULED]
+
+
+def _same_stream(cluster, apps, batch: "SweepBatch", out, s: int) -> bool:
+    """Whether simulate() of size s feeds the pods in the order the batch fed them (the pool's stream without the pods gated at that size).
+    An app's DaemonSet makes one pod per pool node, and the two unstable queue sorts of ScheduleApp (workloads.app_pods) then order the
+    app's pods by the LENGTH of that list, so with such an app the stream of a size need not be the pool's; without one it always is.
+    The comparison builds the size's stream on the host: one build_stream per FAILING size, and only for apps with a DaemonSet."""
+    if not any(app.resource.get("DaemonSet") for app in apps):
+        return True
+    ref = lambda p: (p["metadata"].get("namespace"), p["metadata"]["name"])
+    mine = [ref(batch.flat.pods[pid]) for pid, j in enumerate(out.placement[s].tolist()) if j != capi.GATED]
+    return mine == [ref(p) for p in build_stream(cluster, apps, batch.pool[:int(batch.scen[s, 0])], len(batch.base))[0]]
+
+
+def _sweep_reasons(engine, batch: "SweepBatch", out, replay, same_stream) -> List[List[dict]]:
+    """SweepResult.unscheduled_pods of a batched sweep: every failing size explained in one engine.explain_batch call; engines without it
+    replay size by size (engine.explain on the pool's problem, or -- with per-scenario node ranks, which that call cannot carry -- `replay`,
+    simulate() of the size).  A failing size whose pod stream is not the pool's (not same_stream(s)) is replayed too: the batch's count
+    stands in `unscheduled`, WHICH pods stay out is told by the size's own run, whose list may then be of another length."""
+    flat, scen = batch.flat, batch.scen
+    failing = [s for s in range(len(scen)) if out.unscheduled[s] > 0]
+    reasons: Dict[int, Dict[int, str]] = {}
+    lists: Dict[int, List[dict]] = {s: replay(s) for s in failing if not same_stream(s)}
+    failing = [s for s in failing if s not in lists]
+    if failing and getattr(engine, "supports_explain_batch", False):
+        for e in engine.explain_batch(flat.problem, scen, batch.orders, batch.node_ranks, failing, int(max(out.unscheduled[s] for s in failing))):
+            reasons[e.scenario] = _reason_texts(flat, e.failed, e.rows, e.detail, [(e.n_nodes, b) for b in e.bins])
+    else:
+        for s in failing:
+            if batch.node_ranks is not None:
+                lists[s] = replay(s)
+                continue
+            nf, failed, codes, detail = engine.explain(flat.problem, int(scen[s, 0]), batch.orders[0], int(out.unscheduled[s]))
+            reasons[s] = _reason_texts(flat, failed, codes, detail)
+    return [lists[s] if s in lists else _unscheduled_list(flat, out.placement[s], reasons.get(s, {})) for s in range(len(scen))]
+
+
 @_gc_paused
 def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node: Optional[dict], counts: Sequence[int],
-          engine=None, max_cpu: int = 100, max_mem: int = 100, max_vg: int = 100) -> SweepResult:
+          engine=None, max_cpu: int = 100, max_mem: int = 100, max_vg: int = 100, reasons: bool = False) -> SweepResult:
     """The add-nodes loop of Applier.Run (pkg/apply/apply.go:203-259) as ONE scenario batch: scenario k = the cluster plus
     counts[k] clones of new_node (utils.NewFakeNodes); the answer is the smallest count with no unscheduled pod whose
-    occupancy satisfies MaxCPU / MaxMemory (satisfyResourceSetting, :689-775)."""
+    occupancy satisfies MaxCPU / MaxMemory (satisfyResourceSetting, :689-775).  reasons=True: SweepResult.unscheduled_pods lists, per
+    count, the pods that stay unscheduled with their FitError text (what the loop prints under "show results", :229-232)."""
     engine = engine or HipEngine()
     counts = list(counts)
     if max_cpu > 100 or max_cpu < 0:
@@ -387,7 +499,7 @@ def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node:
             raise
         # ImageLocality scores depend on the cluster size: an engine without the per-size image scores runs every size as its own
         # problem with its own static scores (and an engine without per-scenario node ranks runs a pool of several zones size by size)
-        return _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg)
+        return _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg, reasons)
     flat, scen, orders, node_ranks, pool, base = batch.flat, batch.scen, batch.orders, batch.node_ranks, batch.pool, batch.base
     want_gpu = flat.problem.gpu_mem is not None
     kw = {"want_gpu_slices": True} if want_gpu else {}
@@ -412,15 +524,24 @@ def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node:
         res, per_node, per_dev = _unflatten(flat, out.placement[best], n, {}, out.gpu_slices[best] if want_gpu and out.gpu_slices is not None else None)
         res.node_status = [{"node": _gpu_node_status(pool[j], per_dev[j]) if j in per_dev else _node_out(pool[j]), "pods": per_node[j]} for j in range(n)]
         result = res
+    why = []
+    if reasons:
+        def replay(s):                       # (NeedsReference: the size is flagged in needs_reference; its pods stay without a text)
+            try:
+                return simulate(cluster, apps, engine, wl.new_fake_nodes(new_node, counts[s]) if counts[s] > 0 else ()).unscheduled_pods
+            except NeedsReference:
+                return _unscheduled_list(flat, out.placement[s], {})
+        why = _sweep_reasons(engine, batch, out, replay, lambda s: _same_stream(cluster, apps, batch, out, s))
     return SweepResult(counts, out.unscheduled.tolist(), cpu_pct, mem_pct, None if best is None else counts[best], result, vg_pct,
-                       [_risk(out, s) for s in range(len(counts))])
+                       [_risk(out, s) for s in range(len(counts))], why)
 
 
-def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg) -> SweepResult:
+def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg, reasons: bool = False) -> SweepResult:
     base = list(cluster.get("Node", []))
     if max_vg > 100 or max_vg < 0:
         max_vg = 100
     uns, cpu_pct, mem_pct, vg_pct, kept, risks = [], [], [], [], {}, []
+    why: List[List[dict]] = []
     for s, k in enumerate(counts):
         nodes = base + (wl.new_fake_nodes(new_node, k) if k > 0 else [])
         pods, _ = build_stream(cluster, apps, nodes, len(nodes))
@@ -433,6 +554,12 @@ def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, m
                          **({"want_gpu_slices": True} if want_gpu else {}))
         uns.append(int(out.unscheduled[0]))
         risks.append(_risk(out, 0))
+        if reasons:
+            texts = {}
+            if uns[-1] > 0:
+                nf, failed, codes, detail = engine.explain(flat.problem, len(nodes), np.arange(len(pods), dtype=np.int32), uns[-1])
+                texts = _reason_texts(flat, failed, codes, detail)
+            why.append(_unscheduled_list(flat, out.placement[0], texts))
         cpu_pct.append(occupancy_pct(int(out.used_cpu[0]), int(flat.problem.alloc_cpu.sum())))
         mem_pct.append(occupancy_pct(int(out.used_mem[0]) * 1000, int(flat.problem.alloc_mem.sum()) * 1000))
         vg = 0
@@ -449,7 +576,7 @@ def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, m
         res, per_node, per_dev = _unflatten(flat, out.placement[0], len(nodes), {}, out.gpu_slices[0] if out.gpu_slices is not None else None)
         res.node_status = [{"node": _gpu_node_status(n, per_dev[j]) if j in per_dev else _node_out(n), "pods": per_node[j]} for j, n in enumerate(nodes)]
         result = res
-    return SweepResult(list(counts), uns, cpu_pct, mem_pct, None if best is None else counts[best], result, vg_pct, risks)
+    return SweepResult(list(counts), uns, cpu_pct, mem_pct, None if best is None else counts[best], result, vg_pct, risks, why)
 
 
 @dataclass
