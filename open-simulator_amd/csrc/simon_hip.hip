@@ -168,7 +168,6 @@ struct simon_ctx : simon::HostInputs {
     std::vector<int64_t> explain_detail;   // [failed][n][4] of the last explain (Open-Local error sizes), simon_explain_local_detail
     int explain_nodes = 0;
     bool explain_ran = false;
-    std::vector<int32_t> h_orders;   // host copy of the loaded orders (simon_explain_loaded replays one of them)
     DevBuf<uint64_t> d_mask, d_t_mask;           // static masks by pod class; by table class (simon_table.hip)
     DevBuf<int64_t> d_prefix_cpu, d_prefix_mem, d_prefix_vg;
     DevBuf<int32_t> d_node_rank, d_node_inv;      // [S][N] per-scenario nodeTree ranks (simon_set_node_ranks)
@@ -2007,7 +2006,6 @@ int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, co
     c->h_perm = perm;
     c->scen_ni.assign(S, 0);
     c->orders_perm = false;
-    c->h_orders.assign(orders, orders + (size_t)n_orders * P);
     c->table_perm_ok = false;
     if (c->variant == SIMON_KERNEL_NARROW && c->table_ok) {
         // placements are recorded by scheduling step and gathered back to pod ids through the inverse orders,
@@ -2187,6 +2185,39 @@ int simon_set_scenario_segments(simon_ctx* c, int32_t n_seg, const int32_t* seg_
     }
     const int rc = load_ranks(c, nullptr);
     return rc ? seg_abandon(c, rc) : SIMON_OK;
+}
+
+// The all-feature kernel gives every problem its failure codes and runs the batches no other kernel takes: staged on first use where
+// stage() chose another kernel.
+static int ensure_wide_staged(simon_ctx* c) {
+    const int rc = c->wide_staged ? SIMON_OK : wide_stage(c->wide, *c, c->stream, c->err);
+    c->wide_staged = rc == SIMON_OK;
+    return rc;
+}
+
+// Workgroup shape of the all-feature kernel for a batch of S scenarios (a run, or simon_explain_batch's replays).  A 256-thread
+// group fits twice on a CU (launch bounds 256 x 2: two independent barrier domains per SIMD), which wins as soon as the batch
+// offers two groups per CU; with fewer scenarios than that a CU holds ONE group and the 512-thread shape keeps all four SIMDs at
+// two waves.  Measured on config 5 (50 000 pods x 2 500..5 000 nodes): S = 256: 512 threads 536 ms, 256 threads 734 ms;
+// S = 1 024: 512 threads 2 033 ms, 256 threads 1 611 ms.  SIMON_WG overrides (tuning knob).
+static int wide_workgroup(const simon_ctx* c, int S, int max_n) {
+    const bool two_groups = S >= 2 * c->n_cus && max_n <= 8192;          // 32 nodes per lane at most
+    const int T = c->force_T ? c->force_T : (max_n <= 1024 || two_groups ? 256 : max_n <= 16384 ? 512 : 1024);
+    return T == 128 ? 256 : T;                                  // (SIMON_WG=128: the all-feature kernel is built for 64 / 256 / 512 / 1 024 threads since round 5)
+}
+
+// simon_run_loaded on the all-feature kernel: the loaded batch between the context's event pair; *T_used = the workgroup size.
+static int run_wide_batch(simon_ctx* c, bool want_placement, bool want_slices, int* T_used) {
+    if (int rc = ensure_wide_staged(c)) return rc;   // (a NARROW problem whose batch cannot use the cache kernel but has pinned pods)
+    const int T = *T_used = wide_workgroup(c, c->S, c->max_n);
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    const int rc = wide_run(c->wide, *c, reinterpret_cast<const WideScenario*>(c->d_scen.p), c->S, c->d_orders.p, c->max_n, T, c->d_unsched.p,
+                            c->d_used_cpu.p, c->d_used_mem.p, c->d_used_vg.p, want_placement ? c->d_place.p : nullptr,
+                            c->has_ranks ? c->d_node_rank.p : nullptr, c->has_ranks ? c->d_node_inv.p : nullptr,
+                            want_slices ? c->d_gpu_slices.p : nullptr, c->stream, c->err);
+    if (rc) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    return SIMON_OK;
 }
 
 int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
@@ -2372,29 +2403,8 @@ int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
     if (run_wide && c->seg_n)     // the all-feature kernel takes prefix scenarios only
         return fail(c, SIMON_ESTATE, "run_loaded: segmented batch on a problem the score-table kernel does not take; run each scenario's own problem");
     if (run_wide) {
-        if (!c->wide_staged) {   // a NARROW problem whose batch cannot use the cache kernel but has pinned pods
-            int rcw = wide_stage(c->wide, *c, c->stream, c->err);
-            if (rcw) return rcw;
-            c->wide_staged = true;
-        }
         variant_used = SIMON_KERNEL_WIDE;
-        // Workgroup shape of the all-feature kernel.  A 256-thread group fits twice on a CU (launch bounds 256 x 2: two
-        // independent barrier domains per SIMD), which wins as soon as the batch offers two groups per CU; with fewer
-        // scenarios than that a CU holds ONE group and the 512-thread shape keeps all four SIMDs at two waves.
-        // Measured on config 5 (50 000 pods x 2 500..5 000 nodes): S = 256: 512 threads 536 ms, 256 threads 734 ms;
-        // S = 1 024: 512 threads 2 033 ms, 256 threads 1 611 ms.
-        int n_cu = 256;
-        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-        const bool two_groups = S >= 2 * n_cu && c->max_n <= 8192;          // 32 nodes per lane at most
-        T = c->force_T ? c->force_T : (c->max_n <= 1024 || two_groups ? 256 : c->max_n <= 16384 ? 512 : 1024);
-        if (T == 128) T = 256;                                  // (SIMON_WG=128: the all-feature kernel is built for 64 / 256 / 512 / 1 024 threads since round 5)
-        HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-        int rc = wide_run(c->wide, *c, reinterpret_cast<const WideScenario*>(c->d_scen.p), nullptr, S, c->d_orders.p,
-                          c->max_n, T, c->d_unsched.p, c->d_used_cpu.p, c->d_used_mem.p, c->d_used_vg.p,
-                          want_placement ? c->d_place.p : nullptr, c->has_ranks ? c->d_node_rank.p : nullptr,
-                          c->has_ranks ? c->d_node_inv.p : nullptr, want_slices ? c->d_gpu_slices.p : nullptr, c->stream, c->err);
-        if (rc) return rc;
-        HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+        if (int rc = run_wide_batch(c, want_placement != 0, want_slices, &T)) return rc;
     }
     if (want_risk) {                                             // (behind ev1: not part of kernel_ms; one wave per scenario, P / 64 steps)
         if (!c->prio_staged) {
@@ -2576,38 +2586,43 @@ int simon_min_plan_vg(simon_ctx* c, int32_t max_cpu_pct, int32_t max_mem_pct, in
     return SIMON_OK;
 }
 
-static int explain_impl(simon_ctx* c, int n_nodes, const int32_t* order, int ranked_scenario, int32_t* failed_pods,
-                        uint16_t* fail_codes, int32_t max_failed) {
-    int rc = stage(c);
-    if (rc) return rc;
+// One scenario replayed for simon_explain (order: the caller's, uploaded) and simon_explain_loaded (order == null: the scenario's row
+// of the loaded orders, and with per-scenario node ranks its own rank row, so that the replay breaks ties exactly like the batch did).
+static int explain_impl(simon_ctx* c, int n_nodes, const int32_t* order, int32_t scenario, int32_t* failed_pods, uint16_t* fail_codes,
+                        int32_t max_failed) {
+    if (int rc = stage(c)) return rc;
     if (c->seg_n) return fail(c, SIMON_ESTATE, "explain: segmented batch loaded");
     if (n_nodes < 0 || n_nodes > c->N) return fail(c, SIMON_EINVAL, "explain: n_nodes out of range");
-    for (int i = 0; i < c->P; ++i) if (order[i] < 0 || order[i] >= c->P) return fail(c, SIMON_EINVAL, "explain: bad order");
+    for (int i = 0; order && i < c->P; ++i) if (order[i] < 0 || order[i] >= c->P) return fail(c, SIMON_EINVAL, "explain: bad order");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->wide_staged) {   // NARROW problem: the failure codes still come from the all-feature kernel
-        rc = wide_stage(c->wide, *c, c->stream, c->err);
-        if (rc) return rc;
-        c->wide_staged = true;
-    }
+    if (int rc = ensure_wide_staged(c)) return rc;   // (NARROW problem: the failure codes still come from the all-feature kernel)
+    // not wide_workgroup's rule, on purpose: a single replay is one workgroup, and its thresholds are what existing replays run with
     int T = c->force_T ? c->force_T : (n_nodes <= 512 ? 256 : n_nodes <= 4096 ? 512 : 1024);
     if (T == 128) T = 256;
-    // with per-scenario node ranks the replay must break ties exactly like the batch did: the ranks of THAT scenario
-    const int32_t *rk = nullptr, *iv = nullptr;
-    if (ranked_scenario >= 0) {
-        rk = c->d_node_rank.p + (size_t)ranked_scenario * c->N;
-        iv = c->d_node_inv.p + (size_t)ranked_scenario * c->N;
-    }
+    const WideScenario hs{n_nodes, order ? 0 : c->scen[scenario].order_id};
+    const int32_t slot0 = 0;
+    int32_t nf = 0;
+    std::vector<int64_t> detail;                                   // (the context's own are set once the replay has succeeded)
+    WideReplay job;
+    job.scen = &hs; job.S = 1; job.max_n = n_nodes;
+    job.d_orders = order ? nullptr : c->d_orders.p; job.h_order = order;
+    if (!order && c->has_ranks) { job.rank_row = &scenario; job.d_node_rank = c->d_node_rank.p; job.d_node_inv = c->d_node_inv.p; }
     if (c->img_R > 0) {                  // ImageLocality of THIS size, whether or not the batch has it
         std::vector<unsigned char>& one = c->h_img_explain;
         one.assign((size_t)c->img_R * c->Cn, 0);
         img_slot_scores(c, n_nodes, one.data());
         HIP_TRY(c, c->d_img_explain.upload(one, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->wide.img_explain_ext = c->d_img_explain.p;
+        job.d_img = c->d_img_explain.p; job.img_slot = &slot0;
     }
+    job.max_failed = max_failed; job.n_failed = &nf; job.failed_pods = failed_pods; job.recorded_only = true;
+    job.fail_codes = fail_codes; job.code_stride = n_nodes;       // (no bins: the host folds the rows)
+    job.detail = &detail;
+    if (int rc = wide_replay(c->wide, *c, job, T, c->stream, c->err)) return rc;
+    c->explain_detail.swap(detail);
     c->explain_nodes = n_nodes;
     c->explain_ran = true;
-    return wide_explain(c->wide, *c, n_nodes, order, failed_pods, fail_codes, max_failed, T, rk, iv, c->stream, c->err, &c->explain_detail);
+    return nf;
 }
 
 int simon_explain(simon_ctx* c, simon_scenario scen, const int32_t* order, int32_t* failed_pods, uint16_t* fail_codes,
@@ -2624,9 +2639,7 @@ int simon_explain_loaded(simon_ctx* c, int32_t scenario, int32_t* failed_pods, u
     if (scenario < 0 || scenario >= c->S) return fail(c, SIMON_EINVAL, "explain_loaded: scenario %d outside [0,%d)", scenario, c->S);
     if (c->seg_n)        // the replay runs on the all-feature kernel, which takes prefix scenarios only
         return fail(c, SIMON_ESTATE, "explain_loaded: segmented batch; explain the scenario's own problem (its nodes alone)");
-    const ScenarioDesc& sd = c->scen[scenario];
-    return explain_impl(c, sd.n_nodes, c->h_orders.data() + (size_t)sd.order_id * c->P, c->has_ranks ? scenario : -1,
-                        failed_pods, fail_codes, max_failed);
+    return explain_impl(c, c->scen[scenario].n_nodes, nullptr, scenario, failed_pods, fail_codes, max_failed);
 }
 
 int simon_explain_batch(simon_ctx* c, const int32_t* scenarios, int32_t n_scen, int32_t max_failed, int32_t max_bins, int32_t* n_failed,
@@ -2637,27 +2650,27 @@ int simon_explain_batch(simon_ctx* c, const int32_t* scenarios, int32_t n_scen, 
     if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "explain_batch: no scenarios loaded");
     if (c->seg_n)        // the replay runs on the all-feature kernel, which takes prefix scenarios only
         return fail(c, SIMON_ESTATE, "explain_batch: segmented batch; explain each scenario's own problem (its nodes alone)");
+    const bool image = c->img_R > 0 && !c->img_sizes.empty();
     std::vector<WideScenario> hs((size_t)n_scen);
+    std::vector<int32_t> slots(image ? (size_t)n_scen : 0);
     int max_n = 0;
     for (int k = 0; k < n_scen; ++k) {
         if (scenarios[k] < 0 || scenarios[k] >= c->S) return fail(c, SIMON_EINVAL, "explain_batch: scenario %d outside [0,%d)", scenarios[k], c->S);
         hs[k] = WideScenario{c->scen[scenarios[k]].n_nodes, c->scen[scenarios[k]].order_id};
+        if (image) slots[k] = c->h_img_slot[scenarios[k]];
         max_n = std::max(max_n, hs[k].n_nodes);
     }
     if (fail_codes && code_stride < std::max(max_n, 1)) return fail(c, SIMON_EINVAL, "explain_batch: code_stride %d below the largest listed n_nodes %d", code_stride, max_n);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->wide_staged) {   // the batch ran on another kernel: the failure codes still come from the all-feature kernel
-        int rc = wide_stage(c->wide, *c, c->stream, c->err);
-        if (rc) return rc;
-        c->wide_staged = true;
-    }
-    // workgroup shape as simon_run_loaded chooses it for the all-feature kernel
-    const bool two_groups = n_scen >= 2 * c->n_cus && max_n <= 8192;
-    int T = c->force_T ? c->force_T : (max_n <= 1024 || two_groups ? 256 : max_n <= 16384 ? 512 : 1024);
-    if (T == 128) T = 256;
-    return wide_explain_batch(c->wide, *c, hs.data(), scenarios, n_scen, c->d_orders.p, max_n, T, max_failed, max_bins, n_failed, failed_pods, n_bins,
-                              bins, fail_codes, code_stride, c->has_ranks ? c->d_node_rank.p : nullptr, c->has_ranks ? c->d_node_inv.p : nullptr,
-                              c->img_R > 0 ? c->h_img_slot.data() : nullptr, c->stream, c->err);
+    if (int rc = ensure_wide_staged(c)) return rc;   // (the batch ran on another kernel: the failure codes still come from the all-feature kernel)
+    WideReplay job;
+    job.scen = hs.data(); job.S = n_scen; job.max_n = max_n; job.d_orders = c->d_orders.p;
+    if (c->has_ranks) { job.rank_row = scenarios; job.d_node_rank = c->d_node_rank.p; job.d_node_inv = c->d_node_inv.p; }
+    if (image) { job.d_img = c->wide.img; job.img_slot = slots.data(); }
+    job.max_failed = max_failed; job.n_failed = n_failed; job.failed_pods = failed_pods;
+    job.max_bins = max_bins; job.n_bins = n_bins; job.bins = bins;
+    job.fail_codes = fail_codes; job.code_stride = code_stride;
+    return wide_replay(c->wide, *c, job, wide_workgroup(c, n_scen, max_n), c->stream, c->err);
 }
 
 int simon_get_stats(simon_ctx* c, simon_stats* st) {

@@ -249,9 +249,8 @@ struct WideDevice {
     uint64_t* static_mask = nullptr; uint8_t* static_reason = nullptr; int64_t* simon_raw = nullptr;
     int64_t *na_raw = nullptr, *tt_raw = nullptr, *static_add = nullptr;
     uint8_t* img = nullptr;                  // [slots][img_R][Cn] of the batch
-    int32_t *img_row_of = nullptr, *img_zero = nullptr;
+    int32_t* img_row_of = nullptr;
     const int32_t* img_slot_ext = nullptr;   // [S] slot of every loaded scenario (owned by the context)
-    const uint8_t* img_explain_ext = nullptr;   // [1][img_R][Cn] of the scenario being explained (owned by the context)
     int32_t *term_key = nullptr, *term_dom_off = nullptr, *term_set = nullptr, *anti_off = nullptr, *anti_idx = nullptr,
             *match_off = nullptr, *match_idx = nullptr, *manti_off = nullptr, *manti_idx = nullptr, *mown_off = nullptr, *mown_idx = nullptr, *aff_off = nullptr, *aff_idx = nullptr, *port_off = nullptr, *port_idx = nullptr, *pref_off = nullptr,
             *pref_idx = nullptr, *pref_w = nullptr, *own_off = nullptr, *own_idx = nullptr, *own_w = nullptr,
@@ -286,16 +285,31 @@ struct WideDevice {
 hipError_t wide_launch_local(const WideArgs& a, int T, bool explain, size_t lds, hipStream_t st);
 hipError_t wide_launch_explain(const WideArgs& a, int T, size_t lds, hipStream_t st);
 int wide_stage(WideDevice& w, const HostInputs& in, hipStream_t st, std::string& err);
-int wide_run(WideDevice& w, const HostInputs& in, const WideScenario* d_scen, const int32_t* h_perm_unused, int S,
-             const int32_t* d_orders, int max_n, int T, int32_t* d_unsched, int64_t* d_used_cpu, int64_t* d_used_mem,
-             int64_t* d_used_vg, int32_t* d_place, const int32_t* d_node_rank, const int32_t* d_node_inv, uint64_t* d_gpu_slices,
-             hipStream_t st, std::string& err);
-int wide_explain(WideDevice& w, const HostInputs& in, int n_nodes, const int32_t* order, int32_t* failed_pods,
-                 uint16_t* fail_codes, int32_t max_failed, int T, const int32_t* d_rank_row, const int32_t* d_inv_row, hipStream_t st,
-                 std::string& err, std::vector<int64_t>* local_detail = nullptr);
-int wide_explain_batch(WideDevice& w, const HostInputs& in, const WideScenario* h_scen, const int32_t* h_idx, int S, const int32_t* d_orders,
-                       int max_n, int T, int32_t max_failed, int32_t max_bins, int32_t* n_failed, int32_t* failed_pods, int32_t* n_bins,
-                       simon_fail_bin* bins, uint16_t* fail_codes, int32_t code_stride, const int32_t* d_node_rank, const int32_t* d_node_inv,
-                       const int32_t* h_img_slot, hipStream_t st, std::string& err);
+int wide_run(WideDevice& w, const HostInputs& in, const WideScenario* d_scen, int S, const int32_t* d_orders, int max_n, int T,
+             int32_t* d_unsched, int64_t* d_used_cpu, int64_t* d_used_mem, int64_t* d_used_vg, int32_t* d_place,
+             const int32_t* d_node_rank, const int32_t* d_node_inv, uint64_t* d_gpu_slices, hipStream_t st, std::string& err);
+
+// One EXPLAIN launch (simon_explain, simon_explain_loaded, simon_explain_batch): the listed scenarios replayed by one workgroup each.
+// Host pointers unless named d_; everything per listed scenario is in launch order.
+struct WideReplay {
+    const WideScenario* scen = nullptr;   // [S] listed scenarios: n_nodes, and the row of d_orders (an ad-hoc order: 0)
+    int S = 0, max_n = 0;                 // max_n: the largest listed n_nodes
+    const int32_t* d_orders = nullptr;    // the orders of the loaded batch, or
+    const int32_t* h_order = nullptr;     // ... the one order [P] of an ad-hoc scenario (d_orders == null)
+    // per-scenario node ranks: rank_row[k] = the listed scenario's row of the whole batch's [S_total][N] tables; null = pool order
+    const int32_t* rank_row = nullptr; const int32_t* d_node_rank = nullptr; const int32_t* d_node_inv = nullptr;
+    // ImageLocality: the table and every listed scenario's slot of it (a single replay: a one-slot table of its size, slot 0)
+    const uint8_t* d_img = nullptr; const int32_t* img_slot = nullptr;
+    int32_t max_failed = 0;
+    int32_t* n_failed = nullptr;          // [S] unscheduled pods
+    int32_t* failed_pods = nullptr;       // [S][max_failed]
+    // The single replays' contract (simon_hip.h): failed_pods / fail_codes / detail receive the rows a scenario recorded,
+    // min(n_failed, max_failed) of them, and nothing behind.  Otherwise every output is copied whole: what was not recorded is zero.
+    bool recorded_only = false;
+    int32_t max_bins = 0; int32_t* n_bins = nullptr; simon_fail_bin* bins = nullptr;   // [S][max_failed]([max_bins]); bins == null: no histogram
+    uint16_t* fail_codes = nullptr; int32_t code_stride = 0;                         // [S][max_failed][code_stride], or null
+    std::vector<int64_t>* detail = nullptr;   // Open-Local's error sizes [recorded][n_nodes][4]: one scenario only, with recorded_only
+};
+int wide_replay(WideDevice& w, const HostInputs& in, const WideReplay& job, int T, hipStream_t st, std::string& err);
 
 }  // namespace simon

@@ -1677,9 +1677,8 @@ hipError_t wide_launch_explain(const WideArgs& a, int T, size_t lds, hipStream_t
 #else
 namespace {
 template <bool EXPLAIN>
-hipError_t launch(const WideArgs& a, int T, int max_n, hipStream_t st) {
+hipError_t launch(const WideArgs& a, int T, hipStream_t st) {
     const size_t lds = wide_lds_bytes(a, T);
-    (void)max_n;
     if (a.flags & kArgLocal) return wide_launch_local(a, T, EXPLAIN, lds, st);
     if (!EXPLAIN && (a.flags & kArgLean) && !(a.flags & kArgRanked)) return launch_sized<false, 0>(a, T, lds, st);
     if (EXPLAIN) return wide_launch_explain(a, T, lds, st);
@@ -1726,7 +1725,7 @@ void fill_args(const WideDevice& w, const HostInputs& in, WideArgs& a, WideCold&
     c.static_reason = in.static_reason.empty() ? nullptr : w.static_reason;
     c.na_raw = in.has_na ? w.na_raw : nullptr; c.tt_raw = in.has_tt ? w.tt_raw : nullptr;
     c.static_add = in.has_add ? w.static_add : nullptr;
-    if (in.has_img && in.img_R > 0) {               // (the scenario's table: wide_run / wide_explain)
+    if (in.has_img && in.img_R > 0) {               // (the table and the scenarios' slots: wide_run / wide_replay)
         a.flags = (a.flags | kArgImage) & ~kArgKey32;
         c.img_row_of = w.img_row_of; c.img_R = in.img_R;
     }
@@ -1973,7 +1972,7 @@ int wide_stage(WideDevice& w, const HostInputs& in, hipStream_t st, std::string&
     PUT(i_scalar_req, in.i_scalar_req, 1); PUT(i_gpu_used, in.i_gpu_used, N * SIMON_MAX_GPU_DEV);
     PUT(static_mask, in.static_mask, 1); PUT(static_reason, in.static_reason, 1); PUT(simon_raw, in.simon_raw, 1);
     PUT(na_raw, in.na_raw, 1); PUT(tt_raw, in.tt_raw, 1); PUT(static_add, in.static_add, 1);
-    PUT(img, in.img_cls, 1); PUT(img_row_of, in.img_row_of, 1); PUT(img_zero, std::vector<int32_t>(), 1);   // (no host source: put() zero-fills the one element)
+    PUT(img, in.img_cls, 1); PUT(img_row_of, in.img_row_of, 1);
     PUT(term_key, in.term_key, 1); PUT(term_dom_off, dom_off, 1); PUT(term_set, term_set, 1); PUT(node_sets, in.node_sets, 1);
     PUT(anti_off, anti_off, 1); PUT(anti_idx, anti_sorted, 1); PUT(match_off, match_off, 1); PUT(match_idx, in.match_idx, 1);
     PUT(manti_off, manti_off, 1); PUT(manti_idx, manti_idx, 1); PUT(mown_off, mown_off, 1); PUT(mown_idx, mown_idx, 1);
@@ -1999,33 +1998,74 @@ int wide_stage(WideDevice& w, const HostInputs& in, hipStream_t st, std::string&
     return 0;
 }
 
-// Runs S scenarios in chunks whose per-scenario state fits a fixed HBM budget (the state of a
-// chunk is reused by the next one; kernels on one stream serialise).
-int wide_run(WideDevice& w, const HostInputs& in, const WideScenario* d_scen, const int32_t*, int S,
-             const int32_t* d_orders, int max_n, int T, int32_t* d_unsched, int64_t* d_used_cpu, int64_t* d_used_mem,
-             int64_t* d_used_vg, int32_t* d_place, const int32_t* d_node_rank, const int32_t* d_node_inv, uint64_t* d_gpu_slices, hipStream_t st,
-             std::string& err) {
-    if ((long long)max_n > (long long)kMaxIter * T) { err = "wide kernel: more than 32 nodes per lane"; return SIMON_ERANGE; }
-    const size_t per = state_bytes_per_scenario(w, in);
-    const size_t budget = w.knobs.state_budget;  // default 16 GiB of the 288 GB HBM for scenario state
-    int chunk = (int)std::min<size_t>(S, std::max<size_t>(1, budget / per));
-    int rc = ensure_state(w, in, chunk, err);
-    if (rc) return rc;
-    rc = ensure_mask_lanes(w, in, T, st, err);
-    if (rc) return rc;
+#define TRY(x) if (hipError_t e_ = (x); e_ != hipSuccess) { err = std::string(#x ": ") + hipGetErrorString(e_); return SIMON_ENODEV; }
+
+namespace {
+// What every launch of the all-feature kernel has in common, wide_run's and a replay's: the arguments as staging and the workgroup
+// size decide them, then (launch_chunks) the cold half in its slot of d_cold and the scenarios in chunks whose state fits the HBM
+// budget (the state of a chunk is reused by the next one; kernels on one stream serialise).  Between the two calls the caller
+// sets what is its own, with a.scen and the outputs in a pointing at the FIRST scenario's entries.
+struct WideLaunch {
     WideArgs a;
     WideCold c;
-    fill_args(w, in, a, c);
-    a.mask_lanes = w.mask_lanes;
-    c.node_rank = d_node_rank; c.node_inv = d_node_inv;
+    int S = 0, T = 0, chunk = 0;
+    void ranks(const int32_t* d_rank, const int32_t* d_inv) {     // rows [S][N] of this launch's scenarios, or null
+        c.node_rank = d_rank; c.node_inv = d_inv;
+        if (d_rank && d_inv) a.flags |= kArgRanked;
+    }
+};
+
+int prepare(WideDevice& w, const HostInputs& in, int S, int max_n, int T, hipStream_t st, std::string& err, WideLaunch& L) {
+    if ((long long)max_n > (long long)kMaxIter * T) { err = "wide kernel: more than 32 nodes per lane"; return SIMON_ERANGE; }
+    L.S = S; L.T = T;
+    // default budget: 16 GiB of the 288 GB HBM for scenario state
+    L.chunk = (int)std::min<size_t>(S, std::max<size_t>(1, w.knobs.state_budget / state_bytes_per_scenario(w, in)));
+    if (int rc = ensure_state(w, in, L.chunk, err)) return rc;
+    if (int rc = ensure_mask_lanes(w, in, T, st, err)) return rc;
+    fill_args(w, in, L.a, L.c);
+    L.a.mask_lanes = w.mask_lanes;
+    L.a.bc_words = (std::max(max_n, 1) + 3) & ~3;
+    return 0;
+}
+
+template <bool EXPLAIN>
+int launch_chunks(WideDevice& w, const HostInputs& in, const WideLaunch& L, int slot, hipStream_t st, std::string& err) {
+    WideArgs a = L.a;
+    a.cold = w.d_cold + slot;
+    // the cold half of the arguments lives in device memory (pageable source: the copy is staged before return)
+    TRY(hipMemcpyAsync(w.d_cold + slot, &L.c, sizeof L.c, hipMemcpyHostToDevice, st));
+    TRY(hipStreamSynchronize(st));
+    for (int s0 = 0; s0 < L.S; s0 += L.chunk) {
+        a.S = std::min(L.chunk, L.S - s0);
+        a.scen_base = s0;
+        a.scen = L.a.scen + s0;
+        a.unscheduled = L.a.unscheduled + s0; a.used_cpu = L.a.used_cpu + s0; a.used_mem = L.a.used_mem + s0;
+        a.used_vg = L.a.used_vg ? L.a.used_vg + s0 : nullptr;
+        a.placement = L.a.placement ? L.a.placement + (size_t)s0 * in.P : nullptr;
+        TRY(launch<EXPLAIN>(a, L.T, st));
+    }
+    return 0;
+}
+
+}  // namespace
+
+// A batch run.  Its own: the batch's image slots, the (signature, node) table, the stage-A caches and class rows against the LDS
+// budget, the phase profiler, used_vg / placement / gpu_slices.  Slot [0] of d_cold.
+int wide_run(WideDevice& w, const HostInputs& in, const WideScenario* d_scen, int S, const int32_t* d_orders, int max_n, int T,
+             int32_t* d_unsched, int64_t* d_used_cpu, int64_t* d_used_mem, int64_t* d_used_vg, int32_t* d_place,
+             const int32_t* d_node_rank, const int32_t* d_node_inv, uint64_t* d_gpu_slices, hipStream_t st, std::string& err) {
+    WideLaunch L;
+    if (int rc = prepare(w, in, S, max_n, T, st, err, L)) return rc;
+    WideArgs& a = L.a;
+    WideCold& c = L.c;
+    L.ranks(d_node_rank, d_node_inv);
     c.gpu_slices = d_gpu_slices;
     if (a.flags & kArgImage) {
         if (!w.img_slot_ext || in.img_sizes.empty()) { err = "wide kernel: image scores of the batch are not staged"; return SIMON_ESTATE; }
         c.img = w.img; c.img_slot = w.img_slot_ext;
     }
-    if (d_node_rank && d_node_inv) a.flags |= kArgRanked;
-    a.orders = d_orders;
-    a.bc_words = (std::max(max_n, 1) + 3) & ~3;
+    a.orders = d_orders; a.scen = d_scen;
+    a.unscheduled = d_unsched; a.used_cpu = d_used_cpu; a.used_mem = d_used_mem; a.used_vg = d_used_vg; a.placement = d_place;
     {   // stage-A caches for stage B (kArgIpaCache / kArgPtsCache): only when they leave the workgroups-per-CU of the launch alone
         const size_t budget = (T == 256 ? 72 : 140) * 1024;
         if (!(a.flags & kArgClassMode) && !w.knobs.no_rows_lds) {      // more than 64 node classes: the class rows in LDS when they fit (first call on the budget)
@@ -2059,7 +2099,7 @@ int wide_run(WideDevice& w, const HostInputs& in, const WideScenario* d_scen, co
     }
     unsigned long long* d_prof = nullptr;
 #ifdef SIMON_WIDE_PROFILE
-    const bool prof = w.knobs.prof && chunk >= S;
+    const bool prof = w.knobs.prof && L.chunk >= S;
 #else
     const bool prof = false;
     if (w.knobs.prof) fprintf(stderr, "[SIMON_WIDE_PROF] this build has no phase profiler: bash profiles/build_variant.sh prof -DSIMON_WIDE_PROFILE\n");
@@ -2069,26 +2109,11 @@ int wide_run(WideDevice& w, const HostInputs& in, const WideScenario* d_scen, co
         c.prof = d_prof;
         a.flags |= kArgProf;
     }
-    a.cold = w.d_cold;
-    {   // the cold half of the arguments lives in device memory (pageable source: the copy is staged before return)
-        hipError_t e = hipMemcpyAsync(w.d_cold, &c, sizeof c, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { err = std::string("cold args: ") + hipGetErrorString(e); return SIMON_ENODEV; }
-    }
-    for (int s0 = 0; s0 < S; s0 += chunk) {
-        a.S = std::min(chunk, S - s0);
-        a.scen_base = s0;
-        a.scen = d_scen + s0;
-        a.unscheduled = d_unsched + s0; a.used_cpu = d_used_cpu + s0; a.used_mem = d_used_mem + s0; a.used_vg = d_used_vg ? d_used_vg + s0 : nullptr;
-        a.placement = d_place ? d_place + (size_t)s0 * in.P : nullptr;
-        hipError_t e = launch<false>(a, T, max_n, st);
-        if (e != hipSuccess) { err = std::string("wide launch: ") + hipGetErrorString(e); return SIMON_ENODEV; }
-    }
-    if (d_prof) {   // diagnostics: mean s_memtime ticks per cycle and phase (s_memtime advances at about the shader clock on gfx950: the phase sums match the kernel time at ~2.4 GHz)
+    const int rc = launch_chunks<false>(w, in, L, 0, st, err);
+    if (d_prof && !rc) {   // diagnostics: mean s_memtime ticks per cycle and phase (s_memtime advances at about the shader clock on gfx950: the phase sums match the kernel time at ~2.4 GHz)
         std::vector<unsigned long long> h((size_t)S * 16 * 16);
         (void)hipStreamSynchronize(st);
         (void)hipMemcpy(h.data(), d_prof, h.size() * 8, hipMemcpyDeviceToHost);
-        (void)hipFree(d_prof);
         const char* names[16] = {"pod row", "reduce+barrier", "stage A2 | table-only: batch wait", "stage B + reduce", "assume: counter barrier", "stage A (table only)",
                                  "stage A (node filters)", "stage A (topology terms)", "assume: row load", "assume: row stores + counters",
                                  "assume: column", "table-only: setup", "A: batch arrival + ports/hard/aff", "A: zero-counter list", "A: gpu/local + feasible bookkeeping",
@@ -2102,150 +2127,94 @@ int wide_run(WideDevice& w, const HostInputs& in, const WideScenario* d_scen, co
             fprintf(stderr, "\n");
         }
     }
-    return 0;
+    if (d_prof) { (void)hipStreamSynchronize(st); (void)hipFree(d_prof); }
+    return rc;
 }
 
-int wide_explain(WideDevice& w, const HostInputs& in, int n_nodes, const int32_t* order, int32_t* failed_pods,
-                 uint16_t* fail_codes, int32_t max_failed, int T, const int32_t* d_rank_row, const int32_t* d_inv_row, hipStream_t st,
-                 std::string& err, std::vector<int64_t>* local_detail) {
-    if ((long long)n_nodes > (long long)kMaxIter * T) { err = "wide kernel: more than 32 nodes per lane"; return SIMON_ERANGE; }
-    int rc = ensure_state(w, in, 1, err);
-    if (rc) return rc;
-    const size_t P = in.P;
-    WideScenario hs{n_nodes, 0};
-    void *d_scen = nullptr, *d_order = nullptr, *d_failed = nullptr, *d_codes = nullptr, *d_nf = nullptr, *d_out = nullptr, *d_detail = nullptr;
-    const size_t code_bytes = (size_t)max_failed * std::max(n_nodes, 1) * 2;
-    const bool want_detail = local_detail && in.has_local;             // Open-Local in the problem: [max_failed][n][4] int64
-    const size_t detail_bytes = want_detail ? code_bytes / 2 * 4 * 8 : 0;
-    if (local_detail) local_detail->clear();
-    hipError_t e = hipSuccess;
-    auto cleanup = [&]() { for (void* p : {d_scen, d_order, d_failed, d_codes, d_nf, d_out, d_detail}) if (p) (void)hipFree(p); };
-#define TRY(x) if ((e = (x)) != hipSuccess) { err = std::string(#x ": ") + hipGetErrorString(e); cleanup(); return SIMON_ENODEV; }
-    TRY(hipMalloc(&d_scen, sizeof hs)); TRY(hipMalloc(&d_order, std::max<size_t>(P, 1) * 4));
-    TRY(hipMalloc(&d_failed, (size_t)max_failed * 4)); TRY(hipMalloc(&d_codes, code_bytes));
-    TRY(hipMalloc(&d_nf, 4)); TRY(hipMalloc(&d_out, 4 + 8 + 8 + 8));
-    TRY(hipMemcpyAsync(d_scen, &hs, sizeof hs, hipMemcpyHostToDevice, st));
-    TRY(hipMemcpyAsync(d_order, order, P * 4, hipMemcpyHostToDevice, st));
-    TRY(hipMemsetAsync(d_codes, 0, code_bytes, st));
-    TRY(hipMemsetAsync(d_nf, 0, 4, st));
-    if (want_detail) { TRY(hipMalloc(&d_detail, detail_bytes)); TRY(hipMemsetAsync(d_detail, 0, detail_bytes, st)); }
-    WideArgs a;
-    WideCold c;
-    rc = ensure_mask_lanes(w, in, T, st, err);
-    if (rc) return rc;
-    fill_args(w, in, a, c);
-    a.mask_lanes = w.mask_lanes;
-    c.node_rank = d_rank_row; c.node_inv = d_inv_row;
-    if (d_rank_row && d_inv_row) a.flags |= kArgRanked;
-    if (a.flags & kArgImage) {                   // the image scores of THIS n_nodes, whether or not the batch has the size
-        if (!w.img_explain_ext) { err = "wide explain: image scores of the scenario are not staged"; cleanup(); return SIMON_ESTATE; }
-        c.img = w.img_explain_ext; c.img_slot = w.img_zero;
+// The replay behind simon_explain, simon_explain_loaded and simon_explain_batch: the job's scenarios on the EXPLAIN instantiation, launched
+// as wide_run launches a batch but without the (signature, node) table (failure codes come from the full per-node evaluation) and
+// without the stage-A caches.  Slot [1] of d_cold.  ONE device allocation holds everything of the call -- scenarios, an ad-hoc order,
+// rank rows and image slots gathered into launch order (the kernel indexes both by scen_base + s), every output -- and every way out
+// passes the one hipFree.
+int wide_replay(WideDevice& w, const HostInputs& in, const WideReplay& job, int T, hipStream_t st, std::string& err) {
+    const int S = job.S;
+    const bool want_detail = job.detail && in.has_local;
+    // the kernel indexes fail_detail by recorded pod and node, without the scenario
+    if (job.detail && (S != 1 || !job.recorded_only)) { err = "wide explain: Open-Local detail is for one scenario"; return SIMON_EINVAL; }
+    WideLaunch L;
+    if (int rc = prepare(w, in, S, job.max_n, T, st, err, L)) return rc;
+    WideArgs& a = L.a;
+    WideCold& c = L.c;
+    const bool ranked = job.rank_row && job.d_node_rank && job.d_node_inv, image = (a.flags & kArgImage) != 0u;
+    if (image && (!job.d_img || !job.img_slot)) {
+        err = std::string("wide explain: image scores of the ") + (job.recorded_only ? "scenario" : "batch") + " are not staged";
+        return SIMON_ESTATE;
     }
-    a.S = 1; a.scen = (const WideScenario*)d_scen; a.orders = (const int32_t*)d_order;
-    a.bc_words = (std::max(n_nodes, 1) + 3) & ~3;
-    a.n_sigs = 0;   // failure codes come from the full per-node evaluation
-    a.unscheduled = (int32_t*)d_out; a.used_cpu = (int64_t*)((char*)d_out + 8); a.used_mem = (int64_t*)((char*)d_out + 16);
-    a.placement = nullptr;
-    c.failed_pods = (int32_t*)d_failed; c.fail_codes = (uint16_t*)d_codes; c.max_failed = max_failed; c.n_failed = (int32_t*)d_nf;
-    c.fail_detail = (long long*)d_detail;
-    c.code_stride = n_nodes;                     // (no bins: the host folds the rows)
-    a.cold = w.d_cold + 1;
-    TRY(hipMemcpyAsync(w.d_cold + 1, &c, sizeof c, hipMemcpyHostToDevice, st));
-    TRY(hipStreamSynchronize(st));
-    TRY(launch<true>(a, T, n_nodes, st));
-    int32_t nf = 0;
-    TRY(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, st));
-    TRY(hipStreamSynchronize(st));
-    const int k = std::min(nf, max_failed);
-    if (k > 0) {
-        TRY(hipMemcpy(failed_pods, d_failed, (size_t)k * 4, hipMemcpyDeviceToHost));
-        TRY(hipMemcpy(fail_codes, d_codes, (size_t)k * n_nodes * 2, hipMemcpyDeviceToHost));
-        if (want_detail) {
-            local_detail->resize((size_t)k * n_nodes * 4);
-            TRY(hipMemcpy(local_detail->data(), d_detail, (size_t)k * n_nodes * 4 * 8, hipMemcpyDeviceToHost));
-        }
-    }
-#undef TRY
-    cleanup();
-    return nf;
-}
-
-// simon_explain_batch: the listed scenarios of the loaded batch replayed by one workgroup each, as wide_run launches a batch (state
-// chunks within the budget) but on the EXPLAIN instantiation with wide_explain's arguments (no (signature, node) table, no stage-A
-// caches).  h_scen / h_idx are in launch order; rank rows and image slots of the batch are gathered into launch order, because the
-// kernel indexes both by scen_base + s.  One device allocation holds everything of the call.
-int wide_explain_batch(WideDevice& w, const HostInputs& in, const WideScenario* h_scen, const int32_t* h_idx, int S, const int32_t* d_orders,
-                       int max_n, int T, int32_t max_failed, int32_t max_bins, int32_t* n_failed, int32_t* failed_pods, int32_t* n_bins,
-                       simon_fail_bin* bins, uint16_t* fail_codes, int32_t code_stride, const int32_t* d_node_rank, const int32_t* d_node_inv,
-                       const int32_t* h_img_slot, hipStream_t st, std::string& err) {
-    if ((long long)max_n > (long long)kMaxIter * T) { err = "wide kernel: more than 32 nodes per lane"; return SIMON_ERANGE; }
-    const size_t per = state_bytes_per_scenario(w, in);
-    const int chunk = (int)std::min<size_t>(S, std::max<size_t>(1, w.knobs.state_budget / per));
-    int rc = ensure_state(w, in, chunk, err);
-    if (rc) return rc;
-    rc = ensure_mask_lanes(w, in, T, st, err);
-    if (rc) return rc;
-    WideArgs a;
-    WideCold c;
-    fill_args(w, in, a, c);
-    const bool ranked = d_node_rank && d_node_inv, image = (a.flags & kArgImage) != 0u;
-    if (image && (!h_img_slot || in.img_sizes.empty())) { err = "wide explain: image scores of the batch are not staged"; return SIMON_ESTATE; }
-    const size_t N = in.N, rows = (size_t)S * max_failed;
+    const size_t N = in.N, P = in.P, rows = (size_t)S * job.max_failed,
+                 stride = job.code_stride, cells = rows * std::max(job.code_stride, 1);     // (cells: a row of no node still has an address)
     size_t total = 0;
     auto carve = [&](size_t bytes) { const size_t off = total; total += (bytes + 255) & ~(size_t)255; return off; };
-    const size_t o_scen = carve((size_t)S * sizeof(WideScenario)), o_uns = carve((size_t)S * 4), o_ucpu = carve((size_t)S * 8), o_umem = carve((size_t)S * 8),
+    // (everything from o_nf on is cleared: what a scenario does not record reads as zero)
+    const size_t o_scen = carve((size_t)S * sizeof(WideScenario)), o_order = carve(job.d_orders ? 0 : std::max<size_t>(P, 1) * 4),
+                 o_uns = carve((size_t)S * 4), o_ucpu = carve((size_t)S * 8), o_umem = carve((size_t)S * 8),
                  o_slot = carve(image ? (size_t)S * 4 : 0), o_rank = carve(ranked ? (size_t)S * N * 4 : 0), o_inv = carve(ranked ? (size_t)S * N * 4 : 0),
-                 o_nf = carve((size_t)S * 4), o_failed = carve(rows * 4), o_nb = carve(rows * 4), o_bins = carve(rows * max_bins * sizeof(simon_fail_bin)),
-                 o_codes = carve(fail_codes ? rows * (size_t)code_stride * 2 : 0);
+                 o_nf = carve((size_t)S * 4), o_failed = carve(rows * 4), o_nb = carve(job.bins ? rows * 4 : 0),
+                 o_bins = carve(job.bins ? rows * job.max_bins * sizeof(simon_fail_bin) : 0),
+                 o_codes = carve(job.fail_codes ? cells * 2 : 0), o_detail = carve(want_detail ? cells * 4 * 8 : 0);
     char* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, std::max<size_t>(total, 256));
-    if (e != hipSuccess) { err = std::string("hipMalloc(explain batch): ") + hipGetErrorString(e); return SIMON_ENOMEM; }
-#define TRY(x) if ((e = (x)) != hipSuccess) { err = std::string(#x ": ") + hipGetErrorString(e); (void)hipStreamSynchronize(st); (void)hipFree(d); return SIMON_ENODEV; }
-    std::vector<int32_t> slots;                                          // (outlives the asynchronous upload: synchronised below)
-    TRY(hipMemcpyAsync(d + o_scen, h_scen, (size_t)S * sizeof(WideScenario), hipMemcpyHostToDevice, st));
-    TRY(hipMemsetAsync(d + o_nf, 0, total - o_nf, st));                  // what a scenario does not record reads as zero
-    if (image) {
-        slots.resize(S);
-        for (int k = 0; k < S; ++k) slots[k] = h_img_slot[h_idx[k]];
-        TRY(hipMemcpyAsync(d + o_slot, slots.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
-        c.img = w.img; c.img_slot = (const int32_t*)(d + o_slot);
-    }
-    if (ranked) {
-        for (int k = 0; k < S; ++k) {
-            TRY(hipMemcpyAsync(d + o_rank + (size_t)k * N * 4, d_node_rank + (size_t)h_idx[k] * N, N * 4, hipMemcpyDeviceToDevice, st));
-            TRY(hipMemcpyAsync(d + o_inv + (size_t)k * N * 4, d_node_inv + (size_t)h_idx[k] * N, N * 4, hipMemcpyDeviceToDevice, st));
+    if (hipError_t e = hipMalloc((void**)&d, std::max<size_t>(total, 256)); e != hipSuccess) { err = std::string("hipMalloc(explain): ") + hipGetErrorString(e); return SIMON_ENOMEM; }
+    auto body = [&]() -> int {
+        TRY(hipMemcpyAsync(d + o_scen, job.scen, (size_t)S * sizeof(WideScenario), hipMemcpyHostToDevice, st));
+        TRY(hipMemsetAsync(d + o_nf, 0, total - o_nf, st));
+        if (!job.d_orders) TRY(hipMemcpyAsync(d + o_order, job.h_order, P * 4, hipMemcpyHostToDevice, st));
+        if (image) {
+            TRY(hipMemcpyAsync(d + o_slot, job.img_slot, (size_t)S * 4, hipMemcpyHostToDevice, st));
+            c.img = job.d_img; c.img_slot = (const int32_t*)(d + o_slot);
         }
-        c.node_rank = (const int32_t*)(d + o_rank); c.node_inv = (const int32_t*)(d + o_inv);
-        a.flags |= kArgRanked;
-    }
-    a.mask_lanes = w.mask_lanes;
-    a.orders = d_orders;
-    a.bc_words = (std::max(max_n, 1) + 3) & ~3;
-    a.n_sigs = 0;   // failure codes come from the full per-node evaluation
-    a.placement = nullptr;
-    c.max_failed = max_failed; c.n_failed = (int32_t*)(d + o_nf); c.failed_pods = (int32_t*)(d + o_failed);
-    c.fail_codes = fail_codes ? (uint16_t*)(d + o_codes) : nullptr; c.code_stride = code_stride; c.fail_detail = nullptr;
-    c.max_bins = max_bins; c.bins = (simon_fail_bin*)(d + o_bins); c.n_bins = (int32_t*)(d + o_nb);
-    a.cold = w.d_cold + 1;
-    TRY(hipMemcpyAsync(w.d_cold + 1, &c, sizeof c, hipMemcpyHostToDevice, st));
-    TRY(hipStreamSynchronize(st));
-    for (int s0 = 0; s0 < S; s0 += chunk) {
-        a.S = std::min(chunk, S - s0);
-        a.scen_base = s0;
-        a.scen = (const WideScenario*)(d + o_scen) + s0;
-        a.unscheduled = (int32_t*)(d + o_uns) + s0; a.used_cpu = (int64_t*)(d + o_ucpu) + s0; a.used_mem = (int64_t*)(d + o_umem) + s0;
-        TRY(launch<true>(a, T, max_n, st));
-    }
-    TRY(hipMemcpyAsync(n_failed, d + o_nf, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-    TRY(hipMemcpyAsync(failed_pods, d + o_failed, rows * 4, hipMemcpyDeviceToHost, st));
-    TRY(hipMemcpyAsync(n_bins, d + o_nb, rows * 4, hipMemcpyDeviceToHost, st));
-    TRY(hipMemcpyAsync(bins, d + o_bins, rows * max_bins * sizeof(simon_fail_bin), hipMemcpyDeviceToHost, st));
-    if (fail_codes) TRY(hipMemcpyAsync(fail_codes, d + o_codes, rows * (size_t)code_stride * 2, hipMemcpyDeviceToHost, st));
-    TRY(hipStreamSynchronize(st));
-#undef TRY
+        if (ranked) {
+            for (int k = 0; k < S; ++k) {
+                TRY(hipMemcpyAsync(d + o_rank + (size_t)k * N * 4, job.d_node_rank + (size_t)job.rank_row[k] * N, N * 4, hipMemcpyDeviceToDevice, st));
+                TRY(hipMemcpyAsync(d + o_inv + (size_t)k * N * 4, job.d_node_inv + (size_t)job.rank_row[k] * N, N * 4, hipMemcpyDeviceToDevice, st));
+            }
+            L.ranks((const int32_t*)(d + o_rank), (const int32_t*)(d + o_inv));
+        }
+        a.scen = (const WideScenario*)(d + o_scen);
+        a.orders = job.d_orders ? job.d_orders : (const int32_t*)(d + o_order);
+        a.n_sigs = 0;
+        a.unscheduled = (int32_t*)(d + o_uns); a.used_cpu = (int64_t*)(d + o_ucpu); a.used_mem = (int64_t*)(d + o_umem);
+        c.max_failed = job.max_failed; c.n_failed = (int32_t*)(d + o_nf); c.failed_pods = (int32_t*)(d + o_failed);
+        c.fail_codes = job.fail_codes ? (uint16_t*)(d + o_codes) : nullptr; c.code_stride = (int32_t)stride;
+        c.fail_detail = want_detail ? (long long*)(d + o_detail) : nullptr;
+        if (job.bins) { c.max_bins = job.max_bins; c.bins = (simon_fail_bin*)(d + o_bins); c.n_bins = (int32_t*)(d + o_nb); }
+        if (int rl = launch_chunks<true>(w, in, L, 1, st, err)) return rl;
+        TRY(hipMemcpyAsync(job.n_failed, d + o_nf, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+        if (!job.recorded_only) {
+            TRY(hipMemcpyAsync(job.failed_pods, d + o_failed, rows * 4, hipMemcpyDeviceToHost, st));
+            if (job.bins) {
+                TRY(hipMemcpyAsync(job.n_bins, d + o_nb, rows * 4, hipMemcpyDeviceToHost, st));
+                TRY(hipMemcpyAsync(job.bins, d + o_bins, rows * job.max_bins * sizeof(simon_fail_bin), hipMemcpyDeviceToHost, st));
+            }
+            if (job.fail_codes) TRY(hipMemcpyAsync(job.fail_codes, d + o_codes, rows * stride * 2, hipMemcpyDeviceToHost, st));
+        }
+        TRY(hipStreamSynchronize(st));
+        for (int s = 0; job.recorded_only && s < S; ++s) {
+            const size_t k = std::min(job.n_failed[s], job.max_failed), r0 = (size_t)s * job.max_failed;
+            if (k == 0) continue;
+            TRY(hipMemcpy(job.failed_pods + r0, d + o_failed + r0 * 4, k * 4, hipMemcpyDeviceToHost));
+            if (job.fail_codes) TRY(hipMemcpy(job.fail_codes + r0 * stride, d + o_codes + r0 * stride * 2, k * stride * 2, hipMemcpyDeviceToHost));
+            if (want_detail) {
+                job.detail->resize(k * job.scen[s].n_nodes * 4);
+                TRY(hipMemcpy(job.detail->data(), d + o_detail, job.detail->size() * 8, hipMemcpyDeviceToHost));
+            }
+        }
+        return 0;
+    };
+    const int rc = body();
+    if (rc) (void)hipStreamSynchronize(st);      // (copies out of the arena may still be queued)
     (void)hipFree(d);
-    return 0;
+    return rc;
 }
+#undef TRY
 
 #endif  // SIMON_WIDE_LOCAL_TU / SIMON_WIDE_EXPLAIN_TU
 }  // namespace simon

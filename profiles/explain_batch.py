@@ -9,8 +9,9 @@ and a sweep of config-2-sized scenarios (1 000 pods, 16 .. 63 nodes).  Per workl
   (b) explain_loaded for the same scenarios one after the other (full code rows, binned on the host by np.unique),
 by wall clock around the calls -- the replays record no events of their own, and the copies back are part of what a host waits for;
 the kernels' own time is read from a `rocprofv3 --kernel-trace --stats` run of this script.
-Both must name the same failed pods and the same histograms.  --single N: only N single replays (explain_loaded: no histogram) of the
-first failing scenario, the run such a trace wraps to read the EXPLAIN kernel's time; --single-batch N: the same scenario N times through
+Both must name the same failed pods and the same histograms.  --single N: only single replays (explain_loaded: no histogram) of the
+first failing scenario, four passes of N (a warm-up and three samples; call_ms = the best pass's wall clock per call, the figure that
+shows a change of the host path), the run such a trace wraps to read the EXPLAIN kernel's time; --single-batch N: the same scenario N times through
 explain_batch([s]), one workgroup with the histogram -- the difference between the two is the histogram's cost."""
 import json
 import os
@@ -72,10 +73,15 @@ def single(n, batch):
         ctx.load_problem(prob)
         res = ctx.run_batch(scen, orders, want_placement=False)
         s = int(np.argmax(res.unscheduled > 0))
-        for _ in range(n):
-            nf = int(ctx.explain_batch([s], MAX_FAILED, 32).n_failed[0]) if batch else ctx.explain_loaded(s, MAX_FAILED)[0]
+        per_call = []
+        for _ in range(4):                                              # a warm-up pass and three samples of n replays each
+            t0 = time.perf_counter()
+            for _ in range(n):
+                nf = int(ctx.explain_batch([s], MAX_FAILED, 32).n_failed[0]) if batch else ctx.explain_loaded(s, MAX_FAILED)[0]
+            per_call.append((time.perf_counter() - t0) / n)
     print(json.dumps({"workload": name, "scenario": s, "n_nodes": int(scen[s, 0]), "unscheduled": int(nf), "replays": n,
-                      "call": "explain_batch" if batch else "explain_loaded"}))
+                      "call": "explain_batch" if batch else "explain_loaded", "call_ms": round(min(per_call[1:]) * 1e3, 3),
+                      "call_ms_all": [round(t * 1e3, 3) for t in per_call[1:]]}))
 
 
 if __name__ == "__main__":

@@ -373,3 +373,46 @@ def test_sweep_reasons_from_the_histograms_alone(monkeypatch):
     engine.buffer_bytes = 1
     assert sim.sweep(cluster, apps, types[0], counts, engine=engine, reasons=True).unscheduled_pods == want.unscheduled_pods
     assert calls == [(1, False)] * failing
+
+
+def test_single_replays_write_the_recorded_rows_and_nothing_else():
+    """simon_explain / simon_explain_loaded through the library itself (capi.Context slices buffers of its own): failed_pods and
+    fail_codes are written for the first min(return value, max_failed) pods, rows of the scenario's n_nodes; what lies behind them
+    stays as the caller had it.  5 identical nodes of 1 000 mCPU, 6 identical pods of 600 mCPU: one pod per node, so 3 / 2 / 1 pods
+    fail on 3 / 4 / 5 nodes."""
+    GiB = 1 << 30
+    prob = capi.Problem(alloc_cpu=np.full(5, 1000, np.int64), alloc_mem=np.full(5, 64 * GiB, np.int64), alloc_pods=np.full(5, 110, np.int32),
+                        node_class=np.zeros(5, np.int32), req_cpu=np.full(6, 600, np.int64), req_mem=np.full(6, GiB, np.int64),
+                        pod_class=np.zeros(6, np.int32), n_pod_classes=1, n_node_classes=1, simon_raw=np.zeros((1, 1), np.int64),
+                        const_score=np.full(1, 1000300, np.int64)).normalise()
+    scen = np.array([[3, 0], [5, 0]], np.int32)
+    orders = np.arange(6, dtype=np.int32)[None, :]
+    refs = {n: oracle_explain(prob, np.array([[n, 0]], np.int32), orders, 0, 8) for n in (3, 4, 5)}
+    assert [refs[n][0] for n in (3, 4, 5)] == [3, 2, 1]
+    PODS, CODES, GUARD = -7, 0xABCD, 2
+
+    def replay(ctx, n, max_failed, scenario=None):
+        """One call on sentinel-filled buffers two rows longer than max_failed; checks them against the oracle's run of n nodes."""
+        failed = np.full(max_failed + GUARD, PODS, np.int32)
+        codes = np.full((max_failed + GUARD) * n, CODES, np.uint16)
+        if scenario is None:
+            rc = ctx.lib.simon_explain(ctx.h, capi.Scenario(n, 0), capi._ptr(orders[0], capi.C.c_int32), capi._ptr(failed, capi.C.c_int32),
+                                       capi._ptr(codes, capi.C.c_uint16), max_failed)
+        else:
+            rc = ctx.lib.simon_explain_loaded(ctx.h, scenario, capi._ptr(failed, capi.C.c_int32), capi._ptr(codes, capi.C.c_uint16), max_failed)
+        nf, want_failed, want_codes = refs[n]
+        k = min(nf, max_failed)
+        assert rc == nf
+        assert failed[:k].tolist() == want_failed[:k].tolist() and (failed[k:] == PODS).all()
+        assert codes[:k * n].reshape(k, n).tolist() == want_codes[:k].tolist() and (codes[k * n:] == CODES).all()
+        return rc, failed.tobytes(), codes.tobytes()
+
+    with capi.Context(0) as ctx:
+        ctx.load_problem(prob)
+        ctx.load_scenarios(scen, orders)
+        first = replay(ctx, 3, 2, scenario=0)             # more failed pods than rows: rows 0 - 1, the guard rows untouched
+        replay(ctx, 3, 8, scenario=0)                     # fewer: rows 0 - 2, rows 3 - 9 untouched
+        replay(ctx, 4, 8)                                 # ad hoc, a size the batch does not hold: stride 4
+        eb = ctx.explain_batch([1, 0], 8, 4)
+        assert eb.n_failed.tolist() == [1, 3]
+        assert replay(ctx, 3, 2, scenario=0) == first
