@@ -1530,6 +1530,36 @@ __global__ void plan_kernel(const ScenarioDesc* __restrict__ scen, int S, const 
     if ((threadIdx.x & 63) == 0 && best != ~0ull) atomicMin(out, best);
 }
 
+// simon_batch_out as the caller filled it, widened to the current layout: a v3 struct (no gpu_slices member) reads as gpu_slices = NULL
+bool batch_out_view(const simon_batch_out* out, simon_batch_out* v) {
+    if (out->struct_size == sizeof(simon_batch_out)) { *v = *out; return true; }
+    if (out->struct_size != SIMON_BATCH_OUT_SIZE_V3) return false;
+    std::memset(v, 0, sizeof *v);
+    std::memcpy(v, out, SIMON_BATCH_OUT_SIZE_V3);
+    v->struct_size = sizeof *v;
+    return true;
+}
+
+// the kernel launches of a run between the context's event pair (simon_stats.kernel_ms); launch() returns a SIMON_* code
+template <class F>
+int timed_launch(simon_ctx* c, F&& launch) {
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    if (int rc = launch()) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    return SIMON_OK;
+}
+
+// the pool, state, stream and result pointers FastLaunch and NarrowArgs share (generations 2 and 1; a.pods is each kernel's own row format)
+template <class Args>
+void fill_register_args(const simon_ctx* c, bool want_placement, Args& a) {
+    a.a_cpu = c->d_a_cpu.p; a.a_mem = c->d_a_mem.p; a.a_pods = c->d_a_pods.p; a.ncls = c->d_ncls.p;
+    a.i_rq_cpu = c->d_i_rq_cpu.p; a.i_rq_mem = c->d_i_rq_mem.p; a.i_nz_cpu = c->d_i_nz_cpu.p; a.i_nz_mem = c->d_i_nz_mem.p;
+    a.i_npods = c->d_i_npods.p; a.orders = c->d_orders.p; a.scen = c->d_scen.p; a.perm = c->d_perm.p;
+    a.static_mask = c->has_mask ? c->d_mask.p : nullptr; a.simon_raw = c->d_raw32.p;
+    a.unscheduled = c->d_unsched.p; a.used_cpu = c->d_used_cpu.p; a.used_mem = c->d_used_mem.p;
+    a.placement = want_placement ? c->d_place.p : nullptr;
+}
+
 }  // namespace
 
 // ============================================================================================
@@ -1890,6 +1920,12 @@ int simon_load_class_tables(simon_ctx* c, const simon_class_tables* tb) {
     return SIMON_OK;
 }
 
+// table_lds_bytes' nzk of the staged problem with `team` waves per scenario: -1 without SPREAD, else the zone-key count | kLds* bits
+static int spread_lds_word(const simon_ctx* c, int team) {
+    if (!c->spread) return -1;
+    return (int)c->sp_zkeys.size() | ((c->ipa_fold || c->hard_fold) ? kLdsSecondTable : 0) | (team > 1 ? kLdsTeam : 0) | (c->Cn_t > kTableMaxClasses ? kLdsCn2 : 0);
+}
+
 // padded sizes, summary layout and workspace slices of the loaded batch for the score-table kernel (simon_load_scenarios; again
 // after simon_set_scenario_segments, whose scenarios have their own class counts)
 static int table_layout(simon_ctx* c) {
@@ -1917,8 +1953,7 @@ static int table_layout(simon_ctx* c) {
             // 256 scenarios 7.7 ms, 4 096 14.0 ms, 8 192 27.5 ms one-level / 32.3 ms two-level; 100 signatures 39.5 / 32.1 ms):
             // a round of w waves per CU takes 1 + 0.055 (w - 1) units up to 16 waves and 0.11 per wave beyond.
             auto fit = [](size_t lds) { const size_t g = (lds + 1279) / 1280 * 1280; return g ? (int)std::min<size_t>(32, kTableLdsPerCU / g) : 32; };
-            const int nzk = c->spread ? ((int)c->sp_zkeys.size() | ((c->ipa_fold || c->hard_fold) ? 0x100 : 0) | (Ct > kTableMaxClasses ? 0x400 : 0)) : -1;   // (| 0x100: the second score table of spread_select; | 0x400: CN2's larger one)
-            const size_t lds16 = table_lds_bytes(c->n_sigs, top16, Ct, false, false) + c->lds_pad, lds64 = table_lds_bytes(c->n_sigs, top64, Ct, true, c->rest, nzk) + c->lds_pad;
+            const size_t lds16 = table_lds_bytes(c->n_sigs, top16, Ct, false, false) + c->lds_pad, lds64 = table_lds_bytes(c->n_sigs, top64, Ct, true, c->rest, spread_lds_word(c, 1)) + c->lds_pad;   // (the single-wave shape: teams are a matter of the launch)
             const bool fine_ok = max_n <= kTableMaxNodes && top16 <= kTableMaxPadded && lds16 <= 64 * 1024, coarse_ok = top64 <= kTableMaxPaddedCoarse && lds64 <= kTableLdsMaxWG && Ct <= 128;   // (129 .. 256 classes: one-level only, simon_table_cls4.hip)
             const int per_cu = (S + c->n_cus - 1) / std::max(c->n_cus, 1);
             auto cost = [&](int fits, double factor) {
@@ -2206,18 +2241,221 @@ static int wide_workgroup(const simon_ctx* c, int S, int max_n) {
     return T == 128 ? 256 : T;                                  // (SIMON_WG=128: the all-feature kernel is built for 64 / 256 / 512 / 1 024 threads since round 5)
 }
 
-// simon_run_loaded on the all-feature kernel: the loaded batch between the context's event pair; *T_used = the workgroup size.
-static int run_wide_batch(simon_ctx* c, bool want_placement, bool want_slices, int* T_used) {
+// Where a loaded batch runs and in which shape: route_batch decides, simon_run_loaded's launchers carry it out ("Which kernel runs what")
+struct BatchRoute {
+    int kernel;            // SIMON_KERNEL_*: the kernel that runs the batch
+    int generation;        // simon_stats.kernel_generation (0: the all-feature kernel)
+    int T, slots;          // threads per workgroup; node slots per lane (score table: 64-lane rounds over the summary entries)
+    int team;              // score table: waves per scenario, 1 or kTeamWaves
+    bool lds_ws, lds_x;    // score table: the workspace (generation 4) / the mask rows (generation 6) live in LDS
+    size_t lds;            // dynamic LDS of the launch
+};
+
+// dynamic LDS of a score-table launch with an LDS-resident home: the kernel puts it at the next 128-byte boundary behind tcarve's total
+static size_t lds_with_home(const simon_ctx* c, size_t table_lds, size_t home) { return ((table_lds - c->lds_pad + 127) & ~(size_t)127) + home + c->lds_pad; }
+
+// The route of the loaded batch, from the staged problem and the batch alone: no HIP call, nothing written to the context
+// (SIMON_DEBUG_ROUTE: the `[route] variant` line on stderr).
+static BatchRoute route_batch(const simon_ctx* c) {
+    const int S = c->S;
+    auto wide = [&](int slots) { return BatchRoute{SIMON_KERNEL_WIDE, 0, wide_workgroup(c, S, c->max_n), slots, 1, false, false, 0}; };
+    // per-scenario node ranks: the score-table kernel (own per-class lists) or the all-feature kernel
+    if (c->variant != SIMON_KERNEL_NARROW || (c->has_ranks && !c->table_ranks_ok)) return wide(0);
+    // workgroup shape: T = 256 (4 waves) with up to 8 node slots per lane covers 2048 nodes;
+    // larger pools widen the workgroup.  SIMON_WG overrides (tuning knob).
+    const int T = c->force_T ? c->force_T : (c->max_n <= 2048 ? 256 : c->max_n <= 4096 ? 512 : 1024);
+    int slots = (std::max(c->max_n, 1) + T - 1) / T;
+    const bool too_big = slots > 8;   // pool too large for register residency even at T = 1024: the all-feature kernel takes it
+    if (slots == 5) slots = 6;
+    if (slots == 7) slots = 8;
+    // the score-table kernel: one workgroup (one wave) per scenario, ONE launch, scenarios in LPT order
+    const int ni_top = c->table_ni_top;
+    // team mode: a small batch of a problem with soft spread constraints gets kTeamWaves waves per scenario (the walks of
+    // spread_select and the prologue are split; LDS: + one score table, the canonical indices and the exchange slots)
+    const int team_max = c->team_max_s >= 0 ? c->team_max_s : 2 * c->n_cus;
+    int team = (c->spread && c->table_coarse && (!c->rest || c->rs) && c->team_mode != 0 && (c->team_mode > 0 || S <= team_max)) ? kTeamWaves : 1;
+    auto lds_for = [&](int tm) -> size_t { return c->table_ok ? table_lds_bytes(c->n_sigs, ni_top, c->Cn_t, c->table_coarse, c->rest, spread_lds_word(c, tm)) + c->lds_pad : 0; };
+    if (team > 1 && lds_for(team) > kTableLdsMaxWG) team = 1;           // (its extra table does not fit: the single-wave shape still may)
+    size_t table_lds = lds_for(team);
+    // The LDS-resident homes (LDSWS, LDSX) trade occupancy for latency: a workgroup asks for up to 159 KB, so a CU holds ONE.  They are
+    // the default only where that costs nothing whatever the dispatcher does: a batch of at most one scenario per CU (what a real
+    // Applier.Run offers).  Round 5 also took batches of a few workgroups per CU when ceil(S / CUs) of them fit the CU's LDS together --
+    // which assumed the dispatcher places exactly that many per CU, and left simon_load_scenarios' fine / coarse cost model (lds16 /
+    // lds64, fitted before this LDS growth) describing another launch; those batches keep the HBM homes now (SIMON_LDS_WS=1: whenever
+    // one scenario fits).
+    auto lds_home = [&](size_t need) { return need <= kTableLdsMaxWG && c->ldsws_mode != 0 && (c->ldsws_mode > 0 || S <= std::max(c->n_cus, 1)); };
+    // Generation 4 with the scenario's workspace in LDS (round 5; simon_table.hip: LDSWS), for a problem whose byte table + node state
+    // fit the CU's LDS next to the summaries: the one memory round trip of a scheduling cycle becomes an LDS access
+    bool lds_ws = false;
+    if (c->table_ok && !c->table_coarse && !c->rest && !c->spread && !c->fold && !c->gfold && c->n_sigs <= 128 && c->Cn_t <= 128 && team == 1) {
+        size_t ws_max = 0;
+        for (int s = 0; s < S; ++s) ws_max = std::max(ws_max, table_ws_bytes(c->n_sigs, c->scen_ni[s], c->nzeq, false, c->Cn_t, 0, 0, 0, 0));
+        const size_t need = lds_with_home(c, table_lds, ws_max);
+        if (lds_home(need)) { lds_ws = true; table_lds = need; }
+    }
+    // Generation 6 with its mask rows, row totals and canonical indices in LDS (round 5; simon_table.hip: LDSX), under the same rule
+    bool lds_x = false;
+    if (c->table_ok && c->table_coarse && c->rest && !c->spread && team == 1 && c->Cn_t <= kTableMaxClasses && c->n_sigs <= 128) {   // (65 .. 128 node classes: the rows stay in HBM, simon_table_rest2.hip)
+        const size_t need = lds_with_home(c, table_lds, table_ldsx_bytes(ni_top, c->rest_M));
+        if (lds_home(need)) { lds_x = true; table_lds = need; }
+    }
+    bool use_table = c->table_ok && c->table_perm_ok && (c->Cn_t <= 128 || (!c->table_coarse && !c->fold && !c->gfold && c->n_sigs <= 128)) && !c->no_cache && !c->force_v1 && c->max_n <= (c->table_coarse ? kTableMaxNodesCoarse : kTableMaxNodes) &&
+                     ni_top <= (c->table_coarse ? kTableMaxPaddedCoarse : kTableMaxPadded) && table_lds <= ((c->table_coarse || lds_ws) ? kTableLdsMaxWG : (size_t)64 * 1024);
+    if (c->debug_route)
+        fprintf(stderr, "[route] variant %d rest %d spread %d fold %d gfold %d table_ok %d perm_ok %d coarse %d n_sigs %d Cn_t %d ni_top %d lds %zu max_n %d M %d NZ %d TH %d TZ %d segments %d\n", c->variant, (int)c->rest,
+                (int)c->spread, (int)c->fold, (int)c->gfold, (int)c->table_ok, (int)c->table_perm_ok, (int)c->table_coarse, c->n_sigs, c->Cn_t, ni_top, table_lds, c->max_n,
+                c->rest_M, (int)c->zone_keys.size(), c->sp_TH, c->sp_TZ, c->seg_n);
+    // pinned pods (pin_node) are known to the score-table kernel and the all-feature kernel only
+    const bool needs_table_or_wide = c->has_pin || too_big || c->rest || c->spread || c->fold || c->gfold || !c->raw_fits_lds || c->has_ranks || c->has_static;
+    const bool fast = c->fast_ok && !c->force_v1 && T >= 128;      // generation 2 is built for 128 threads and more
+    // Beyond 256 signatures generation 2 (register-resident state, every node re-evaluated per cycle: its time does not depend on
+    // the signature count) overtakes the score table (measured, profiles/r03: 300 signatures 124 ms against 119 ms, 384: 169 ms) --
+    // where it is eligible; otherwise the table (K <= 384) still beats the all-feature kernel by far.
+    if (use_table && c->n_sigs > 256 && !needs_table_or_wide && fast && !c->force_table) use_table = false;
+    if (use_table)
+        return BatchRoute{SIMON_KERNEL_NARROW_CACHE, c->spread ? 7 : c->rest ? 6 : c->table_coarse ? 5 : 4, 64 * team, (ni_top / (c->table_coarse ? 64 : 16) + 63) / 64, team, lds_ws, lds_x, table_lds};
+    if (needs_table_or_wide) return wide(slots);                   // (simon_stats keeps the slot count weighed here)
+    // the register-resident kernels: simon_raw in LDS, generation 2 with its second copy
+    const size_t raw = (size_t)c->Cp * c->Cn * sizeof(int32_t);
+    if (fast) return BatchRoute{SIMON_KERNEL_NARROW_FAST, 2, T, slots, 1, false, false, (raw * 2 + 15) & ~(size_t)15};
+    return BatchRoute{SIMON_KERNEL_NARROW, 1, T, slots, 1, false, false, (raw + 15) & ~(size_t)15};
+}
+
+// SIMON_DEBUG_ROUTE: what became of a segmented batch
+static void trace_segmented(const simon_ctx* c, const char* outcome) {
+    if (c->debug_route && c->seg_n) fprintf(stderr, "[route] segmented batch (%d segments, %d fixed nodes): %s\n", c->seg_n, c->seg_start[0], outcome);
+}
+
+// The launchers of simon_run_loaded, one per kernel: the loaded batch on route `r`, its launches between the context's event pair.
+static int run_wide_batch(simon_ctx* c, const BatchRoute& r, bool want_placement, bool want_slices) {
     if (int rc = ensure_wide_staged(c)) return rc;   // (a NARROW problem whose batch cannot use the cache kernel but has pinned pods)
-    const int T = *T_used = wide_workgroup(c, c->S, c->max_n);
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    const int rc = wide_run(c->wide, *c, reinterpret_cast<const WideScenario*>(c->d_scen.p), c->S, c->d_orders.p, c->max_n, T, c->d_unsched.p,
-                            c->d_used_cpu.p, c->d_used_mem.p, c->d_used_vg.p, want_placement ? c->d_place.p : nullptr,
-                            c->has_ranks ? c->d_node_rank.p : nullptr, c->has_ranks ? c->d_node_inv.p : nullptr,
-                            want_slices ? c->d_gpu_slices.p : nullptr, c->stream, c->err);
-    if (rc) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    return timed_launch(c, [&] {
+        return wide_run(c->wide, *c, reinterpret_cast<const WideScenario*>(c->d_scen.p), c->S, c->d_orders.p, c->max_n, r.T, c->d_unsched.p,
+                        c->d_used_cpu.p, c->d_used_mem.p, c->d_used_vg.p, want_placement ? c->d_place.p : nullptr,
+                        c->has_ranks ? c->d_node_rank.p : nullptr, c->has_ranks ? c->d_node_inv.p : nullptr,
+                        want_slices ? c->d_gpu_slices.p : nullptr, c->stream, c->err);
+    });
+}
+
+// the score-table kernel's device-resident pointer block for the loaded batch (TableCold::prof: run_table_batch)
+static TableCold table_cold(const simon_ctx* c, bool want_slices) {
+    TableCold cold{};
+    cold.ncls = c->d_t_ncls.p; cold.rank = c->d_rank.p; cold.cls_off = c->d_cls_off.p;
+    cold.clsprefix = c->d_clsprefix.p; cold.a_pods = c->d_a_pods.p;
+    cold.i_rq_cpu = c->d_i_rq_cpu.p; cold.i_rq_mem = c->d_i_rq_mem.p; cold.i_nz_cpu = c->d_i_nz_cpu.p; cold.i_nz_mem = c->d_i_nz_mem.p;
+    cold.foldx = c->fold ? c->d_foldx.p : nullptr; cold.i_npods = c->d_i_npods.p; cold.sigs = c->d_sigs.p; cold.shapes = c->d_shapes.p; cold.scen = c->d_scen.p;
+    cold.static_mask = c->has_mask ? c->d_t_mask.p : nullptr; cold.simon_raw = c->d_t_raw.p;
+    cold.unscheduled = c->d_unsched.p; cold.used_cpu = c->d_used_cpu.p; cold.used_mem = c->d_used_mem.p;
+    cold.N = c->N;
+    cold.gpu_slices = want_slices ? reinterpret_cast<unsigned long long*>(c->d_gpu_slices.p) : nullptr;
+    cold.na_raw = c->has_na ? c->d_t_na.p : nullptr; cold.tt_raw = c->has_tt ? c->d_t_tt.p : nullptr; cold.add_raw = c->has_add ? c->d_t_add.p : nullptr;
+    if (c->has_ranks) { cold.rk_pos = c->d_rk_pos.p; cold.rk_rank = c->d_node_rank.p; }
+    if (c->seg_n) cold.scls = c->d_scls.p;
+    if (c->img_R > 0) { cold.img = c->d_t_img.p; cold.img_slot = c->d_img_slot.p; cold.img_stride = c->img_stride_t; }
+    if (c->rest) { cold.xrows = c->d_xrows.p; cold.zdom = c->d_zdom.p; cold.xsig = c->d_xsig.p; cold.xalloc = c->d_xalloc.p; cold.i_xused = c->d_i_xused.p; cold.gsig = c->d_gsig.p; }
+    if (c->rest || c->gfold) { cold.gpu_cnt = c->d_gpu_cnt.p; cold.gpu_devtot = c->d_gpu_devtot.p; cold.i_gused = c->d_i_gused.p; }
+    if (c->spread) {
+        cold.sp_ent = (const int2*)c->d_sp_ent.p; cold.spread_log = c->d_spread_log.p;
+        cold.node_sets = c->d_node_sets.p; cold.set_words = (c->N + 63) / 64; cold.cls_zdom = c->d_cls_zdom.p;
+        if (c->rest) cold.sp_word = c->d_sp_word.p;
+    }
+    return cold;
+}
+
+// TableScalars::static_tables of the loaded batch
+static int32_t table_static_bits(const simon_ctx* c, bool want_slices) {
+    return (c->has_na ? kStNa : 0) | (c->has_tt ? kStTt : 0) | (c->has_add ? kStAdd : 0) | (want_slices ? kStGpuSlices : 0) | (c->sig_twins ? kStTwins : 0) |
+           (c->fold ? kStFold : 0) | ((c->spread && (c->ipa_fold || c->hard_fold)) ? kStSpreadAff : 0) | (c->gfold ? kStGpuFold : 0) | (c->img_R > 0 ? kStImg : 0) |
+           (c->seg_n ? kStSegments : 0);
+}
+
+static TableScalars table_scalars(const simon_ctx* c, bool want_slices) {
+    TableScalars sc{};
+    sc.mask_words = (c->N + 63) / 64;
+    sc.Cn = c->Cn_t;
+    sc.Cp = c->Cp;
+    sc.P = c->P;
+    sc.S = c->S;
+    sc.K = c->n_sigs;
+    sc.rk_stride = c->has_ranks ? c->N : 0;
+    sc.static_tables = table_static_bits(c, want_slices);
+    sc.NZ = c->rest ? (int)c->zone_keys.size() : 0;
+    sc.M = c->rest ? c->rest_M : 0;
+    sc.G = c->rest ? c->rest_G : 0;
+    sc.X = c->rest ? c->rest_X : 0;
+    sc.TH = c->spread ? c->sp_TH : 0;
+    sc.TZ = c->spread ? c->sp_TZ : 0;
+    sc.NZK = c->spread ? (int)c->sp_zkeys.size() : 0;
+    sc.ni_max = c->table_ni_top;
+    sc.g_cpu = c->g_cpu;
+    sc.g_mem = c->g_mem;
+    return sc;
+}
+
+// SIMON_TABLE_PROF (profile builds only): mean ticks per scheduling cycle over the batch that just ran, by phase
+static int report_table_prof(simon_ctx* c) {
+    const int S = c->S, P = c->P;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::vector<unsigned long long> hp((size_t)S * 24);
+    HIP_TRY(c, hipMemcpy(hp.data(), c->d_table_prof.p, hp.size() * 8, hipMemcpyDeviceToHost));
+    double acc[24] = {0};
+    for (int s = 0; s < S; ++s) for (int q = 0; q < 24; ++q) acc[q] += (double)hp[(size_t)s * 24 + q];
+    for (double& a : acc) a = a / S / P;
+    fprintf(stderr, "[SIMON_TABLE_PROF] S=%d ticks/cycle: loop %.0f | row+summary read %.0f | key+wavemax %.0f | tie check %.0f | lds(shape,sn) %.0f | mem(state,row) %.0f | state update %.0f | eval+patch+store %.0f | REST assume %.0f | REST select %.0f | canonical tie-breaks per cycle %.3f\n",
+            S, acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], acc[8], acc[9], acc[6], acc[10], acc[7]);
+    if (c->rest)
+        fprintf(stderr, "[SIMON_TABLE_PROF] REST select, ticks/cycle (averaged over ALL pods): pod row %.0f | filter words + summaries %.0f | candidates %.0f | table rows of excluded bests %.0f (needed on %.3f of the cycles) | per-class best %.0f | class term %.0f | totals + tie %.0f | rest %.0f\n",
+                acc[11], acc[12], acc[13], acc[14], acc[20], acc[15], acc[16], acc[17], acc[10]);
+    if (c->spread)
+        fprintf(stderr, "[SIMON_TABLE_PROF] spread pods, ticks/cycle: entries arrived %.0f | descriptor + first loads %.0f | counters, sizes %.0f | zone counters, Log, raw table %.0f | pass 1 %.0f | extremes, totals table %.0f | pass 2 %.0f | winner %.0f | counter stores %.0f\n",
+                acc[21], acc[12], acc[13], acc[14], acc[15], acc[16], acc[17], acc[18], acc[19]);
     return SIMON_OK;
+}
+
+static int run_table_batch(simon_ctx* c, const BatchRoute& r, bool want_placement, bool want_slices) {
+    const int S = c->S, P = c->P;
+    HIP_TRY(c, c->d_ws.ensure(c->ws_total));
+    if (const char* fill = getenv("SIMON_WS_FILL"))          // debugging aid: the workspace starts from a byte pattern (a read of something the prologue never wrote shows)
+        HIP_TRY(c, hipMemsetAsync(c->d_ws.p, atoi(fill), c->ws_total, c->stream));
+    if (want_placement) HIP_TRY(c, c->d_place_step.ensure((size_t)S * P));
+    TableCold cold = table_cold(c, want_slices);
+    if (c->table_prof) { HIP_TRY(c, c->d_table_prof.ensure((size_t)S * 24)); HIP_TRY(c, hipMemsetAsync(c->d_table_prof.p, 0, (size_t)S * 192, c->stream)); cold.prof = c->d_table_prof.p; }
+    HIP_TRY(c, c->d_table_cold.ensure(sizeof cold));
+    HIP_TRY(c, hipMemcpyAsync(c->d_table_cold.p, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));             // `cold` is a stack object
+    TableLaunch f{};
+    f.cold = reinterpret_cast<const TableCold*>(c->d_table_cold.p);
+    f.cls_list = c->has_ranks ? c->d_rk_ids.p : c->d_cls_list.p; f.pods = c->d_podsC.p; f.orders = c->d_orders.p; f.perm = c->d_perm.p;
+    f.place_step = want_placement ? c->d_place_step.p : nullptr;
+    f.ws_off = c->d_ws_off.p; f.ws = c->d_ws.p;
+    f.team = r.team; f.lds_ws = r.lds_ws; f.lds_x = r.lds_x;
+    f.coarse = c->table_coarse; f.rest = c->rest; f.spread = c->spread; f.aff = c->rest && !c->aff_idx.empty(); f.nzeq = c->nzeq; f.has_pin = c->has_pin;
+    f.sc = table_scalars(c, want_slices);
+    if (c->debug_route) fprintf(stderr, "[route] unit %s nzeq %d team %d\n", table_unit_name(f), (int)f.nzeq, f.team);
+    trace_segmented(c, "score-table kernel, ranked instantiation");
+    if (int rc = timed_launch(c, [&] {
+            HIP_TRY(c, launch_table(f, S, r.lds, c->stream));
+            if (want_placement) HIP_TRY(c, launch_unpermute(c->d_place_step.p, c->d_inv_orders.p, c->d_scen.p, S, P, c->d_place.p, c->stream));
+            return (int)SIMON_OK;
+        })) return rc;
+    return c->table_prof ? report_table_prof(c) : SIMON_OK;
+}
+
+static int run_fast_batch(simon_ctx* c, const BatchRoute& r, bool want_placement) {
+    FastLaunch f{};
+    fill_register_args(c, want_placement, f);
+    f.pods = c->d_podsF.p;
+    f.sc = FastScalars{(c->N + 63) / 64, c->Cn, c->Cp, c->P, c->S, c->g_cpu, c->g_mem};
+    return timed_launch(c, [&] { HIP_TRY(c, launch_fast(f, r.T, r.slots, c->has_mask, c->nzeq, r.lds, c->stream)); return (int)SIMON_OK; });
+}
+
+static int run_narrow_batch(simon_ctx* c, const BatchRoute& r, bool want_placement) {
+    NarrowArgs a{};
+    fill_register_args(c, want_placement, a);
+    a.pods = c->d_podsN.p;
+    a.mask_words = (c->N + 63) / 64; a.Cn = c->Cn; a.Cp = c->Cp; a.P = c->P; a.S = c->S;
+    a.g_cpu = c->g_cpu; a.g_mem = c->g_mem;
+    return timed_launch(c, [&] { HIP_TRY(c, launch_narrow(a, r.T, r.slots, c->has_mask, c->rcp_div, r.lds, c->stream)); return (int)SIMON_OK; });
 }
 
 int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
@@ -2227,185 +2465,27 @@ int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
     const int S = c->S, P = c->P;
     // bit 1: also record the devices Reserve books for every placed GPU pod (only problems with GPU requests have any)
     const bool want_slices = (want_placement & SIMON_WANT_GPU_SLICES) != 0 && c->has_gpu;
-    want_placement &= SIMON_WANT_PLACEMENT;
     const bool want_risk = !c->p_priority.empty();               // pods of unequal priority: the flags come from the placement matrix
-    if (want_risk) want_placement = SIMON_WANT_PLACEMENT;
+    const bool want_place = (want_placement & SIMON_WANT_PLACEMENT) != 0 || want_risk;
     c->have_slices = false; c->have_risk = false;
     if (want_slices) {
         HIP_TRY(c, c->d_gpu_slices.ensure((size_t)S * P));
         HIP_TRY(c, hipMemsetAsync(c->d_gpu_slices.p, 0, (size_t)S * P * 8, c->stream));
     }
-    if (want_placement) HIP_TRY(c, c->d_place.ensure((size_t)S * P));
-    int T = 0, slots = 0, variant_used = c->variant;
-    bool table_used = false;
-    size_t lds = 0;
-    // per-scenario node ranks: the score-table kernel (own per-class lists) or the all-feature kernel
-    bool run_wide = c->variant != SIMON_KERNEL_NARROW || (c->has_ranks && !c->table_ranks_ok);
-    if (!run_wide) {
-        // workgroup shape: T = 256 (4 waves) with up to 8 node slots per lane covers 2048 nodes;
-        // larger pools widen the workgroup.  SIMON_WG overrides (tuning knob).
-        T = c->force_T ? c->force_T : (c->max_n <= 2048 ? 256 : c->max_n <= 4096 ? 512 : 1024);
-        slots = (std::max(c->max_n, 1) + T - 1) / T;
-        const bool too_big = slots > 8;   // pool too large for register residency even at T = 1024: the all-feature kernel takes it
-        if (slots == 5) slots = 6;
-        if (slots == 7) slots = 8;
-        // the score-table kernel: one workgroup (one wave) per scenario, ONE launch, scenarios in LPT order
-        const int ni_top = c->table_ni_top;
-        // team mode: a small batch of a problem with soft spread constraints gets kTeamWaves waves per scenario (the walks of
-        // spread_select and the prologue are split; LDS: + one score table, the canonical indices and the exchange slots)
-        const int team_max = c->team_max_s >= 0 ? c->team_max_s : 2 * c->n_cus;
-        int team = (c->spread && c->table_coarse && (!c->rest || c->rs) && c->team_mode != 0 && (c->team_mode > 0 || S <= team_max)) ? kTeamWaves : 1;
-        auto lds_for = [&](int tm) -> size_t {
-            return c->table_ok ? table_lds_bytes(c->n_sigs, ni_top, c->Cn_t, c->table_coarse, c->rest, c->spread ? ((int)c->sp_zkeys.size() | ((c->ipa_fold || c->hard_fold) ? 0x100 : 0) | (tm > 1 ? 0x200 : 0) | (c->Cn_t > kTableMaxClasses ? 0x400 : 0)) : -1) + c->lds_pad : 0;
-        };
-        if (team > 1 && lds_for(team) > kTableLdsMaxWG) team = 1;           // (its extra table does not fit: the single-wave shape still may)
-        size_t table_lds = lds_for(team);
-        // Generation 4 with the scenario's workspace in LDS (round 5; simon_table.hip: LDSWS): a batch of at most one scenario per CU -- what
-        // a real Applier.Run offers -- of a problem whose byte table + node state fit the CU's LDS next to the summaries.  The one memory
-        // round trip of a scheduling cycle becomes an LDS access.
-        // The LDS-resident homes (LDSWS, LDSX) trade occupancy for latency: a workgroup asks for up to 159 KB, so a CU holds ONE.  They are
-        // the default only where that costs nothing whatever the dispatcher does: a batch of at most one scenario per CU (what a real
-        // Applier.Run offers).  Round 5 also took batches of a few workgroups per CU when ceil(S / CUs) of them fit the CU's LDS together --
-        // which assumed the dispatcher places exactly that many per CU, and left simon_load_scenarios' fine / coarse cost model (lds16 /
-        // lds64, fitted before this LDS growth) describing another launch; those batches keep the HBM homes now (SIMON_LDS_WS=1: whenever
-        // one scenario fits).
-        auto lds_home = [&](size_t need) -> bool {
-            if (need > kTableLdsMaxWG || c->ldsws_mode == 0) return false;
-            return c->ldsws_mode > 0 || S <= std::max(c->n_cus, 1);
-        };
-        bool lds_ws = false;
-        if (c->table_ok && !c->table_coarse && !c->rest && !c->spread && !c->fold && !c->gfold && c->n_sigs <= 128 && c->Cn_t <= 128 && team == 1) {
-            size_t ws_max = 0;
-            for (int s2 = 0; s2 < S; ++s2) ws_max = std::max(ws_max, table_ws_bytes(c->n_sigs, c->scen_ni[s2], c->nzeq, false, c->Cn_t, 0, 0, 0, 0));
-            const size_t need = ((table_lds - c->lds_pad + 127) & ~(size_t)127) + ws_max + c->lds_pad;   // (the kernel puts the workspace at the next 128-byte boundary behind tcarve's total)
-            if (lds_home(need)) { lds_ws = true; table_lds = need; }
-        }
-        // Generation 6 with its mask rows, row totals and canonical indices in LDS (round 5; simon_table.hip: LDSX), under the same rule
-        bool lds_x = false;
-        if (c->table_ok && c->table_coarse && c->rest && !c->spread && team == 1 && c->Cn_t <= kTableMaxClasses && c->n_sigs <= 128) {   // (65 .. 128 node classes: the rows stay in HBM, simon_table_rest2.hip)
-            const size_t need = ((table_lds - c->lds_pad + 127) & ~(size_t)127) + table_ldsx_bytes(ni_top, c->rest_M) + c->lds_pad;
-            if (lds_home(need)) { lds_x = true; table_lds = need; }
-        }
-        bool use_table = c->table_ok && c->table_perm_ok && (c->Cn_t <= 128 || (!c->table_coarse && !c->fold && !c->gfold && c->n_sigs <= 128)) && !c->no_cache && !c->force_v1 && c->max_n <= (c->table_coarse ? kTableMaxNodesCoarse : kTableMaxNodes) &&
-                               ni_top <= (c->table_coarse ? kTableMaxPaddedCoarse : kTableMaxPadded) && table_lds <= ((c->table_coarse || lds_ws) ? kTableLdsMaxWG : (size_t)64 * 1024);
-        // pinned pods (pin_node) are known to the score-table kernel and the all-feature kernel only
-        if (c->debug_route)
-            fprintf(stderr, "[route] variant %d rest %d spread %d fold %d gfold %d table_ok %d perm_ok %d coarse %d n_sigs %d Cn_t %d ni_top %d lds %zu max_n %d M %d NZ %d TH %d TZ %d segments %d\n", c->variant, (int)c->rest,
-                    (int)c->spread, (int)c->fold, (int)c->gfold, (int)c->table_ok, (int)c->table_perm_ok, (int)c->table_coarse, c->n_sigs, c->Cn_t, ni_top, table_lds, c->max_n,
-                    c->rest_M, (int)c->zone_keys.size(), c->sp_TH, c->sp_TZ, c->seg_n);
-        const bool needs_table_or_wide = c->has_pin || too_big || c->rest || c->spread || c->fold || c->gfold || !c->raw_fits_lds || c->has_ranks || c->has_static;
-        // Beyond 256 signatures generation 2 (register-resident state, every node re-evaluated per cycle: its time does not depend on
-        // the signature count) overtakes the score table (measured, profiles/r03: 300 signatures 124 ms against 119 ms, 384: 169 ms) --
-        // where it is eligible; otherwise the table (K <= 384) still beats the all-feature kernel by far.
-        if (use_table && c->n_sigs > 256 && !needs_table_or_wide && c->fast_ok && !c->force_v1 && T >= 128 && !c->force_table) use_table = false;
-        if (needs_table_or_wide && !use_table) run_wide = true;
-        if (run_wide) {
-            // falls through to the all-feature kernel below
-        } else if (use_table) {
-            HIP_TRY(c, c->d_ws.ensure(c->ws_total));
-            if (const char* fill = getenv("SIMON_WS_FILL"))          // debugging aid: the workspace starts from a byte pattern (a read of something the prologue never wrote shows)
-                HIP_TRY(c, hipMemsetAsync(c->d_ws.p, atoi(fill), c->ws_total, c->stream));
-            if (want_placement) HIP_TRY(c, c->d_place_step.ensure((size_t)S * P));
-            TableCold cold{};
-            cold.ncls = c->d_t_ncls.p; cold.rank = c->d_rank.p; cold.cls_off = c->d_cls_off.p;
-            cold.clsprefix = c->d_clsprefix.p; cold.a_pods = c->d_a_pods.p;
-            cold.i_rq_cpu = c->d_i_rq_cpu.p; cold.i_rq_mem = c->d_i_rq_mem.p; cold.i_nz_cpu = c->d_i_nz_cpu.p; cold.i_nz_mem = c->d_i_nz_mem.p;
-            cold.foldx = c->fold ? c->d_foldx.p : nullptr; cold.i_npods = c->d_i_npods.p; cold.sigs = c->d_sigs.p; cold.shapes = c->d_shapes.p; cold.scen = c->d_scen.p;
-            cold.static_mask = c->has_mask ? c->d_t_mask.p : nullptr; cold.simon_raw = c->d_t_raw.p;
-            cold.unscheduled = c->d_unsched.p; cold.used_cpu = c->d_used_cpu.p; cold.used_mem = c->d_used_mem.p;
-            cold.N = c->N;
-            cold.gpu_slices = want_slices ? reinterpret_cast<unsigned long long*>(c->d_gpu_slices.p) : nullptr;
-            cold.na_raw = c->has_na ? c->d_t_na.p : nullptr; cold.tt_raw = c->has_tt ? c->d_t_tt.p : nullptr; cold.add_raw = c->has_add ? c->d_t_add.p : nullptr;
-            if (c->has_ranks) { cold.rk_pos = c->d_rk_pos.p; cold.rk_rank = c->d_node_rank.p; }
-            if (c->seg_n) cold.scls = c->d_scls.p;
-            if (c->img_R > 0) { cold.img = c->d_t_img.p; cold.img_slot = c->d_img_slot.p; cold.img_stride = c->img_stride_t; }
-            if (c->rest) {
-                cold.xrows = c->d_xrows.p; cold.zdom = c->d_zdom.p; cold.xsig = c->d_xsig.p; cold.xalloc = c->d_xalloc.p; cold.i_xused = c->d_i_xused.p;
-                cold.gsig = c->d_gsig.p; cold.gpu_cnt = c->d_gpu_cnt.p; cold.gpu_devtot = c->d_gpu_devtot.p; cold.i_gused = c->d_i_gused.p;
-            }
-            if (c->gfold && !c->rest) { cold.gpu_cnt = c->d_gpu_cnt.p; cold.gpu_devtot = c->d_gpu_devtot.p; cold.i_gused = c->d_i_gused.p; }
-            if (c->spread) {
-                cold.sp_ent = (const int2*)c->d_sp_ent.p; cold.spread_log = c->d_spread_log.p;
-                cold.node_sets = c->d_node_sets.p; cold.set_words = (c->N + 63) / 64; cold.cls_zdom = c->d_cls_zdom.p;
-                if (c->rest) cold.sp_word = c->d_sp_word.p;
-            }
-            const bool tprof = c->table_prof;
-            if (tprof) { HIP_TRY(c, c->d_table_prof.ensure((size_t)S * 24)); HIP_TRY(c, hipMemsetAsync(c->d_table_prof.p, 0, (size_t)S * 192, c->stream)); cold.prof = c->d_table_prof.p; }
-            HIP_TRY(c, c->d_table_cold.ensure(sizeof cold));
-            HIP_TRY(c, hipMemcpyAsync(c->d_table_cold.p, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));             // `cold` is a stack object
-            TableLaunch f{};
-            f.cold = reinterpret_cast<const TableCold*>(c->d_table_cold.p);
-            f.cls_list = c->has_ranks ? c->d_rk_ids.p : c->d_cls_list.p; f.pods = c->d_podsC.p; f.orders = c->d_orders.p; f.perm = c->d_perm.p;
-            f.ws_off = c->d_ws_off.p; f.ws = c->d_ws.p; f.coarse = c->table_coarse; f.rest = c->rest; f.spread = c->spread; f.aff = c->rest && !c->aff_idx.empty(); f.team = team; f.lds_ws = lds_ws; f.lds_x = lds_x; f.nzeq = c->nzeq; f.has_pin = c->has_pin;
-            f.place_step = want_placement ? c->d_place_step.p : nullptr;
-            f.sc = TableScalars{(c->N + 63) / 64, c->Cn_t, c->Cp, P, S, c->n_sigs, c->has_ranks ? c->N : 0, (c->has_na ? kStNa : 0) | (c->has_tt ? kStTt : 0) | (c->has_add ? kStAdd : 0) | (want_slices ? kStGpuSlices : 0) | (c->sig_twins ? kStTwins : 0) | (c->fold ? kStFold : 0) | ((c->spread && (c->ipa_fold || c->hard_fold)) ? kStSpreadAff : 0) | (c->gfold ? kStGpuFold : 0) | (c->img_R > 0 ? kStImg : 0) | (c->seg_n ? kStSegments : 0), c->rest ? (int)c->zone_keys.size() : 0, c->rest ? c->rest_M : 0, c->rest ? c->rest_G : 0, c->rest ? c->rest_X : 0, c->spread ? c->sp_TH : 0, c->spread ? c->sp_TZ : 0, c->spread ? (int)c->sp_zkeys.size() : 0, ni_top, c->g_cpu, c->g_mem};
-            if (c->debug_route) fprintf(stderr, "[route] unit %s nzeq %d team %d\n", table_unit_name(f), (int)f.nzeq, f.team);
-            HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-            HIP_TRY(c, launch_table(f, S, table_lds, c->stream));
-            if (want_placement)
-                HIP_TRY(c, launch_unpermute(c->d_place_step.p, c->d_inv_orders.p, c->d_scen.p, S, P, c->d_place.p, c->stream));
-            HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-            if (tprof) {     // phase profile: mean ticks per scheduling cycle over the batch (profile builds only)
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                std::vector<unsigned long long> hp((size_t)S * 24);
-                HIP_TRY(c, hipMemcpy(hp.data(), c->d_table_prof.p, hp.size() * 8, hipMemcpyDeviceToHost));
-                double acc[24] = {0};
-                for (int s2 = 0; s2 < S; ++s2) for (int q = 0; q < 24; ++q) acc[q] += (double)hp[(size_t)s2 * 24 + q];
-                fprintf(stderr, "[SIMON_TABLE_PROF] S=%d ticks/cycle: loop %.0f | row+summary read %.0f | key+wavemax %.0f | tie check %.0f | lds(shape,sn) %.0f | mem(state,row) %.0f | state update %.0f | eval+patch+store %.0f | REST assume %.0f | REST select %.0f | canonical tie-breaks per cycle %.3f\n",
-                        S, acc[0] / S / P, acc[1] / S / P, acc[2] / S / P, acc[3] / S / P, acc[4] / S / P, acc[5] / S / P, acc[8] / S / P, acc[9] / S / P, acc[6] / S / P, acc[10] / S / P, acc[7] / S / P);
-                if (c->rest)
-                    fprintf(stderr, "[SIMON_TABLE_PROF] REST select, ticks/cycle (averaged over ALL pods): pod row %.0f | filter words + summaries %.0f | candidates %.0f | table rows of excluded bests %.0f (needed on %.3f of the cycles) | per-class best %.0f | class term %.0f | totals + tie %.0f | rest %.0f\n",
-                            acc[11] / S / P, acc[12] / S / P, acc[13] / S / P, acc[14] / S / P, acc[20] / S / P, acc[15] / S / P, acc[16] / S / P, acc[17] / S / P, acc[10] / S / P);
-                if (c->spread)
-                    fprintf(stderr, "[SIMON_TABLE_PROF] spread pods, ticks/cycle: entries arrived %.0f | descriptor + first loads %.0f | counters, sizes %.0f | zone counters, Log, raw table %.0f | pass 1 %.0f | extremes, totals table %.0f | pass 2 %.0f | winner %.0f | counter stores %.0f\n",
-                            acc[21] / S / P, acc[12] / S / P, acc[13] / S / P, acc[14] / S / P, acc[15] / S / P, acc[16] / S / P, acc[17] / S / P, acc[18] / S / P, acc[19] / S / P);
-            }
-            variant_used = SIMON_KERNEL_NARROW_CACHE;
-            T = 64 * team; slots = (ni_top / (c->table_coarse ? 64 : 16) + 63) / 64; lds = table_lds;
-            c->stats.n_launches = 1;
-            table_used = true;
-        } else if (c->fast_ok && !c->force_v1 && T >= 128) {
-            lds = ((size_t)c->Cp * c->Cn * 2 * sizeof(int32_t) + 15) & ~(size_t)15;
-            FastLaunch f{};
-            f.a_cpu = c->d_a_cpu.p; f.a_mem = c->d_a_mem.p; f.a_pods = c->d_a_pods.p; f.ncls = c->d_ncls.p;
-            f.i_rq_cpu = c->d_i_rq_cpu.p; f.i_rq_mem = c->d_i_rq_mem.p; f.i_nz_cpu = c->d_i_nz_cpu.p; f.i_nz_mem = c->d_i_nz_mem.p;
-            f.i_npods = c->d_i_npods.p; f.pods = c->d_podsF.p; f.orders = c->d_orders.p; f.scen = c->d_scen.p; f.perm = c->d_perm.p;
-            f.static_mask = c->has_mask ? c->d_mask.p : nullptr; f.simon_raw = c->d_raw32.p;
-            f.unscheduled = c->d_unsched.p; f.used_cpu = c->d_used_cpu.p; f.used_mem = c->d_used_mem.p;
-            f.placement = want_placement ? c->d_place.p : nullptr;
-            f.sc = FastScalars{(c->N + 63) / 64, c->Cn, c->Cp, P, S, c->g_cpu, c->g_mem};
-            HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-            HIP_TRY(c, launch_fast(f, T, slots, c->has_mask, c->nzeq, lds, c->stream));
-            HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-            variant_used = SIMON_KERNEL_NARROW_FAST;
-        } else {
-            lds = ((size_t)c->Cp * c->Cn * sizeof(int32_t) + 15) & ~(size_t)15;
-            NarrowArgs a{};
-            a.a_cpu = c->d_a_cpu.p; a.a_mem = c->d_a_mem.p; a.a_pods = c->d_a_pods.p; a.ncls = c->d_ncls.p;
-            a.i_rq_cpu = c->d_i_rq_cpu.p; a.i_rq_mem = c->d_i_rq_mem.p; a.i_nz_cpu = c->d_i_nz_cpu.p; a.i_nz_mem = c->d_i_nz_mem.p;
-            a.i_npods = c->d_i_npods.p;
-            a.pods = c->d_podsN.p; a.orders = c->d_orders.p; a.scen = c->d_scen.p; a.perm = c->d_perm.p;
-            a.static_mask = c->has_mask ? c->d_mask.p : nullptr;
-            a.simon_raw = c->d_raw32.p;
-            a.mask_words = (c->N + 63) / 64; a.Cn = c->Cn; a.Cp = c->Cp; a.P = P; a.S = S;
-            a.g_cpu = c->g_cpu; a.g_mem = c->g_mem;
-            a.unscheduled = c->d_unsched.p; a.used_cpu = c->d_used_cpu.p; a.used_mem = c->d_used_mem.p;
-            a.placement = want_placement ? c->d_place.p : nullptr;
-            HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-            HIP_TRY(c, launch_narrow(a, T, slots, c->has_mask, c->rcp_div, lds, c->stream));
-            HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-        }
-    }
-    if (c->debug_route && c->seg_n)
-        fprintf(stderr, "[route] segmented batch (%d segments, %d fixed nodes): %s\n", c->seg_n, c->seg_start[0],
-                run_wide ? "all-feature kernel -- refused" : table_used ? "score-table kernel, ranked instantiation" : "refused");
-    if (run_wide && c->seg_n)     // the all-feature kernel takes prefix scenarios only
+    if (want_place) HIP_TRY(c, c->d_place.ensure((size_t)S * P));
+    const BatchRoute r = route_batch(c);
+    if (r.kernel == SIMON_KERNEL_WIDE && c->seg_n) {     // the all-feature kernel takes prefix scenarios only
+        trace_segmented(c, "all-feature kernel -- refused");
         return fail(c, SIMON_ESTATE, "run_loaded: segmented batch on a problem the score-table kernel does not take; run each scenario's own problem");
-    if (run_wide) {
-        variant_used = SIMON_KERNEL_WIDE;
-        if (int rc = run_wide_batch(c, want_placement != 0, want_slices, &T)) return rc;
     }
+    int rc;
+    switch (r.kernel) {
+        case SIMON_KERNEL_WIDE: rc = run_wide_batch(c, r, want_place, want_slices); break;
+        case SIMON_KERNEL_NARROW_CACHE: rc = run_table_batch(c, r, want_place, want_slices); break;
+        case SIMON_KERNEL_NARROW_FAST: rc = run_fast_batch(c, r, want_place); break;
+        default: rc = run_narrow_batch(c, r, want_place);
+    }
+    if (rc) return rc;
     if (want_risk) {                                             // (behind ev1: not part of kernel_ms; one wave per scenario, P / 64 steps)
         if (!c->prio_staged) {
             HIP_TRY(c, c->d_prio.ensure((size_t)P));
@@ -2423,30 +2503,16 @@ int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
     (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
     c->stats.kernel_ms = ms;
     c->stats.n_launches = 1;
-    c->stats.kernel_variant = variant_used;
-    c->stats.kernel_generation = table_used ? (c->spread ? 7 : c->rest ? 6 : c->table_coarse ? 5 : 4) : variant_used == SIMON_KERNEL_NARROW_FAST ? 2 : variant_used == SIMON_KERNEL_NARROW ? 1 : 0;
-    c->stats.workgroup_size = T;
-    c->stats.slots_per_lane = slots;
-    c->stats.lds_bytes = (int64_t)lds;
+    c->stats.kernel_variant = r.kernel;
+    c->stats.kernel_generation = r.generation;
+    c->stats.workgroup_size = r.T;
+    c->stats.slots_per_lane = r.slots;
+    c->stats.lds_bytes = (int64_t)r.lds;
     c->have_results = true;
-    c->have_placement = want_placement != 0;
+    c->have_placement = want_place;
     c->have_slices = want_slices;
-    // generations 1 / 2 never see a GPU request (has_gpu routes the problem to generation 6 or the all-feature kernel)
     return SIMON_OK;
 }
-
-
-// simon_batch_out as the caller filled it, widened to the current layout: a v3 struct (no gpu_slices member) reads as gpu_slices = NULL
-}  // extern "C"
-static bool batch_out_view(const simon_batch_out* out, simon_batch_out* v) {
-    if (out->struct_size == sizeof(simon_batch_out)) { *v = *out; return true; }
-    if (out->struct_size != SIMON_BATCH_OUT_SIZE_V3) return false;
-    std::memset(v, 0, sizeof *v);
-    std::memcpy(v, out, SIMON_BATCH_OUT_SIZE_V3);
-    v->struct_size = sizeof *v;
-    return true;
-}
-extern "C" {
 
 int simon_fetch_results(simon_ctx* c, simon_batch_out* caller_out) {
     if (!c || !caller_out) return SIMON_EINVAL;

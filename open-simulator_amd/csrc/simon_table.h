@@ -147,7 +147,9 @@ constexpr int kTableMaxClasses = 64;    // internal node classes = distinct (col
 constexpr int kTableMaxClassesSpread = 128;  // ... two per lane in the REST select and in the SPREAD walks that score soft constraints only (CN2, round 6)
 constexpr int kTableMaxClassesPlain = 256;   // ... up to four per lane where only the prologue and the class terms' re-base are lane-shaped (no REST rows, no SPREAD; 129 .. 256: end of round 6)
 
-size_t table_lds_bytes(int K, int ni_max, int Cn, bool coarse, bool rest, int nzk = -1);   // LDS per workgroup for padded scenario sizes up to ni_max (nzk >= 0: SPREAD; | 0x100: second score table; | 0x200: team mode; | 0x400: CN2's larger score table)
+// bits of table_lds_bytes' nzk next to the zone-key count: spread_select's second score table, team mode, CN2's larger score table
+constexpr int kLdsSecondTable = 0x100, kLdsTeam = 0x200, kLdsCn2 = 0x400;
+size_t table_lds_bytes(int K, int ni_max, int Cn, bool coarse, bool rest, int nzk = -1);   // LDS per workgroup for padded scenario sizes up to ni_max (nzk >= 0: SPREAD, the zone-key count | kLds* bits)
 size_t table_ws_bytes(int K, int ni, bool nzeq, bool coarse, int Cn, int M, int NZ, int TH = 0, int TZ = 0);  // HBM workspace of ONE scenario with ni padded positions
 // launches n_blocks scenarios (one workgroup of 64 * max(team, 1) threads each), scenario of block b = a.perm[b], on the translation unit that
 // serves the launch (simon_table.hip: table_route)
