@@ -102,6 +102,12 @@ struct simon_ctx : simon::HostInputs {
     DevBuf<int32_t> d_t_ncls, d_rank, d_clsprefix, d_inv_orders, d_place_step, d_cls_list, d_cls_off, d_t_raw;
     std::vector<int32_t> h_clsprefix, scen_ni;   // [(N+1)][Cn_t]; padded (class-major) size of every loaded scenario
     size_t ws_total = 0;
+    // shared initial image of the score-table kernel (simon_table.h: TableImage): sized by table_layout next to ws_total, filled in every run
+    DevBuf<unsigned char> d_pro_image;
+    DevBuf<int32_t> d_pro_seg;
+    size_t pro_bytes = 0;
+    int pro_nb = 0;
+    bool no_shared_prologue = false;              // env SIMON_NO_SHARED_PROLOGUE: every scenario evaluates its own initial table (A/B + tests)
     // REST path of the score-table kernel (Open-Gpu-Share + node-level required anti-affinity): decided by choose_variant
     std::vector<int32_t> h_ncls_t, h_cls_off;    // internal node class of every node; class offsets into the per-class node lists
     DevBuf<int32_t> d_rk_ids, d_rk_pos;          // per-scenario node order for the score-table kernel (simon_set_node_ranks)
@@ -1607,6 +1613,7 @@ simon_ctx* simon_ctx_create(int device_id) {
     c->no_gpu_split = getenv("SIMON_TABLE_NO_GPU_SPLIT") != nullptr;
     c->no_class_content = getenv("SIMON_TABLE_NO_CLASS_CONTENT") != nullptr;
     c->no_gpu_fold = getenv("SIMON_NO_GPU_FOLD") != nullptr;
+    c->no_shared_prologue = getenv("SIMON_NO_SHARED_PROLOGUE") != nullptr;
     c->debug_route = getenv("SIMON_DEBUG_ROUTE") != nullptr;
     c->force_table = getenv("SIMON_FORCE_TABLE") != nullptr;         // A/B + tests: keep 257 .. 384 signatures on the score-table kernel   // A/B: node classes not split into with / without devices
 #ifdef SIMON_TABLE_PROFILE
@@ -1978,6 +1985,15 @@ static int table_layout(simon_ctx* c) {
                                                                     + (c->gfold ? (((size_t)c->scen_ni[perm[b]] * 40 + 127) & ~(size_t)127) : 0); }   // + GPU fold: devices by position
             c->ws_total = off;
             HIP_TRY(c, c->d_ws_off.upload(ws_off, c->stream));
+            // the shared initial image: the batch's largest scenario in the one-level layout (a prefix scenario's class lists are prefixes of its lists)
+            c->pro_nb = 0; c->pro_bytes = 0;
+            std::vector<int32_t> seg(Ct + 1, 0);                    // (alive until the synchronise below)
+            if (!coarse && !c->seg_n) {
+                for (int d = 0; d < Ct; ++d) seg[d + 1] = seg[d] + ((c->h_clsprefix[(size_t)max_n * Ct + d] + 15) & ~15);
+                c->pro_nb = seg[Ct] / 16;
+                c->pro_bytes = table_image_of(c->n_sigs, c->pro_nb, c->nzeq).total;
+                HIP_TRY(c, c->d_pro_seg.upload(seg, c->stream));
+            }
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             // more than 128 signatures: two-level layout without the REST path (simon_table.hip: MANY; since round 4 also under generation 7's
             // walks); else generation 2 / all-feature kernel
@@ -2400,6 +2416,12 @@ static int report_table_prof(simon_ctx* c) {
     HIP_TRY(c, hipMemcpy(hp.data(), c->d_table_prof.p, hp.size() * 8, hipMemcpyDeviceToHost));
     double acc[24] = {0};
     for (int s = 0; s < S; ++s) for (int q = 0; q < 24; ++q) acc[q] += (double)hp[(size_t)s * 24 + q];
+    // the prologue (slots 22 / 23, stamped once per scenario): ticks per scenario, and its share of everything the wave stamped
+    double all = 0;
+    for (double a : acc) all += a;
+    all -= acc[7] + acc[20] + acc[23];                                // (7 and 20 count events; 23 is a part of 22)
+    fprintf(stderr, "[SIMON_TABLE_PROF] S=%d ticks/scenario: prologue %.0f (%.2f %% of the wave's %.0f) | of it the table pass %.0f (%.2f %%)\n",
+            S, acc[22] / S, all > 0 ? 100.0 * acc[22] / all : 0.0, all / S, acc[23] / S, all > 0 ? 100.0 * acc[23] / all : 0.0);
     for (double& a : acc) a = a / S / P;
     fprintf(stderr, "[SIMON_TABLE_PROF] S=%d ticks/cycle: loop %.0f | row+summary read %.0f | key+wavemax %.0f | tie check %.0f | lds(shape,sn) %.0f | mem(state,row) %.0f | state update %.0f | eval+patch+store %.0f | REST assume %.0f | REST select %.0f | canonical tie-breaks per cycle %.3f\n",
             S, acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], acc[8], acc[9], acc[6], acc[10], acc[7]);
@@ -2419,21 +2441,29 @@ static int run_table_batch(simon_ctx* c, const BatchRoute& r, bool want_placemen
         HIP_TRY(c, hipMemsetAsync(c->d_ws.p, atoi(fill), c->ws_total, c->stream));
     if (want_placement) HIP_TRY(c, c->d_place_step.ensure((size_t)S * P));
     TableCold cold = table_cold(c, want_slices);
+    TableLaunch f{};
+    f.team = r.team; f.lds_ws = r.lds_ws; f.lds_x = r.lds_x;
+    f.coarse = c->table_coarse; f.rest = c->rest; f.spread = c->spread; f.aff = c->rest && !c->aff_idx.empty(); f.nzeq = c->nzeq; f.has_pin = c->has_pin;
+    f.sc = table_scalars(c, want_slices);
+    // Prefix scenarios in canonical order on the one-level kernels take their initial table from an image of the largest scenario, written once per run (not
+    // kept across runs: the initial state may change between them, and the image costs a launch of microseconds)
+    const bool shared_pro = !c->no_shared_prologue && c->pro_nb > 0 && !c->has_ranks && !c->seg_n && table_shared_prologue(f);
+    if (shared_pro) {
+        HIP_TRY(c, c->d_pro_image.ensure(c->pro_bytes));
+        cold.pro_image = c->d_pro_image.p; cold.pro_seg = c->d_pro_seg.p; cold.pro_nb = c->pro_nb; cold.pro_n = c->max_n;
+    }
     if (c->table_prof) { HIP_TRY(c, c->d_table_prof.ensure((size_t)S * 24)); HIP_TRY(c, hipMemsetAsync(c->d_table_prof.p, 0, (size_t)S * 192, c->stream)); cold.prof = c->d_table_prof.p; }
     HIP_TRY(c, c->d_table_cold.ensure(sizeof cold));
     HIP_TRY(c, hipMemcpyAsync(c->d_table_cold.p, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));             // `cold` is a stack object
-    TableLaunch f{};
     f.cold = reinterpret_cast<const TableCold*>(c->d_table_cold.p);
     f.cls_list = c->has_ranks ? c->d_rk_ids.p : c->d_cls_list.p; f.pods = c->d_podsC.p; f.orders = c->d_orders.p; f.perm = c->d_perm.p;
     f.place_step = want_placement ? c->d_place_step.p : nullptr;
     f.ws_off = c->d_ws_off.p; f.ws = c->d_ws.p;
-    f.team = r.team; f.lds_ws = r.lds_ws; f.lds_x = r.lds_x;
-    f.coarse = c->table_coarse; f.rest = c->rest; f.spread = c->spread; f.aff = c->rest && !c->aff_idx.empty(); f.nzeq = c->nzeq; f.has_pin = c->has_pin;
-    f.sc = table_scalars(c, want_slices);
-    if (c->debug_route) fprintf(stderr, "[route] unit %s nzeq %d team %d\n", table_unit_name(f), (int)f.nzeq, f.team);
+    if (c->debug_route) fprintf(stderr, "[route] unit %s nzeq %d team %d prologue %s\n", table_unit_name(f), (int)f.nzeq, f.team, shared_pro ? "shared-image" : "per-scenario");
     trace_segmented(c, "score-table kernel, ranked instantiation");
     if (int rc = timed_launch(c, [&] {
+            if (shared_pro) HIP_TRY(c, launch_table_image(f, c->pro_nb, c->stream));
             HIP_TRY(c, launch_table(f, S, r.lds, c->stream));
             if (want_placement) HIP_TRY(c, launch_unpermute(c->d_place_step.p, c->d_inv_orders.p, c->d_scen.p, S, P, c->d_place.p, c->stream));
             return (int)SIMON_OK;

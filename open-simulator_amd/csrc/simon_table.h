@@ -100,7 +100,27 @@ struct TableCold {
     int32_t img_stride;             // table classes x internal node classes
     // segmented batch (simon_set_scenario_segments, TableScalars::static_tables & kStSegments): [S][Cn] nodes of class d that scenario s holds
     const int32_t* scls;
+    // Shared initial image (table_image_kernel, round 8): the table, node state and block summaries of the batch's LARGEST scenario before any pod is placed,
+    // written once per run; a prefix scenario copies its blocks instead of evaluating them (table_kernel: kSharedPro).  Null: every scenario evaluates its own.
+    unsigned char* pro_image;       // TableImage layout
+    const int32_t* pro_seg;         // [Cn + 1] first position of a class segment in the image (classes padded to 16)
+    int32_t pro_nb, pro_n;          // blocks of 16 positions in the image; node count of the scenario it holds
 };
+
+// Byte offsets inside the shared initial image of `nb` blocks: tile [nb][K][16] bytes, state [nb * 16] x 12 B, (when NonZeroRequested differs from
+// Requested) nz [nb * 16] x 8 B, and per (block, signature) a u32: summary entry (best byte << 4 | 15 - position, class term 0) | feasible bytes << 16
+struct TableImage { unsigned tile, state, nz, sc, total; };
+__host__ __device__ inline TableImage table_image_of(int K, int nb, bool nzeq) {
+    auto al = [](unsigned x) { return (x + 127u) & ~127u; };
+    TableImage t;
+    unsigned o = 0;
+    t.tile = o; o += al((unsigned)nb * (unsigned)K * 16u);
+    t.state = o; o += al((unsigned)nb * 16u * 12u);
+    t.nz = o; o += nzeq ? 0u : al((unsigned)nb * 16u * 8u);
+    t.sc = o; o += al((unsigned)nb * (unsigned)K * 4u);
+    t.total = o;
+    return t;
+}
 
 struct TableLaunch {
     const TableCold* cold;      // device pointer
@@ -155,6 +175,10 @@ size_t table_ws_bytes(int K, int ni, bool nzeq, bool coarse, int Cn, int M, int 
 // serves the launch (simon_table.hip: table_route)
 hipError_t launch_table(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);
 const char* table_unit_name(const TableLaunch& a);   // the unit launch_table sends `a` to, by file name (SIMON_DEBUG_ROUTE)
+// Can the launch take its initial table from the shared image (a.cold's pro_image)?  The one-level instantiations of simon_table.hip on prefix scenarios in
+// canonical order: neither ranked nor segmented.  launch_table_image fills the image (the batch's largest scenario, `nb` blocks) on `st`, ahead of launch_table.
+bool table_shared_prologue(const TableLaunch& a);
+hipError_t launch_table_image(const TableLaunch& a, int nb, hipStream_t st);
 inline size_t table_ldsx_bytes(int ni_max, int M) {   // rows [M][ni_max / 16] u16, row totals [M] u32, canonical indices [ni_max] u16 (each rounded up to 128 bytes)
     return ((((size_t)(ni_max >> 4) * M * 2) + 127) & ~(size_t)127) + (((size_t)M * 4 + 127) & ~(size_t)127) + (((size_t)ni_max * 2 + 127) & ~(size_t)127);
 }

@@ -46,18 +46,33 @@
 // Phase profile of the scheduling cycle (profiles/build_variant.sh ... -DSIMON_TABLE_PROFILE): s_memtime stamps at the phase
 // boundaries, accumulated per wave, written to TableCold::prof ([workgroup][12] ticks).  Not compiled into the product build.
 #ifdef SIMON_TABLE_PROFILE
-#define TPROF_DECL unsigned long long tp_prev = __builtin_readcyclecounter(), tp_acc[24] = {0};
+#define TPROF_DECL unsigned long long tp_prev = __builtin_readcyclecounter(), tp_acc[24] = {0}; tp_acc[22] = tp_prev - tp_pro0; tp_acc[23] = tp_pro2;
+#define TPROF_PROLOGUE_BEGIN const unsigned long long tp_pro0 = __builtin_readcyclecounter(); unsigned long long tp_pro2 = 0;   // slots 22 / 23: whole prologue / its table pass, ticks per scenario
+#define TPROF_TABLE_PASS_BEGIN tp_pro2 = __builtin_readcyclecounter()
+#define TPROF_TABLE_PASS_END do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); tp_pro2 = __builtin_readcyclecounter() - tp_pro2; } while (0)
 #define TPROF(i) do { const unsigned long long t_ = __builtin_readcyclecounter(); tp_acc[i] += t_ - tp_prev; tp_prev = t_; } while (0)
 #define TPROF_WAIT_LDS asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #define TPROF_WAIT_MEM asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 #else
 #define TPROF_DECL
+#define TPROF_PROLOGUE_BEGIN
+#define TPROF_TABLE_PASS_BEGIN do { } while (0)
+#define TPROF_TABLE_PASS_END do { } while (0)
 #define TPROF(i) do { } while (0)
 #define TPROF_WAIT_LDS do { } while (0)
 #define TPROF_WAIT_MEM do { } while (0)
 #endif
 
 namespace simon {
+
+// The shared initial image (table_image_kernel, table_kernel: kSharedPro) belongs to the base unit: every unit that compiles this file a second time
+// (simon_table_<name>.hip) keeps its prologue as it is.
+#if defined(SIMON_TABLE_TEAM_TU) || defined(SIMON_TABLE_SPREAD_TU) || defined(SIMON_TABLE_SPREAD2_TU) || defined(SIMON_TABLE_LDS_TU) || defined(SIMON_TABLE_RESTLDS_TU) || \
+    defined(SIMON_TABLE_RS_TU) || defined(SIMON_TABLE_CLS4_TU) || defined(SIMON_TABLE_REST2_TU) || defined(SIMON_TABLE_REST_TU) || defined(SIMON_IMAGE_TU)
+constexpr bool kSharedPrologueTU = false;
+#else
+constexpr bool kSharedPrologueTU = true;
+#endif
 
 // Pointers that arrive through TableCold -- a struct in device memory -- are generic to the compiler: every access through them was a
 // FLAT instruction (round 6: 40 .. 90 per kernel, among them the REST select's Simon row and the pod's filter entries).  A flat load
@@ -104,39 +119,40 @@ __device__ __forceinline__ unsigned block_key16_t(const uint4 R) {
     return max(m0 & 0xFFFFu, m0 >> 16);
 }
 
-// Block key of a table row whose byte at position `pos` is being replaced: the v_perm selectors that expand the row's bytes to
-// u16 pairs take the touched byte from `nb` (selector 4 = byte 0 of the first operand) instead of the row -- the patch costs no
-// instruction.  kSel[pos] = 8 selectors: dword i pair lo (bytes 0, 1), pair hi (bytes 2, 3); 0x0c = constant 0.
+// Block key of a table row whose byte at position `pos` is being replaced.  v_perm_b32 lays the position constant next to the byte by
+// itself: its first operand holds {15 - 4i, 14 - 4i, 13 - 4i, 12 - 4i} for row dword i (selectors 4 .. 7; kPosC, four loop-invariant VGPRs --
+// a gfx9 VOP3 reads ONE scalar operand, and that is the selector), its second the row dword (selectors 0 .. 3), and every u16 comes out as
+// byte << 8 | 15 - position: ordered by byte, then by the earlier position, as byte * 16 + 15 - position was (round 8: eight v_pk_mad_u16
+// fewer).  The touched position selects constant 0 (0x0c) for both bytes; the new byte enters behind the packed maxima.
+// kSel[pos] = 8 selectors: dword i pair lo (bytes 0, 1), pair hi (bytes 2, 3).
 struct SelTab { unsigned v[16][8]; };
 constexpr SelTab make_sel_tab() {
     SelTab t{};
     for (int pos = 0; pos < 16; ++pos)
         for (int i = 0; i < 4; ++i)
             for (int h = 0; h < 2; ++h) {
-                unsigned b0 = (unsigned)(2 * h), b1 = (unsigned)(2 * h + 1);            // byte indices inside dword i
-                if (pos == 4 * i + 2 * h) b0 = 4;
-                if (pos == 4 * i + 2 * h + 1) b1 = 4;
-                t.v[pos][2 * i + h] = 0x0c000c00u | b0 | (b1 << 16);
+                const unsigned b0 = (unsigned)(2 * h), b1 = (unsigned)(2 * h + 1);      // byte indices inside dword i
+                unsigned lo = (4u + b0) | (b0 << 8), hi = (4u + b1) | (b1 << 8);         // u16 = row byte << 8 | position constant
+                if (pos == 4 * i + 2 * h) lo = 0x0c0cu;
+                if (pos == 4 * i + 2 * h + 1) hi = 0x0c0cu;
+                t.v[pos][2 * i + h] = lo | (hi << 16);
             }
     return t;
 }
 static __device__ __constant__ SelTab kSelTab = make_sel_tab();   // (static: simon_table_team.hip compiles this file a second time)
 #define kSel (kSelTab.v)
+// position constants of row dword i: byte j = 15 - (4 i + j)
+#define SIMON_POSC(i) (0x0C0D0E0Fu - 0x04040404u * (unsigned)(i))
 
-__device__ __forceinline__ unsigned pk_key(unsigned pair, unsigned c) {   // (x << 4) + c on both halves in ONE instruction
-    unsigned d;
-    asm("v_pk_mad_u16 %0, %1, 16, %2 op_sel_hi:[1,0,1]" : "=v"(d) : "v"(pair), "v"(c));
-    return d;
-}
-__device__ __forceinline__ unsigned block_key16_patched(const uint4 R, unsigned nb, const uint4 sa, const uint4 sb) {
-#define SIMON_C(q4) ((unsigned)((15 - (q4)) | ((15 - ((q4) + 1)) << 16)))
-    const unsigned m0 = pkmax_t(pk_key(__builtin_amdgcn_perm(nb, R.x, sa.x), SIMON_C(0)), pk_key(__builtin_amdgcn_perm(nb, R.x, sa.y), SIMON_C(2)));
-    const unsigned m1 = pkmax_t(pk_key(__builtin_amdgcn_perm(nb, R.y, sa.z), SIMON_C(4)), pk_key(__builtin_amdgcn_perm(nb, R.y, sa.w), SIMON_C(6)));
-    const unsigned m2 = pkmax_t(pk_key(__builtin_amdgcn_perm(nb, R.z, sb.x), SIMON_C(8)), pk_key(__builtin_amdgcn_perm(nb, R.z, sb.y), SIMON_C(10)));
-    const unsigned m3 = pkmax_t(pk_key(__builtin_amdgcn_perm(nb, R.w, sb.z), SIMON_C(12)), pk_key(__builtin_amdgcn_perm(nb, R.w, sb.w), SIMON_C(14)));
-#undef SIMON_C
+// returns max over the 16 positions of (byte << 4 | 15 - position), the row's byte at `pos` replaced by `nb` (<= 255)
+__device__ __forceinline__ unsigned block_key16_patched(const uint4 R, unsigned nb, int pos, const uint4 sa, const uint4 sb, const uint4 pc) {
+    const unsigned m0 = pkmax_t(__builtin_amdgcn_perm(pc.x, R.x, sa.x), __builtin_amdgcn_perm(pc.x, R.x, sa.y));
+    const unsigned m1 = pkmax_t(__builtin_amdgcn_perm(pc.y, R.y, sa.z), __builtin_amdgcn_perm(pc.y, R.y, sa.w));
+    const unsigned m2 = pkmax_t(__builtin_amdgcn_perm(pc.z, R.z, sb.x), __builtin_amdgcn_perm(pc.z, R.z, sb.y));
+    const unsigned m3 = pkmax_t(__builtin_amdgcn_perm(pc.w, R.w, sb.z), __builtin_amdgcn_perm(pc.w, R.w, sb.w));
     const unsigned m = pkmax_t(pkmax_t(m0, m1), pkmax_t(m2, m3));
-    return max(m & 0xFFFFu, m >> 16);
+    const unsigned best = max(max(m & 0xFFFFu, m >> 16), (nb << 8) | (unsigned)(15 - pos));
+    return (best & 15u) | (best >> 4);                                // byte << 8 | c (c < 16)  ->  byte << 4 | c
 }
 
 // max over each 16-lane row (result in every lane of the row)
@@ -292,6 +308,27 @@ __device__ __forceinline__ unsigned long long gpu_commit_t(unsigned (&u)[8], int
     return 0ull;
 }
 
+// (feasible, LeastAllocated + BalancedAllocation) of one signature on one node: 0 when NodeResourcesFit fails
+// (fit.go:230-302), else 1 + score.  Same fp64 sequences as simon_fast.hip::eval_slot.  Shared by table_kernel (prologue, refresh) and table_image_kernel.
+template <bool NZEQ>
+__device__ __forceinline__ unsigned eval_node_t(double q_req_c, double q_req_m, double q_nz_c, double q_nz_m, bool q_zero, double rq_c, double rq_m,
+                                                double nzs_c, double nzs_m, int freep, const ShapeRow& sh) {
+    const double t_c = rq_c + q_req_c, t_m = rq_m + q_req_m;
+    const bool res_ok = (sh.cap_c >= t_c) && (sh.cap_m >= t_m);
+    const bool ok = (freep >= 1) && (q_zero || res_ok);
+    // resource_allocation.go:91-98: requested = NonZeroRequested + pod non-zero request
+    const double r_c = NZEQ ? t_c : nzs_c + q_nz_c;
+    const double r_m = NZEQ ? t_m : nzs_m + q_nz_m;
+    const bool ge_c = r_c >= sh.cap_c, ge_m = r_m >= sh.cap_m;
+    const int la_c = ge_c ? 0 : la_term_t(r_c, sh.rc100_c);           // least_allocated.go:108-117
+    const int la_m = ge_m ? 0 : la_term_t(r_m, sh.rc100_m);
+    const double cf = div_by_rcp1(r_c, sh.cap_c, sh.rc_c);            // balanced_allocation.go:82-119; operands < 2^31 (simon_device.h)
+    const double mf = div_by_rcp1(r_m, sh.cap_m, sh.rc_m);
+    const int bs = (int)((1.0 - __builtin_fabs(cf - mf)) * 100.0);
+    const int base = ((la_c + la_m) >> 1) + ((ge_c || ge_m) ? 0 : bs);
+    return ok ? (unsigned)(base + 1) : 0u;
+}
+
 // KQ: signatures per lane (1: K <= 64, 2: K <= 128).  HAS_PIN: the stream holds pinned pods (own instantiation: the extra
 // branch costs the common kernel time).
 // NBQ: blocks per lane (1, 2 or 4: padded scenario sizes up to 1024 / 2048 / 4096 positions) -- a template parameter so that the
@@ -411,6 +448,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     // instantiations whose select is the summary scan alone.  REST rows, SPREAD walks and the further signature groups of MANY hold too much in
     // registers for a second copy of the assume; they keep one call behind the merge of their selects.
     constexpr bool kStraight = !REST && !SPREAD && !MANY;
+    // the initial table by copy from the shared image (prologue 2): this unit's one-level instantiations on prefix scenarios in canonical order
+    constexpr bool kSharedPro = kSharedPrologueTU && !COARSE && !REST && !SPREAD && !MANY && !kCls4 && !RANKED && !LDSWS && NW == 1;
     static_assert(!MANY || (KQ == 2 && COARSE && !CN2 && !LDSX), "MANY = groups of 128 signatures on the two-level layout (since round 6 also under the REST select: its rows and counters are indexed by signature already)");
     constexpr int NG = MANY ? 2 : 0;                                  // further signature groups (K <= 128 (1 + NG))
     static_assert(!SPREAD || COARSE, "SPREAD is built on the two-level layout");
@@ -485,6 +524,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     };
 
     // ---- prologue 1: clear, tables -> LDS, class segments --------------------------------------
+    TPROF_PROLOGUE_BEGIN
     for (int i = tid; i < K * Cn; i += TT) { if (CNT_LDS) s_cnt[i] = 0; s_sn[i] = 0; }
     if constexpr (kCls4) { for (int i = tid; i < Cn * 8; i += TT) ((int*)(smem + cv.shape))[i] = ((const int*)shapes)[(i >> 3) * 12 + (i & 7)]; }
     else for (int i = tid; i < Cn * 12; i += TT) ((int*)(smem + cv.shape))[i] = ((const int*)shapes)[i];
@@ -590,27 +630,71 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         return d < Cn ? d : Cn - 1;
     };
 
-    // (feasible, LeastAllocated + BalancedAllocation) of one signature on one node: 0 when NodeResourcesFit fails
-    // (fit.go:230-302), else 1 + score.  Same fp64 sequences as simon_fast.hip::eval_slot.
     auto eval_node = [&](double q_req_c, double q_req_m, double q_nz_c, double q_nz_m, bool q_zero, double rq_c, double rq_m,
                          double nzs_c, double nzs_m, int freep, const ShapeRow& sh) -> unsigned {
-        const double t_c = rq_c + q_req_c, t_m = rq_m + q_req_m;
-        const bool res_ok = (sh.cap_c >= t_c) && (sh.cap_m >= t_m);
-        const bool ok = (freep >= 1) && (q_zero || res_ok);
-        // resource_allocation.go:91-98: requested = NonZeroRequested + pod non-zero request
-        const double r_c = NZEQ ? t_c : nzs_c + q_nz_c;
-        const double r_m = NZEQ ? t_m : nzs_m + q_nz_m;
-        const bool ge_c = r_c >= sh.cap_c, ge_m = r_m >= sh.cap_m;
-        const int la_c = ge_c ? 0 : la_term_t(r_c, sh.rc100_c);           // least_allocated.go:108-117
-        const int la_m = ge_m ? 0 : la_term_t(r_m, sh.rc100_m);
-        const double cf = div_by_rcp1(r_c, sh.cap_c, sh.rc_c);            // balanced_allocation.go:82-119; operands < 2^31 (simon_device.h)
-        const double mf = div_by_rcp1(r_m, sh.cap_m, sh.rc_m);
-        const int bs = (int)((1.0 - __builtin_fabs(cf - mf)) * 100.0);
-        const int base = ((la_c + la_m) >> 1) + ((ge_c || ge_m) ? 0 : bs);
-        return ok ? (unsigned)(base + 1) : 0u;
+        return eval_node_t<NZEQ>(q_req_c, q_req_m, q_nz_c, q_nz_m, q_zero, rq_c, rq_m, nzs_c, nzs_m, freep, sh);
     };
 
     // ---- prologue 2: node rows, table and summary; lanes = 64 consecutive positions (4 blocks) ----
+    TPROF_TABLE_PASS_BEGIN;
+    // Prologue by copy (round 8).  Before any pod is placed, the byte of (signature, node), the node's state and a block's summary entry depend on the problem
+    // alone, and a prefix scenario in canonical order holds, per class, a PREFIX of the class's nodes in the batch's largest scenario: table_image_kernel wrote
+    // that scenario's initial table once for this run (TableCold::pro_image, class segments at pro_seg), and a scenario copies, class by class, its whole blocks
+    // of 16 positions -- table rows, state, summary entries, feasible counts -- and masks the one block its class count cuts.  The one-level instantiations of
+    // this unit without ranks (a ranked or segmented scenario orders or picks its nodes itself); the host passes no image to force the evaluation below.
+    bool by_copy = false;
+    if constexpr (kSharedPro) by_copy = gp(cold->pro_image) != nullptr;
+    if (by_copy) {
+        if constexpr (kSharedPro) {
+            GPtr<const unsigned char> const img = gp((const unsigned char*)cold->pro_image);
+            GPtr<const int32_t> const mseg = gp(cold->pro_seg);
+            const TableImage im = table_image_of(K, cold->pro_nb, NZEQ);
+            GPtr<const u32x4n> const i_tile = (GPtr<const u32x4n>)(img + im.tile);
+            GPtr<const u32x4n> const i_state = (GPtr<const u32x4n>)(img + im.state);
+            GPtr<const u32x4n> const i_nz = (GPtr<const u32x4n>)(img + im.nz);
+            GPtr<const unsigned> const i_sc = (GPtr<const unsigned>)(img + im.sc);
+            uint4* const o_tile = (uint4*)g_tile;
+            uint4* const o_state = (uint4*)g_state;
+            uint4* const o_nz = (uint4*)g_nz;
+            // dword e of a run of 4-byte words that holds `keep` valid ones: the words behind them (nodes the scenario does not hold, padding) are 0
+            auto keep4 = [](u32x4n v, int e0, int keep) -> uint4 {
+                return make_uint4(e0 < keep ? v.x : 0u, e0 + 1 < keep ? v.y : 0u, e0 + 2 < keep ? v.z : 0u, e0 + 3 < keep ? v.w : 0u);
+            };
+            for (int d = 0; d < Cn; ++d) {
+                const int cnt = __builtin_amdgcn_readfirstlane(count_of_class(d));
+                if (cnt == 0) continue;                                   // (no block, counters stay 0)
+                const int sb = __builtin_amdgcn_readfirstlane(s_seg[d]) >> 4, mb = __builtin_amdgcn_readfirstlane(mseg[d]) >> 4;   // first block here / in the image
+                const int nfull = cnt >> 4, rem = cnt & 15, nb = (cnt + 15) >> 4;
+                // table rows of the whole blocks: [block][K][16] is one contiguous run on both sides
+                for (int i = lane; i < nfull * K; i += 64) o_tile[(unsigned)(sb * K + i)] = ldg_u4(i_tile + (unsigned)(mb * K + i));
+                // node state (12 B per position) and NonZeroRequested (8 B), 16 B per lane
+                for (int i = lane; i < nb * 12; i += 64) o_state[(unsigned)(sb * 12 + i)] = keep4(i_state[(unsigned)(mb * 12 + i)], i * 4, cnt * 3);
+                if constexpr (!NZEQ) {
+                    for (int i = lane; i < nb * 8; i += 64) o_nz[(unsigned)(sb * 8 + i)] = keep4(i_nz[(unsigned)(mb * 8 + i)], i * 4, cnt * 2);
+                }
+                // summary entries and feasible-node counter of (signature k, class d): lane k, the one writer
+                for (int k = lane; k < K; k += 64) {
+                    int nfe = 0;
+                    for (int b = 0; b < nfull; ++b) {
+                        const unsigned v = i_sc[(unsigned)((mb + b) * K + k)];
+                        s_sum[k * nbp + sb + b] = (unsigned short)v;
+                        nfe += (int)(v >> 16);
+                    }
+                    if (rem) {                                            // the block the class count cuts: bytes at and beyond `rem` are not this scenario's
+                        auto below = [&](int q4) -> unsigned { const int nv = rem - q4; return nv >= 4 ? 0xFFFFFFFFu : nv <= 0 ? 0u : (1u << (8 * nv)) - 1u; };
+                        auto nonzero_bytes = [](unsigned w) -> int { return __popc((((w & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | w) & 0x80808080u); };
+                        uint4 R = ldg_u4(i_tile + (unsigned)((mb + nfull) * K + k));
+                        R.x &= below(0); R.y &= below(4); R.z &= below(8); R.w &= below(12);
+                        o_tile[(unsigned)((sb + nfull) * K + k)] = R;
+                        const unsigned m = block_key16_t(R);
+                        s_sum[k * nbp + sb + nfull] = (unsigned short)((m >> 4) ? m : 0u);
+                        nfe += nonzero_bytes(R.x) + nonzero_bytes(R.y) + nonzero_bytes(R.z) + nonzero_bytes(R.w);
+                    }
+                    s_cnt[k * Cn + d] = nfe;
+                }
+            }
+        }
+    } else
     for (int p0 = wv * 64; p0 < ni; p0 += TT) {                          // (team mode: chunk i belongs to wave i % NW)
         const int p = p0 + lane;
         const int d = class_of_pos(p < ni ? p : 0);
@@ -690,6 +774,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
 
         }
     }
+    TPROF_TABLE_PASS_END;
     if constexpr (REST) {
         for (int i = lane; i < nblk * M; i += 64) g_xm[i] = 0;            // no pod placed yet: every term row clear
         for (int i = lane; i < M; i += 64) g_rowtot[i] = 0u;
@@ -1905,6 +1990,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         else return 0;
     };
     int nxt_sw = load_spw(0);
+    // block_key16_patched's position constants: four VGPRs for the whole loop (opaque to the compiler, or it forms them again per cycle)
+    uint4 pos_c = make_uint4(SIMON_POSC(0), SIMON_POSC(1), SIMON_POSC(2), SIMON_POSC(3));
+    asm volatile("" : "+v"(pos_c.x), "+v"(pos_c.y), "+v"(pos_c.z), "+v"(pos_c.w));
 
     for (int i0 = 0; i0 < P; i0 += 64) {
         const int4 cur = nxt;
@@ -2266,6 +2354,59 @@ hipError_t launch_table_rest(const TableLaunch& a, int n_blocks, size_t lds_byte
         else return launch_kernel(table_kernel<true, Z, true, KQ, NBQ, true, true, RANKED, AFF, MANY, false>, a, n_blocks, 1, lds_bytes, st);
     }, a.nzeq, table_kq(a), table_nbq64(a), table_ranked(a), a.aff, table_many(a));
 }
+#elif defined(SIMON_IMAGE_TU)
+// ---- this translation unit (simon_image.hip) holds the shared initial image (TableCold::pro_image, layout table_image_of): what prologue 2 of table_kernel computes for the batch's LARGEST scenario, once per
+// run instead of once per scenario.  One lane per position of that scenario's class-major layout, 64 positions (4 blocks) per workgroup, blockIdx.y strides the
+// signatures; the same eval_node_t and the same static-mask test as the prologue, so a copied byte is the byte the scenario would have computed.
+// A unit of its own like every kernel family of this file (build() runs one hipcc process per unit; profiles/kernel_manifest.txt pins each unit's kernels).
+template <bool NZEQ>
+__global__ __launch_bounds__(64) void table_image_kernel(const TableCold* __restrict__ cold_, const int32_t* __restrict__ cls_list, const TableScalars sc) {
+    GPtr<const TableCold> const cold = gp(cold_);
+    const int Cn = sc.Cn, K = sc.K, NB = cold->pro_nb, ni = NB * 16;
+    GPtr<const int32_t> const mseg = gp(cold->pro_seg);
+    GPtr<const int32_t> const cls_off = gp(cold->cls_off);
+    GPtr<const uint64_t> const static_mask = gp(cold->static_mask);
+    const TableImage im = table_image_of(K, NB, NZEQ);
+    GPtr<unsigned char> const img = gp(cold->pro_image);
+    const int lane = threadIdx.x, p = blockIdx.x * 64 + lane;
+    const bool inside = p < ni;                                       // (ni is a multiple of 16: a group of 16 lanes is inside or outside as a whole)
+    int d = 0;
+    for (int e = 1; e <= Cn; ++e) d += (inside && p >= mseg[e]) ? 1 : 0;
+    d = d < Cn ? d : Cn - 1;
+    const int r = p - mseg[d];
+    const bool real = inside && r < gp(cold->clsprefix)[(size_t)cold->pro_n * Cn + d];
+    const int j = real ? cls_list[cls_off[d] + r] : 0;                // r-th node of class d in canonical order
+    const NodeState st = real ? NodeState{gp(cold->i_rq_cpu)[j], gp(cold->i_rq_mem)[j], (unsigned)(gp(cold->a_pods)[j] - gp(cold->i_npods)[j])} : NodeState{0, 0, 0};
+    uint2 z = make_uint2(0, 0);
+    if (!NZEQ && real) z = make_uint2(gp(cold->i_nz_cpu)[j], gp(cold->i_nz_mem)[j]);
+    if (inside && blockIdx.y == 0) {
+        GPtr<unsigned> const sp = (GPtr<unsigned>)(img + im.state) + (unsigned)p * 3u;
+        sp[0] = st.rq_c; sp[1] = st.rq_m; sp[2] = st.freep;
+        if (!NZEQ) ((GPtr<u32x2n>)(img + im.nz))[p] = u32x2n{z.x, z.y};
+    }
+    const ShapeRow sh = cold->shapes[d];
+    for (int k = blockIdx.y; k < K; k += gridDim.y) {
+        const SigRow q = cold->sigs[k];
+        unsigned b = eval_node_t<NZEQ>(q.req_c, q.req_m, q.nz_c, q.nz_m, q.flags & 1u, (double)st.rq_c, (double)st.rq_m, (double)z.x, (double)z.y, (int)st.freep, sh);
+        b = real ? b : 0u;
+        if (static_mask != nullptr) {                                 // NodeUnschedulable/NodeName/TaintToleration/NodeAffinity: static per (class, node)
+            const uint64_t w = static_mask[(size_t)q.cls * sc.mask_words + (j >> 6)];
+            b = ((w >> (j & 63)) & 1ull) ? b : 0u;
+        }
+        if (inside) img[im.tile + ((unsigned)(p >> 4) * (unsigned)K + (unsigned)k) * 16u + (unsigned)(p & 15)] = (unsigned char)b;
+        const unsigned m16 = row16_max_t(b ? ((b << 4) | (unsigned)(15 - (p & 15))) : 0u);   // class term 0, as the prologue's entry
+        const unsigned n16 = (unsigned)__popc((unsigned)((__ballot(b != 0) >> (lane & 48)) & 0xFFFFull));
+        if ((lane & 15) == 0 && inside) ((GPtr<unsigned>)(img + im.sc))[(unsigned)(p >> 4) * (unsigned)K + (unsigned)k] = m16 | (n16 << 16);
+    }
+}
+
+hipError_t launch_table_image(const TableLaunch& a, int nb, hipStream_t st) {
+    if (!table_shared_prologue(a) || nb <= 0) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(nb + 3) / 4, (unsigned)std::max(1, std::min(a.sc.K, 8)));   // (K = 0, a batch without pods: state alone)
+    if (a.nzeq) hipLaunchKernelGGL(table_image_kernel<true>, grid, dim3(64), 0, st, a.cold, a.cls_list, a.sc);
+    else hipLaunchKernelGGL(table_image_kernel<false>, grid, dim3(64), 0, st, a.cold, a.cls_list, a.sc);
+    return hipGetLastError();
+}
 #else
 // placement[s][pod] = place_step[s][inv_order[order_id(s)][pod]]: gather (scattered reads hit L2, stores coalesced)
 __global__ __launch_bounds__(256) void unpermute_kernel(const int32_t* __restrict__ place_step, const int32_t* __restrict__ inv_orders,
@@ -2311,6 +2452,11 @@ hipError_t launch_unpermute(const int32_t* place_step, const int32_t* inv_orders
 size_t table_lds_bytes(int K, int ni_max, int Cn, bool coarse, bool rest, int nzk) { return (size_t)tcarve(K, ni_max, Cn, coarse, rest, nzk, !coarse && Cn > 128).total; }
 size_t table_ws_bytes(int K, int ni, bool nzeq, bool coarse, int Cn, int M, int NZ, int TH, int TZ) { return table_ws_of(K, ni, nzeq, coarse, Cn, M, NZ, TH, TZ, !coarse && Cn > 128); }
 
+static bool table_base_unit(const TableLaunch& a);
+bool table_shared_prologue(const TableLaunch& a) {
+    return table_base_unit(a) && !a.coarse && a.sc.K <= 128 && !table_ranked(a) && !(a.sc.static_tables & kStSegments);
+}
+
 // ---- this translation unit (simon_table.hip) holds generations 4 and 5 without rows and walks, and the route to every other unit ----
 static hipError_t launch_table_base(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
     if (a.spread || a.rest || a.team > 1 || a.lds_ws || (!a.coarse && a.sc.Cn > 128)) return hipErrorInvalidValue;
@@ -2338,6 +2484,8 @@ static TableUnit table_route(const TableLaunch& a) {
     if (!a.coarse && a.sc.Cn > 128) return TableUnit::Cls4;           // generation 4, 129 .. 256 node classes
     return TableUnit::Base;                                           // generations 4 and 5
 }
+
+static bool table_base_unit(const TableLaunch& a) { return table_route(a) == TableUnit::Base; }
 
 const char* table_unit_name(const TableLaunch& a) {
     static const char* const names[] = {"simon_table_team4", "simon_table_rs", "simon_table_spread2", "simon_table_spread", "simon_table_lds",

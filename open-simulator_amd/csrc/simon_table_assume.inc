@@ -189,7 +189,7 @@
                 // observe these stores; no cache maintenance, no wait.
                 if (valid && nb != old) {
                     row_byte(rowk, pos) = (unsigned char)nb;
-                    const unsigned m = block_key16_patched(Tk, nb, selA, selB);
+                    const unsigned m = block_key16_patched(Tk, nb, pos, selA, selB, pos_c);
                     const unsigned e16 = (m >> 4) ? m + (snk << 4) : 0u;
                     if constexpr (COARSE) {
                         // per-16 entry to the workspace; the entry of the 64 positions = max over its four per-16 entries, each
