@@ -74,6 +74,9 @@ constexpr bool kSharedPrologueTU = false;
 constexpr bool kSharedPrologueTU = true;
 #endif
 
+// v_writelane_b32 through the intrinsic (this toolchain has no builtin for it): the compiler picks the registers and manages M0
+__device__ int llvm_amdgcn_writelane(int val, int lane, int old) __asm("llvm.amdgcn.writelane");
+
 // Pointers that arrive through TableCold -- a struct in device memory -- are generic to the compiler: every access through them was a
 // FLAT instruction (round 6: 40 .. 90 per kernel, among them the REST select's Simon row and the pod's filter entries).  A flat load
 // counts on vmcnt AND lgkmcnt, so the next wait for an LDS read also waited for the memory round trip.  gp() names the address
@@ -145,13 +148,23 @@ static __device__ __constant__ SelTab kSelTab = make_sel_tab();   // (static: si
 #define SIMON_POSC(i) (0x0C0D0E0Fu - 0x04040404u * (unsigned)(i))
 
 // returns max over the 16 positions of (byte << 4 | 15 - position), the row's byte at `pos` replaced by `nb` (<= 255)
-__device__ __forceinline__ unsigned block_key16_patched(const uint4 R, unsigned nb, int pos, const uint4 sa, const uint4 sb, const uint4 pc) {
+// SHORT (the straight-line instantiations): `c15` = 15 - pos arrives as a scalar, so the new byte's term is one shift-or; the two u16 halves meet in one maximum
+// of their own (kept apart from the second by an opaque copy: as a three-input maximum it needs the halves extracted first, apart it selects them as SDWA operands)
+template <bool SHORT>
+__device__ __forceinline__ unsigned block_key16_patched(const uint4 R, unsigned nb, int pos, const uint4 sa, const uint4 sb, const uint4 pc, int c15 = 0) {
     const unsigned m0 = pkmax_t(__builtin_amdgcn_perm(pc.x, R.x, sa.x), __builtin_amdgcn_perm(pc.x, R.x, sa.y));
     const unsigned m1 = pkmax_t(__builtin_amdgcn_perm(pc.y, R.y, sa.z), __builtin_amdgcn_perm(pc.y, R.y, sa.w));
     const unsigned m2 = pkmax_t(__builtin_amdgcn_perm(pc.z, R.z, sb.x), __builtin_amdgcn_perm(pc.z, R.z, sb.y));
     const unsigned m3 = pkmax_t(__builtin_amdgcn_perm(pc.w, R.w, sb.z), __builtin_amdgcn_perm(pc.w, R.w, sb.w));
     const unsigned m = pkmax_t(pkmax_t(m0, m1), pkmax_t(m2, m3));
-    const unsigned best = max(max(m & 0xFFFFu, m >> 16), (nb << 8) | (unsigned)(15 - pos));
+    unsigned best;
+    if constexpr (SHORT) {
+        unsigned h = max(m & 0xFFFFu, m >> 16);
+        asm("" : "+v"(h));
+        best = max(h, (nb << 8) | (unsigned)c15);
+    } else {
+        best = max(max(m & 0xFFFFu, m >> 16), (nb << 8) | (unsigned)(15 - pos));
+    }
     return (best & 15u) | (best >> 4);                                // byte << 8 | c (c < 16)  ->  byte << 4 | c
 }
 
@@ -448,6 +461,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     // instantiations whose select is the summary scan alone.  REST rows, SPREAD walks and the further signature groups of MANY hold too much in
     // registers for a second copy of the assume; they keep one call behind the merge of their selects.
     constexpr bool kStraight = !REST && !SPREAD && !MANY;
+    static_assert(!(kStraight && TIE_FIRST), "the straight-line cycle defines the winner's class and record index behind the assume's loads: nothing ahead of them may read dstar / res");
+    static_assert(!kStraight || NW == 1, "team mode is SPREAD: a straight-line instantiation has no helper waves");
     // the initial table by copy from the shared image (prologue 2): this unit's one-level instantiations on prefix scenarios in canonical order
     constexpr bool kSharedPro = kSharedPrologueTU && !COARSE && !REST && !SPREAD && !MANY && !kCls4 && !RANKED && !LDSWS && NW == 1;
     static_assert(!MANY || (KQ == 2 && COARSE && !CN2 && !LDSX), "MANY = groups of 128 signatures on the two-level layout (since round 6 also under the REST select: its rows and counters are indexed by signature already)");
@@ -1999,7 +2014,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         nxt = load_chunk(i0 + 64);
         const int cur_sw = nxt_sw;
         if constexpr (RS) nxt_sw = load_spw(i0 + 64);
-        const int steps = P - i0 < 64 ? P - i0 : 64;
+        int steps = P - i0 < 64 ? P - i0 : 64;
+        if constexpr (kStraight) asm volatile("" : "+s"(steps));   // the inner loop's bound in an SGPR: the latch is a scalar compare (`lane < steps` below would keep it in a VGPR)
         int plreg = -2;
         for (int il = 0; il < steps; ++il) {
         TPROF(0);                                                      // loop control, placement flush, pod chunk
@@ -2121,7 +2137,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
                     unsigned e;
                     asm("v_lshrrev_b32 %0, %2, %1" : "=v"(e) : "v"(m16), "n"(UB));
                     e16q[q] = e;
-                    key = max(key, (e << KB) + ((m16 & UMASK) | (unsigned)cb[q]));
+                    unsigned lo;                                      // position bits | entry constant as ONE and-or the compiler cannot split: it kept m16 & UMASK for the cold canonical_first, which masks for itself
+                    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(lo) : "v"(m16), "n"(UMASK), "v"(cb[q]));
+                    key = max(key, (e << KB) | lo);
                 } else {
                     key = max(key, (((m16 << (KB - UB)) & ~PMASK) | (unsigned)cb[q]) | (m16 & UMASK));
                 }
@@ -2134,11 +2152,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
             } else {
                 pstar = (int)(PMASK - (key & PMASK));                  // first maximum in POSITION order (speculative: tie check below)
                 top = key >> KB;
-                const int info = winner_info(pstar >> UB);
-                dstar = info >> 16;
-                res = (info & 0xFFFF) - 8192 + pstar;                  // index into cls_list
                 scanned = true;
-                if constexpr (kStraight) assume(true, false, pstar, dstar, res, top, m16q, e16q);
+                if constexpr (kStraight) {
+                    assume(true, false, pstar, dstar, res, top, m16q, e16q);   // (class and record index: behind the assume's loads, see there)
+                } else {
+                    const int info = winner_info(pstar >> UB);
+                    dstar = info >> 16;
+                    res = (info & 0xFFFF) - 8192 + pstar;              // index into cls_list
+                }
             }
         }
         if constexpr (NW > 1) {
@@ -2158,7 +2179,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         if (lane == 0) printf("DBG s=%d step=%d sig=%d cls=%d pstar=%d dstar=%d res=%d top=%u ni=%d nblk=%d\n", s, i0 + il, r_sig, r_cls, pstar, dstar, res, top, ni, nblk);
 #endif
         // -------- placement, recorded by STEP (coalesced); simon_hip.hip permutes to pod ids ---
-        plreg = (il == lane) ? res : plreg;
+        // (res is wave-uniform: where the cycle is straight-line code it sits in an SGPR and one v_writelane_b32 records it.  Helper waves exist in
+        // team mode only, which is SPREAD and never straight-line -- asserted next to kStraight -- so they keep the select and record nothing, as before)
+        if constexpr (kStraight) plreg = llvm_amdgcn_writelane(res, il, plreg);
+        else plreg = (il == lane) ? res : plreg;
         }
         // unschedulable pods: counted off the chunk's recorded results (res == -1), not carried through the cycle as a counter
         unsched += __popcll(__ballot(lane < steps && plreg == -1));

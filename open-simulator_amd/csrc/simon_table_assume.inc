@@ -60,7 +60,16 @@
             auto row_ref = [&](unsigned off) -> RowRef { if constexpr (MANY) return g_tile + off; else return off; };
             auto row_vec = [&](RowRef r) -> uint4 { if constexpr (MANY) return *(const uint4*)r; else return *(const uint4*)(g_tile + r); };
             auto row_byte = [&](RowRef r, int i) -> unsigned char& { if constexpr (MANY) return r[i]; else return g_tile[r + (unsigned)i]; };
-            RowRef rowp[KQ];
+            // (round 9, straight-line instantiations: the byte's offset is formed once and serves the load and the store -- left to the compiler, the
+            // load took an `or` and the store an `add` of the same two values.  It is made opaque BEHIND the loads: an inline-asm result costs the
+            // instructions that read it next a hazard s_nop each, and ahead of the loads those sat on the cycle's chain)
+            // (a byte reference: the byte's own offset where it is kept, else the row's -- what refresh_sig is handed either way)
+            auto byte_ref = [&](RowRef r, int i) -> RowRef {
+                if constexpr (kStraight) return r + (unsigned)i;
+                else return r;
+            };
+            auto byte_at = [&](RowRef b, int i) -> unsigned char& { if constexpr (kStraight) return g_tile[b]; else return row_byte(b, i); };
+            RowRef rowp[KQ], bytep[KQ];
             uint4 T[KQ];
             uint2 F[KQ];                                               // COARSE: the four per-16 entries of (signature, touched 64 positions)
             unsigned oldq[KQ];
@@ -68,7 +77,8 @@
             for (int q = 0; q < KQ; ++q) {
                 rowp[q] = row_ref(tile_blk((unsigned)(pstar >> 4)) + koff[q]);
                 T[q] = row_vec(rowp[q]);
-                oldq[q] = row_byte(rowp[q], pstar & 15);                         // this signature's byte before the cycle (same cache line as the row)
+                bytep[q] = byte_ref(rowp[q], pstar & 15);
+                oldq[q] = byte_at(bytep[q], pstar & 15);                         // this signature's byte before the cycle (same cache line as the row)
                 if (COARSE) F[q] = *(const uint2*)(g_fine + ((unsigned)(pstar >> 6) * (unsigned)K + (unsigned)kk[q]) * 4u);
             }
             // Fold (TableScalars::static_tables & kStFold): required anti-affinity / host ports on node-level keys.  The landing pod's signature
@@ -112,6 +122,18 @@
             }
             uint2 z = make_uint2(0, 0);
             if (!NZEQ) z = g_nz[pstar];
+            if constexpr (kStraight) {
+                // The scan's winner: its class and record index are read off the lanes' entry constants BEHIND the loads of its state, row and
+                // byte -- only the position feeds their addresses, and the memory round trip is the longest link of the cycle's chain.
+                if (scanned) {
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int q = 0; q < KQ; ++q) asm volatile("" : "+v"(bytep[q]));
+                    const int info = winner_info(pstar >> UB);
+                    dstar = info >> 16;
+                    res = (info & 0xFFFF) - 8192 + pstar;              // index into cls_list
+                }
+            }
             if (!TIE_FIRST && scanned && __builtin_expect(tie_with_other_class(), 0)) {   // rare: first maximum in CANONICAL order
                 const int p2 = canonical_first();
                 if (p2 != pstar) {                                     // the speculated winner loses the tie: load the real one
@@ -125,13 +147,16 @@
                     for (int q = 0; q < KQ; ++q) {
                         rowp[q] = row_ref(tile_blk((unsigned)(pstar >> 4)) + koff[q]);
                         T[q] = row_vec(rowp[q]);
-                        oldq[q] = row_byte(rowp[q], pstar & 15);
+                        bytep[q] = byte_ref(rowp[q], pstar & 15);
+                        oldq[q] = byte_at(bytep[q], pstar & 15);
                         if (COARSE) F[q] = *(const uint2*)(g_fine + ((unsigned)(pstar >> 6) * (unsigned)K + (unsigned)kk[q]) * 4u);
                     }
                     if (!NZEQ) z = g_nz[pstar];
                 }
             }
             const int blk = pstar >> 4, pos = pstar & 15;
+            int c15 = 15 - pos;                                        // block_key16_patched's constant of the touched position
+            if constexpr (kStraight) asm volatile("" : "+s"(c15));  // (uniform: a scalar subtract, not a vector xor per signature)
             RestLoads RL{};
             if (REST && __builtin_expect(rw != 0, 0)) RL = rest_assume_load(pstar, r_nrows, rowv, bound ? -1 : r_gs, r_xs);
             // GPU fold: the landing position's devices travel with the assume's loads (uniform addresses)
@@ -183,13 +208,13 @@
             TPROF(8);                                                  // state update (readlanes of the signature's request), state store
             // Signature k's byte of the touched node, its block key, summary entries and feasible-node counter (lane-local k).
             auto refresh_sig = [&](int k, bool valid, unsigned nb_raw,
-                                   RowRef rowk, const uint4 Tk, const uint2 Fk, unsigned old, unsigned snk, int dirty_bit) {
+                                   RowRef bytek, const uint4 Tk, const uint2 Fk, unsigned old, unsigned snk, int dirty_bit) {
                 const unsigned nb = old ? nb_raw : 0u;                    // static mask / monotone infeasibility
                 // One wave: its vector memory accesses are served in order, so the next cycle's loads of this row / state
                 // observe these stores; no cache maintenance, no wait.
                 if (valid && nb != old) {
-                    row_byte(rowk, pos) = (unsigned char)nb;
-                    const unsigned m = block_key16_patched(Tk, nb, pos, selA, selB, pos_c);
+                    byte_at(bytek, pos) = (unsigned char)nb;
+                    const unsigned m = block_key16_patched<kStraight>(Tk, nb, pos, selA, selB, pos_c, c15);
                     const unsigned e16 = (m >> 4) ? m + (snk << 4) : 0u;
                     if constexpr (COARSE) {
                         // per-16 entry to the workspace; the entry of the 64 positions = max over its four per-16 entries, each
@@ -284,7 +309,7 @@
             }
 #pragma unroll
             for (int q = 0; q < KQ; ++q)
-                refresh_sig(kk[q], kvalid[q], nbq[q], rowp[q], T[q], COARSE ? F[q] : make_uint2(0u, 0u),
+                refresh_sig(kk[q], kvalid[q], nbq[q], bytep[q], T[q], COARSE ? F[q] : make_uint2(0u, 0u),
                             oldq[q], snq[q], q);
             // MANY: the further groups (their table rows arrived with group 0's; the signature rows of TableCold::sigs are L2-hot)
             if constexpr (MANY) {
