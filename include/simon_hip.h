@@ -409,6 +409,32 @@ int simon_set_node_ranks(simon_ctx* ctx, const int32_t* rank /* [S][N] */);
 #define SIMON_MAX_SEGMENTS 8
 int simon_set_scenario_segments(simon_ctx* ctx, int32_t n_seg, const int32_t* seg_start, const int32_t* count /* [S][n_seg] */);
 
+/* Node-subset batches: scenario s holds exactly the pool nodes whose bit is set in row s of `present` -- the cluster without a failure
+ * domain (a node, a rack, a zone), or any other subset.  scen[s].n_nodes must equal the popcount of row s.  The canonical order of a
+ * scenario is nodeTree.list() of its own nodes inserted in pool order (V/internal/cache/node_tree.go:119-143): node_zone[j] = zone id
+ * of pool node j, zones in first-appearance order among the scenario's nodes, one node per zone per round, exhausted zones skipped;
+ * node_zone == NULL = one zone = pool order restricted to the scenario.  simon_set_node_ranks called afterwards overrides with the
+ * caller's rows over each scenario's own nodes, as for segments (also the road for more than SIMON_MAX_ZONES zones); with NULL it
+ * restores the batch's own order.  Gates, pins, simon_min_plan* and simon_fetch_preempt_risk behave as for segmented batches: a gated
+ * pod exists in scenario s iff s holds gate_node, a pinned pod whose node s lacks is unschedulable there, the plan's denominators are
+ * the allocatable / VG totals of the scenario's own nodes.  Unlike segments, a preset pod may target a node that some scenario lacks
+ * if it is gated on that same node: it vanishes with the node and is bound where the node is present.
+ * Call after simon_load_scenarios (which clears it); present == NULL returns to prefix scenarios.  It replaces segments and is replaced
+ * by them.  SIMON_EINVAL: bits set at or beyond N, an n_nodes mismatch, a scenario of no nodes, zone ids outside [0, n_zones) or
+ * n_zones outside [1, SIMON_MAX_ZONES] with node_zone given, a node absent from some scenario that carries pods bound before the
+ * stream (init_*) or is the preset target of a pod not gated on it.  SIMON_ESTATE: nothing loaded, ImageLocality in effect.  A call that
+ * fails leaves the batch a prefix batch.  Like a segmented batch it runs on the score-table kernel only: simon_run_loaded refuses
+ * (SIMON_ESTATE, "node-subset batch") a problem that needs the all-feature kernel, and simon_explain / simon_explain_loaded /
+ * simon_explain_batch refuse while one is loaded.  The per-scenario arrays are built on the device from the presence words
+ * (env SIMON_SUBSET_STAGE=host: in host loops, read once in simon_ctx_create). */
+#define SIMON_MAX_ZONES 64
+int simon_set_scenario_nodes(simon_ctx* ctx, const uint32_t* present /* [S][(N+31)/32], node j = bit (j & 31) of word j >> 5 */,
+                             const int32_t* node_zone /* [N] ids in [0, n_zones), or NULL = one zone */, int32_t n_zones);
+
+/* The rank rows in effect, rank[s][j] = position of pool node j in scenario s's canonical order: the caller's (simon_set_node_ranks) or
+ * those of a segmented / node-subset batch, where nodes a scenario lacks read N.  SIMON_ESTATE for a batch without rank rows. */
+int simon_fetch_node_ranks(simon_ctx* ctx, int32_t* rank /* [S][N] */);
+
 /* ABI v6.  Which extended resources the pod's computed request holds an ENTRY for, whatever the quantity: bit k of entries[p] =
  * resource k of simon_nodes_soa.scalar_alloc, bit 7 = an entry for a resource no node of the pool advertises.
  * computePodResourceRequest builds the request with Resource.Add / SetMaxResource (V/framework/plugins/noderesources/fit.go:148-165,

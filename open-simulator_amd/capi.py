@@ -25,6 +25,7 @@ GATED = -2
 ESTATE = -1      # SIMON_ESTATE (SimonError.code)
 EINVAL = -22     # SIMON_EINVAL
 MAX_SEGMENTS = 8 # SIMON_MAX_SEGMENTS
+MAX_ZONES = 64 # SIMON_MAX_ZONES
 
 FAIL_STATIC = 0x8000
 REASON_NODE_AFFINITY = 3
@@ -537,7 +538,7 @@ EXPORTS = [
     "simon_set_scalar_entries", "simon_set_pod_priorities", "simon_fetch_preempt_risk",
     "simon_group_set_scalar_entries", "simon_group_set_pod_priorities", "simon_group_fetch_preempt_risk",
     "simon_set_image_locality", "simon_group_set_image_locality",
-    "simon_set_scenario_segments",
+    "simon_set_scenario_segments", "simon_set_scenario_nodes", "simon_fetch_node_ranks",
     "simon_group_create", "simon_group_destroy", "simon_group_last_error", "simon_group_size", "simon_group_member",
     "simon_group_load_nodes", "simon_group_load_pods", "simon_group_load_class_tables", "simon_group_load_scenarios",
     "simon_group_run_loaded", "simon_group_fetch_results", "simon_group_run_batch", "simon_group_fetch_placement", "simon_group_fetch_gpu_slices",
@@ -576,6 +577,9 @@ def load_library(path: Optional[str] = None):
     lib.simon_run_batch.argtypes = [vp, C.POINTER(Scenario), C.c_int32, _p32, C.c_int32, C.POINTER(BatchOut)]
     lib.simon_set_node_ranks.argtypes = [vp, _p32]
     lib.simon_set_scenario_segments.argtypes = [vp, C.c_int32, _p32, _p32]
+    lib.simon_set_scenario_nodes.argtypes = [vp, C.POINTER(C.c_uint32), _p32, C.c_int32]
+    lib.simon_set_scenario_nodes.restype = C.c_int
+    lib.simon_fetch_node_ranks.argtypes = [vp, _p32]
     lib.simon_min_plan.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(Plan)]
     lib.simon_min_plan_vg.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Plan), C.POINTER(C.c_int32)]
     lib.simon_explain.argtypes = [vp, Scenario, _p32, _p32, _pu16, C.c_int32]
@@ -628,6 +632,15 @@ def load_library(path: Optional[str] = None):
     if path == library_path():
         _LIB = lib
     return lib
+
+
+def presence_words(present) -> np.ndarray:
+    """bool [S][N] -> uint32 [S][ceil(N / 32)], node j = bit (j & 31) of word j >> 5 (simon_set_scenario_nodes)."""
+    m = np.ascontiguousarray(present, dtype=bool)
+    if m.ndim != 2:
+        raise ValueError("presence rows are [S][N]")
+    m = np.pad(m, ((0, 0), (0, -m.shape[1] % 32)))
+    return np.ascontiguousarray(np.packbits(m, axis=1, bitorder="little")).view("<u4").astype(np.uint32).reshape(len(m), -1)
 
 
 EXPLAIN_BINS = 64     # SIMON_EXPLAIN_BINS
@@ -780,6 +793,30 @@ class Context:
         cn = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1, len(st))
         self._check(self.lib.simon_set_scenario_segments(self.h, len(st), _ptr(st, C.c_int32), _ptr(cn, C.c_int32)),
                     "simon_set_scenario_segments")
+
+    def set_scenario_nodes(self, present, node_zone=None, n_zones: Optional[int] = None) -> None:
+        """Node subsets: scenario s holds exactly the pool nodes with present[s][j] true (bool [S][N]); node_zone [N] = nodeTree zone id of
+        every node (None: one zone, each scenario in pool order) -- include/simon_hip.h: simon_set_scenario_nodes.  present None: back to
+        prefix scenarios.  n_zones: default the largest id + 1."""
+        if present is None:
+            self._check(self.lib.simon_set_scenario_nodes(self.h, None, None, 0), "simon_set_scenario_nodes")
+            return
+        words = presence_words(present)
+        if node_zone is None:
+            self._check(self.lib.simon_set_scenario_nodes(self.h, _ptr(words, C.c_uint32), None, 0), "simon_set_scenario_nodes")
+            return
+        z = np.ascontiguousarray(node_zone, dtype=np.int32)
+        if z.shape != (np.asarray(present).shape[1],):
+            raise ValueError(f"node_zone has shape {z.shape}, the pool {np.asarray(present).shape[1]} nodes")
+        self._check(self.lib.simon_set_scenario_nodes(self.h, _ptr(words, C.c_uint32), _ptr(z, C.c_int32),
+                                                       int(z.max(initial=0)) + 1 if n_zones is None else int(n_zones)),
+                    "simon_set_scenario_nodes")
+
+    def fetch_node_ranks(self) -> np.ndarray:
+        """[S][N] the rank rows in effect (nodes a segmented / node-subset scenario lacks: N); SIMON_ESTATE for a batch without rows."""
+        rank = np.zeros((self.S, self.problem.n_nodes), np.int32)
+        self._check(self.lib.simon_fetch_node_ranks(self.h, _ptr(rank, C.c_int32)), "simon_fetch_node_ranks")
+        return rank
 
     def min_plan(self, max_cpu_pct: int = 100, max_mem_pct: int = 100) -> Plan:
         plan = Plan()

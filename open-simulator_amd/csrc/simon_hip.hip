@@ -12,6 +12,7 @@
 #include "simon_device.h"
 #include "simon_wide.h"
 #include "simon_table.h"
+#include "simon_subset.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -186,6 +187,15 @@ struct simon_ctx : simon::HostInputs {
     std::vector<int64_t> seg_tot;
     DevBuf<int32_t> d_scls;
     DevBuf<int64_t> d_seg_tot;
+    // node-subset batch (simon_set_scenario_nodes): scenario s holds exactly the pool nodes whose bit is set in sub_words[s][sub_W] (node j =
+    // bit j & 31 of word j >> 5).  Rides on the segmented batch's kernel path (ranks, h_scls, seg_tot); a context holds one kind at a time.
+    // sub_zone [N]: nodeTree zone ids (empty: one zone).  subset_host: env SIMON_SUBSET_STAGE=host -- the arrays from host loops (A/B + tests)
+    bool sub_on = false, subset_host = false;
+    int sub_W = 0;
+    std::vector<uint32_t> sub_words;
+    std::vector<int32_t> sub_zone;
+    DevBuf<uint32_t> d_sub_words;
+    DevBuf<int32_t> d_sub_zone;
     bool orders_perm = false;                     // every loaded order is a permutation of [0, P) (the score-table kernel's placement gather)
     std::vector<int64_t> prefix_cpu, prefix_mem;   // [N+1] allocatable of the first n nodes
     std::vector<int64_t> prefix_vg;   // [N+1] Open-Local VG capacity of the first n nodes (0 without local storage)
@@ -1614,6 +1624,7 @@ simon_ctx* simon_ctx_create(int device_id) {
     c->no_class_content = getenv("SIMON_TABLE_NO_CLASS_CONTENT") != nullptr;
     c->no_gpu_fold = getenv("SIMON_NO_GPU_FOLD") != nullptr;
     c->no_shared_prologue = getenv("SIMON_NO_SHARED_PROLOGUE") != nullptr;
+    if (const char* e = getenv("SIMON_SUBSET_STAGE")) c->subset_host = strcmp(e, "host") == 0;   // A/B + tests: node-subset staging in host loops
     c->debug_route = getenv("SIMON_DEBUG_ROUTE") != nullptr;
     c->force_table = getenv("SIMON_FORCE_TABLE") != nullptr;         // A/B + tests: keep 257 .. 384 signatures on the score-table kernel   // A/B: node classes not split into with / without devices
 #ifdef SIMON_TABLE_PROFILE
@@ -1927,6 +1938,10 @@ int simon_load_class_tables(simon_ctx* c, const simon_class_tables* tb) {
     return SIMON_OK;
 }
 
+// does every scenario of the loaded batch bring its own node set (segmented or node-subset batch) instead of a prefix of the pool?
+static inline bool own_nodes(const simon_ctx* c) { return c->seg_n > 0 || c->sub_on; }
+static inline const char* own_kind(const simon_ctx* c) { return c->sub_on ? "node-subset" : "segmented"; }
+
 // table_lds_bytes' nzk of the staged problem with `team` waves per scenario: -1 without SPREAD, else the zone-key count | kLds* bits
 static int spread_lds_word(const simon_ctx* c, int team) {
     if (!c->spread) return -1;
@@ -1946,7 +1961,7 @@ static int table_layout(simon_ctx* c) {
         for (int s = 0; s < S; ++s) {
             int a = 0, b = 0;
             for (int d = 0; d < Ct; ++d) {
-                const int cnt = c->seg_n ? c->h_scls[(size_t)s * Ct + d] : c->h_clsprefix[(size_t)c->scen[s].n_nodes * Ct + d];   // (segmented: the scenario's own count)
+                const int cnt = own_nodes(c) ? c->h_scls[(size_t)s * Ct + d] : c->h_clsprefix[(size_t)c->scen[s].n_nodes * Ct + d];   // (segmented / node-subset: the scenario's own count)
                 a += (cnt + 15) & ~15; b += (cnt + 63) & ~63;
             }
             ni16[s] = std::max(a, 16); ni64[s] = std::max(b, 64);
@@ -1988,7 +2003,7 @@ static int table_layout(simon_ctx* c) {
             // the shared initial image: the batch's largest scenario in the one-level layout (a prefix scenario's class lists are prefixes of its lists)
             c->pro_nb = 0; c->pro_bytes = 0;
             std::vector<int32_t> seg(Ct + 1, 0);                    // (alive until the synchronise below)
-            if (!coarse && !c->seg_n) {
+            if (!coarse && !own_nodes(c)) {
                 for (int d = 0; d < Ct; ++d) seg[d + 1] = seg[d] + ((c->h_clsprefix[(size_t)max_n * Ct + d] + 15) & ~15);
                 c->pro_nb = seg[Ct] / 16;
                 c->pro_bytes = table_image_of(c->n_sigs, c->pro_nb, c->nzeq).total;
@@ -2005,7 +2020,7 @@ static int table_layout(simon_ctx* c) {
 
 int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, const int32_t* orders, int32_t n_orders) {
     if (!c || !scen || S <= 0 || !orders || n_orders <= 0) return c ? fail(c, SIMON_EINVAL, "load_scenarios: bad arguments") : SIMON_EINVAL;
-    c->seg_n = 0;                                        // (segments belong to the batch they were set for)
+    c->seg_n = 0; c->sub_on = false;                     // (segments and node subsets belong to the batch they were set for)
     if (c->has_img) {                    // ImageLocality: one slot per distinct cluster size; another set of sizes re-stages the tables
         std::vector<int32_t> sizes(S);
         for (int s = 0; s < S; ++s) sizes[s] = scen[s].n_nodes;
@@ -2088,33 +2103,37 @@ int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, co
     return SIMON_OK;
 }
 
-// is pool node j part of loaded scenario s?  Prefix batches: j < n_nodes; segmented ones: a fixed node or within its segment's count
+// is pool node j part of loaded scenario s?  Node-subset batches: its presence bit; prefix batches: j < n_nodes; segmented ones: a
+// fixed node or within its segment's count
 static inline bool node_in(const simon_ctx* c, size_t s, int j) {
+    if (c->sub_on) return (c->sub_words[s * (size_t)c->sub_W + (j >> 5)] >> (j & 31)) & 1u;
     if (!c->seg_n) return j < c->scen[s].n_nodes;
     const int g = c->seg_of[j];
     return g < 0 || j - c->seg_start[g] < c->seg_count[s * c->seg_n + g];
 }
 
 // rank rows of the loaded batch: the caller's (validated over each scenario's own nodes) or, rank == NULL on a segmented batch, pool
-// order restricted to the scenario.  Nodes outside a scenario get rank N (the score-table kernel tests presence by it).
+// order restricted to the scenario (own: the batch's scenarios bring their own node sets, own_nodes()).  Nodes outside a scenario get
+// rank N (the score-table kernel tests presence by it).
 static int load_ranks(simon_ctx* c, const int32_t* rank) {
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t S = c->S, N = c->N;
+    const bool own = own_nodes(c);
     std::vector<int32_t> inv(S * N, 0);
-    std::vector<int32_t> rk = c->seg_n ? std::vector<int32_t>(S * N, (int32_t)N) : std::vector<int32_t>(rank, rank + S * N);
+    std::vector<int32_t> rk = own ? std::vector<int32_t>(S * N, (int32_t)N) : std::vector<int32_t>(rank, rank + S * N);
     std::vector<char> seen;
     for (size_t s = 0; s < S; ++s) {
         const int n = c->scen[s].n_nodes;
         seen.assign(n, 0);
         int next = 0;
-        const int hi = c->seg_n ? (int)N : n;
+        const int hi = own ? (int)N : n;
         for (int j = 0; j < hi; ++j) {
-            if (c->seg_n && !node_in(c, s, j)) continue;
+            if (own && !node_in(c, s, j)) continue;
             const int r = rank ? rank[s * N + j] : next++;
             if (r < 0 || r >= n || seen[r]) return fail(c, SIMON_EINVAL, "set_node_ranks: scenario %d: not a permutation of 0..%d over its nodes", (int)s, n - 1);
             seen[r] = 1;
             inv[s * N + r] = j;
-            if (c->seg_n) rk[s * N + j] = r;
+            if (own) rk[s * N + j] = r;
         }
     }
     HIP_TRY(c, c->d_node_rank.upload(rk, c->stream));
@@ -2145,22 +2164,36 @@ static int load_ranks(simon_ctx* c, const int32_t* rank) {
     return SIMON_OK;
 }
 
+static int subset_stage(simon_ctx* c);
+
 int simon_set_node_ranks(simon_ctx* c, const int32_t* rank) {
     if (!c) return SIMON_EINVAL;
     if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "set_node_ranks: load scenarios first");
     if (!rank) {
+        if (c->sub_on) return subset_stage(c);                // a node-subset batch keeps its own rows: nodeTree order of its nodes
         if (c->seg_n) return load_ranks(c, nullptr);          // a segmented batch keeps its own rows: pool order over its nodes
         c->has_ranks = false; return SIMON_OK;
     }
     return load_ranks(c, rank);
 }
 
-// a failed simon_set_scenario_segments leaves the batch as a prefix batch: its own layout again, no ranks
+// a failed simon_set_scenario_segments / simon_set_scenario_nodes leaves the batch as a prefix batch: its own layout again, no ranks
 static int seg_abandon(simon_ctx* c, int rc) {
-    c->seg_n = 0;
+    c->seg_n = 0; c->sub_on = false;
     c->has_ranks = false; c->table_ranks_ok = false; c->have_results = false;
     if (c->variant == SIMON_KERNEL_NARROW && c->table_ok && c->orders_perm) (void)table_layout(c);
     return rc;
+}
+
+// does pool node j carry pods bound before the stream (init_* state)?  Such a node has to be part of every scenario.
+static bool node_busy(const simon_ctx* c, int j) {
+    const int N = c->N;
+    auto nz = [](const auto& v, size_t i) { return i < v.size() && v[i] != 0; };
+    bool busy = nz(c->i_npods, j) || nz(c->i_req_cpu, j) || nz(c->i_req_mem, j) || nz(c->i_req_eph, j) || nz(c->i_nz_cpu, j) || nz(c->i_nz_mem, j) || nz(c->l_dev_alloc, j);
+    for (int k = 0; k < SIMON_MAX_GPU_DEV; ++k) busy = busy || nz(c->i_gpu_used, (size_t)j * SIMON_MAX_GPU_DEV + k);
+    for (int k = 0; k < SIMON_MAX_VG; ++k) busy = busy || nz(c->l_vg_req, (size_t)j * SIMON_MAX_VG + k);
+    for (size_t k = 0; k < c->i_scalar_req.size() / std::max(N, 1); ++k) busy = busy || nz(c->i_scalar_req, k * N + j);
+    return busy;
 }
 
 int simon_set_scenario_segments(simon_ctx* c, int32_t n_seg, const int32_t* seg_start, const int32_t* count) {
@@ -2171,8 +2204,8 @@ int simon_set_scenario_segments(simon_ctx* c, int32_t n_seg, const int32_t* seg_
     if (n_seg < 0 || n_seg > SIMON_MAX_SEGMENTS) return fail(c, SIMON_EINVAL, "set_scenario_segments: n_seg %d outside [0,%d]", n_seg, SIMON_MAX_SEGMENTS);
     if (n_seg > 0 && (!seg_start || !count)) return fail(c, SIMON_EINVAL, "set_scenario_segments: %d segments without starts / counts", n_seg);
     if (n_seg == 0) {                                        // back to prefix scenarios
-        if (!c->seg_n) return SIMON_OK;
-        c->seg_n = 0;
+        if (!own_nodes(c)) return SIMON_OK;
+        c->seg_n = 0; c->sub_on = false;
         c->has_ranks = false; c->table_ranks_ok = false; c->have_results = false;
         return (c->variant == SIMON_KERNEL_NARROW && c->table_ok && c->orders_perm) ? table_layout(c) : SIMON_OK;
     }
@@ -2192,17 +2225,12 @@ int simon_set_scenario_segments(simon_ctx* c, int32_t n_seg, const int32_t* seg_
         if (tot == 0) return fail(c, SIMON_EINVAL, "set_scenario_segments: scenario %d holds no node at all (no fixed nodes, every count 0)", s);   // (the ranked instantiations have never run an empty scenario)
     }
     // a segment node starts empty: pods bound before the stream or by Spec.NodeName would need it in every scenario
-    auto nz = [](const auto& v, size_t i) { return i < v.size() && v[i] != 0; };
     for (int j = fixed; j < N; ++j) {
-        bool busy = nz(c->i_npods, j) || nz(c->i_req_cpu, j) || nz(c->i_req_mem, j) || nz(c->i_req_eph, j) || nz(c->i_nz_cpu, j) || nz(c->i_nz_mem, j) || nz(c->l_dev_alloc, j);
-        for (int k = 0; k < SIMON_MAX_GPU_DEV; ++k) busy = busy || nz(c->i_gpu_used, (size_t)j * SIMON_MAX_GPU_DEV + k);
-        for (int k = 0; k < SIMON_MAX_VG; ++k) busy = busy || nz(c->l_vg_req, (size_t)j * SIMON_MAX_VG + k);
-        for (size_t k = 0; k < c->i_scalar_req.size() / std::max(N, 1); ++k) busy = busy || nz(c->i_scalar_req, k * N + j);
-        if (busy) return fail(c, SIMON_EINVAL, "set_scenario_segments: segment node %d carries pods bound before the stream", j);
+        if (node_busy(c, j)) return fail(c, SIMON_EINVAL, "set_scenario_segments: segment node %d carries pods bound before the stream", j);
     }
     for (int p = 0; p < c->P; ++p)
         if (c->p_preset[p] >= fixed) return fail(c, SIMON_EINVAL, "set_scenario_segments: pod %d is preset to segment node %d", p, c->p_preset[p]);
-    c->seg_n = n_seg;
+    c->seg_n = n_seg; c->sub_on = false;                       // (segments replace a node-subset batch)
     c->seg_start.assign(seg_start, seg_start + n_seg);
     c->seg_count.assign(count, count + (size_t)S * n_seg);
     c->seg_of.assign(N, -1);
@@ -2236,6 +2264,130 @@ int simon_set_scenario_segments(simon_ctx* c, int32_t n_seg, const int32_t* seg_
     }
     const int rc = load_ranks(c, nullptr);
     return rc ? seg_abandon(c, rc) : SIMON_OK;
+}
+
+// The per-scenario arrays of a node-subset batch (c->sub_words, c->sub_zone): rank rows in each scenario's nodeTree order and their
+// inverse, per-class node lists, class counts (h_scls) and allocatable / VG totals (seg_tot), then the score-table layout of the batch.
+// On the device (simon_subset.hip; only the counts and totals come back), or with SIMON_SUBSET_STAGE=host in the loops a segmented
+// batch uses.
+static int subset_stage(simon_ctx* c) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t S = c->S, N = c->N;
+    const int Ct = c->Cn_t;
+    const bool cls = c->variant == SIMON_KERNEL_NARROW && c->table_ok;
+    c->has_ranks = false; c->table_ranks_ok = false; c->have_results = false;
+    c->seg_tot.assign(3 * S, 0);
+    if (cls) c->h_scls.assign(S * Ct, 0);
+    if (c->subset_host) {
+        // nodeTree.list() of every scenario: its nodes by zone in pool order, zones in first-appearance order, one node per zone per round
+        std::vector<int32_t> rows(S * N, (int32_t)N);
+        std::vector<std::vector<int>> tree;
+        std::vector<int> slot;
+        for (size_t s = 0; s < S; ++s) {
+            tree.clear();
+            slot.assign(SIMON_MAX_ZONES, -1);
+            for (int j = 0; j < (int)N; ++j) {
+                if (!node_in(c, s, j)) continue;
+                const int z = c->sub_zone.empty() ? 0 : c->sub_zone[j];
+                if (slot[z] < 0) { slot[z] = (int)tree.size(); tree.emplace_back(); }
+                tree[slot[z]].push_back(j);
+                c->seg_tot[s] += c->alloc_cpu[j];
+                c->seg_tot[S + s] += c->alloc_mem[j];
+                c->seg_tot[2 * S + s] += c->prefix_vg[j + 1] - c->prefix_vg[j];
+                if (cls) ++c->h_scls[s * Ct + c->h_ncls_t[j]];
+            }
+            int r = 0;
+            for (size_t round = 0; r < c->scen[s].n_nodes; ++round)
+                for (const std::vector<int>& zone : tree)
+                    if (round < zone.size()) rows[s * N + zone[round]] = r++;
+        }
+        HIP_TRY(c, c->d_seg_tot.upload(c->seg_tot, c->stream));
+        if (cls) {
+            HIP_TRY(c, c->d_scls.upload(c->h_scls, c->stream));
+            if (c->orders_perm)
+                if (const int rc = table_layout(c)) return rc;
+        }
+        return load_ranks(c, rows.data());
+    }
+    HIP_TRY(c, c->d_node_rank.ensure(S * N));
+    HIP_TRY(c, c->d_node_inv.ensure(S * N));
+    HIP_TRY(c, c->d_seg_tot.ensure(3 * S));
+    HIP_TRY(c, hipMemsetAsync(c->d_node_inv.p, 0, S * N * sizeof(int32_t), c->stream));
+    if (cls) {
+        HIP_TRY(c, c->d_rk_ids.ensure(S * N));
+        HIP_TRY(c, c->d_rk_pos.ensure(S * N));
+        HIP_TRY(c, c->d_scls.ensure(S * Ct));
+        HIP_TRY(c, hipMemsetAsync(c->d_rk_ids.p, 0, S * N * sizeof(int32_t), c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_rk_pos.p, 0, S * N * sizeof(int32_t), c->stream));
+    }
+    SubsetStage a{};
+    a.present = c->d_sub_words.p; a.node_zone = c->sub_zone.empty() ? nullptr : c->d_sub_zone.p;
+    a.ncls = cls ? c->d_t_ncls.p : nullptr; a.cls_off = c->d_cls_off.p;
+    a.prefix_cpu = c->d_prefix_cpu.p; a.prefix_mem = c->d_prefix_mem.p; a.prefix_vg = c->d_prefix_vg.p;
+    a.S = (int32_t)S; a.N = (int32_t)N; a.W = c->sub_W; a.Ct = Ct;
+    a.rank = c->d_node_rank.p; a.inv = c->d_node_inv.p; a.rk_ids = c->d_rk_ids.p; a.rk_pos = c->d_rk_pos.p; a.scls = c->d_scls.p; a.tot = c->d_seg_tot.p;
+    HIP_TRY(c, launch_subset_stage(a, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->seg_tot.data(), c->d_seg_tot.p, 3 * S * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (cls) HIP_TRY(c, hipMemcpyAsync(c->h_scls.data(), c->d_scls.p, S * Ct * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (cls && c->orders_perm)
+        if (const int rc = table_layout(c)) return rc;
+    c->table_ranks_ok = cls && c->table_perm_ok;
+    c->has_ranks = true;
+    return SIMON_OK;
+}
+
+int simon_set_scenario_nodes(simon_ctx* c, const uint32_t* present, const int32_t* node_zone, int32_t n_zones) {
+    if (!c) return SIMON_EINVAL;
+    if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "set_scenario_nodes: load scenarios first");
+    if (!present) return simon_set_scenario_segments(c, 0, nullptr, nullptr);        // back to prefix scenarios
+    if (c->has_img) return fail(c, SIMON_ESTATE, "set_scenario_nodes: ImageLocality is in effect (its image counts depend on the node set)");
+    const int S = c->S, N = c->N, W = (N + 31) / 32;
+    // every refusal leaves a prefix batch, whatever the batch was before
+    if (node_zone) {
+        if (n_zones < 1 || n_zones > SIMON_MAX_ZONES) return seg_abandon(c, fail(c, SIMON_EINVAL, "set_scenario_nodes: n_zones %d outside [1,%d]", n_zones, SIMON_MAX_ZONES));
+        for (int j = 0; j < N; ++j)
+            if (node_zone[j] < 0 || node_zone[j] >= n_zones) return seg_abandon(c, fail(c, SIMON_EINVAL, "set_scenario_nodes: node %d: zone %d outside [0,%d)", j, node_zone[j], n_zones));
+    }
+    const uint32_t tail = (N & 31) ? ~0u << (N & 31) : 0u;           // bits of the last word at or beyond N
+    std::vector<uint32_t> every(W, ~0u);                             // nodes that every scenario holds
+    for (int s = 0; s < S; ++s) {
+        const uint32_t* row = present + (size_t)s * W;
+        if (row[W - 1] & tail) return seg_abandon(c, fail(c, SIMON_EINVAL, "set_scenario_nodes: scenario %d: bits set at or beyond node %d", s, N));
+        int n = 0;
+        for (int w = 0; w < W; ++w) { n += __builtin_popcount(row[w]); every[w] &= row[w]; }
+        if (n == 0) return seg_abandon(c, fail(c, SIMON_EINVAL, "set_scenario_nodes: scenario %d holds no node at all", s));   // (the ranked instantiations have never run an empty scenario)
+        if (n != c->scen[s].n_nodes) return seg_abandon(c, fail(c, SIMON_EINVAL, "set_scenario_nodes: scenario %d: n_nodes %d, but its row holds %d nodes", s, c->scen[s].n_nodes, n));
+    }
+    auto always = [&](int j) { return (every[j >> 5] >> (j & 31)) & 1u; };
+    // a node that some scenario lacks starts empty there: pods bound before the stream would need it in every scenario; a pod preset to
+    // it has to vanish with it (gated on that same node)
+    for (int j = 0; j < N; ++j)
+        if (!always(j) && node_busy(c, j)) return seg_abandon(c, fail(c, SIMON_EINVAL, "set_scenario_nodes: node %d, absent from some scenario, carries pods bound before the stream", j));
+    for (int p = 0; p < c->P; ++p)
+        if (c->p_preset[p] >= 0 && !always(c->p_preset[p]) && c->p_gate[p] != c->p_preset[p])
+            return seg_abandon(c, fail(c, SIMON_EINVAL, "set_scenario_nodes: pod %d is preset to node %d, absent from some scenario, and not gated on it", p, c->p_preset[p]));
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->seg_n = 0; c->sub_on = true; c->sub_W = W;                    // (a node-subset batch replaces segments)
+    c->sub_words.assign(present, present + (size_t)S * W);
+    if (node_zone) c->sub_zone.assign(node_zone, node_zone + N); else c->sub_zone.clear();
+    int rc = SIMON_OK;
+    if (!c->subset_host) {
+        hipError_t e = c->d_sub_words.upload(c->sub_words, c->stream);
+        if (e == hipSuccess && node_zone) e = c->d_sub_zone.upload(c->sub_zone, c->stream);
+        if (e != hipSuccess) rc = fail(c, e == hipErrorOutOfMemory ? SIMON_ENOMEM : SIMON_ENODEV, "set_scenario_nodes: %s", hipGetErrorString(e));
+    }
+    if (!rc) rc = subset_stage(c);
+    return rc ? seg_abandon(c, rc) : SIMON_OK;
+}
+
+int simon_fetch_node_ranks(simon_ctx* c, int32_t* rank) {
+    if (!c || !rank) return c ? fail(c, SIMON_EINVAL, "fetch_node_ranks: bad arguments") : SIMON_EINVAL;
+    if (!c->staged || c->S <= 0 || !c->has_ranks) return fail(c, SIMON_ESTATE, "fetch_node_ranks: the loaded batch has no rank rows");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(rank, c->d_node_rank.p, (size_t)c->S * c->N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SIMON_OK;
 }
 
 // The all-feature kernel gives every problem its failure codes and runs the batches no other kernel takes: staged on first use where
@@ -2340,6 +2492,7 @@ static BatchRoute route_batch(const simon_ctx* c) {
 // SIMON_DEBUG_ROUTE: what became of a segmented batch
 static void trace_segmented(const simon_ctx* c, const char* outcome) {
     if (c->debug_route && c->seg_n) fprintf(stderr, "[route] segmented batch (%d segments, %d fixed nodes): %s\n", c->seg_n, c->seg_start[0], outcome);
+    if (c->debug_route && c->sub_on) fprintf(stderr, "[route] node-subset batch (%s staging): %s\n", c->subset_host ? "host" : "device", outcome);
 }
 
 // The launchers of simon_run_loaded, one per kernel: the loaded batch on route `r`, its launches between the context's event pair.
@@ -2366,7 +2519,7 @@ static TableCold table_cold(const simon_ctx* c, bool want_slices) {
     cold.gpu_slices = want_slices ? reinterpret_cast<unsigned long long*>(c->d_gpu_slices.p) : nullptr;
     cold.na_raw = c->has_na ? c->d_t_na.p : nullptr; cold.tt_raw = c->has_tt ? c->d_t_tt.p : nullptr; cold.add_raw = c->has_add ? c->d_t_add.p : nullptr;
     if (c->has_ranks) { cold.rk_pos = c->d_rk_pos.p; cold.rk_rank = c->d_node_rank.p; }
-    if (c->seg_n) cold.scls = c->d_scls.p;
+    if (own_nodes(c)) cold.scls = c->d_scls.p;
     if (c->img_R > 0) { cold.img = c->d_t_img.p; cold.img_slot = c->d_img_slot.p; cold.img_stride = c->img_stride_t; }
     if (c->rest) { cold.xrows = c->d_xrows.p; cold.zdom = c->d_zdom.p; cold.xsig = c->d_xsig.p; cold.xalloc = c->d_xalloc.p; cold.i_xused = c->d_i_xused.p; cold.gsig = c->d_gsig.p; }
     if (c->rest || c->gfold) { cold.gpu_cnt = c->d_gpu_cnt.p; cold.gpu_devtot = c->d_gpu_devtot.p; cold.i_gused = c->d_i_gused.p; }
@@ -2382,7 +2535,7 @@ static TableCold table_cold(const simon_ctx* c, bool want_slices) {
 static int32_t table_static_bits(const simon_ctx* c, bool want_slices) {
     return (c->has_na ? kStNa : 0) | (c->has_tt ? kStTt : 0) | (c->has_add ? kStAdd : 0) | (want_slices ? kStGpuSlices : 0) | (c->sig_twins ? kStTwins : 0) |
            (c->fold ? kStFold : 0) | ((c->spread && (c->ipa_fold || c->hard_fold)) ? kStSpreadAff : 0) | (c->gfold ? kStGpuFold : 0) | (c->img_R > 0 ? kStImg : 0) |
-           (c->seg_n ? kStSegments : 0);
+           (own_nodes(c) ? kStSegments : 0);
 }
 
 static TableScalars table_scalars(const simon_ctx* c, bool want_slices) {
@@ -2447,7 +2600,7 @@ static int run_table_batch(simon_ctx* c, const BatchRoute& r, bool want_placemen
     f.sc = table_scalars(c, want_slices);
     // Prefix scenarios in canonical order on the one-level kernels take their initial table from an image of the largest scenario, written once per run (not
     // kept across runs: the initial state may change between them, and the image costs a launch of microseconds)
-    const bool shared_pro = !c->no_shared_prologue && c->pro_nb > 0 && !c->has_ranks && !c->seg_n && table_shared_prologue(f);
+    const bool shared_pro = !c->no_shared_prologue && c->pro_nb > 0 && !c->has_ranks && !own_nodes(c) && table_shared_prologue(f);
     if (shared_pro) {
         HIP_TRY(c, c->d_pro_image.ensure(c->pro_bytes));
         cold.pro_image = c->d_pro_image.p; cold.pro_seg = c->d_pro_seg.p; cold.pro_nb = c->pro_nb; cold.pro_n = c->max_n;
@@ -2504,9 +2657,9 @@ int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
     }
     if (want_place) HIP_TRY(c, c->d_place.ensure((size_t)S * P));
     const BatchRoute r = route_batch(c);
-    if (r.kernel == SIMON_KERNEL_WIDE && c->seg_n) {     // the all-feature kernel takes prefix scenarios only
+    if (r.kernel == SIMON_KERNEL_WIDE && own_nodes(c)) {     // the all-feature kernel takes prefix scenarios only
         trace_segmented(c, "all-feature kernel -- refused");
-        return fail(c, SIMON_ESTATE, "run_loaded: segmented batch on a problem the score-table kernel does not take; run each scenario's own problem");
+        return fail(c, SIMON_ESTATE, "run_loaded: %s batch on a problem the score-table kernel does not take; run each scenario's own problem", own_kind(c));
     }
     int rc;
     switch (r.kernel) {
@@ -2635,7 +2788,7 @@ static int launch_plan(simon_ctx* c, int32_t max_cpu_pct, int32_t max_mem_pct, i
     const int blocks = std::min(64, (c->S + 255) / 256);
     hipLaunchKernelGGL(plan_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_scen.p, c->S, c->d_unsched.p,
                        c->d_used_cpu.p, c->d_used_mem.p, c->d_prefix_cpu.p, c->d_prefix_mem.p, max_cpu_pct, max_mem_pct,
-                       c->has_local ? c->d_used_vg.p : nullptr, c->d_prefix_vg.p, max_vg_pct, c->seg_n ? c->d_seg_tot.p : nullptr, c->d_plan.p);
+                       c->has_local ? c->d_used_vg.p : nullptr, c->d_prefix_vg.p, max_vg_pct, own_nodes(c) ? c->d_seg_tot.p : nullptr, c->d_plan.p);
     HIP_TRY(c, hipGetLastError());
     return SIMON_OK;
 }
@@ -2673,7 +2826,7 @@ int simon_min_plan_vg(simon_ctx* c, int32_t max_cpu_pct, int32_t max_mem_pct, in
     best->cpu_pct = (int)((double)uc / (double)ac * 100.0);
     best->mem_pct = (int)((double)(um * 1000) / (double)(am * 1000) * 100.0);
     best->used_cpu = uc; best->used_mem = um;
-    const int64_t av = c->seg_n ? c->seg_tot[(size_t)2 * c->S + s] : c->prefix_vg[n];
+    const int64_t av = own_nodes(c) ? c->seg_tot[(size_t)2 * c->S + s] : c->prefix_vg[n];
     if (vg_pct && c->has_local && av != 0) {
         int64_t uv = 0;
         HIP_TRY(c, hipMemcpy(&uv, c->d_used_vg.p + s, 8, hipMemcpyDeviceToHost));
@@ -2687,7 +2840,7 @@ int simon_min_plan_vg(simon_ctx* c, int32_t max_cpu_pct, int32_t max_mem_pct, in
 static int explain_impl(simon_ctx* c, int n_nodes, const int32_t* order, int32_t scenario, int32_t* failed_pods, uint16_t* fail_codes,
                         int32_t max_failed) {
     if (int rc = stage(c)) return rc;
-    if (c->seg_n) return fail(c, SIMON_ESTATE, "explain: segmented batch loaded");
+    if (own_nodes(c)) return fail(c, SIMON_ESTATE, "explain: %s batch loaded", own_kind(c));
     if (n_nodes < 0 || n_nodes > c->N) return fail(c, SIMON_EINVAL, "explain: n_nodes out of range");
     for (int i = 0; order && i < c->P; ++i) if (order[i] < 0 || order[i] >= c->P) return fail(c, SIMON_EINVAL, "explain: bad order");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2724,6 +2877,7 @@ static int explain_impl(simon_ctx* c, int n_nodes, const int32_t* order, int32_t
 int simon_explain(simon_ctx* c, simon_scenario scen, const int32_t* order, int32_t* failed_pods, uint16_t* fail_codes,
                   int32_t max_failed) {
     if (!c || !order || !failed_pods || !fail_codes || max_failed <= 0) return c ? fail(c, SIMON_EINVAL, "explain: bad arguments") : SIMON_EINVAL;
+    if (c->sub_on) return fail(c, SIMON_ESTATE, "explain: node-subset batch loaded; explain the scenario's own problem (its nodes alone)");
     if (c->has_ranks)   // an ad-hoc scenario has no rank row: which loaded scenario's tie-break order would apply is ambiguous
         return fail(c, SIMON_ESTATE, "explain: per-scenario node ranks are loaded; use simon_explain_loaded(scenario index)");
     return explain_impl(c, scen.n_nodes, order, -1, failed_pods, fail_codes, max_failed);
@@ -2733,8 +2887,8 @@ int simon_explain_loaded(simon_ctx* c, int32_t scenario, int32_t* failed_pods, u
     if (!c || !failed_pods || !fail_codes || max_failed <= 0) return c ? fail(c, SIMON_EINVAL, "explain_loaded: bad arguments") : SIMON_EINVAL;
     if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "explain_loaded: no scenarios loaded");
     if (scenario < 0 || scenario >= c->S) return fail(c, SIMON_EINVAL, "explain_loaded: scenario %d outside [0,%d)", scenario, c->S);
-    if (c->seg_n)        // the replay runs on the all-feature kernel, which takes prefix scenarios only
-        return fail(c, SIMON_ESTATE, "explain_loaded: segmented batch; explain the scenario's own problem (its nodes alone)");
+    if (own_nodes(c))    // the replay runs on the all-feature kernel, which takes prefix scenarios only
+        return fail(c, SIMON_ESTATE, "explain_loaded: %s batch; explain the scenario's own problem (its nodes alone)", own_kind(c));
     return explain_impl(c, c->scen[scenario].n_nodes, nullptr, scenario, failed_pods, fail_codes, max_failed);
 }
 
@@ -2744,8 +2898,8 @@ int simon_explain_batch(simon_ctx* c, const int32_t* scenarios, int32_t n_scen, 
     if (!scenarios || n_scen <= 0 || max_failed <= 0 || max_bins < 1 || max_bins > SIMON_EXPLAIN_BINS || !n_failed || !failed_pods || !n_bins || !bins)
         return fail(c, SIMON_EINVAL, "explain_batch: bad arguments");
     if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "explain_batch: no scenarios loaded");
-    if (c->seg_n)        // the replay runs on the all-feature kernel, which takes prefix scenarios only
-        return fail(c, SIMON_ESTATE, "explain_batch: segmented batch; explain each scenario's own problem (its nodes alone)");
+    if (own_nodes(c))    // the replay runs on the all-feature kernel, which takes prefix scenarios only
+        return fail(c, SIMON_ESTATE, "explain_batch: %s batch; explain each scenario's own problem (its nodes alone)", own_kind(c));
     const bool image = c->img_R > 0 && !c->img_sizes.empty();
     std::vector<WideScenario> hs((size_t)n_scen);
     std::vector<int32_t> slots(image ? (size_t)n_scen : 0);

@@ -1,0 +1,128 @@
+// simon_subset.hip -- subset_stage_kernel: the per-scenario arrays of a node-subset batch (simon_set_scenario_nodes), built on the
+// device from the presence words.  One wave per scenario; every order comes from ballots and prefix counts (no atomics), so the
+// arrays are the same on every run and equal to what the host loops of simon_hip.hip build (SIMON_SUBSET_STAGE=host).
+//
+// The canonical order of a scenario is nodeTree.list() of its own nodes inserted in pool order (V/internal/cache/node_tree.go:119-143):
+// zones in first-appearance order, one node per zone per round, exhausted zones skipped.  A present node with index i inside its zone
+// (among the scenario's nodes) and zone order q comes after, of the zone of order q', min(cnt, i + 1) nodes for q' < q and min(cnt, i)
+// nodes for q' >= q:   rank = sum_z min(cnt_z, i) + #{z' : order(z') < q, cnt_z' > i}.
+#include "simon_subset.h"
+
+namespace simon {
+namespace {
+
+__global__ __launch_bounds__(64) void subset_stage_kernel(SubsetStage a) {
+    extern __shared__ int32_t smem[];
+    int32_t* const s_ocnt = smem;            // [64] nodes of the zone with order q
+    int32_t* const s_zord = smem + 64;       // [64] order of zone z
+    int32_t* const s_fill = smem + 128;      // [Ct] nodes of class d met so far (pass 2)
+    const int s = blockIdx.x, lane = threadIdx.x, N = a.N;
+    const uint32_t* __restrict__ const row = a.present + (size_t)s * a.W;
+    int32_t* const rank = a.rank + (size_t)s * N;
+    int32_t* const inv = a.inv + (size_t)s * N;
+    const unsigned long long below = (1ull << lane) - 1;
+
+    // ---- pass 0, pool order: index of every present node inside its zone; lane z keeps zone z's count and first node; the totals ----
+    int zcnt = 0, zfirst = N;
+    long long t_cpu = 0, t_mem = 0, t_vg = 0;
+    for (int base = 0; base < N; base += 64) {
+        const int j = base + lane;
+        const bool in = j < N && ((row[j >> 5] >> (j & 31)) & 1u) != 0;
+        const int z = (in && a.node_zone) ? a.node_zone[j] : 0;
+        if (in) {
+            t_cpu += a.prefix_cpu[j + 1] - a.prefix_cpu[j];
+            t_mem += a.prefix_mem[j + 1] - a.prefix_mem[j];
+            t_vg += a.prefix_vg[j + 1] - a.prefix_vg[j];
+        }
+        int idx = 0;
+        unsigned long long left = __ballot(in);
+        while (left) {                                                // one turn per distinct zone among the chunk's present nodes
+            const int lead = __ffsll(left) - 1;
+            const int zz = __shfl(z, lead, 64);
+            const bool mine = in && z == zz;
+            const unsigned long long m = __ballot(mine);
+            const int before = __shfl(zcnt, zz, 64);
+            if (mine) idx = before + __popcll(m & below);
+            if (lane == zz) {
+                zcnt = before + __popcll(m);
+                if (before == 0) zfirst = base + lead;
+            }
+            left &= ~m;
+        }
+        if (j < N) rank[j] = in ? idx : N;                            // (the index inside the zone: pass 1 turns it into the rank)
+    }
+    // zone order = first appearance among the scenario's nodes (the first nodes of two zones differ, so no ties)
+    int q = 0, nz = 0, n = 0;
+    for (int k = 0; k < 64; ++k) {
+        const int ck = __shfl(zcnt, k, 64), fk = __shfl(zfirst, k, 64);
+        q += (ck > 0 && fk < zfirst) ? 1 : 0;
+        nz += ck > 0 ? 1 : 0;
+        n += ck;
+    }
+    if (zcnt > 0) s_ocnt[q] = zcnt;
+    s_zord[lane] = q;
+    for (int off = 32; off > 0; off >>= 1) {
+        t_cpu += __shfl_xor(t_cpu, off, 64);
+        t_mem += __shfl_xor(t_mem, off, 64);
+        t_vg += __shfl_xor(t_vg, off, 64);
+    }
+    if (lane == 0) {
+        a.tot[s] = t_cpu;
+        a.tot[(size_t)a.S + s] = t_mem;
+        a.tot[(size_t)2 * a.S + s] = t_vg;
+    }
+    __syncthreads();
+
+    // ---- pass 1: ranks from the closed form, and their inverse ----
+    for (int base = 0; base < N; base += 64) {
+        const int j = base + lane;
+        if (j >= N || ((row[j >> 5] >> (j & 31)) & 1u) == 0) continue;
+        const int i = rank[j], zq = s_zord[a.node_zone ? a.node_zone[j] : 0];
+        int r = 0;
+        for (int k = 0; k < nz; ++k) r += min(s_ocnt[k], i + (k < zq ? 1 : 0));
+        rank[j] = r;
+        if (r < N) inv[r] = j;
+    }
+    if (!a.ncls) return;
+
+    // ---- pass 2, rank order: per-class node lists, a node's index inside its class, the class counts ----
+    const int Ct = a.Ct;
+    for (int d = lane; d < Ct; d += 64) s_fill[d] = 0;
+    __syncthreads();                                                  // (also: pass 1's inv is visible to the whole wave)
+    int32_t* const ids = a.rk_ids + (size_t)s * N;
+    int32_t* const pos = a.rk_pos + (size_t)s * N;
+    for (int base = 0; base < n; base += 64) {
+        const int r = base + lane;
+        const bool in = r < n;
+        const int j = in ? inv[r] : 0;
+        const int d = in ? a.ncls[j] : -1;
+        unsigned long long left = __ballot(in);
+        while (left) {                                                // one turn per distinct class among the chunk's nodes
+            const int lead = __ffsll(left) - 1;
+            const int dd = __shfl(d, lead, 64);
+            const bool mine = in && d == dd;
+            const unsigned long long m = __ballot(mine);
+            const int before = s_fill[dd];
+            if (mine) {
+                const int p = before + __popcll(m & below);
+                pos[j] = p;
+                if (a.cls_off[dd] + p < N) ids[a.cls_off[dd] + p] = j;
+            }
+            if (lane == lead) s_fill[dd] = before + __popcll(m);
+            left &= ~m;
+        }
+        __syncthreads();
+    }
+    for (int d = lane; d < Ct; d += 64) a.scls[(size_t)s * Ct + d] = s_fill[d];
+}
+
+}  // namespace
+
+hipError_t launch_subset_stage(const SubsetStage& a, hipStream_t st) {
+    if (a.S <= 0 || a.N <= 0) return hipSuccess;
+    const size_t lds = (size_t)(128 + (a.ncls ? a.Ct : 0)) * sizeof(int32_t);
+    hipLaunchKernelGGL(subset_stage_kernel, dim3((unsigned)a.S), dim3(64), lds, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace simon

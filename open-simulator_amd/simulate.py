@@ -25,22 +25,28 @@ class HipEngine:
 
     supports_image_locality = True            # ImageLocality per scenario size on the device (ABI v7): sweep() batches image clusters
     supports_scenario_segments = True         # pool segments (simon_set_scenario_segments): sweep_mix() batches node-type mixes
+    supports_scenario_subsets = True          # node subsets (simon_set_scenario_nodes): sweep_failures() batches the loss of every failure domain
 
     def __init__(self, device_id: int = 0):
         self.device_id = device_id
 
     def run(self, prob: capi.Problem, scen, orders, want_placement=True, node_ranks=None, want_gpu_slices=False,
-            segments=None) -> capi.BatchResult:
+            segments=None, present=None) -> capi.BatchResult:
         """segments: (seg_start [G], counts [S][G]) -- scenario s holds the pool nodes before seg_start[0] and the first counts[s][g] of every
-        segment g (sweep_mix); None = every scenario is a prefix of the pool."""
+        segment g (sweep_mix).  present: (mask bool [S][N], node_zone [N] or None) -- scenario s holds exactly the pool nodes of its row, in
+        the nodeTree order of those nodes (sweep_failures).  Neither = every scenario is a prefix of the pool; both = ValueError."""
+        if segments is not None and present is not None:
+            raise ValueError("a batch has pool segments or node subsets, not both")
         with capi.Context(self.device_id) as ctx:
             ctx.load_problem(prob)
-            if node_ranks is None and segments is None:
+            if node_ranks is None and segments is None and present is None:
                 res = ctx.run_batch(scen, orders, want_placement, want_gpu_slices)
             else:
                 ctx.load_scenarios(scen, orders)
                 if segments is not None:
                     ctx.set_scenario_segments(*segments)
+                if present is not None:
+                    ctx.set_scenario_nodes(*present)
                 if node_ranks is not None:
                     ctx.set_node_ranks(node_ranks)    # per-scenario nodeTree order (clusters with several zones)
                 ctx.run_loaded(want_placement, want_gpu_slices)
@@ -784,6 +790,206 @@ def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why
         result = res
     return MixSweepResult(mixes, uns, cpu_pct, mem_pct, vg_pct, risks, None if best is None else mixes[best],
                           None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result, batched=False, fallback=why)
+
+
+@dataclass
+class FailureSweepResult:
+    """sweep_failures: what the cluster still holds without each failure domain.  Lists run over the domains; `baseline` is the same row
+    for the whole cluster."""
+    domains: List[List[str]]             # node names of every domain
+    unscheduled: List[int]               # pods of the domain's scenario that stay unscheduled (pods that die with their node do not count)
+    cpu_pct: List[int]                   # occupancies over the scenario's own nodes (satisfyResourceSetting)
+    mem_pct: List[int]
+    vg_pct: List[int]
+    survives: List[bool]                 # no unscheduled pod and the caps hold
+    needs_reference: List[bool]          # DefaultPreemption could have acted there (simon_fetch_preempt_risk)
+    baseline: Dict[str, object]          # {"unscheduled", "cpu_pct", "mem_pct", "vg_pct", "survives", "needs_reference"} of the whole cluster
+    critical: List[int]                  # indices of the domains that do not survive, by descending unscheduled count (ties: domain order)
+    rows: List[tuple]                    # per scenario ([0] the whole cluster, [d + 1] without domain d): (Flat, placement row by pod id)
+    unscheduled_pods: List[List[dict]] = field(default_factory=list)   # reasons=True: per domain, simulate()'s list for the failing scenarios
+    batched: bool = True                 # one node-subset engine batch (False: every scenario ran as its own simulate())
+    fallback: Optional[str] = None       # why the scenarios ran one by one (None when batched); sweep_failures also warns
+
+    def placement(self, s: int) -> Dict[tuple, Optional[str]]:
+        """Scenario s (0 = the whole cluster, d + 1 = without domain d): (namespace, pod name) -> node name, None where unscheduled; the
+        pods that died with the domain are not listed.  Built on request: an N-1 sweep holds N + 1 scenarios of every pod."""
+        flat, row = self.rows[s]
+        return {flat.pod_refs[pid]: (None if j == capi.UNSCHEDULED else flat.node_names[j]) for pid, j in enumerate(row.tolist()) if j != capi.GATED}
+
+    @property
+    def placements(self) -> List[Dict[tuple, Optional[str]]]:
+        return [self.placement(s) for s in range(len(self.rows))]
+
+
+class FailureFallbackWarning(UserWarning):
+    """sweep_failures could not batch the scenarios and runs each as its own problem: one engine context, flatten and launch per
+    failure domain.  The reason names what refused: an engine without node subsets, nodes that list the pods' images (ImageLocality
+    over a node set), an app whose pod order depends on the node set (a DaemonSet, a pod bound to a node: _same_stream), or a problem
+    the score-table kernel does not take (the all-feature kernel runs prefix scenarios only)."""
+
+
+def failure_domains(nodes: List[dict], domains) -> List[List[str]]:
+    """The node names of every failure domain: "node" = every node alone; a label key = one domain per value, in first-appearance
+    order (nodes without the label belong to none); or the caller's lists of node names."""
+    names = [n["metadata"]["name"] for n in nodes]
+    if isinstance(domains, str):
+        if domains == "node":
+            return [[n] for n in names]
+        by_value: Dict[str, List[str]] = {}
+        for n in nodes:
+            v = (n["metadata"].get("labels") or {}).get(domains)
+            if v is not None:
+                by_value.setdefault(v, []).append(n["metadata"]["name"])
+        if not by_value:
+            raise ValueError(f"sweep_failures: no node carries the label {domains!r}")
+        return list(by_value.values())
+    out = [list(d) for d in domains]
+    known = set(names)
+    for d in out:
+        if not d:
+            raise ValueError("sweep_failures: an empty failure domain")
+        for n in d:
+            if n not in known:
+                raise ValueError(f"sweep_failures: unknown node {n!r} in a failure domain")
+    return out
+
+
+def cluster_without(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], names):
+    """The cluster and apps after the loss of the nodes `names`: without those nodes and without the pods whose spec.nodeName names one of
+    them (they die with the node; the DaemonSet pods of a lost node are never made, simulate() makes them per remaining node)."""
+    gone = set(names)
+    alive = lambda pods: [p for p in pods if (p.get("spec") or {}).get("nodeName") not in gone]   # noqa: E731
+    reduced = dict(cluster, Node=[n for n in cluster.get("Node", []) if n["metadata"]["name"] not in gone])
+    if "Pod" in cluster:
+        reduced["Pod"] = alive(cluster["Pod"])
+    return reduced, [AppResource(a.name, dict(a.resource, Pod=alive(a.resource["Pod"]))) if "Pod" in a.resource else a for a in apps]
+
+
+def _vg_caps(pr: capi.Problem, out) -> Optional[np.ndarray]:
+    if pr.local_flags is None or out.used_vg is None:
+        return None
+    return (pr.local_vg_cap * (np.arange(capi.MAX_VG)[None, :] < pr.local_vg_cnt[:, None])).sum(1)
+
+
+def _failure_result(doms, rows, caps, where, why, batched, fallback) -> FailureSweepResult:
+    """rows[s] = (unscheduled, cpu_pct, mem_pct, vg_pct, needs_reference) of scenario s (0 = the whole cluster)."""
+    ok = [u == 0 and c <= caps[0] and m <= caps[1] and v <= caps[2] for u, c, m, v, _ in rows]
+    base = dict(zip(("unscheduled", "cpu_pct", "mem_pct", "vg_pct", "needs_reference"), rows[0]), survives=ok[0])
+    per = rows[1:]
+    critical = sorted((d for d in range(len(doms)) if not ok[d + 1]), key=lambda d: (-per[d][0], d))
+    return FailureSweepResult(doms, [r[0] for r in per], [r[1] for r in per], [r[2] for r in per], [r[3] for r in per], ok[1:],
+                              [r[4] for r in per], base, critical, where, why, batched, fallback)
+
+
+def _failure_replay(cluster, apps, names, engine) -> List[dict]:
+    """SimulateResult.unscheduled_pods of the cluster without `names`: explain refuses node-subset batches, the scenario's own problem tells."""
+    try:
+        return simulate(*cluster_without(cluster, apps, names), engine=engine).unscheduled_pods
+    except NeedsReference:
+        return []
+
+
+@_gc_paused
+def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], domains="node", engine=None, max_cpu: int = 100,
+                   max_mem: int = 100, max_vg: int = 100, reasons: bool = False, batch_scenarios: int = 4096) -> FailureSweepResult:
+    """The node-failure what-if sweep: does the cluster still hold its workloads when a node, a rack or a zone is lost?  Scenario 0 is
+    the whole cluster; scenario d + 1 is simulate() of the cluster without failure domain d (failure_domains: "node", a label key, or
+    lists of node names), without the pods bound to its nodes and without their DaemonSet pods (cluster_without) -- lost pods are
+    dropped, not rescheduled.  One node-subset engine batch over the cluster's nodes (simon_set_scenario_nodes; batch_scenarios per
+    launch): every node-bound pod is gated on its node, each scenario runs in the nodeTree order of its own nodes.  reasons=True
+    replays the failing scenarios one by one through simulate() for their unscheduled_pods.  Engines without node subsets, clusters
+    whose nodes list the pods' images, apps whose pod list depends on the node set and problems the score-table kernel does not take
+    run every scenario as its own problem (FailureFallbackWarning, batched=False).  A domain that leaves no node: ValueError."""
+    engine = engine or HipEngine()
+    pool = list(cluster.get("Node", []))
+    doms = failure_domains(pool, domains)
+    index = {n["metadata"]["name"]: j for j, n in enumerate(pool)}
+    present = np.ones((len(doms) + 1, len(pool)), bool)
+    for d, names in enumerate(doms):
+        present[d + 1, [index[n] for n in names]] = False
+    if not present.any(axis=1).all():
+        raise ValueError("sweep_failures: a failure domain holds every node of the cluster")
+    caps = _caps(max_cpu, max_mem, max_vg)
+    each = lambda why: _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why)   # noqa: E731
+    if not getattr(engine, "supports_scenario_subsets", False):
+        return each("the engine has no node subsets")
+    pods, gates = build_stream(cluster, apps, pool, 0)
+    if any(a.resource.get("DaemonSet") or any((p.get("spec") or {}).get("nodeName") for p in a.resource.get("Pod", [])) for a in apps):
+        # such an app's pod list depends on the node set, and ScheduleApp's unstable sorts order it by its length (_same_stream): the
+        # batch stands only if every scenario's own stream is the pool's without the pods that die with the domain
+        ref = lambda p: (p["metadata"].get("namespace"), p["metadata"]["name"])                # noqa: E731
+        for names in doms:
+            lost = {index[n] for n in names}
+            mine = [ref(p) for p, g in zip(pods, gates) if g not in lost]
+            cl, ap = cluster_without(cluster, apps, names)
+            if mine != [ref(p) for p in build_stream(cl, ap, cl["Node"], len(cl["Node"]))[0]]:
+                return each("an app holds a DaemonSet or a pod bound to a node, and a scenario's pod order is not the cluster's")
+    for p in pods:
+        if p["spec"].get("nodeName") and p["metadata"].get("ownerReferences"):
+            raise fl.Unsupported(f"workload pod {p['metadata']['name']} is bound to node {p['spec']['nodeName']} by its template")
+    try:
+        flat = fl.flatten(pool, pods, cluster.get("Service", []), cluster.get("ReplicaSet", []), cluster.get("StatefulSet", []), gates,
+                          storage_classes=_storage_classes(cluster, apps))
+    except fl.Unsupported as e:
+        if "ImageLocality" not in str(e):
+            raise
+        return each("nodes list the pods' images: ImageLocality depends on the node set")
+    zid: Dict[str, int] = {}
+    zone = np.array([zid.setdefault(k8s.zone_key(n), len(zid)) for n in pool], np.int32)
+    pr = flat.problem
+    orders = np.arange(len(pods), dtype=np.int32)[None, :]
+    want_gpu = pr.gpu_mem is not None
+    rows, where = [], []
+    for lo in range(0, len(present), max(1, int(batch_scenarios))):
+        part = present[lo:lo + max(1, int(batch_scenarios))]
+        scen = np.stack([part.sum(1), np.zeros(len(part), np.int64)], 1).astype(np.int32)
+        kw = {"want_gpu_slices": True} if want_gpu else {}
+        if len(zid) > capi.MAX_ZONES:            # more zones than the device staging takes: the rank rows travel instead
+            kw["node_ranks"] = mix_node_ranks(pool, part)
+        try:
+            out = engine.run(pr, scen, orders, present=(part, zone if 1 < len(zid) <= capi.MAX_ZONES else None), **kw)
+        except capi.SimonError as e:
+            if getattr(e, "code", None) != capi.ESTATE:
+                raise
+            return each(f"the engine refused the node-subset batch: {e}")
+        vg_cap = _vg_caps(pr, out)
+        ac, am = part @ np.asarray(pr.alloc_cpu, np.int64), part @ np.asarray(pr.alloc_mem, np.int64)
+        av = part @ np.asarray(vg_cap, np.int64) if vg_cap is not None else None
+        for s in range(len(part)):
+            rows.append((int(out.unscheduled[s]), occupancy_pct(int(out.used_cpu[s]), int(ac[s])),
+                         occupancy_pct(int(out.used_mem[s]) * 1000, int(am[s]) * 1000),
+                         occupancy_pct(int(out.used_vg[s]), int(av[s])) if av is not None else 0, _risk(out, s)))
+            where.append((flat, out.placement[s]))
+    why = []
+    if reasons:
+        why = [_failure_replay(cluster, apps, names, engine) if rows[d + 1][0] > 0 else [] for d, names in enumerate(doms)]
+    return _failure_result(doms, rows, caps, where, why, True, None)
+
+
+def _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why: str) -> FailureSweepResult:
+    """Every scenario as its own Simulate(): the cluster without the domain, canonical nodeTree order."""
+    import warnings
+    warnings.warn(f"sweep_failures runs {len(doms) + 1} scenarios one by one ({why})", FailureFallbackWarning, stacklevel=3)
+    rows, where, lists = [], [], []
+    for names in [[]] + doms:
+        cl, ap = cluster_without(cluster, apps, names)
+        nodes = list(cl.get("Node", []))
+        pods, _ = build_stream(cl, ap, nodes, len(nodes))
+        arrival = [n["metadata"]["name"] for n in nodes]
+        nodes = [nodes[j] for j in k8s.canonical_node_order(nodes)]
+        flat = fl.flatten(nodes, pods, cl.get("Service", []), cl.get("ReplicaSet", []), cl.get("StatefulSet", []),
+                          storage_classes=_storage_classes(cl, ap), image_total=len(nodes), node_arrival_order=arrival)
+        pr = flat.problem
+        out = engine.run(pr, np.array([[len(nodes), 0]], np.int32), np.arange(len(pods), dtype=np.int32)[None, :],
+                         **({"want_gpu_slices": True} if pr.gpu_mem is not None else {}))
+        vg_cap = _vg_caps(pr, out)
+        rows.append((int(out.unscheduled[0]), occupancy_pct(int(out.used_cpu[0]), int(pr.alloc_cpu.sum())),
+                     occupancy_pct(int(out.used_mem[0]) * 1000, int(pr.alloc_mem.sum()) * 1000),
+                     occupancy_pct(int(out.used_vg[0]), int(vg_cap.sum())) if vg_cap is not None else 0, _risk(out, 0)))
+        where.append((flat, out.placement[0]))
+        if reasons and names:
+            lists.append(_failure_replay(cluster, apps, names, engine) if rows[-1][0] > 0 else [])
+    return _failure_result(doms, rows, caps, where, lists, False, why)
 
 
 def load_config(path: str, base_dir: str = ".") -> dict:
