@@ -538,7 +538,7 @@ EXPORTS = [
     "simon_set_scalar_entries", "simon_set_pod_priorities", "simon_fetch_preempt_risk",
     "simon_group_set_scalar_entries", "simon_group_set_pod_priorities", "simon_group_fetch_preempt_risk",
     "simon_set_image_locality", "simon_group_set_image_locality",
-    "simon_set_scenario_segments", "simon_set_scenario_nodes", "simon_fetch_node_ranks",
+    "simon_set_scenario_segments", "simon_set_scenario_nodes", "simon_fetch_node_ranks", "simon_set_pod_eviction",
     "simon_group_create", "simon_group_destroy", "simon_group_last_error", "simon_group_size", "simon_group_member",
     "simon_group_load_nodes", "simon_group_load_pods", "simon_group_load_class_tables", "simon_group_load_scenarios",
     "simon_group_run_loaded", "simon_group_fetch_results", "simon_group_run_batch", "simon_group_fetch_placement", "simon_group_fetch_gpu_slices",
@@ -580,6 +580,8 @@ def load_library(path: Optional[str] = None):
     lib.simon_set_scenario_nodes.argtypes = [vp, C.POINTER(C.c_uint32), _p32, C.c_int32]
     lib.simon_set_scenario_nodes.restype = C.c_int
     lib.simon_fetch_node_ranks.argtypes = [vp, _p32]
+    lib.simon_set_pod_eviction.argtypes = [vp, C.POINTER(C.c_uint8)]
+    lib.simon_set_pod_eviction.restype = C.c_int
     lib.simon_min_plan.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(Plan)]
     lib.simon_min_plan_vg.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Plan), C.POINTER(C.c_int32)]
     lib.simon_explain.argtypes = [vp, Scenario, _p32, _p32, _pu16, C.c_int32]
@@ -811,6 +813,17 @@ class Context:
         self._check(self.lib.simon_set_scenario_nodes(self.h, _ptr(words, C.c_uint32), _ptr(z, C.c_int32),
                                                        int(z.max(initial=0)) + 1 if n_zones is None else int(n_zones)),
                     "simon_set_scenario_nodes")
+
+    def set_pod_eviction(self, evict) -> None:
+        """evict bool [P]: the preset pods that a node-subset batch schedules like fresh pods in the scenarios that lack their node
+        (include/simon_hip.h: simon_set_pod_eviction).  After load_problem, before set_scenario_nodes; None detaches."""
+        if evict is None:
+            self._check(self.lib.simon_set_pod_eviction(self.h, None), "simon_set_pod_eviction")
+            return
+        e = np.ascontiguousarray(np.asarray(evict) != 0, dtype=np.uint8)
+        if e.shape != (self.problem.n_pods,):
+            raise ValueError(f"evict has shape {e.shape}, the problem {self.problem.n_pods} pods")
+        self._check(self.lib.simon_set_pod_eviction(self.h, _ptr(e, C.c_uint8)), "simon_set_pod_eviction")
 
     def fetch_node_ranks(self) -> np.ndarray:
         """[S][N] the rank rows in effect (nodes a segmented / node-subset scenario lacks: N); SIMON_ESTATE for a batch without rows."""

@@ -196,6 +196,10 @@ struct simon_ctx : simon::HostInputs {
     std::vector<int32_t> sub_zone;
     DevBuf<uint32_t> d_sub_words;
     DevBuf<int32_t> d_sub_zone;
+    // simon_set_pod_eviction: p_evict [P] (empty: none) flags preset pods that a node-subset scenario without their node schedules like
+    // any other pod.  evict_short: a flagged pod whose node the loaded PREFIX batch lacks (-1: none) -- such a batch waits for its node rows
+    std::vector<uint8_t> p_evict;
+    int evict_short = -1;
     bool orders_perm = false;                     // every loaded order is a permutation of [0, P) (the score-table kernel's placement gather)
     std::vector<int64_t> prefix_cpu, prefix_mem;   // [N+1] allocatable of the first n nodes
     std::vector<int64_t> prefix_vg;   // [N+1] Open-Local VG capacity of the first n nodes (0 without local storage)
@@ -434,7 +438,7 @@ bool rest_supported(simon_ctx* c) {
                 key.push_back(q); any = any || q != 0;
             }
             if (!any) continue;
-            if (c->p_preset[p] >= 0) return false;
+            if (c->p_preset[p] >= 0) return false;                // (flagged for eviction or not: where its node is present the pod is bound there)
             g = gcd_u64(g, (uint64_t)c->p_req_eph[p]);
             sigs.insert(key);
             if ((int)sigs.size() > kTableMaxXres) return false;
@@ -550,7 +554,8 @@ bool spread_supported(simon_ctx* c) {
     if (!c->ss_idx.empty() && c->spread_log.size() < (size_t)c->N + 1) return false;
     int64_t max_pods = 0;
     // the per-position counters are bytes.  Pods that pass NodeResourcesFit number at most alloc_pods on a node; pods bound by
-    // Spec.NodeName (presets) skip the filters (V/eventhandlers.go:223-236) and come on top
+    // Spec.NodeName (presets) skip the filters (V/eventhandlers.go:223-236) and come on top.  (A pod flagged for eviction counts on its
+    // preset node where it is bound and among the alloc_pods of the node it is scheduled to where it is not: the bound holds for both.)
     {
         std::vector<int32_t> preset_on(c->N, 0);
         for (int p = 0; p < c->P && !c->p_preset.empty(); ++p)
@@ -1746,6 +1751,7 @@ int simon_load_pods(simon_ctx* c, const simon_pods_soa* pd) {
         c->has_pin = c->has_pin || c->p_pin[p] >= 0;
     }
     c->p_entries.clear(); c->p_priority.clear(); c->init_min_priority = 0x7fffffff;   // (ABI v6 additions: set after the pods)
+    c->p_evict.clear(); c->evict_short = -1;
     c->have_pods = true; c->staged = false; c->have_results = false;
     return SIMON_OK;
 }
@@ -1762,6 +1768,22 @@ int simon_set_scalar_entries(simon_ctx* c, const uint8_t* entries) {
         }
     } else c->p_entries.clear();
     c->staged = false; c->wide_staged = false; c->have_results = false;
+    return SIMON_OK;
+}
+
+static inline bool evicted_pod(const simon_ctx* c, int p) { return !c->p_evict.empty() && c->p_evict[p] != 0; }
+
+int simon_set_pod_eviction(simon_ctx* c, const uint8_t* evict) {
+    if (!c) return SIMON_EINVAL;
+    if (!c->have_pods) return fail(c, SIMON_ESTATE, "set_pod_eviction: load pods first");
+    if (c->seg_n > 0 || c->sub_on) return fail(c, SIMON_ESTATE, "set_pod_eviction: a %s batch is in effect; set the flags before simon_set_scenario_nodes", c->sub_on ? "node-subset" : "segmented");
+    if (!evict) { c->p_evict.clear(); return SIMON_OK; }
+    for (int p = 0; p < c->P; ++p) {
+        if (!evict[p]) continue;
+        if (c->p_preset[p] < 0) return fail(c, SIMON_EINVAL, "set_pod_eviction: pod %d is flagged but not preset to a node", p);
+        if (c->p_gate[p] != -1) return fail(c, SIMON_EINVAL, "set_pod_eviction: pod %d is flagged and gated on node %d (a gated pod vanishes with its node)", p, c->p_gate[p]);
+    }
+    c->p_evict.assign(evict, evict + c->P);
     return SIMON_OK;
 }
 
@@ -2045,9 +2067,14 @@ int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, co
         if (orders[i] < 0 || orders[i] >= P) return fail(c, SIMON_EINVAL, "orders[%zu] = %d is not a pod id", i, orders[i]);
     int min_n = c->N;
     for (int s = 0; s < S; ++s) min_n = std::min(min_n, scen[s].n_nodes);
+    // (a pod flagged for eviction may lack its node in a node-subset batch, whose rows arrive after this call: evict_short holds the batch
+    // back until they have -- simon_run_loaded)
+    c->evict_short = -1;
     for (int p = 0; p < P; ++p)
-        if (c->p_preset[p] >= 0 && c->p_preset[p] >= min_n && c->p_gate[p] < c->p_preset[p])
+        if (c->p_preset[p] >= 0 && c->p_preset[p] >= min_n && c->p_gate[p] < c->p_preset[p]) {
+            if (evicted_pod(c, p)) { if (c->evict_short < 0) c->evict_short = p; continue; }
             return fail(c, SIMON_EINVAL, "pod %d is preset to node %d which a %d-node scenario lacks (gate it)", p, c->p_preset[p], min_n);
+        }
     // LPT launch order: biggest scenarios first (cost ~ ceil(n / T) per pod)
     std::vector<int32_t> perm(S);
     std::iota(perm.begin(), perm.end(), 0);
@@ -2361,11 +2388,12 @@ int simon_set_scenario_nodes(simon_ctx* c, const uint32_t* present, const int32_
     }
     auto always = [&](int j) { return (every[j >> 5] >> (j & 31)) & 1u; };
     // a node that some scenario lacks starts empty there: pods bound before the stream would need it in every scenario; a pod preset to
-    // it has to vanish with it (gated on that same node)
+    // it has to vanish with it (gated on that same node) or be flagged for eviction (simon_set_pod_eviction: scheduled where the node is
+    // absent).  The score-table kernel relies on this: "preset, not gated on it, node absent" is a flagged pod, it reads no flag array.
     for (int j = 0; j < N; ++j)
         if (!always(j) && node_busy(c, j)) return seg_abandon(c, fail(c, SIMON_EINVAL, "set_scenario_nodes: node %d, absent from some scenario, carries pods bound before the stream", j));
     for (int p = 0; p < c->P; ++p)
-        if (c->p_preset[p] >= 0 && !always(c->p_preset[p]) && c->p_gate[p] != c->p_preset[p])
+        if (c->p_preset[p] >= 0 && !always(c->p_preset[p]) && c->p_gate[p] != c->p_preset[p] && !evicted_pod(c, p))
             return seg_abandon(c, fail(c, SIMON_EINVAL, "set_scenario_nodes: pod %d is preset to node %d, absent from some scenario, and not gated on it", p, c->p_preset[p]));
     HIP_TRY(c, hipSetDevice(c->device));
     c->seg_n = 0; c->sub_on = true; c->sub_W = W;                    // (a node-subset batch replaces segments)
@@ -2644,6 +2672,8 @@ static int run_narrow_batch(simon_ctx* c, const BatchRoute& r, bool want_placeme
 int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
     if (!c) return SIMON_EINVAL;
     if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "run_loaded: no scenarios loaded");
+    if (c->evict_short >= 0 && !c->sub_on)   // (the prefix rule of simon_load_scenarios, deferred for flagged pods)
+        return fail(c, SIMON_ESTATE, "run_loaded: pod %d, flagged for eviction, is preset to node %d which a scenario of this prefix batch lacks; set the batch's node rows (simon_set_scenario_nodes)", c->evict_short, c->p_preset[c->evict_short]);
     HIP_TRY(c, hipSetDevice(c->device));
     const int S = c->S, P = c->P;
     // bit 1: also record the devices Reserve books for every placed GPU pod (only problems with GPU requests have any)
@@ -2889,6 +2919,7 @@ int simon_explain_loaded(simon_ctx* c, int32_t scenario, int32_t* failed_pods, u
     if (scenario < 0 || scenario >= c->S) return fail(c, SIMON_EINVAL, "explain_loaded: scenario %d outside [0,%d)", scenario, c->S);
     if (own_nodes(c))    // the replay runs on the all-feature kernel, which takes prefix scenarios only
         return fail(c, SIMON_ESTATE, "explain_loaded: %s batch; explain the scenario's own problem (its nodes alone)", own_kind(c));
+    if (c->evict_short >= 0) return fail(c, SIMON_ESTATE, "explain_loaded: pod %d, flagged for eviction, lacks its node in this prefix batch", c->evict_short);
     return explain_impl(c, c->scen[scenario].n_nodes, nullptr, scenario, failed_pods, fail_codes, max_failed);
 }
 
@@ -2900,6 +2931,7 @@ int simon_explain_batch(simon_ctx* c, const int32_t* scenarios, int32_t n_scen, 
     if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "explain_batch: no scenarios loaded");
     if (own_nodes(c))    // the replay runs on the all-feature kernel, which takes prefix scenarios only
         return fail(c, SIMON_ESTATE, "explain_batch: %s batch; explain each scenario's own problem (its nodes alone)", own_kind(c));
+    if (c->evict_short >= 0) return fail(c, SIMON_ESTATE, "explain_batch: pod %d, flagged for eviction, lacks its node in this prefix batch", c->evict_short);
     const bool image = c->img_R > 0 && !c->img_sizes.empty();
     std::vector<WideScenario> hs((size_t)n_scen);
     std::vector<int32_t> slots(image ? (size_t)n_scen : 0);

@@ -1996,7 +1996,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         const PodRowC r = pods[order[idx]];
         // (segmented: the gate node is absent iff its rank is N -- one gather per chunk, only for gated pods of a segmented batch)
         const bool gated_out = segd ? (r.gate >= 0 && gp(cold->rk_rank)[(size_t)s * (size_t)cold->N + r.gate] >= n) : r.gate >= n;
-        const bool special = gated_out || r.preset != -1;
+        bool special = gated_out || r.preset != -1;
+        // A pod flagged for eviction (simon_set_pod_eviction) in a scenario that lacks its node is scheduled like any other pod
+        // (scheduleOne instead of addPodToCache): the special bit goes, the pod takes the plain / REST / SPREAD path of its signature,
+        // decided here for every wave of a team alike.  No flag array: in an own-nodes batch the validators leave "preset, not gated
+        // out, node absent" to flagged pods alone (simon_set_scenario_nodes; a segment node is never a preset target).
+        if (segd && r.preset >= 0 && !gated_out && gp(cold->rk_rank)[(size_t)s * (size_t)cold->N + r.preset] >= n) special = false;
         return make_int4(r.sigcls | (special ? (int)0x80000000 : 0), r.preset, r.gate, r.rest);
     };
     int4 nxt = load_chunk(0);
