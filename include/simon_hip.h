@@ -404,8 +404,8 @@ int simon_set_node_ranks(simon_ctx* ctx, const int32_t* rank /* [S][N] */);
  * (no fixed nodes, every count 0), n_seg > SIMON_MAX_SEGMENTS, a segment node with pods bound before the
  * stream (init_*) or the target of a preset pod.  SIMON_ESTATE: ImageLocality in effect (simon_set_image_locality).  A segmented batch
  * runs on the score-table kernel only: simon_run_loaded refuses (SIMON_ESTATE) a problem that needs the all-feature kernel, and
- * simon_explain / simon_explain_loaded refuse while one is loaded -- replay the scenario's own problem instead.  A call that fails
- * leaves the batch a prefix batch. */
+ * simon_explain / simon_explain_loaded / simon_explain_batch refuse while one is loaded -- simon_explain_own_batch explains its
+ * scenarios.  A call that fails leaves the batch a prefix batch. */
 #define SIMON_MAX_SEGMENTS 8
 int simon_set_scenario_segments(simon_ctx* ctx, int32_t n_seg, const int32_t* seg_start, const int32_t* count /* [S][n_seg] */);
 
@@ -425,7 +425,8 @@ int simon_set_scenario_segments(simon_ctx* ctx, int32_t n_seg, const int32_t* se
  * stream (init_*) or is the preset target of a pod neither gated on it nor flagged (simon_set_pod_eviction).  SIMON_ESTATE: nothing loaded, ImageLocality in effect.  A call that
  * fails leaves the batch a prefix batch.  Like a segmented batch it runs on the score-table kernel only: simon_run_loaded refuses
  * (SIMON_ESTATE, "node-subset batch") a problem that needs the all-feature kernel, and simon_explain / simon_explain_loaded /
- * simon_explain_batch refuse while one is loaded.  The per-scenario arrays are built on the device from the presence words
+ * simon_explain_batch refuse while one is loaded (simon_explain_own_batch explains its scenarios).  The per-scenario arrays are built on
+ * the device from the presence words
  * (env SIMON_SUBSET_STAGE=host: in host loops, read once in simon_ctx_create). */
 #define SIMON_MAX_ZONES 64
 int simon_set_scenario_nodes(simon_ctx* ctx, const uint32_t* present /* [S][(N+31)/32], node j = bit (j & 31) of word j >> 5 */,
@@ -561,6 +562,24 @@ int simon_explain_batch(simon_ctx* ctx, const int32_t* scenarios, int32_t n_scen
                         int32_t* n_bins        /* [n_scen][max_failed] distinct codes (may exceed max_bins), -1 = more than SIMON_EXPLAIN_BINS */,
                         simon_fail_bin* bins   /* [n_scen][max_failed][max_bins], ascending code */,
                         uint16_t* fail_codes   /* NULL, or [n_scen][max_failed][code_stride] full rows */, int32_t code_stride);
+
+/* simon_explain_batch for a SEGMENTED or NODE-SUBSET batch (simon_set_scenario_segments / simon_set_scenario_nodes): the listed
+ * scenarios replayed in one launch, each over its own node set.  Arguments and buffer shapes are simon_explain_batch's, except:
+ *  - valid only while such a batch is loaded; a prefix batch gets SIMON_ESTATE ("use simon_explain_batch");
+ *  - code rows are indexed by POOL node, so code_stride >= N (the pool size) is required.  Nodes a scenario lacks read 0
+ *    (SIMON_FAIL_NONE); no node it holds reads 0 in the row of a failed pod;
+ *  - bins count the scenario's own nodes only: a recorded pod's counts sum to the scenario's n_nodes;
+ *  - the replay uses the rank rows in effect -- the batch's own or simon_set_node_ranks' -- so ties break as the run broke them; a pod
+ *    flagged with simon_set_pod_eviction whose node the scenario lacks is scheduled like a fresh pod, as the run does;
+ *  - it needs no prior simon_run_loaded and disturbs neither the loaded batch nor its results.
+ * SIMON_ESTATE also where simon_run_loaded would refuse the batch: a problem whose route is the all-feature kernel (env
+ * SIMON_FORCE_WIDE=1 included).  SIMON_EINVAL: an index outside the batch, bad sizes (as simon_explain_batch), code_stride < N with
+ * fail_codes given.  simon_explain / simon_explain_loaded / simon_explain_batch keep refusing such batches.
+ * Not covered: no simon_group_* forward and no Go shim; no Open-Local sizes and no ImageLocality (neither occurs in such a batch).
+ * (additive: the ABI stays 7) */
+int simon_explain_own_batch(simon_ctx* ctx, const int32_t* scenarios, int32_t n_scen, int32_t max_failed, int32_t max_bins,
+                            int32_t* n_failed, int32_t* failed_pods, int32_t* n_bins, simon_fail_bin* bins,
+                            uint16_t* fail_codes /* may be NULL */, int32_t code_stride);
 
 int simon_get_stats(simon_ctx* ctx, simon_stats* stats);
 

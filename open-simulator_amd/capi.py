@@ -535,6 +535,7 @@ EXPORTS = [
     "simon_load_nodes", "simon_load_pods", "simon_load_class_tables", "simon_load_scenarios", "simon_run_loaded",
     "simon_fetch_results", "simon_fetch_placement", "simon_fetch_gpu_slices", "simon_run_batch", "simon_min_plan", "simon_min_plan_vg", "simon_min_plan_device", "simon_explain", "simon_set_node_ranks",
     "simon_get_stats", "simon_device_results", "simon_explain_loaded", "simon_explain_local_detail", "simon_explain_batch",
+    "simon_explain_own_batch",
     "simon_set_scalar_entries", "simon_set_pod_priorities", "simon_fetch_preempt_risk",
     "simon_group_set_scalar_entries", "simon_group_set_pod_priorities", "simon_group_fetch_preempt_risk",
     "simon_set_image_locality", "simon_group_set_image_locality",
@@ -588,6 +589,7 @@ def load_library(path: Optional[str] = None):
     lib.simon_explain_loaded.argtypes = [vp, C.c_int32, _p32, _pu16, C.c_int32]
     lib.simon_explain_local_detail.argtypes = [vp, _p64, C.c_int32]
     lib.simon_explain_batch.argtypes = [vp, _p32, C.c_int32, C.c_int32, C.c_int32, _p32, _p32, _p32, C.c_void_p, _pu16, C.c_int32]
+    lib.simon_explain_own_batch.argtypes = lib.simon_explain_batch.argtypes
     _pu8 = C.POINTER(C.c_uint8)
     for pre in ("simon_", "simon_group_"):
         getattr(lib, pre + "set_scalar_entries").argtypes = [vp, _pu8]
@@ -887,6 +889,22 @@ class Context:
                                                  _ptr(codes, C.c_uint16), stride), "simon_explain_batch")
         n_nodes = self.scen[idx, 0].astype(np.int32)
         return ExplainBatch(idx, n_nodes, n_failed, failed, n_bins, bins, codes)
+
+    def explain_own_batch(self, scenarios, max_failed: int = 64, max_bins: int = 32, rows: bool = False) -> "ExplainBatch":
+        """simon_explain_own_batch: explain_batch for the loaded segmented / node-subset batch.  Bins count each scenario's own nodes; with
+        rows=True the code rows are [k][max_failed][N], indexed by POOL node, 0 on the nodes a scenario lacks."""
+        idx = np.ascontiguousarray(scenarios, dtype=np.int32).reshape(-1)
+        k, mf, mb = len(idx), max(int(max_failed), 0), max(int(max_bins), 0)
+        stride = self.problem.n_nodes if rows else 0
+        n_failed = np.zeros(k, np.int32)
+        failed = np.zeros((k, mf), np.int32)
+        n_bins = np.zeros((k, mf), np.int32)
+        bins = np.zeros((k, mf, mb), FAIL_BIN_DTYPE)
+        codes = np.zeros((k, mf, stride), np.uint16) if rows else None
+        self._check(self.lib.simon_explain_own_batch(self.h, _ptr(idx, C.c_int32), k, int(max_failed), int(max_bins), _ptr(n_failed, C.c_int32),
+                                                     _ptr(failed, C.c_int32), _ptr(n_bins, C.c_int32), bins.ctypes.data_as(C.c_void_p),
+                                                     _ptr(codes, C.c_uint16), stride), "simon_explain_own_batch")
+        return ExplainBatch(idx, self.scen[idx, 0].astype(np.int32), n_failed, failed, n_bins, bins, codes)
 
     def explain_local_detail(self, n_failed: int, n_nodes: int) -> Optional[np.ndarray]:
         """simon_explain_local_detail after explain / explain_loaded: [n_failed][n_nodes][4] int64 {LOCAL_ERR_*, a, b, c} -- what

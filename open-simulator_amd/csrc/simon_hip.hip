@@ -2955,6 +2955,36 @@ int simon_explain_batch(simon_ctx* c, const int32_t* scenarios, int32_t n_scen, 
     return wide_replay(c->wide, *c, job, wide_workgroup(c, n_scen, max_n), c->stream, c->err);
 }
 
+// simon_explain_batch for segmented and node-subset batches: the replay in its own-nodes mode (simon_wide.h: kArgOwn), where a scenario
+// holds the pool nodes that its rank row -- the batch's own or the caller's -- ranks below N.  Everything the launch sizes by a node count is
+// sized by the pool; code rows are indexed by pool node.  The route decision is simon_run_loaded's: what that refuses, this refuses.
+int simon_explain_own_batch(simon_ctx* c, const int32_t* scenarios, int32_t n_scen, int32_t max_failed, int32_t max_bins, int32_t* n_failed,
+                            int32_t* failed_pods, int32_t* n_bins, simon_fail_bin* bins, uint16_t* fail_codes, int32_t code_stride) {
+    if (!c) return SIMON_EINVAL;
+    if (!scenarios || n_scen <= 0 || max_failed <= 0 || max_bins < 1 || max_bins > SIMON_EXPLAIN_BINS || !n_failed || !failed_pods || !n_bins || !bins)
+        return fail(c, SIMON_EINVAL, "explain_own_batch: bad arguments");
+    if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "explain_own_batch: no scenarios loaded");
+    if (!own_nodes(c)) return fail(c, SIMON_ESTATE, "explain_own_batch: prefix batch; use simon_explain_batch");
+    if (!c->has_ranks || route_batch(c).kernel == SIMON_KERNEL_WIDE)     // (the batch simon_run_loaded refuses: its pods' gates and presets were never checked against a run)
+        return fail(c, SIMON_ESTATE, "explain_own_batch: %s batch on a problem the score-table kernel does not take; explain each scenario's own problem", own_kind(c));
+    const int N = c->N;
+    std::vector<WideScenario> hs((size_t)n_scen);
+    for (int k = 0; k < n_scen; ++k) {
+        if (scenarios[k] < 0 || scenarios[k] >= c->S) return fail(c, SIMON_EINVAL, "explain_own_batch: scenario %d outside [0,%d)", scenarios[k], c->S);
+        hs[k] = WideScenario{c->scen[scenarios[k]].n_nodes, c->scen[scenarios[k]].order_id};
+    }
+    if (fail_codes && code_stride < N) return fail(c, SIMON_EINVAL, "explain_own_batch: code_stride %d below the pool's %d nodes (rows are indexed by pool node)", code_stride, N);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = ensure_wide_staged(c)) return rc;   // (the batch runs on the score-table kernel: the failure codes come from the all-feature kernel)
+    WideReplay job;
+    job.scen = hs.data(); job.S = n_scen; job.max_n = N; job.d_orders = c->d_orders.p; job.own = true;
+    job.rank_row = scenarios; job.d_node_rank = c->d_node_rank.p; job.d_node_inv = c->d_node_inv.p;
+    job.max_failed = max_failed; job.n_failed = n_failed; job.failed_pods = failed_pods;
+    job.max_bins = max_bins; job.n_bins = n_bins; job.bins = bins;
+    job.fail_codes = fail_codes; job.code_stride = code_stride;
+    return wide_replay(c->wide, *c, job, wide_workgroup(c, n_scen, N), c->stream, c->err);
+}
+
 int simon_get_stats(simon_ctx* c, simon_stats* st) {
     if (!c || !st) return SIMON_EINVAL;
     *st = c->stats;

@@ -186,6 +186,10 @@ struct WideCold {
     // codes, -1 beyond SIMON_EXPLAIN_BINS.  bins == null: no histogram.  The single-scenario replay is k = 0 with code_stride = n_nodes.
     int32_t code_stride, max_bins;
     simon_fail_bin* bins; int32_t* n_bins;
+    // own-nodes replay (kArgOwn, simon_explain_own_batch): own_reg[k][e * own_reg_R + d] != 0 = some node of the launch's scenario k lies in
+    // hard spread constraint e's node set and in domain d of its key ("registered", TpPairToMatchNum); written by the kernel's prologue
+    // over zeros.  Appended: the offsets of the fields above are those every other instantiation was built with.
+    uint8_t* own_reg; int32_t own_reg_R, own_reg_E /*domains per key at most; hard spread constraints*/;
 };
 
 struct WideArgs {
@@ -218,7 +222,10 @@ constexpr uint32_t kArgGpu = 1u, kArgMask = 2u, kArgEph = 4u, kArgNzeq = 8u, kAr
                    // staged in LDS all the same when they fit (round 6: per feasible node they were up to seven dependent FLAT loads)
                    kArgRowsLds = 65536u,
                    // ABI v7: ImageLocality scores per (size slot of the scenario, pod class, node class), added to the class term
-                   kArgImage = 131072u;
+                   kArgImage = 131072u,
+                   // simon_explain_own_batch: a scenario holds pool node j iff its rank row says node_rank[j] < N (segmented / node-subset
+                   // batches), not the prefix j < n_nodes.  Honoured by the EXPLAIN form of the full variant alone (wide_kernel: kCanOwn)
+                   kArgOwn = 262144u;
 
 // tuning / experiment knobs: environment variables read ONCE, when the context is created (simon_ctx_create)
 struct WideKnobs {
@@ -309,6 +316,9 @@ struct WideReplay {
     int32_t max_bins = 0; int32_t* n_bins = nullptr; simon_fail_bin* bins = nullptr;   // [S][max_failed]([max_bins]); bins == null: no histogram
     uint16_t* fail_codes = nullptr; int32_t code_stride = 0;                         // [S][max_failed][code_stride], or null
     std::vector<int64_t>* detail = nullptr;   // Open-Local's error sizes [recorded][n_nodes][4]: one scenario only, with recorded_only
+    // own-nodes replay (simon_explain_own_batch): the listed scenarios hold the pool nodes their rank rows rank below N.  The rank rows are
+    // required, max_n is the pool size (LDS words, code rows and the workgroup are sized by it) and code rows are indexed by pool node.
+    bool own = false;
 };
 int wide_replay(WideDevice& w, const HostInputs& in, const WideReplay& job, int T, hipStream_t st, std::string& err);
 

@@ -497,8 +497,9 @@ __device__ __forceinline__ bool ports_conflict(const WideArgs& A, const NodeView
 // The filters after NodeResourcesFit, in registry order (registry.go:87-104 + pkg/simulator/utils.go:321-333):
 // PodTopologySpread, InterPodAffinity, Open-Gpu-Share.  Each returns a SIMON_FAIL_* code (0 = pass).
 // head_code: PodTopologySpread.Filter + the required-affinity half of InterPodAffinity.Filter.
+// own_reg != null (own-nodes replay, kArgOwn): the scenario's registered flags [constraint][domain] replace the prefix rule.
 __device__ __forceinline__ unsigned head_code(const WideArgs& A, const NodeView& v, const WidePod& p, int j, int n,
-                                              const Hard4& hard_min) {
+                                              const Hard4& hard_min, const uint8_t* own_reg = nullptr) {
     const int N = A.N;
     // PodTopologySpread.Filter, podtopologyspread/filtering.go:283-333
     if (p.flags & kPodHard) {
@@ -507,7 +508,8 @@ __device__ __forceinline__ unsigned head_code(const WideArgs& A, const NodeView&
             const int t = COLD(A)->sh_idx[e];
             const int d = term_dom(A, t, j);
             if (d < 0) return SIMON_FAIL_SPREAD_LABEL;
-            const bool registered = COLD(A)->sh_first_reg[(size_t)e * N + j] < n;        // TpPairToMatchNum has the pair (:321-324)
+            const bool registered = own_reg ? own_reg[(size_t)e * COLD(A)->own_reg_R + d] != 0      // TpPairToMatchNum has the pair (:321-324)
+                                            : COLD(A)->sh_first_reg[(size_t)e * N + j] < n;
             const long long match = registered ? v.cnt_match()[COLD(A)->term_dom_off[t] + d] : 0;
             const long long skew = match + (COLD(A)->sh_self[e] ? 1 : 0) - sel4(hard_min, e - lo);
             if (skew > COLD(A)->sh_skew[e]) return SIMON_FAIL_SPREAD;
@@ -533,8 +535,8 @@ __device__ __forceinline__ unsigned head_code(const WideArgs& A, const NodeView&
 }
 
 __device__ __forceinline__ unsigned rest_code(const WideArgs& A, const NodeView& v, const WidePod& p, int j, int n,
-                                              const Hard4& hard_min) {
-    const unsigned h = head_code(A, v, p, j, n, hard_min);
+                                              const Hard4& hard_min, const uint8_t* own_reg = nullptr) {
+    const unsigned h = head_code(A, v, p, j, n, hard_min, own_reg);
     if (h) return h;
     // incoming anti-affinity (filtering.go:334-346), then existing pods' anti-affinity (:319-332; only terms some class owns
     // as required anti-affinity can have owners: the trimmed list)
@@ -565,14 +567,14 @@ __device__ __forceinline__ unsigned rest_code(const WideArgs& A, const NodeView&
 
 // One (pod, node) filter evaluation in plugin order with early exit (V/framework/runtime/framework.go:527-552).
 __device__ __forceinline__ unsigned filter_code(const WideArgs& A, const NodeView& v, const WidePod& p, int j, int n,
-                                                const NodeLoads& L, bool mask_ok, const Hard4& hard_min) {
+                                                const NodeLoads& L, bool mask_ok, const Hard4& hard_min, const uint8_t* own_reg = nullptr) {
     const unsigned fit = fit_bits(A, p, L, load_extra(A, v, j));
     // NodeUnschedulable / NodeName / TaintToleration / NodeAffinity come first in filter order
     if (!mask_ok) return SIMON_FAIL_STATIC | (COLD(A)->static_reason ? COLD(A)->static_reason[(size_t)p.cls * A.N + j] : 0u);
     if (p.pin >= 0 && j != p.pin) return SIMON_FAIL_STATIC | SIMON_REASON_NODE_AFFINITY;   // pinned pod: NodeAffinity fails elsewhere
     if ((p.flags & kPodPorts) && ports_conflict(A, v, p, j)) return SIMON_FAIL_PORTS;
     if (fit) return SIMON_FAIL_FIT | fit;
-    return rest_code(A, v, p, j, n, hard_min);
+    return rest_code(A, v, p, j, n, hard_min, own_reg);
 }
 
 // InterPodAffinity.Score raw value (interpodaffinity/scoring.go:87-131,211-236) and PodTopologySpread.Score raw value
@@ -680,8 +682,12 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int s = blockIdx.x;
-    const int n = A.scen[s].n_nodes;
     const int N = A.N, P = A.P, K = A.K, Cn = A.Cn;
+    // Own-nodes replay (kArgOwn, simon_explain_own_batch): the scenario holds pool node j iff its rank row says so, and every node loop
+    // runs over the pool.  Only the EXPLAIN form of the full variant honours the flag; everywhere else `own` is a constant.
+    constexpr bool kCanOwn = EXPLAIN && VAR == 1;
+    const bool own = kCanOwn && (A.flags & kArgOwn) != 0u;
+    const int n = own ? N : A.scen[s].n_nodes;
     if (((A.flags & kArgClassMode) != 0u) && Cn <= 8)
         for (int c = 0; c < Cn; ++c) s_kc[c * T + tid] = 0u;
     const int32_t* order = A.orders + (size_t)A.scen[s].order_id * P;
@@ -732,6 +738,29 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
     }
     for (int i = tid; i < cnt_stride; i += T) v.cnt_match()[i] = 0;
     for (int i = tid; i < COLD(A)->seen_stride; i += T) v.seen()[i] = 0;
+    // own: this lane's presence bits (bit it = node tid + it*T, mask_lanes' layout), and the scenario's "registered" flags of the hard
+    // spread constraints -- some PRESENT node of constraint e's node set lies in domain d -- set over the host's zeros; the barrier
+    // below publishes them.  absent(j): an arbitrary pool node (a pod's gate / preset), from the rank row.
+    unsigned pres = 0xFFFFFFFFu;
+    const uint8_t* own_reg = nullptr;
+    auto absent = [&](int j) -> bool { return COLD(A)->node_rank[(size_t)(A.scen_base + s) * N + j] >= N; };
+    if constexpr (kCanOwn) {
+        if (own) {
+            const int E = COLD(A)->own_reg_E, R = COLD(A)->own_reg_R;
+            uint8_t* const reg = COLD(A)->own_reg + (size_t)(A.scen_base + s) * E * R;
+            pres = 0u;
+            for (int j = tid, it = 0; j < N; j += T, ++it) {
+                if (absent(j)) continue;
+                pres |= 1u << it;
+                for (int e = 0; e < E; ++e) {
+                    if (!in_set(A, COLD(A)->sh_set[e], j)) continue;
+                    const int d = term_dom(A, COLD(A)->sh_idx[e], j);
+                    if (d >= 0 && d < R) reg[(size_t)e * R + d] = 1;
+                }
+            }
+            own_reg = reg;
+        }
+    }
     __syncthreads();
     if (use_tab) {
         for (int j = tid; j < n; j += T) {
@@ -769,7 +798,10 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
         if (VAR == 0) p.flags &= (kPodZero | kPodTerms | kPodFilt);
         if (kProfile && (A.flags & kArgProf) && p.cls < 0) continue;   // forces the pod row to have arrived before the timestamp
         SIMON_PROF(0);
-        if (p.gate >= n) { if (place && tid == 0) place[pid] = SIMON_GATED; continue; }
+        if ((kCanOwn && own) ? (p.gate >= 0 && absent(p.gate)) : p.gate >= n) { if (place && tid == 0) place[pid] = SIMON_GATED; continue; }
+        // own: "preset, not gated out, node absent" is a pod flagged for eviction (simon_set_scenario_nodes' validator leaves nobody else):
+        // scheduled like a fresh pod, as the score-table kernel's load_chunk does
+        if (kCanOwn && own && p.preset >= 0 && absent(p.preset)) p.preset = -1;
         int jstar;
         if (p.preset >= 0) {
             jstar = p.preset;
@@ -842,7 +874,8 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
                 const int lo = COLD(A)->sh_off[p.cls], cnt = COLD(A)->sh_off[p.cls + 1] - lo;
 #pragma unroll
                 for (int k = 0; k < kRed; ++k) r[k] = -(long long)INT_MAX;             // newCriticalPaths: math.MaxInt32
-                for (int j = tid; j < n; j += T) {
+                for (int j = tid, it = 0; j < n; j += T, ++it) {
+                    if (kCanOwn && own && !((pres >> it) & 1u)) continue;               // (a node the scenario lacks)
 #pragma unroll
                     for (int q = 0; q < SIMON_MAX_SPREAD; ++q) {
                         if (q >= cnt) continue;
@@ -861,6 +894,7 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
             // ---------------- stage A: filter + base score + reductions --------------------------------
             // static filters of this lane's nodes: ONE word of the lane-major mask (bit it = node tid + it*T)
             unsigned mbits = A.mask_lanes ? A.mask_lanes[(size_t)p.cls * T + tid] : 0xFFFFFFFFu;
+            if (kCanOwn && own) mbits &= pres;                 // absent nodes are skipped (and with them a pin to one of them)
             if (p.pin >= 0) mbits = (p.pin < n && tid == p.pin % T) ? (mbits & (1u << (p.pin / T))) : 0u;   // pinned pod: one node of one lane
             // ... and only the batch that holds that node is evaluated (nothing at all when the node is outside the scenario)
             const int itA_lo = p.pin < 0 ? 0 : (p.pin / T / kUT) * kUT, itB_lo = p.pin < 0 ? 0 : (p.pin / T / kU) * kU;
@@ -1138,7 +1172,7 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
                     for (int u = 0; u < kU; ++u) {
                         const int j = tid + (it0 + u) * T;
                         if (j >= n) continue;
-                        if (filter_code(A, v, p, j, n, L[u], mk[u], hard_min) != 0u) continue;
+                        if (filter_code(A, v, p, j, n, L[u], mk[u], hard_min, own_reg) != 0u) continue;
                         on_feasible(j, it0 + u, base_score(p, L[u]), ncl[u]);
                         m[u] = true; jn[u] = j;
                     }
@@ -1270,8 +1304,12 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
                             if (tid < 2) h_meta[tid] = 0;
                             __syncthreads();
                         }
-                        for (int j = tid; j < n; j += T) {
-                            const unsigned code = filter_code(A, v, p, j, n, load_state(A, v, j), mask_bit(A, p.cls, j), hard_min);
+                        for (int j = tid, it = 0; j < n; j += T, ++it) {
+                            if (kCanOwn && own && !((pres >> it) & 1u)) {      // a node the scenario lacks: no code, no count
+                                if (codes) codes[j] = (uint16_t)SIMON_FAIL_NONE;
+                                continue;
+                            }
+                            const unsigned code = filter_code(A, v, p, j, n, load_state(A, v, j), mask_bit(A, p.cls, j), hard_min, own_reg);
                             if (codes) codes[j] = (uint16_t)code;
                             if (hist) {
                                 const unsigned key = code & 0xffffu;
@@ -1588,7 +1626,8 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
 #endif
 
     long long uc = 0, um = 0, uv = 0;
-    for (int j = tid; j < n; j += T) {
+    for (int j = tid, it = 0; j < n; j += T, ++it) {
+        if (kCanOwn && own && !((pres >> it) & 1u)) continue;
         uc += v.req_cpu[j]; um += v.req_mem[j];
         if (LOCAL && (A.flags & kArgLocal) && (COLD(A)->l_flags[j] & 1))
             for (int q = 0; q < COLD(A)->l_vg_cnt[j]; ++q) uv += v.st_vg()[(size_t)j * SIMON_MAX_VG + q];
@@ -2131,7 +2170,8 @@ int wide_run(WideDevice& w, const HostInputs& in, const WideScenario* d_scen, in
     return rc;
 }
 
-// The replay behind simon_explain, simon_explain_loaded and simon_explain_batch: the job's scenarios on the EXPLAIN instantiation, launched
+// The replay behind simon_explain, simon_explain_loaded, simon_explain_batch and (job.own: own-nodes mode, kArgOwn) simon_explain_own_batch:
+// the job's scenarios on the EXPLAIN instantiation, launched
 // as wide_run launches a batch but without the (signature, node) table (failure codes come from the full per-node evaluation) and
 // without the stage-A caches.  Slot [1] of d_cold.  ONE device allocation holds everything of the call -- scenarios, an ad-hoc order,
 // rank rows and image slots gathered into launch order (the kernel indexes both by scen_base + s), every output -- and every way out
@@ -2146,6 +2186,9 @@ int wide_replay(WideDevice& w, const HostInputs& in, const WideReplay& job, int 
     WideArgs& a = L.a;
     WideCold& c = L.c;
     const bool ranked = job.rank_row && job.d_node_rank && job.d_node_inv, image = (a.flags & kArgImage) != 0u;
+    if (job.own && (!ranked || in.has_local || job.max_n != in.N)) { err = "wide explain: an own-nodes replay needs rank rows, the pool size and no local storage"; return SIMON_EINVAL; }
+    // own-nodes replay: the registered flags of the hard spread constraints, [S][E][R] bytes (R: the most domains a topology key has)
+    const size_t reg_E = in.sh_idx.size(), reg_R = (size_t)std::max(1, in.topo_n_dom.empty() ? 1 : *std::max_element(in.topo_n_dom.begin(), in.topo_n_dom.end()));
     if (image && (!job.d_img || !job.img_slot)) {
         err = std::string("wide explain: image scores of the ") + (job.recorded_only ? "scenario" : "batch") + " are not staged";
         return SIMON_ESTATE;
@@ -2160,7 +2203,8 @@ int wide_replay(WideDevice& w, const HostInputs& in, const WideReplay& job, int 
                  o_slot = carve(image ? (size_t)S * 4 : 0), o_rank = carve(ranked ? (size_t)S * N * 4 : 0), o_inv = carve(ranked ? (size_t)S * N * 4 : 0),
                  o_nf = carve((size_t)S * 4), o_failed = carve(rows * 4), o_nb = carve(job.bins ? rows * 4 : 0),
                  o_bins = carve(job.bins ? rows * job.max_bins * sizeof(simon_fail_bin) : 0),
-                 o_codes = carve(job.fail_codes ? cells * 2 : 0), o_detail = carve(want_detail ? cells * 4 * 8 : 0);
+                 o_codes = carve(job.fail_codes ? cells * 2 : 0), o_detail = carve(want_detail ? cells * 4 * 8 : 0),
+                 o_reg = carve(job.own ? (size_t)S * reg_E * reg_R : 0);
     char* d = nullptr;
     if (hipError_t e = hipMalloc((void**)&d, std::max<size_t>(total, 256)); e != hipSuccess) { err = std::string("hipMalloc(explain): ") + hipGetErrorString(e); return SIMON_ENOMEM; }
     auto body = [&]() -> int {
@@ -2186,6 +2230,7 @@ int wide_replay(WideDevice& w, const HostInputs& in, const WideReplay& job, int 
         c.fail_codes = job.fail_codes ? (uint16_t*)(d + o_codes) : nullptr; c.code_stride = (int32_t)stride;
         c.fail_detail = want_detail ? (long long*)(d + o_detail) : nullptr;
         if (job.bins) { c.max_bins = job.max_bins; c.bins = (simon_fail_bin*)(d + o_bins); c.n_bins = (int32_t*)(d + o_nb); }
+        if (job.own) { a.flags |= kArgOwn; c.own_reg = (uint8_t*)(d + o_reg); c.own_reg_R = (int32_t)reg_R; c.own_reg_E = (int32_t)reg_E; }
         if (int rl = launch_chunks<true>(w, in, L, 1, st, err)) return rl;
         TRY(hipMemcpyAsync(job.n_failed, d + o_nf, (size_t)S * 4, hipMemcpyDeviceToHost, st));
         if (!job.recorded_only) {

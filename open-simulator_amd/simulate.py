@@ -103,7 +103,47 @@ class HipEngine:
                         e.detail = ctx.explain_local_detail(len(e.failed), e.n_nodes)
             return out
 
+    def explain_own_batch(self, prob: capi.Problem, scen, orders, node_ranks, ids, max_failed: int, max_bins: int = 32, *, present=None,
+                          segments=None, evict=None) -> List["ExplainedScenario"]:
+        """explain_batch for a batch with pool segments or node subsets (simon_explain_own_batch), on the context shape run() gives such a
+        batch: `segments` / `present` / `evict` / `node_ranks` as run() takes them.  Bins count each scenario's own nodes; the rows of the
+        second pass are [failed][N], indexed by POOL node, 0 on the nodes the scenario lacks.  capi.SimonError (ESTATE) where the
+        library refuses: a problem whose route is the all-feature kernel."""
+        if (segments is None) == (present is None):
+            raise ValueError("an own-nodes batch has pool segments or node subsets (exactly one of them)")
+        if evict is not None and present is None:
+            raise ValueError("evicted pods belong to a node-subset batch: pass present")
+        ids = [int(s) for s in ids]
+        per_bins = max_failed * (8 + 8 * max_bins)                           # failed_pods + n_bins + bins, per listed scenario
+        with capi.Context(self.device_id) as ctx:
+            ctx.load_problem(prob)
+            if evict is not None:
+                ctx.set_pod_eviction(evict)
+            ctx.load_scenarios(scen, orders)
+            if segments is not None:
+                ctx.set_scenario_segments(*segments)
+            if present is not None:
+                ctx.set_scenario_nodes(*present)
+            if node_ranks is not None:
+                ctx.set_node_ranks(node_ranks)
+            out, again = [], []
+            for group in _groups(ids, max(1, self.buffer_bytes // per_bins)):
+                eb = ctx.explain_own_batch(group, max_failed, max_bins)
+                for k, s in enumerate(group):
+                    rec = eb.recorded(k)
+                    bins = [eb.pod_bins(k, i) for i in range(rec)]
+                    if any(b is None or any(c in fiterror.NODE_SPECIFIC_CODES for c, _ in b) for b in bins):
+                        again.append(len(out))
+                    out.append(ExplainedScenario(s, int(eb.n_nodes[k]), int(eb.n_failed[k]), eb.failed_pods[k, :rec].copy(), bins))
+            per_rows = per_bins + 2 * max_failed * prob.n_nodes
+            for group in _groups(again, max(1, self.buffer_bytes // per_rows)):
+                er = ctx.explain_own_batch([out[k].scenario for k in group], max_failed, max_bins, rows=True)
+                for q, k in enumerate(group):
+                    out[k].rows = er.rows[q, :len(out[k].failed)].copy()
+            return out
+
     supports_explain_batch = True             # sweep(..., reasons=True) explains every failing size in one launch
+    supports_explain_own = True               # ... and sweep_failures / sweep_mix (reasons=True) every failing scenario of an own-nodes batch
     buffer_bytes = 256 << 20                  # explain_batch: host (and device) output buffers per simon_explain_batch call
 
 
@@ -436,16 +476,18 @@ def sweep_batch(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new
     return SweepBatch(flat, scen, orders, node_ranks, pool, base)
 
 
-def _reason_texts(flat: fl.Flat, failed, rows, detail, bins=None) -> Dict[int, str]:
-    """UnscheduledPod.Reason by pod id, from the pods' code rows (as simulate() does) or, where a pod has one, its histogram."""
+def _reason_texts(flat: fl.Flat, failed, rows, detail, bins=None, node_names=None) -> Dict[int, str]:
+    """UnscheduledPod.Reason by pod id, from the pods' code rows (as simulate() does) or, where a pod has one, its histogram.
+    node_names: the nodes behind the rows' columns (default: the flat problem's)."""
     reasons = {}
+    node_names = flat.node_names if node_names is None else node_names
     for i, pid in enumerate(np.asarray(failed).tolist()):
         ns, name = flat.pod_refs[pid]
         if rows is None:
             reasons[pid] = fiterror.unscheduled_reason_bins(ns, name, bins[i][0], bins[i][1], static_reasons=flat.static_reasons,
                                                             scalar_names=flat.scalar_names)
         else:
-            reasons[pid] = fiterror.unscheduled_reason(ns, name, rows[i], node_names=flat.node_names, static_reasons=flat.static_reasons,
+            reasons[pid] = fiterror.unscheduled_reason(ns, name, rows[i], node_names=node_names, static_reasons=flat.static_reasons,
                                                        scalar_names=flat.scalar_names, local_detail=None if detail is None else detail[i],
                                                        vg_names=flat.info.get("vg_names", ()))
     return reasons
@@ -453,6 +495,14 @@ def _reason_texts(flat: fl.Flat, failed, rows, detail, bins=None) -> Dict[int, s
 
 def _unscheduled_list(flat: fl.Flat, placement: np.ndarray, reasons: Dict[int, str]) -> List[dict]:
     return [{"pod": _public(flat.pods[pid]), "reason": reasons.get(pid, "")} for pid, j in enumerate(placement.tolist()) if j == capi.UNSCHEDULED]
+
+
+def _own_reason_texts(flat: fl.Flat, e: "ExplainedScenario", present_row) -> Dict[int, str]:
+    """_reason_texts for one scenario of HipEngine.explain_own_batch: the node count is the scenario's own, and its pool-indexed rows are
+    cut down to the nodes it holds before they become text."""
+    own = np.flatnonzero(np.asarray(present_row, bool))
+    rows = None if e.rows is None else np.asarray(e.rows)[:, own]
+    return _reason_texts(flat, e.failed, rows, None, [(e.n_nodes, b) for b in e.bins], [flat.node_names[j] for j in own.tolist()])
 
 
 def _same_stream(cluster, apps, batch: "SweepBatch", out, s: int) -> bool:
@@ -605,6 +655,7 @@ class MixSweepResult:
     result: Optional[SimulateResult]     # SimulateResult of that mix (node_status over its own nodes)
     batched: bool = True                 # one segmented engine batch (False: every mix ran as its own problem)
     fallback: Optional[str] = None       # why the mixes ran one by one (None when batched); sweep_mix also warns (MixFallbackWarning)
+    unscheduled_pods: List[List[dict]] = field(default_factory=list)   # reasons=True: per mix, simulate()'s list of that mix
 
 
 class MixFallbackWarning(UserWarning):
@@ -671,14 +722,17 @@ def _caps(max_cpu, max_mem, max_vg):
 
 @_gc_paused
 def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_nodes: Sequence[dict], counts: Sequence[Sequence[int]],
-              costs: Optional[Sequence[float]] = None, engine=None, max_cpu: int = 100, max_mem: int = 100, max_vg: int = 100) -> MixSweepResult:
+              costs: Optional[Sequence[float]] = None, engine=None, max_cpu: int = 100, max_mem: int = 100, max_vg: int = 100,
+              reasons: bool = False) -> MixSweepResult:
     """The add-nodes search over mixes of several new-node types (Applier.Run clones ONE template, pkg/apply/apply.go:155-166): mix
     (c_1 .. c_T) = Simulate(cluster + NewFakeNodes(type_1, c_1) + ... + NewFakeNodes(type_T, c_T)), the grid = the Cartesian product of
     counts (one iterable per type).  The answer is the mix of least total cost sum_t costs[t] * c_t (default 1 per node) with no
     unscheduled pod and the MaxCPU / MaxMemory / MaxVG caps of satisfyResourceSetting over its own nodes; ties go to fewer new nodes,
     then to the smallest count vector.  One engine batch over the pool cluster + every type's clones up to its largest count, one
     segment per type (simon_set_scenario_segments); engines without segments, clusters whose nodes list the pods' images and problems
-    the segmented kernel does not take run every mix as its own problem."""
+    the segmented kernel does not take run every mix as its own problem.  reasons=True: MixSweepResult.unscheduled_pods lists, per mix,
+    the pods that stay unscheduled with their FitError text, as sweep() does per count -- every failing mix of the batch explained in
+    one engine.explain_own_batch call (engines without it, and mixes whose pod stream is not the pool's: simulate() of the mix)."""
     import itertools
     engine = engine or HipEngine()
     new_nodes = list(new_nodes)
@@ -697,7 +751,7 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
     mixes = [tuple(int(k) for k in m) for m in itertools.product(*counts)]
     caps = _caps(max_cpu, max_mem, max_vg)
     if not getattr(engine, "supports_scenario_segments", False):
-        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, "the engine has no pool segments")
+        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, "the engine has no pool segments", reasons)
     base = list(cluster.get("Node", []))
     if not base and any(sum(m) == 0 for m in mixes):   # (a scenario holds one node at least: simon_set_scenario_segments, and flatten)
         raise ValueError("sweep_mix: a cluster without nodes needs at least one new node in every mix")
@@ -718,7 +772,7 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
         if "ImageLocality" not in str(e):
             raise
         return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps,
-                                  "nodes list the pods' images: ImageLocality depends on the node set")
+                                  "nodes list the pods' images: ImageLocality depends on the node set", reasons)
     scen = np.stack([len(base) + cnt.sum(1), np.zeros(len(mixes), np.int64)], 1).astype(np.int32)
     orders = np.arange(len(pods), dtype=np.int32)[None, :]
     want_gpu = flat.problem.gpu_mem is not None
@@ -731,7 +785,7 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
         if getattr(e, "code", None) != capi.ESTATE:
             raise
         # a problem on the all-feature kernel (prefix scenarios only): every mix as its own problem
-        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, f"the engine refused the segmented batch: {e}")
+        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, f"the engine refused the segmented batch: {e}", reasons)
     # satisfyResourceSetting over each mix's own nodes: the fixed nodes + a prefix of every segment
     pr = flat.problem
     vg_cap = None
@@ -756,16 +810,61 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
         res.node_status = [{"node": _gpu_node_status(pool[j], per_dev[j]) if j in per_dev else _node_out(pool[j]), "pods": per_node[j]}
                            for j in np.flatnonzero(present[best]).tolist()]
         result = res
+    why = []
+    if reasons:
+        why = _mix_reasons(engine, cluster, apps, flat, pool, len(base), present, scen, orders, node_ranks, (seg_start, cnt), out)
     return MixSweepResult(mixes, out.unscheduled.tolist(), cpu_pct, mem_pct, vg_pct, [_risk(out, s) for s in range(len(mixes))],
-                          None if best is None else mixes[best], None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result)
+                          None if best is None else mixes[best], None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result,
+                          unscheduled_pods=why)
 
 
-def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why: str) -> MixSweepResult:
+def _mix_reasons(engine, cluster, apps, flat, pool, n_base, present, scen, orders, node_ranks, segments, out) -> List[List[dict]]:
+    """MixSweepResult.unscheduled_pods of a batched sweep_mix, as _sweep_reasons fills SweepResult's: every failing mix explained in one
+    engine.explain_own_batch call; a failing mix whose pod stream is not the pool's (an app with a DaemonSet, _same_stream), an engine
+    without the call and a batch the library refuses to explain take simulate() of the mix's own cluster."""
+    ref = lambda p: (p["metadata"].get("namespace"), p["metadata"]["name"])                    # noqa: E731
+    with_ds = any(app.resource.get("DaemonSet") for app in apps)
+
+    def nodes_of(s):
+        return [pool[j] for j in np.flatnonzero(present[s]).tolist()]
+
+    def same_stream(s):
+        if not with_ds:
+            return True
+        mine = [ref(flat.pods[pid]) for pid, j in enumerate(out.placement[s].tolist()) if j != capi.GATED]
+        return mine == [ref(p) for p in build_stream(cluster, apps, nodes_of(s), n_base)[0]]
+
+    def replay(s):                           # (NeedsReference: the mix is flagged in needs_reference; its pods stay without a text)
+        try:
+            return simulate(cluster, apps, engine, nodes_of(s)[n_base:]).unscheduled_pods
+        except NeedsReference:
+            return _unscheduled_list(flat, out.placement[s], {})
+
+    failing = [s for s in range(len(scen)) if out.unscheduled[s] > 0]
+    lists: Dict[int, List[dict]] = {s: replay(s) for s in failing if not same_stream(s)}
+    failing = [s for s in failing if s not in lists]
+    texts: Dict[int, Dict[int, str]] = {}
+    if failing and getattr(engine, "supports_explain_own", False):
+        try:
+            for e in engine.explain_own_batch(flat.problem, scen, orders, node_ranks, failing, int(max(out.unscheduled[s] for s in failing)),
+                                              segments=segments):
+                texts[e.scenario] = _own_reason_texts(flat, e, present[e.scenario])
+        except capi.SimonError as err:
+            if getattr(err, "code", None) != capi.ESTATE:
+                raise
+    for s in failing:
+        if s not in texts:
+            lists[s] = replay(s)
+    return [lists[s] if s in lists else _unscheduled_list(flat, out.placement[s], texts.get(s, {})) for s in range(len(scen))]
+
+
+def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why: str, reasons: bool = False) -> MixSweepResult:
     """Every mix as its own Simulate(): cluster + each type's clones in type order, canonical nodeTree order."""
     import warnings
     warnings.warn(f"sweep_mix runs {len(mixes)} mixes one by one ({why})", MixFallbackWarning, stacklevel=3)
     base = list(cluster.get("Node", []))
     uns, cpu_pct, mem_pct, vg_pct, risks, kept = [], [], [], [], [], {}
+    lists: List[List[dict]] = []
     for s, mix in enumerate(mixes):
         nodes = base + [n for nodes in mix_fake_nodes(new_nodes, mix) for n in nodes]
         pods, _ = build_stream(cluster, apps, nodes, len(nodes))
@@ -778,6 +877,12 @@ def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why
                          **({"want_gpu_slices": True} if want_gpu else {}))
         uns.append(int(out.unscheduled[0]))
         risks.append(_risk(out, 0))
+        if reasons:
+            texts = {}
+            if uns[-1] > 0:
+                nf, failed, codes, detail = engine.explain(flat.problem, len(nodes), np.arange(len(pods), dtype=np.int32), uns[-1])
+                texts = _reason_texts(flat, failed, codes, detail)
+            lists.append(_unscheduled_list(flat, out.placement[0], texts))
         cpu_pct.append(occupancy_pct(int(out.used_cpu[0]), int(flat.problem.alloc_cpu.sum())))
         mem_pct.append(occupancy_pct(int(out.used_mem[0]) * 1000, int(flat.problem.alloc_mem.sum()) * 1000))
         vg = 0
@@ -795,7 +900,8 @@ def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why
         res.node_status = [{"node": _gpu_node_status(n, per_dev[j]) if j in per_dev else _node_out(n), "pods": per_node[j]} for j, n in enumerate(nodes)]
         result = res
     return MixSweepResult(mixes, uns, cpu_pct, mem_pct, vg_pct, risks, None if best is None else mixes[best],
-                          None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result, batched=False, fallback=why)
+                          None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result, batched=False, fallback=why,
+                          unscheduled_pods=lists)
 
 
 @dataclass
@@ -982,7 +1088,8 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     lists of node names), without the pods bound to its nodes and without their DaemonSet pods (cluster_without) -- lost pods are
     dropped, not rescheduled.  One node-subset engine batch over the cluster's nodes (simon_set_scenario_nodes; batch_scenarios per
     launch): every node-bound pod is gated on its node, each scenario runs in the nodeTree order of its own nodes.  reasons=True
-    replays the failing scenarios one by one through simulate() for their unscheduled_pods.  Engines without node subsets, clusters
+    explains the failing scenarios of every launch in one engine.explain_own_batch call for their unscheduled_pods (an engine without
+    supports_explain_own, and a batch the library refuses to explain: simulate() of every failing scenario, one by one).  Engines without node subsets, clusters
     whose nodes list the pods' images, apps whose pod list depends on the node set and problems the score-table kernel does not take
     run every scenario as its own problem (FailureFallbackWarning, batched=False).  A domain that leaves no node: ValueError.
     reschedule="owned" / "all": the N-1 / drain / scale-down question for a cluster ingested with its Running pods -- scenario d + 1 is
@@ -1043,6 +1150,7 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     orders = np.arange(len(pods), dtype=np.int32)[None, :]
     want_gpu = pr.gpu_mem is not None
     rows, where = [], []
+    told: Dict[int, List[dict]] = {}             # reasons: scenario -> its unscheduled_pods, from the batch's own explain
     for lo in range(0, len(present), max(1, int(batch_scenarios))):
         part = present[lo:lo + max(1, int(batch_scenarios))]
         scen = np.stack([part.sum(1), np.zeros(len(part), np.int64)], 1).astype(np.int32)
@@ -1057,6 +1165,21 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
             if getattr(e, "code", None) != capi.ESTATE:
                 raise
             return each(f"the engine refused the node-subset batch: {e}")
+        failing = [s for s in range(len(part)) if lo + s > 0 and out.unscheduled[s] > 0 and not _risk(out, s)] if reasons else []
+        if failing and getattr(engine, "supports_explain_own", False):
+            # the failing scenarios of this launch on the context shape it ran with; a pod evicted in a scenario is listed as its
+            # controller recreates it (cluster_evicted; status as make_valid_pod leaves it), like simulate() of that scenario's own cluster
+            try:
+                for e in engine.explain_own_batch(pr, scen, orders, kw.get("node_ranks"), failing, int(max(out.unscheduled[s] for s in failing)),
+                                                  present=(part, zone if 1 < len(zid) <= capi.MAX_ZONES else None), evict=kw.get("evict")):
+                    s = e.scenario
+                    texts = _own_reason_texts(flat, e, part[s])
+                    gone = evict & ~part[s][np.maximum(np.asarray(pr.preset_node), 0)] if evict.any() else evict
+                    told[lo + s] = [{"pod": _public(dict(_recreated(flat.pods[pid]), status={}) if gone[pid] else flat.pods[pid]), "reason": texts.get(pid, "")}
+                                    for pid, j in enumerate(out.placement[s].tolist()) if j == capi.UNSCHEDULED]
+            except capi.SimonError as e:
+                if getattr(e, "code", None) != capi.ESTATE:
+                    raise
         vg_cap = _vg_caps(pr, out)
         ac, am = part @ np.asarray(pr.alloc_cpu, np.int64), part @ np.asarray(pr.alloc_mem, np.int64)
         av = part @ np.asarray(vg_cap, np.int64) if vg_cap is not None else None
@@ -1067,7 +1190,8 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
             where.append((flat, out.placement[s]))
     why = []
     if reasons:
-        why = [_failure_replay(cluster, apps, names, engine, reschedule) if rows[d + 1][0] > 0 else [] for d, names in enumerate(doms)]
+        why = [told[d + 1] if d + 1 in told else _failure_replay(cluster, apps, names, engine, reschedule) if rows[d + 1][0] > 0 else []
+               for d, names in enumerate(doms)]
     moved = None
     if evict.any():
         preset = np.asarray(pr.preset_node)
