@@ -70,6 +70,8 @@ struct PlanKernelOut {
 
 }  // namespace
 
+constexpr int kPlanRecWords = 4;     // simon_ctx::d_plan: plan key, used cpu, used memory, used VG of the winner
+
 struct simon_ctx : simon::HostInputs {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -215,7 +217,7 @@ struct simon_ctx : simon::HostInputs {
     DevBuf<unsigned char> d_risk;                 // [S] DefaultPreemption could have acted in the scenario (simon_fetch_preempt_risk)
     bool prio_staged = false, have_risk = false;
     DevBuf<int64_t> d_used_cpu, d_used_mem, d_used_vg;
-    DevBuf<unsigned long long> d_plan;
+    DevBuf<unsigned long long> d_plan;           // kPlanRecWords: plan key, then the winner's used cpu / memory / VG (plan_record_kernel)
     bool have_results = false, have_placement = false, have_slices = false;
     DevBuf<uint64_t> d_gpu_slices;      // [S][P] devices Reserve booked (simon_batch_out.gpu_slices), recorded on request
     // ABI v7 ImageLocality: the caller's node classes and (pod class, node class) tables before the image split (img_refine)
@@ -1551,6 +1553,18 @@ __global__ void plan_kernel(const ScenarioDesc* __restrict__ scen, int S, const 
     if ((threadIdx.x & 63) == 0 && best != ~0ull) atomicMin(out, best);
 }
 
+// One thread behind plan_kernel: the winner's sums next to its key, so that simon_min_plan_vg reads ONE record back.
+// rec = {key, used_cpu[s], used_mem[s], used_vg[s] (0 without local storage)}; without a plan only the key (~0) is meaningful.
+__global__ void plan_record_kernel(const int64_t* __restrict__ used_cpu, const int64_t* __restrict__ used_mem,
+                                   const int64_t* __restrict__ used_vg, unsigned long long* __restrict__ rec) {
+    const unsigned long long key = rec[0];
+    if (key == ~0ull) return;
+    const unsigned s = (unsigned)(key & 0xFFFFFFFFu);
+    rec[1] = (unsigned long long)used_cpu[s];
+    rec[2] = (unsigned long long)used_mem[s];
+    rec[3] = used_vg ? (unsigned long long)used_vg[s] : 0ull;
+}
+
 // simon_batch_out as the caller filled it, widened to the current layout: a v3 struct (no gpu_slices member) reads as gpu_slices = NULL
 bool batch_out_view(const simon_batch_out* out, simon_batch_out* v) {
     if (out->struct_size == sizeof(simon_batch_out)) { *v = *out; return true; }
@@ -2088,7 +2102,7 @@ int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, co
     HIP_TRY(c, c->d_used_cpu.ensure(S));
     HIP_TRY(c, c->d_used_mem.ensure(S));
     HIP_TRY(c, c->d_used_vg.ensure(S));
-    HIP_TRY(c, c->d_plan.ensure(1));
+    HIP_TRY(c, c->d_plan.ensure(kPlanRecWords));
     if (c->img_R > 0) {
         std::vector<int32_t>& slot = c->h_img_slot;
         slot.resize(S);
@@ -2600,12 +2614,14 @@ static int report_table_prof(simon_ctx* c) {
     // the prologue (slots 22 / 23, stamped once per scenario): ticks per scenario, and its share of everything the wave stamped
     double all = 0;
     for (double a : acc) all += a;
-    all -= acc[7] + acc[20] + acc[23];                                // (7 and 20 count events; 23 is a part of 22)
+    all -= acc[7] + (c->rest ? acc[20] : 0.0) + acc[23];              // (7 and REST's 20 count events; 23 is a part of 22)
     fprintf(stderr, "[SIMON_TABLE_PROF] S=%d ticks/scenario: prologue %.0f (%.2f %% of the wave's %.0f) | of it the table pass %.0f (%.2f %%)\n",
             S, acc[22] / S, all > 0 ? 100.0 * acc[22] / all : 0.0, all / S, acc[23] / S, all > 0 ? 100.0 * acc[23] / all : 0.0);
     for (double& a : acc) a = a / S / P;
     fprintf(stderr, "[SIMON_TABLE_PROF] S=%d ticks/cycle: loop %.0f | row+summary read %.0f | key+wavemax %.0f | tie check %.0f | lds(shape,sn) %.0f | mem(state,row) %.0f | state update %.0f | eval+patch+store %.0f | REST assume %.0f | REST select %.0f | canonical tie-breaks per cycle %.3f\n",
-            S, acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], acc[8], acc[9], acc[6], acc[10], acc[7]);
+            S, acc[0], acc[1], acc[2], acc[3], acc[4], acc[5] + ((c->rest || c->spread) ? 0.0 : acc[20]), acc[8], acc[9], acc[6], acc[10], acc[7]);
+    if (!c->rest && !c->spread)                                       // (straight-line instantiations: slot 20 splits the memory wait, slot 5 is the rest of it)
+        fprintf(stderr, "[SIMON_TABLE_PROF] S=%d ticks/cycle, of mem(state,row): state arrived %.0f | row and byte arrived after it %.0f\n", S, acc[20], acc[5]);
     if (c->rest)
         fprintf(stderr, "[SIMON_TABLE_PROF] REST select, ticks/cycle (averaged over ALL pods): pod row %.0f | filter words + summaries %.0f | candidates %.0f | table rows of excluded bests %.0f (needed on %.3f of the cycles) | per-class best %.0f | class term %.0f | totals + tie %.0f | rest %.0f\n",
                 acc[11], acc[12], acc[13], acc[14], acc[20], acc[15], acc[16], acc[17], acc[10]);
@@ -2807,7 +2823,8 @@ int simon_min_plan(simon_ctx* c, int32_t max_cpu_pct, int32_t max_mem_pct, simon
     return simon_min_plan_vg(c, max_cpu_pct, max_mem_pct, 100, best, nullptr);
 }
 
-// satisfyResourceSetting + minimum over the batch on the device: leaves the key (n_nodes << 32 | scenario, ~0 = none) in c->d_plan
+// satisfyResourceSetting + minimum over the batch on the device: leaves the key (n_nodes << 32 | scenario, ~0 = none) in c->d_plan[0]
+// and, behind it, the winner's used cpu / memory / VG sums (plan_record_kernel)
 static int launch_plan(simon_ctx* c, int32_t max_cpu_pct, int32_t max_mem_pct, int32_t max_vg_pct) {
     if (max_vg_pct > 100 || max_vg_pct < 0) max_vg_pct = 100;
     if (!c->have_results) return fail(c, SIMON_ESTATE, "min_plan: nothing has run");
@@ -2819,6 +2836,9 @@ static int launch_plan(simon_ctx* c, int32_t max_cpu_pct, int32_t max_mem_pct, i
     hipLaunchKernelGGL(plan_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_scen.p, c->S, c->d_unsched.p,
                        c->d_used_cpu.p, c->d_used_mem.p, c->d_prefix_cpu.p, c->d_prefix_mem.p, max_cpu_pct, max_mem_pct,
                        c->has_local ? c->d_used_vg.p : nullptr, c->d_prefix_vg.p, max_vg_pct, own_nodes(c) ? c->d_seg_tot.p : nullptr, c->d_plan.p);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(plan_record_kernel, dim3(1), dim3(1), 0, c->stream, c->d_used_cpu.p, c->d_used_mem.p,
+                       c->has_local ? c->d_used_vg.p : nullptr, c->d_plan.p);
     HIP_TRY(c, hipGetLastError());
     return SIMON_OK;
 }
@@ -2838,30 +2858,29 @@ int simon_min_plan_vg(simon_ctx* c, int32_t max_cpu_pct, int32_t max_mem_pct, in
     if (vg_pct) *vg_pct = 0;
     const int rcl = launch_plan(c, max_cpu_pct, max_mem_pct, max_vg_pct);
     if (rcl) return rcl;
-    unsigned long long key = 0;
-    HIP_TRY(c, hipMemcpyAsync(&key, c->d_plan.p, sizeof key, hipMemcpyDeviceToHost, c->stream));
+    unsigned long long rec[kPlanRecWords] = {0, 0, 0, 0};          // one read-back per plan: key and the winner's sums
+    HIP_TRY(c, hipMemcpyAsync(rec, c->d_plan.p, sizeof rec, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const unsigned long long key = rec[0];
     memset(best, 0, sizeof *best);
     best->scenario = -1;
     if (key == ~0ull) return SIMON_OK;
     const int s = (int)(key & 0xFFFFFFFFu);
-    int64_t uc = 0, um = 0;
-    HIP_TRY(c, hipMemcpy(&uc, c->d_used_cpu.p + s, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(&um, c->d_used_mem.p + s, 8, hipMemcpyDeviceToHost));
+    const int64_t uc = (int64_t)rec[1], um = (int64_t)rec[2];
     const int n = c->scen[s].n_nodes;
     int64_t ac = 0, am = 0;
-    for (int j = 0; j < c->N; ++j)
-        if (node_in(c, s, j)) { ac += c->alloc_cpu[j]; am += c->alloc_mem[j]; }
+    if (own_nodes(c)) {
+        for (int j = 0; j < c->N; ++j)
+            if (node_in(c, s, j)) { ac += c->alloc_cpu[j]; am += c->alloc_mem[j]; }
+    } else {                                                       // a prefix scenario: the first n nodes
+        ac = c->prefix_cpu[n]; am = c->prefix_mem[n];
+    }
     best->found = 1; best->scenario = s; best->n_nodes = n; best->order_id = c->scen[s].order_id;
     best->cpu_pct = (int)((double)uc / (double)ac * 100.0);
     best->mem_pct = (int)((double)(um * 1000) / (double)(am * 1000) * 100.0);
     best->used_cpu = uc; best->used_mem = um;
     const int64_t av = own_nodes(c) ? c->seg_tot[(size_t)2 * c->S + s] : c->prefix_vg[n];
-    if (vg_pct && c->has_local && av != 0) {
-        int64_t uv = 0;
-        HIP_TRY(c, hipMemcpy(&uv, c->d_used_vg.p + s, 8, hipMemcpyDeviceToHost));
-        *vg_pct = (int)((double)uv / (double)av * 100.0);
-    }
+    if (vg_pct && c->has_local && av != 0) *vg_pct = (int)((double)(int64_t)rec[3] / (double)av * 100.0);
     return SIMON_OK;
 }
 

@@ -53,6 +53,7 @@
 #define TPROF(i) do { const unsigned long long t_ = __builtin_readcyclecounter(); tp_acc[i] += t_ - tp_prev; tp_prev = t_; } while (0)
 #define TPROF_WAIT_LDS asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #define TPROF_WAIT_MEM asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#define TPROF_WAIT_STATE(n) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(n) : "memory")   // all but the n youngest vector loads (the state is issued first)
 #else
 #define TPROF_DECL
 #define TPROF_PROLOGUE_BEGIN
@@ -61,6 +62,7 @@
 #define TPROF(i) do { } while (0)
 #define TPROF_WAIT_LDS do { } while (0)
 #define TPROF_WAIT_MEM do { } while (0)
+#define TPROF_WAIT_STATE(n) do { } while (0)
 #endif
 
 namespace simon {

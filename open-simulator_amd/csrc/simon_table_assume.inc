@@ -53,6 +53,11 @@
             }
             NodeState* stp = g_state + pstar;                          // (kept for the store: one 64-bit scalar address per cycle)
             NodeState st = *stp;
+            // (round 10, straight-line instantiations: the state's load goes out AHEAD of the row and the byte -- left to the scheduler the 16-byte row went
+            // first, and the state update, its store and the whole evaluation waited for the row's six or seven cache lines, which they do not read.
+            // Vector loads return in order: with the state first its wait is vmcnt(2), and the row and the byte are waited for at the patch.
+            // Not with the workspace in LDS: nothing leaves the chip there, and the barrier alone cost config 3 at 64 scenarios 0.3 %)
+            if constexpr (kStraight && !LDSWS) __builtin_amdgcn_sched_barrier(0);
             // A table row is named by its 32-bit byte offset: row and byte accesses are uniform base + lane offset, and the byte's address is one
             // add, shared by the load and the store.  MANY keeps 64-bit pointers: with its eighteen row accesses per cycle the offsets measured
             // slower (config 3 with 200 signatures 83.4 -> 87.7 ms; the others gain, config 3 13.1 -> 12.7 ms).
@@ -143,6 +148,7 @@
                     res = (info & 0xFFFF) - 8192 + pstar;
                     stp = g_state + pstar;
                     st = *stp;
+                    if constexpr (kStraight && !LDSWS) __builtin_amdgcn_sched_barrier(0);   // (the same order as above: the two paths meet in front of the state's wait)
 #pragma unroll
                     for (int q = 0; q < KQ; ++q) {
                         rowp[q] = row_ref(tile_blk((unsigned)(pstar >> 4)) + koff[q]);
@@ -178,7 +184,8 @@
             // byte -> u16 expansion selectors of the touched block row with the new byte already in place (kSel, above)
             const uint4 selA = sel_tab[pos * 2], selB = sel_tab[pos * 2 + 1];
             TPROF_WAIT_LDS; TPROF(4);                                  // loads issued; shape row and class term arrived (LDS)
-            TPROF_WAIT_MEM; TPROF(5);                                  // node state and table row arrived (L2 / HBM)
+            if constexpr (kStraight && !LDSWS) { TPROF_WAIT_STATE(KQ * (COARSE ? 3 : 2) + (NZEQ ? 0 : 1)); TPROF(20); }   // node state arrived (the loads issued behind it still in flight)
+            TPROF_WAIT_MEM; TPROF(5);                                  // ... and table row and byte arrived (L2 / HBM)
             const int sl = r_sig & 63;
             const bool hiq = KQ > 1 && (r_sig >> 6);
             unsigned add_c, add_m, addz_c = 0, addz_m = 0;

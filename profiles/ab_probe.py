@@ -2,6 +2,7 @@
 """Same-box A/B of library builds over the digest workloads: kernel time (HIP events, best and mean of `reps`) and a checksum of every
 placement row, so that two builds can be compared for speed AND for identical results in one gpurun call.
 usage: python profiles/ab_probe.py <workload,workload,...> [reps=3]      (library: SIMON_HIP_LIB, see profiles/build_variant.sh)
+AB_PLACEMENT=0 runs without the placement matrix (no step records, no unpermute): the checksum then covers the counts and sums only.
 workloads: c5s256 c5s2048 c5s64 c3 c3s64 c2 widemix typical service64 service shapes30 c5shapes80 c5asdrawn c5asdrawn64 c5service c3sig200 c3cls80 c3cls160"""
 import hashlib
 import os
@@ -55,6 +56,7 @@ def main():
     names = sys.argv[1].split(",")
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
     lib = os.environ.get("SIMON_HIP_LIB", "libsimon_hip.so")
+    placement = os.environ.get("AB_PLACEMENT", "1") != "0"
     for name in names:
         t0 = time.perf_counter()
         prob, scen, orders = build(name)
@@ -64,15 +66,16 @@ def main():
             ctx.load_scenarios(scen, orders)
             ts = []
             for _ in range(reps + 1):
-                ctx.run_loaded(True)
+                ctx.run_loaded(placement)
                 ts.append(ctx.stats().kernel_ms)
             st = ctx.stats()
-            res = ctx.fetch(True)
+            res = ctx.fetch(placement)
         h = hashlib.sha256()
-        h.update(np.ascontiguousarray(res.placement).tobytes())
+        if placement:
+            h.update(np.ascontiguousarray(res.placement).tobytes())
         h.update(np.ascontiguousarray(res.unscheduled).tobytes())
         h.update(np.ascontiguousarray(res.used_cpu).tobytes())
-        print(f"AB {os.path.basename(lib)} {name}: S={len(scen)} gen={st.kernel_generation} var={st.kernel_variant} wg={st.workgroup_size} "
+        print(f"AB {os.path.basename(lib)} {name}{'' if placement else ' (no placement)'}: S={len(scen)} gen={st.kernel_generation} var={st.kernel_variant} wg={st.workgroup_size} "
               f"lds={st.lds_bytes} best_ms={min(ts[1:]):.3f} mean_ms={np.mean(ts[1:]):.3f} unsched_sum={int(res.unscheduled.sum())} "
               f"sha={h.hexdigest()[:16]} (build {t_build:.1f}s)", flush=True)
 
