@@ -449,6 +449,35 @@ int simon_set_scenario_nodes(simon_ctx* ctx, const uint32_t* present /* [S][(N+3
  * node-subset batch is in effect. */
 int simon_set_pod_eviction(simon_ctx* ctx, const uint8_t* evict /* [P] */);
 
+/* Pod-subset batches: the workload itself varies by scenario -- which of these apps fit on the cluster together, what has to be left
+ * out, how many new nodes each release combination costs.  Scenario s holds pod p iff bit (p & 31) of present[s][p >> 5] is set (by
+ * POD ID, not by stream position) AND its gate admits it (the prefix rule gate_node < n_nodes, or "the scenario holds gate_node" in a
+ * segmented / node-subset batch).  An absent pod is not fed to the scheduler: placement SIMON_GATED, no AddPod, no Reserve, not counted
+ * in unscheduled, the used sums, gpu_slices or simon_fetch_preempt_risk -- whether it is preset, pinned, gated or flagged with
+ * simon_set_pod_eviction (it is neither bound nor rescheduled).  The scenario's stream is the loaded order restricted to its pods.  A
+ * scenario holding no pod is legal: unscheduled 0, used sums = the state before the stream.
+ * Orthogonal to the node dimension: the rows survive simon_set_node_ranks, simon_set_scenario_segments and simon_set_scenario_nodes and
+ * may be set before or after them; the refusals of those calls and simon_load_scenarios' "preset to a node the smallest scenario lacks"
+ * are unchanged (they do not look at the rows).  Call after simon_load_scenarios (which clears the rows, as simon_load_pods does);
+ * NULL detaches.  SIMON_EINVAL: a bit set at or beyond P.  SIMON_ESTATE: nothing loaded.  A call that fails leaves the batch as it was.
+ * simon_run_loaded honours the rows on every kernel route and adds no refusal; a run with rows loaded stores the placement matrix
+ * whatever want_placement says (as priorities do).  simon_explain_loaded, simon_explain_batch and simon_explain_own_batch replay a
+ * scenario with its row; simon_explain refuses (SIMON_ESTATE) while rows are loaded: an ad-hoc scenario has no row, as with ranks.
+ * simon_min_plan* and simon_fetch_preempt_risk keep their definitions.  The words travel to the device as given (S x ceil(P / 32) u32).
+ * Not covered: no simon_group_* forward and no Go shim; no replica-level subsets within one app on the Python side (ScheduleApp's
+ * unstable sorts order an app's pods by list length, so a shorter replica list is not a restriction of the longer one's stream).
+ * (additive: the ABI stays 7) */
+int simon_set_scenario_pods(simon_ctx* ctx, const uint32_t* present /* [S][(P+31)/32], pod p = bit (p & 31) of word p >> 5 */);
+
+/* Per scenario of the last run and per pod group (an app, a Deployment): the pods left unscheduled and the pods placed, computed on the
+ * device from the placement matrix -- S x G counters come back instead of S x P placements.  pod_group[p] in [0, G) or -1 (not
+ * counted).  A pod that is not part of a scenario (SIMON_GATED) counts in neither array.  placed may be NULL.
+ * SIMON_ESTATE without a run that stored placements (SIMON_WANT_PLACEMENT, priorities or pod rows loaded).  SIMON_EINVAL: G outside
+ * [1, SIMON_MAX_POD_GROUPS], a group id outside [-1, G).  No simon_group_* forward and no Go shim.  (additive: the ABI stays 7) */
+#define SIMON_MAX_POD_GROUPS 1024
+int simon_fetch_group_counts(simon_ctx* ctx, const int32_t* pod_group /* [P] */, int32_t G,
+                             int32_t* unscheduled /* [S][G] */, int32_t* placed /* [S][G], may be NULL */);
+
 /* The rank rows in effect, rank[s][j] = position of pool node j in scenario s's canonical order: the caller's (simon_set_node_ranks) or
  * those of a segmented / node-subset batch, where nodes a scenario lacks read N.  SIMON_ESTATE for a batch without rank rows. */
 int simon_fetch_node_ranks(simon_ctx* ctx, int32_t* rank /* [S][N] */);

@@ -26,6 +26,7 @@ ESTATE = -1      # SIMON_ESTATE (SimonError.code)
 EINVAL = -22     # SIMON_EINVAL
 MAX_SEGMENTS = 8 # SIMON_MAX_SEGMENTS
 MAX_ZONES = 64 # SIMON_MAX_ZONES
+MAX_POD_GROUPS = 1024 # SIMON_MAX_POD_GROUPS
 
 FAIL_STATIC = 0x8000
 REASON_NODE_AFFINITY = 3
@@ -474,6 +475,8 @@ class BatchResult:
     used_vg: Optional[np.ndarray] = None
     gpu_slices: Optional[np.ndarray] = None        # [S][P] uint64: byte d = gpu-mem slices booked on device d (gpu_ids_of)
     preempt_risk: Optional[np.ndarray] = None      # [S] uint8 (oracle runs; the library: Context.fetch_preempt_risk)
+    group_unscheduled: Optional[np.ndarray] = None # [S][G] int32: pods of group g left unscheduled (Context.fetch_group_counts; engines fill it on request)
+    group_placed: Optional[np.ndarray] = None      # [S][G] int32: pods of group g placed
 
     def c_out(self) -> BatchOut:
         o = BatchOut()
@@ -540,6 +543,7 @@ EXPORTS = [
     "simon_group_set_scalar_entries", "simon_group_set_pod_priorities", "simon_group_fetch_preempt_risk",
     "simon_set_image_locality", "simon_group_set_image_locality",
     "simon_set_scenario_segments", "simon_set_scenario_nodes", "simon_fetch_node_ranks", "simon_set_pod_eviction",
+    "simon_set_scenario_pods", "simon_fetch_group_counts",
     "simon_group_create", "simon_group_destroy", "simon_group_last_error", "simon_group_size", "simon_group_member",
     "simon_group_load_nodes", "simon_group_load_pods", "simon_group_load_class_tables", "simon_group_load_scenarios",
     "simon_group_run_loaded", "simon_group_fetch_results", "simon_group_run_batch", "simon_group_fetch_placement", "simon_group_fetch_gpu_slices",
@@ -583,6 +587,10 @@ def load_library(path: Optional[str] = None):
     lib.simon_fetch_node_ranks.argtypes = [vp, _p32]
     lib.simon_set_pod_eviction.argtypes = [vp, C.POINTER(C.c_uint8)]
     lib.simon_set_pod_eviction.restype = C.c_int
+    lib.simon_set_scenario_pods.argtypes = [vp, C.POINTER(C.c_uint32)]
+    lib.simon_set_scenario_pods.restype = C.c_int
+    lib.simon_fetch_group_counts.argtypes = [vp, _p32, C.c_int32, _p32, _p32]
+    lib.simon_fetch_group_counts.restype = C.c_int
     lib.simon_min_plan.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(Plan)]
     lib.simon_min_plan_vg.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Plan), C.POINTER(C.c_int32)]
     lib.simon_explain.argtypes = [vp, Scenario, _p32, _p32, _pu16, C.c_int32]
@@ -826,6 +834,42 @@ class Context:
         if e.shape != (self.problem.n_pods,):
             raise ValueError(f"evict has shape {e.shape}, the problem {self.problem.n_pods} pods")
         self._check(self.lib.simon_set_pod_eviction(self.h, _ptr(e, C.c_uint8)), "simon_set_pod_eviction")
+
+    def set_scenario_pods(self, present) -> None:
+        """Pod subsets: scenario s holds pod p iff present[s][p] (bool [S][P], or the packed uint32 words [S][ceil(P / 32)]) and its gate
+        admits it; an absent pod reads GATED and is counted nowhere (include/simon_hip.h: simon_set_scenario_pods).  After load_scenarios,
+        before or after the node rows; None detaches."""
+        if present is None:
+            self._check(self.lib.simon_set_scenario_pods(self.h, None), "simon_set_scenario_pods")
+            return
+        P = self.problem.n_pods
+        a = np.asarray(present)
+        if a.dtype == np.uint32:
+            words = np.ascontiguousarray(a)
+            if words.ndim != 2 or words.shape[1] != (P + 31) // 32:
+                raise ValueError(f"packed pod rows have shape {words.shape}, the problem {(P + 31) // 32} words per scenario")
+        else:
+            if a.ndim != 2 or a.shape[1] != P:
+                raise ValueError(f"pod rows have shape {a.shape}, the problem {P} pods")
+            words = presence_words(a)
+            if words.shape[1] == 0:
+                words = np.zeros((len(a), 0), np.uint32)
+        if len(words) != self.S:
+            raise ValueError(f"{len(words)} pod rows for {self.S} loaded scenarios")
+        self._check(self.lib.simon_set_scenario_pods(self.h, _ptr(words, C.c_uint32)), "simon_set_scenario_pods")
+
+    def fetch_group_counts(self, pod_group, G: int, placed: bool = False):
+        """simon_fetch_group_counts: per scenario of the last run and pod group, the pods left unscheduled [S][G] -- and with placed=True
+        the pair (unscheduled, placed).  pod_group [P] in [0, G) or -1 (not counted)."""
+        g = np.ascontiguousarray(pod_group, dtype=np.int32)
+        if g.shape != (self.problem.n_pods,):
+            raise ValueError(f"pod_group has shape {g.shape}, the problem {self.problem.n_pods} pods")
+        cells = (self.S, max(int(G), 0))
+        uns = np.zeros(cells, np.int32)
+        pl = np.zeros(cells, np.int32) if placed else None
+        self._check(self.lib.simon_fetch_group_counts(self.h, _ptr(g, C.c_int32), int(G), _ptr(uns, C.c_int32), _ptr(pl, C.c_int32)),
+                    "simon_fetch_group_counts")
+        return (uns, pl) if placed else uns
 
     def fetch_node_ranks(self) -> np.ndarray:
         """[S][N] the rank rows in effect (nodes a segmented / node-subset scenario lacks: N); SIMON_ESTATE for a batch without rows."""

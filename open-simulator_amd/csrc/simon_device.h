@@ -57,6 +57,10 @@ struct NarrowArgs {
     int64_t* __restrict__ used_cpu;        // [S]
     int64_t* __restrict__ used_mem;        // [S]
     int32_t* __restrict__ placement;       // [S][P] by pod id, or nullptr
+    // pod-subset batch (simon_set_scenario_pods): pod p is part of scenario s iff bit (p & 31) of pod_present[s * pp_words + (p >> 5)].
+    // nullptr = no rows: every scenario holds every pod (narrow_kernel: PODSETS = false)
+    const uint32_t* __restrict__ pod_present;
+    int32_t pp_words;
 };
 
 // ---- wave64 reductions on DPP (gfx9 row/bank permutes; result is wave-uniform) -----------------

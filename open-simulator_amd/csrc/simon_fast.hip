@@ -62,9 +62,12 @@ __device__ __forceinline__ int la_term_f(double r, double rc100) {
 struct FastScalars {
     int32_t mask_words, Cn, Cp, P, S;
     uint64_t g_cpu, g_mem;
+    const uint32_t* pod_present;   // pod-subset batch (simon_set_scenario_pods): presence bits by pod id, row s at s * pp_words; nullptr = no rows (fast_kernel: PODSETS = false)
+    int32_t pp_words;              // row stride in words
 };
 
-template <int T, int SLOTS, bool HAS_MASK, bool NZEQ>
+// PODSETS: a pod-subset batch (simon_set_scenario_pods); a template parameter, so that batches without rows run the loop they always ran
+template <int T, int SLOTS, bool HAS_MASK, bool NZEQ, bool PODSETS>
 __global__ __launch_bounds__(T) void fast_kernel(
     const uint32_t* __restrict__ a_cpu, const uint32_t* __restrict__ a_mem, const int32_t* __restrict__ a_pods,
     const int32_t* __restrict__ ncls, const uint32_t* __restrict__ i_rq_cpu, const uint32_t* __restrict__ i_rq_mem,
@@ -162,15 +165,20 @@ __global__ __launch_bounds__(T) void fast_kernel(
     int pid_next = P > 0 ? order[0] : 0;
     PodRowF row_next = pods[pid_next];
     int pid_next2 = P > 1 ? order[1] : 0;
+    // pod-subset batch: the scenario's presence word of the pod travels with its row (wave-uniform, one load per pod)
+    const uint32_t* __restrict__ const prow = PODSETS ? sc.pod_present + (size_t)s * sc.pp_words : nullptr;
+    unsigned pw_next = PODSETS ? prow[pid_next >> 5] : ~0u;
 
     for (int i = 0; i < P; ++i) {
         const int pid = pid_next;
         const PodRowF row = row_next;
+        const unsigned pw = pw_next;
         pid_next = pid_next2;
         row_next = pods[pid_next];
+        if constexpr (PODSETS) pw_next = prow[pid_next >> 5];
         pid_next2 = (i + 2 < P) ? order[i + 2] : 0;
 
-        if (row.gate >= n) {
+        if ((PODSETS ? (((pw >> (pid & 31)) & 1u) ? row.gate : 0x7fffffff) : row.gate) >= n) {   // pod not part of this scenario: gated out, or absent from its pod row
             if (place && tid == 0) place[pid] = -2;
             continue;
         }
@@ -322,9 +330,11 @@ struct FastLaunch {
 
 template <int T, int SLOTS, bool M, bool Z>
 static void launch_one(const FastLaunch& a, size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL((fast_kernel<T, SLOTS, M, Z>), dim3(a.sc.S), dim3(T), lds, st, a.a_cpu, a.a_mem, a.a_pods, a.ncls,
-                       a.i_rq_cpu, a.i_rq_mem, a.i_nz_cpu, a.i_nz_mem, a.i_npods, a.pods, a.orders, a.scen, a.perm,
-                       a.static_mask, a.simon_raw, a.unscheduled, a.used_cpu, a.used_mem, a.placement, a.sc);
+#define SIMON_F(PS) hipLaunchKernelGGL((fast_kernel<T, SLOTS, M, Z, PS>), dim3(a.sc.S), dim3(T), lds, st, a.a_cpu, a.a_mem, a.a_pods, a.ncls, \
+                                      a.i_rq_cpu, a.i_rq_mem, a.i_nz_cpu, a.i_nz_mem, a.i_npods, a.pods, a.orders, a.scen, a.perm,            \
+                                      a.static_mask, a.simon_raw, a.unscheduled, a.used_cpu, a.used_mem, a.placement, a.sc)
+    if (a.sc.pod_present) SIMON_F(true); else SIMON_F(false);
+#undef SIMON_F
 }
 
 template <int T, int SLOTS>

@@ -13,6 +13,7 @@
 #include "simon_wide.h"
 #include "simon_table.h"
 #include "simon_subset.h"
+#include "simon_podsets.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -28,7 +29,7 @@
 
 namespace simon {
 struct PodRowF { double req_c, req_m, nz_c, nz_m; int32_t cls, preset, gate; uint32_t flags; };
-struct FastScalars { int32_t mask_words, Cn, Cp, P, S; uint64_t g_cpu, g_mem; };
+struct FastScalars { int32_t mask_words, Cn, Cp, P, S; uint64_t g_cpu, g_mem; const uint32_t* pod_present; int32_t pp_words; };
 struct FastLaunch {
     const uint32_t *a_cpu, *a_mem; const int32_t *a_pods, *ncls; const uint32_t *i_rq_cpu, *i_rq_mem, *i_nz_cpu, *i_nz_mem;
     const int32_t* i_npods; const PodRowF* pods; const int32_t* orders; const ScenarioDesc* scen; const int32_t* perm;
@@ -202,6 +203,13 @@ struct simon_ctx : simon::HostInputs {
     // any other pod.  evict_short: a flagged pod whose node the loaded PREFIX batch lacks (-1: none) -- such a batch waits for its node rows
     std::vector<uint8_t> p_evict;
     int evict_short = -1;
+    // pod-subset batch (simon_set_scenario_pods): scenario s holds pod p iff bit p & 31 of pod_words[s][pod_W] word p >> 5 (by pod id); the
+    // words go to the device as given.  Orthogonal to the node dimension: survives ranks, segments and node subsets; cleared by
+    // simon_load_scenarios and simon_load_pods.  d_pod_group / d_grp_*: simon_fetch_group_counts' staging
+    bool pods_on = false;
+    int pod_W = 0;
+    DevBuf<uint32_t> d_pod_words;
+    DevBuf<int32_t> d_pod_group, d_grp_uns, d_grp_placed;
     bool orders_perm = false;                     // every loaded order is a permutation of [0, P) (the score-table kernel's placement gather)
     std::vector<int64_t> prefix_cpu, prefix_mem;   // [N+1] allocatable of the first n nodes
     std::vector<int64_t> prefix_vg;   // [N+1] Open-Local VG capacity of the first n nodes (0 without local storage)
@@ -1595,6 +1603,9 @@ void fill_register_args(const simon_ctx* c, bool want_placement, Args& a) {
     a.placement = want_placement ? c->d_place.p : nullptr;
 }
 
+// the presence rows of a pod-subset batch (simon_set_scenario_pods), or null
+inline const uint32_t* pod_rows(const simon_ctx* c) { return c->pods_on ? c->d_pod_words.p : nullptr; }
+
 }  // namespace
 
 // ============================================================================================
@@ -1766,6 +1777,7 @@ int simon_load_pods(simon_ctx* c, const simon_pods_soa* pd) {
     }
     c->p_entries.clear(); c->p_priority.clear(); c->init_min_priority = 0x7fffffff;   // (ABI v6 additions: set after the pods)
     c->p_evict.clear(); c->evict_short = -1;
+    c->pods_on = false;
     c->have_pods = true; c->staged = false; c->have_results = false;
     return SIMON_OK;
 }
@@ -2057,6 +2069,7 @@ static int table_layout(simon_ctx* c) {
 int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, const int32_t* orders, int32_t n_orders) {
     if (!c || !scen || S <= 0 || !orders || n_orders <= 0) return c ? fail(c, SIMON_EINVAL, "load_scenarios: bad arguments") : SIMON_EINVAL;
     c->seg_n = 0; c->sub_on = false;                     // (segments and node subsets belong to the batch they were set for)
+    c->pods_on = false;                                  // (and so do pod rows)
     if (c->has_img) {                    // ImageLocality: one slot per distinct cluster size; another set of sizes re-stages the tables
         std::vector<int32_t> sizes(S);
         for (int s = 0; s < S; ++s) sizes[s] = scen[s].n_nodes;
@@ -2432,6 +2445,46 @@ int simon_fetch_node_ranks(simon_ctx* c, int32_t* rank) {
     return SIMON_OK;
 }
 
+// Pod-subset batches: the presence words go to the device as given ([S][ceil(P / 32)] u32); every kernel tests the pod's bit next to its gate.
+int simon_set_scenario_pods(simon_ctx* c, const uint32_t* present) {
+    if (!c) return SIMON_EINVAL;
+    if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "set_scenario_pods: load scenarios first");
+    if (!present) { c->pods_on = false; c->have_results = false; return SIMON_OK; }
+    const int S = c->S, P = c->P, W = pod_row_words(P);
+    int bit = 0;
+    if (const int s = pod_rows_first_bad(present, S, P, &bit); s >= 0)
+        return fail(c, SIMON_EINVAL, "set_scenario_pods: scenario %d sets bit %d, the problem has %d pods", s, bit, P);
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<uint32_t> words(present, present + (size_t)S * W);
+    DevBuf<uint32_t> fresh;                                      // (a failed upload leaves the batch as it was)
+    HIP_TRY(c, fresh.upload(words, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::swap(c->d_pod_words.p, fresh.p); std::swap(c->d_pod_words.n, fresh.n);
+    c->pod_W = W;
+    c->pods_on = true;
+    c->have_results = false;
+    return SIMON_OK;
+}
+
+int simon_fetch_group_counts(simon_ctx* c, const int32_t* pod_group, int32_t G, int32_t* unscheduled, int32_t* placed) {
+    if (!c || !pod_group || !unscheduled) return c ? fail(c, SIMON_EINVAL, "fetch_group_counts: bad arguments") : SIMON_EINVAL;
+    if (G < 1 || G > SIMON_MAX_POD_GROUPS) return fail(c, SIMON_EINVAL, "fetch_group_counts: %d groups outside [1, %d]", G, SIMON_MAX_POD_GROUPS);
+    if (const int p = pod_groups_first_bad(pod_group, c->P, G); p >= 0)
+        return fail(c, SIMON_EINVAL, "fetch_group_counts: pod %d has group %d outside [-1, %d)", p, pod_group[p], G);
+    if (!c->have_results || !c->have_placement) return fail(c, SIMON_ESTATE, "fetch_group_counts: no placements on device (run with SIMON_WANT_PLACEMENT)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t S = c->S, P = c->P, cells = S * (size_t)G;
+    HIP_TRY(c, c->d_pod_group.ensure(P));
+    HIP_TRY(c, c->d_grp_uns.ensure(cells));
+    if (placed) HIP_TRY(c, c->d_grp_placed.ensure(cells));
+    HIP_TRY(c, hipMemcpyAsync(c->d_pod_group.p, pod_group, P * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, launch_group_counts(c->d_place.p, c->d_pod_group.p, (int)S, (int)P, G, c->d_grp_uns.p, placed ? c->d_grp_placed.p : nullptr, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(unscheduled, c->d_grp_uns.p, cells * 4, hipMemcpyDeviceToHost, c->stream));
+    if (placed) HIP_TRY(c, hipMemcpyAsync(placed, c->d_grp_placed.p, cells * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));                 // (simon_stats is left alone: d2h_ms stays the last result fetch's)
+    return SIMON_OK;
+}
+
 // The all-feature kernel gives every problem its failure codes and runs the batches no other kernel takes: staged on first use where
 // stage() chose another kernel.
 static int ensure_wide_staged(simon_ctx* c) {
@@ -2544,7 +2597,7 @@ static int run_wide_batch(simon_ctx* c, const BatchRoute& r, bool want_placement
         return wide_run(c->wide, *c, reinterpret_cast<const WideScenario*>(c->d_scen.p), c->S, c->d_orders.p, c->max_n, r.T, c->d_unsched.p,
                         c->d_used_cpu.p, c->d_used_mem.p, c->d_used_vg.p, want_placement ? c->d_place.p : nullptr,
                         c->has_ranks ? c->d_node_rank.p : nullptr, c->has_ranks ? c->d_node_inv.p : nullptr,
-                        want_slices ? c->d_gpu_slices.p : nullptr, c->stream, c->err);
+                        want_slices ? c->d_gpu_slices.p : nullptr, c->stream, c->err, pod_rows(c), c->pod_W);
     });
 }
 
@@ -2562,6 +2615,7 @@ static TableCold table_cold(const simon_ctx* c, bool want_slices) {
     cold.na_raw = c->has_na ? c->d_t_na.p : nullptr; cold.tt_raw = c->has_tt ? c->d_t_tt.p : nullptr; cold.add_raw = c->has_add ? c->d_t_add.p : nullptr;
     if (c->has_ranks) { cold.rk_pos = c->d_rk_pos.p; cold.rk_rank = c->d_node_rank.p; }
     if (own_nodes(c)) cold.scls = c->d_scls.p;
+    if (c->pods_on) { cold.pod_present = c->d_pod_words.p; cold.pp_words = c->pod_W; }
     if (c->img_R > 0) { cold.img = c->d_t_img.p; cold.img_slot = c->d_img_slot.p; cold.img_stride = c->img_stride_t; }
     if (c->rest) { cold.xrows = c->d_xrows.p; cold.zdom = c->d_zdom.p; cold.xsig = c->d_xsig.p; cold.xalloc = c->d_xalloc.p; cold.i_xused = c->d_i_xused.p; cold.gsig = c->d_gsig.p; }
     if (c->rest || c->gfold) { cold.gpu_cnt = c->d_gpu_cnt.p; cold.gpu_devtot = c->d_gpu_devtot.p; cold.i_gused = c->d_i_gused.p; }
@@ -2577,7 +2631,7 @@ static TableCold table_cold(const simon_ctx* c, bool want_slices) {
 static int32_t table_static_bits(const simon_ctx* c, bool want_slices) {
     return (c->has_na ? kStNa : 0) | (c->has_tt ? kStTt : 0) | (c->has_add ? kStAdd : 0) | (want_slices ? kStGpuSlices : 0) | (c->sig_twins ? kStTwins : 0) |
            (c->fold ? kStFold : 0) | ((c->spread && (c->ipa_fold || c->hard_fold)) ? kStSpreadAff : 0) | (c->gfold ? kStGpuFold : 0) | (c->img_R > 0 ? kStImg : 0) |
-           (own_nodes(c) ? kStSegments : 0);
+           (own_nodes(c) ? kStSegments : 0) | (c->pods_on ? kStPodSets : 0);
 }
 
 static TableScalars table_scalars(const simon_ctx* c, bool want_slices) {
@@ -2672,7 +2726,7 @@ static int run_fast_batch(simon_ctx* c, const BatchRoute& r, bool want_placement
     FastLaunch f{};
     fill_register_args(c, want_placement, f);
     f.pods = c->d_podsF.p;
-    f.sc = FastScalars{(c->N + 63) / 64, c->Cn, c->Cp, c->P, c->S, c->g_cpu, c->g_mem};
+    f.sc = FastScalars{(c->N + 63) / 64, c->Cn, c->Cp, c->P, c->S, c->g_cpu, c->g_mem, pod_rows(c), c->pod_W};
     return timed_launch(c, [&] { HIP_TRY(c, launch_fast(f, r.T, r.slots, c->has_mask, c->nzeq, r.lds, c->stream)); return (int)SIMON_OK; });
 }
 
@@ -2682,6 +2736,7 @@ static int run_narrow_batch(simon_ctx* c, const BatchRoute& r, bool want_placeme
     a.pods = c->d_podsN.p;
     a.mask_words = (c->N + 63) / 64; a.Cn = c->Cn; a.Cp = c->Cp; a.P = c->P; a.S = c->S;
     a.g_cpu = c->g_cpu; a.g_mem = c->g_mem;
+    a.pod_present = pod_rows(c); a.pp_words = c->pod_W;
     return timed_launch(c, [&] { HIP_TRY(c, launch_narrow(a, r.T, r.slots, c->has_mask, c->rcp_div, r.lds, c->stream)); return (int)SIMON_OK; });
 }
 
@@ -2695,7 +2750,8 @@ int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
     // bit 1: also record the devices Reserve books for every placed GPU pod (only problems with GPU requests have any)
     const bool want_slices = (want_placement & SIMON_WANT_GPU_SLICES) != 0 && c->has_gpu;
     const bool want_risk = !c->p_priority.empty();               // pods of unequal priority: the flags come from the placement matrix
-    const bool want_place = (want_placement & SIMON_WANT_PLACEMENT) != 0 || want_risk;
+    // (a pod-subset batch stores it too: simon_fetch_group_counts reads it)
+    const bool want_place = (want_placement & SIMON_WANT_PLACEMENT) != 0 || want_risk || c->pods_on;
     c->have_slices = false; c->have_risk = false;
     if (want_slices) {
         HIP_TRY(c, c->d_gpu_slices.ensure((size_t)S * P));
@@ -2905,6 +2961,7 @@ static int explain_impl(simon_ctx* c, int n_nodes, const int32_t* order, int32_t
     job.scen = &hs; job.S = 1; job.max_n = n_nodes;
     job.d_orders = order ? nullptr : c->d_orders.p; job.h_order = order;
     if (!order && c->has_ranks) { job.rank_row = &scenario; job.d_node_rank = c->d_node_rank.p; job.d_node_inv = c->d_node_inv.p; }
+    if (!order && c->pods_on) { job.d_pod_present = c->d_pod_words.p; job.pod_row = &scenario; job.pp_words = c->pod_W; }
     if (c->img_R > 0) {                  // ImageLocality of THIS size, whether or not the batch has it
         std::vector<unsigned char>& one = c->h_img_explain;
         one.assign((size_t)c->img_R * c->Cn, 0);
@@ -2927,6 +2984,8 @@ int simon_explain(simon_ctx* c, simon_scenario scen, const int32_t* order, int32
                   int32_t max_failed) {
     if (!c || !order || !failed_pods || !fail_codes || max_failed <= 0) return c ? fail(c, SIMON_EINVAL, "explain: bad arguments") : SIMON_EINVAL;
     if (c->sub_on) return fail(c, SIMON_ESTATE, "explain: node-subset batch loaded; explain the scenario's own problem (its nodes alone)");
+    if (c->pods_on)     // ... and no pod row
+        return fail(c, SIMON_ESTATE, "explain: per-scenario pod rows are loaded; use simon_explain_loaded(scenario index)");
     if (c->has_ranks)   // an ad-hoc scenario has no rank row: which loaded scenario's tie-break order would apply is ambiguous
         return fail(c, SIMON_ESTATE, "explain: per-scenario node ranks are loaded; use simon_explain_loaded(scenario index)");
     return explain_impl(c, scen.n_nodes, order, -1, failed_pods, fail_codes, max_failed);
@@ -2968,6 +3027,7 @@ int simon_explain_batch(simon_ctx* c, const int32_t* scenarios, int32_t n_scen, 
     job.scen = hs.data(); job.S = n_scen; job.max_n = max_n; job.d_orders = c->d_orders.p;
     if (c->has_ranks) { job.rank_row = scenarios; job.d_node_rank = c->d_node_rank.p; job.d_node_inv = c->d_node_inv.p; }
     if (image) { job.d_img = c->wide.img; job.img_slot = slots.data(); }
+    if (c->pods_on) { job.d_pod_present = c->d_pod_words.p; job.pod_row = scenarios; job.pp_words = c->pod_W; }
     job.max_failed = max_failed; job.n_failed = n_failed; job.failed_pods = failed_pods;
     job.max_bins = max_bins; job.n_bins = n_bins; job.bins = bins;
     job.fail_codes = fail_codes; job.code_stride = code_stride;
@@ -2998,6 +3058,7 @@ int simon_explain_own_batch(simon_ctx* c, const int32_t* scenarios, int32_t n_sc
     WideReplay job;
     job.scen = hs.data(); job.S = n_scen; job.max_n = N; job.d_orders = c->d_orders.p; job.own = true;
     job.rank_row = scenarios; job.d_node_rank = c->d_node_rank.p; job.d_node_inv = c->d_node_inv.p;
+    if (c->pods_on) { job.d_pod_present = c->d_pod_words.p; job.pod_row = scenarios; job.pp_words = c->pod_W; }
     job.max_failed = max_failed; job.n_failed = n_failed; job.failed_pods = failed_pods;
     job.max_bins = max_bins; job.n_bins = n_bins; job.bins = bins;
     job.fail_codes = fail_codes; job.code_stride = code_stride;

@@ -20,7 +20,9 @@
 
 namespace simon {
 
-template <int T, int SLOTS, bool HAS_MASK, bool RCP_DIV>
+// PODSETS: a pod-subset batch (simon_set_scenario_pods).  A template parameter, so that batches without rows run the loop they always ran:
+// carried through the loop at run time, the presence word cost some instantiations 14 to 16 VGPRs and a wave per SIMD.
+template <int T, int SLOTS, bool HAS_MASK, bool RCP_DIV, bool PODSETS>
 __global__ __launch_bounds__(T) void narrow_kernel(const NarrowArgs A) {
     constexpr int NW = T / kWave;
     __shared__ int2 mbA[2][NW > 1 ? NW : 1];      // phase A mailboxes: (lo, hi) per wave
@@ -71,15 +73,20 @@ __global__ __launch_bounds__(T) void narrow_kernel(const NarrowArgs A) {
     int pid_next = P > 0 ? order[0] : 0;
     PodRowN row_next = A.pods[pid_next];
     int pid_next2 = P > 1 ? order[1] : 0;
+    // pod-subset batch: the scenario's presence word of the pod travels with its row (wave-uniform, one load per pod)
+    const uint32_t* __restrict__ const prow = PODSETS ? A.pod_present + (size_t)s * A.pp_words : nullptr;
+    unsigned pw_next = PODSETS ? prow[pid_next >> 5] : ~0u;
 
     for (int i = 0; i < P; ++i) {
         const int pid = pid_next;
         const PodRowN row = row_next;
+        const unsigned pw = pw_next;
         pid_next = pid_next2;
         row_next = A.pods[pid_next];
+        if constexpr (PODSETS) pw_next = prow[pid_next >> 5];
         pid_next2 = (i + 2 < P) ? order[i + 2] : 0;
 
-        if (row.gate >= n) {                       // pod not part of this scenario
+        if ((PODSETS ? (((pw >> (pid & 31)) & 1u) ? row.gate : 0x7fffffff) : row.gate) >= n) {   // pod not part of this scenario: gated out, or absent from its pod row
             if (place && tid == 0) place[pid] = -2;
             continue;
         }
@@ -204,7 +211,8 @@ __global__ __launch_bounds__(T) void narrow_kernel(const NarrowArgs A) {
 template <int T, int SLOTS>
 static hipError_t launch_ts(const NarrowArgs& a, bool has_mask, bool rcp_div, size_t lds, hipStream_t st) {
     dim3 grid(a.S), block(T);
-#define SIMON_L(M, R) hipLaunchKernelGGL((narrow_kernel<T, SLOTS, M, R>), grid, block, lds, st, a)
+#define SIMON_L(M, R) do { if (a.pod_present) hipLaunchKernelGGL((narrow_kernel<T, SLOTS, M, R, true>), grid, block, lds, st, a); \
+                          else hipLaunchKernelGGL((narrow_kernel<T, SLOTS, M, R, false>), grid, block, lds, st, a); } while (0)
     if (has_mask) { if (rcp_div) SIMON_L(true, true); else SIMON_L(true, false); }
     else { if (rcp_div) SIMON_L(false, true); else SIMON_L(false, false); }
 #undef SIMON_L

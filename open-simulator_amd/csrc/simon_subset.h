@@ -27,4 +27,11 @@ struct SubsetStage {
 // one wave per scenario on `st`; nothing is read back here
 hipError_t launch_subset_stage(const SubsetStage& a, hipStream_t st);
 
+// simon_fetch_group_counts: per scenario and pod group, the pods left unscheduled (placement == -1) and the pods placed (>= 0) -- a pod that
+// is not part of the scenario (-2) counts in neither.  placement [S][P] by pod id, pod_group [P] in [0, G) or -1 (validated by the caller),
+// unscheduled / placed [S][G] (placed may be null).  One workgroup per scenario, two G-entry histograms in LDS.
+constexpr int kMaxPodGroups = 1024;          // SIMON_MAX_POD_GROUPS
+hipError_t launch_group_counts(const int32_t* placement, const int32_t* pod_group, int S, int P, int G, int32_t* unscheduled, int32_t* placed,
+                               hipStream_t st);
+
 }  // namespace simon

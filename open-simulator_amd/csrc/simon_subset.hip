@@ -116,7 +116,37 @@ __global__ __launch_bounds__(64) void subset_stage_kernel(SubsetStage a) {
     for (int d = lane; d < Ct; d += 64) a.scls[(size_t)s * Ct + d] = s_fill[d];
 }
 
+// group_counts_kernel: the placement row and pod_group are read coalesced (8 B per pod: the kernel is HBM-bound), the two histograms live in
+// LDS behind LDS atomics and leave as rows of [S][G].
+__global__ __launch_bounds__(256) void group_counts_kernel(const int32_t* __restrict__ placement, const int32_t* __restrict__ pod_group, int P, int G,
+                                                           int32_t* __restrict__ unscheduled, int32_t* __restrict__ placed) {
+    extern __shared__ int32_t smem[];
+    int32_t* const h_uns = smem;             // [G] placement == SIMON_UNSCHEDULED
+    int32_t* const h_pl = smem + G;          // [G] placement >= 0
+    const int s = blockIdx.x, tid = threadIdx.x;
+    for (int g = tid; g < 2 * G; g += 256) smem[g] = 0;
+    __syncthreads();
+    const int32_t* __restrict__ const row = placement + (size_t)s * P;
+    for (int p = tid; p < P; p += 256) {
+        const int g = pod_group[p], v = row[p];
+        if (g < 0 || g >= G || v < -1) continue;                      // not counted; not part of the scenario (SIMON_GATED)
+        atomicAdd(v < 0 ? &h_uns[g] : &h_pl[g], 1);
+    }
+    __syncthreads();
+    for (int g = tid; g < G; g += 256) {
+        unscheduled[(size_t)s * G + g] = h_uns[g];
+        if (placed) placed[(size_t)s * G + g] = h_pl[g];
+    }
+}
+
 }  // namespace
+
+hipError_t launch_group_counts(const int32_t* placement, const int32_t* pod_group, int S, int P, int G, int32_t* unscheduled, int32_t* placed,
+                               hipStream_t st) {
+    if (S <= 0 || G <= 0 || G > kMaxPodGroups) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(group_counts_kernel, dim3((unsigned)S), dim3(256), (size_t)2 * G * sizeof(int32_t), st, placement, pod_group, P, G, unscheduled, placed);
+    return hipGetLastError();
+}
 
 hipError_t launch_subset_stage(const SubsetStage& a, hipStream_t st) {
     if (a.S <= 0 || a.N <= 0) return hipSuccess;

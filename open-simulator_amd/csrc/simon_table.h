@@ -42,6 +42,7 @@ enum TableStatic : int32_t {
     kStGpuFold = 128,    // Open-Gpu-Share folded into the table (SigRow::pad = GPU request, devices per position behind the workspace)
     kStImg = 256,        // TableCold::img present (ImageLocality)
     kStSegments = 512,   // segmented batch (TableCold::scls, ranked instantiations only)
+    kStPodSets = 1024,   // pod-subset batch (simon_set_scenario_pods): TableCold::pod_present decides, next to the gate, which pods a scenario holds
     kStClassTerms = kStNa | kStTt | kStAdd | kStImg,   // any static score table next to the Simon raw scores in the class term
 };
 
@@ -105,6 +106,9 @@ struct TableCold {
     unsigned char* pro_image;       // TableImage layout
     const int32_t* pro_seg;         // [Cn + 1] first position of a class segment in the image (classes padded to 16)
     int32_t pro_nb, pro_n;          // blocks of 16 positions in the image; node count of the scenario it holds
+    // pod-subset batch (simon_set_scenario_pods, TableScalars::static_tables & kStPodSets): [S][pp_words], pod p = bit (p & 31) of word p >> 5
+    const uint32_t* pod_present;
+    int32_t pp_words;
 };
 
 // Byte offsets inside the shared initial image of `nb` blocks: tile [nb][K][16] bytes, state [nb * 16] x 12 B, (when NonZeroRequested differs from

@@ -535,6 +535,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     // prefix of every pool segment, not a prefix of the pool.  Its per-class lists hold its own nodes alone, so the class counts come from
     // its own row (TableCold::scls) and a node is in the scenario iff its rank is below n (the host gives absent nodes rank N).
     const bool segd = RANKED && (sc.static_tables & kStSegments) != 0;
+    // pod-subset batch (simon_set_scenario_pods): a run-time flag like segd, read once -- tested per 64-step chunk in load_chunk
+    const bool podsets = (sc.static_tables & kStPodSets) != 0;
     auto cnt_at = [&](int d) -> int {                                 // nodes of class d in this scenario (the instantiations without ranks: as before)
         if constexpr (RANKED) { if (segd) return gp(cold->scls)[(size_t)s * Cn + d]; }
         return clsprefix[(size_t)n * Cn + d];
@@ -1995,16 +1997,27 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     auto load_chunk = [&](int i0) -> int4 {
         const int idx = i0 + lane;
         if (idx >= P) return make_int4((int)0x80000000, -1, 0x7fffffff, 0);
-        const PodRowC r = pods[order[idx]];
+        const int pid = order[idx];
+        const PodRowC r = pods[pid];
         // (segmented: the gate node is absent iff its rank is N -- one gather per chunk, only for gated pods of a segmented batch)
-        const bool gated_out = segd ? (r.gate >= 0 && gp(cold->rk_rank)[(size_t)s * (size_t)cold->N + r.gate] >= n) : r.gate >= n;
+        bool gated_out = segd ? (r.gate >= 0 && gp(cold->rk_rank)[(size_t)s * (size_t)cold->N + r.gate] >= n) : r.gate >= n;
+        // Pod-subset batch (simon_set_scenario_pods; static_tables & kStPodSets): the pod is part of the scenario iff its bit, by POD ID, is set in
+        // the scenario's row -- one gather per chunk, only when rows are loaded.  An absent pod travels as a pod gated out for good: z becomes the
+        // filler row's 0x7fffffff, which the cold branch below turns into res = -2 without a load of its own (and without indexing rk_rank by it).
+        int zgate = r.gate;
+        if (__builtin_expect(podsets, 0)) {
+            GPtr<const TableCold> cc = cold;
+            asm volatile("" : "+s"(cc));                               // rare paths: fetch their pointers here, not in loop-long SGPRs
+            const unsigned w = gp(cc->pod_present)[(size_t)s * (size_t)cc->pp_words + ((unsigned)pid >> 5)];
+            if (!((w >> (pid & 31)) & 1u)) { gated_out = true; zgate = 0x7fffffff; }
+        }
         bool special = gated_out || r.preset != -1;
         // A pod flagged for eviction (simon_set_pod_eviction) in a scenario that lacks its node is scheduled like any other pod
         // (scheduleOne instead of addPodToCache): the special bit goes, the pod takes the plain / REST / SPREAD path of its signature,
         // decided here for every wave of a team alike.  No flag array: in an own-nodes batch the validators leave "preset, not gated
         // out, node absent" to flagged pods alone (simon_set_scenario_nodes; a segment node is never a preset target).
         if (segd && r.preset >= 0 && !gated_out && gp(cold->rk_rank)[(size_t)s * (size_t)cold->N + r.preset] >= n) special = false;
-        return make_int4(r.sigcls | (special ? (int)0x80000000 : 0), r.preset, r.gate, r.rest);
+        return make_int4(r.sigcls | (special ? (int)0x80000000 : 0), r.preset, zgate, r.rest);
     };
     int4 nxt = load_chunk(0);
     auto load_spw = [&](int i0) -> int {                                   // REST && SPREAD: the SPREAD descriptor, by pod id (TableCold::sp_word)
@@ -2070,7 +2083,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
             const int r_preset = __builtin_amdgcn_readlane(cur.y, il), r_gate = __builtin_amdgcn_readlane(cur.z, il);
             GPtr<const TableCold> cc = cold;
             asm volatile("" : "+s"(cc));                               // rare paths: fetch their pointers here, not in loop-long SGPRs
-            if (segd ? (r_gate >= 0 && __builtin_amdgcn_readfirstlane(gp(cc->rk_rank)[(size_t)s * (size_t)cc->N + r_gate]) >= n) : r_gate >= n) {
+            // (0x7fffffff: the filler row, or a pod absent from a pod-subset scenario -- no node, so never an index into rk_rank)
+            if (segd ? (r_gate >= 0 && (r_gate == 0x7fffffff || __builtin_amdgcn_readfirstlane(gp(cc->rk_rank)[(size_t)s * (size_t)cc->N + r_gate]) >= n)) : r_gate >= n) {
                 res = -2;                                              // pod not part of this scenario
             } else if (r_preset >= 0) {                                // addPodToCache path (V/eventhandlers.go:223-236)
                 bound = true;

@@ -190,6 +190,9 @@ struct WideCold {
     // hard spread constraint e's node set and in domain d of its key ("registered", TpPairToMatchNum); written by the kernel's prologue
     // over zeros.  Appended: the offsets of the fields above are those every other instantiation was built with.
     uint8_t* own_reg; int32_t own_reg_R, own_reg_E /*domains per key at most; hard spread constraints*/;
+    // pod-subset batch (kArgPodSets, simon_set_scenario_pods): pod p is part of the launch's scenario k = scen_base + s iff bit (p & 31) of
+    // pod_present[k][p >> 5] is set.  Rows of the whole batch (a run) or gathered into launch order (a replay).  Appended, as above.
+    const uint32_t* pod_present; int32_t pp_words;
 };
 
 struct WideArgs {
@@ -225,7 +228,9 @@ constexpr uint32_t kArgGpu = 1u, kArgMask = 2u, kArgEph = 4u, kArgNzeq = 8u, kAr
                    kArgImage = 131072u,
                    // simon_explain_own_batch: a scenario holds pool node j iff its rank row says node_rank[j] < N (segmented / node-subset
                    // batches), not the prefix j < n_nodes.  Honoured by the EXPLAIN form of the full variant alone (wide_kernel: kCanOwn)
-                   kArgOwn = 262144u;
+                   kArgOwn = 262144u,
+                   // simon_set_scenario_pods: WideCold::pod_present decides, next to the gate, which pods a scenario holds
+                   kArgPodSets = 524288u;
 
 // tuning / experiment knobs: environment variables read ONCE, when the context is created (simon_ctx_create)
 struct WideKnobs {
@@ -294,7 +299,8 @@ hipError_t wide_launch_explain(const WideArgs& a, int T, size_t lds, hipStream_t
 int wide_stage(WideDevice& w, const HostInputs& in, hipStream_t st, std::string& err);
 int wide_run(WideDevice& w, const HostInputs& in, const WideScenario* d_scen, int S, const int32_t* d_orders, int max_n, int T,
              int32_t* d_unsched, int64_t* d_used_cpu, int64_t* d_used_mem, int64_t* d_used_vg, int32_t* d_place,
-             const int32_t* d_node_rank, const int32_t* d_node_inv, uint64_t* d_gpu_slices, hipStream_t st, std::string& err);
+             const int32_t* d_node_rank, const int32_t* d_node_inv, uint64_t* d_gpu_slices, hipStream_t st, std::string& err,
+             const uint32_t* d_pod_present = nullptr /*[S][pp_words] or null*/, int pp_words = 0);
 
 // One EXPLAIN launch (simon_explain, simon_explain_loaded, simon_explain_batch): the listed scenarios replayed by one workgroup each.
 // Host pointers unless named d_; everything per listed scenario is in launch order.
@@ -319,6 +325,8 @@ struct WideReplay {
     // own-nodes replay (simon_explain_own_batch): the listed scenarios hold the pool nodes their rank rows rank below N.  The rank rows are
     // required, max_n is the pool size (LDS words, code rows and the workgroup are sized by it) and code rows are indexed by pool node.
     bool own = false;
+    // pod-subset batch (simon_set_scenario_pods): the whole batch's presence rows [S_total][pp_words]; pod_row[k] = the listed scenario's row
+    const uint32_t* d_pod_present = nullptr; const int32_t* pod_row = nullptr; int pp_words = 0;
 };
 int wide_replay(WideDevice& w, const HostInputs& in, const WideReplay& job, int T, hipStream_t st, std::string& err);
 

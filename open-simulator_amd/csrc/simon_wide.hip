@@ -794,11 +794,15 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
         const int pid = next_pid;
         next_pid = (i + 1 < P) ? order[i + 1] : 0;
         WidePod p = A.pods[pid];
+        // pod-subset batch (kArgPodSets): the scenario's presence word of the pod, issued with its row (wave-uniform)
+        unsigned pw = ~0u;
+        if ((A.flags & kArgPodSets) != 0u) pw = COLD(A)->pod_present[(size_t)(A.scen_base + s) * COLD(A)->pp_words + (pid >> 5)];
         if (!LOCAL) p.flags &= ~kPodLocal;          // the Open-Local code folds away in the variants for problems without it
         if (VAR == 0) p.flags &= (kPodZero | kPodTerms | kPodFilt);
         if (kProfile && (A.flags & kArgProf) && p.cls < 0) continue;   // forces the pod row to have arrived before the timestamp
         SIMON_PROF(0);
-        if ((kCanOwn && own) ? (p.gate >= 0 && absent(p.gate)) : p.gate >= n) { if (place && tid == 0) place[pid] = SIMON_GATED; continue; }
+        const bool here = (pw >> (pid & 31)) & 1u;      // (folded into the one gate test: an absent pod is a pod gated out for good)
+        if ((kCanOwn && own) ? (!here || (p.gate >= 0 && absent(p.gate))) : (here ? p.gate : 0x7fffffff) >= n) { if (place && tid == 0) place[pid] = SIMON_GATED; continue; }
         // own: "preset, not gated out, node absent" is a pod flagged for eviction (simon_set_scenario_nodes' validator leaves nobody else):
         // scheduled like a fresh pod, as the score-table kernel's load_chunk does
         if (kCanOwn && own && p.preset >= 0 && absent(p.preset)) p.preset = -1;
@@ -2092,13 +2096,15 @@ int launch_chunks(WideDevice& w, const HostInputs& in, const WideLaunch& L, int 
 // budget, the phase profiler, used_vg / placement / gpu_slices.  Slot [0] of d_cold.
 int wide_run(WideDevice& w, const HostInputs& in, const WideScenario* d_scen, int S, const int32_t* d_orders, int max_n, int T,
              int32_t* d_unsched, int64_t* d_used_cpu, int64_t* d_used_mem, int64_t* d_used_vg, int32_t* d_place,
-             const int32_t* d_node_rank, const int32_t* d_node_inv, uint64_t* d_gpu_slices, hipStream_t st, std::string& err) {
+             const int32_t* d_node_rank, const int32_t* d_node_inv, uint64_t* d_gpu_slices, hipStream_t st, std::string& err,
+             const uint32_t* d_pod_present, int pp_words) {
     WideLaunch L;
     if (int rc = prepare(w, in, S, max_n, T, st, err, L)) return rc;
     WideArgs& a = L.a;
     WideCold& c = L.c;
     L.ranks(d_node_rank, d_node_inv);
     c.gpu_slices = d_gpu_slices;
+    if (d_pod_present) { c.pod_present = d_pod_present; c.pp_words = pp_words; a.flags |= kArgPodSets; }
     if (a.flags & kArgImage) {
         if (!w.img_slot_ext || in.img_sizes.empty()) { err = "wide kernel: image scores of the batch are not staged"; return SIMON_ESTATE; }
         c.img = w.img; c.img_slot = w.img_slot_ext;
@@ -2205,6 +2211,8 @@ int wide_replay(WideDevice& w, const HostInputs& in, const WideReplay& job, int 
                  o_bins = carve(job.bins ? rows * job.max_bins * sizeof(simon_fail_bin) : 0),
                  o_codes = carve(job.fail_codes ? cells * 2 : 0), o_detail = carve(want_detail ? cells * 4 * 8 : 0),
                  o_reg = carve(job.own ? (size_t)S * reg_E * reg_R : 0);
+    const bool podsets = job.d_pod_present && job.pod_row && job.pp_words > 0;
+    const size_t o_pods = carve(podsets ? (size_t)S * job.pp_words * 4 : 0);
     char* d = nullptr;
     if (hipError_t e = hipMalloc((void**)&d, std::max<size_t>(total, 256)); e != hipSuccess) { err = std::string("hipMalloc(explain): ") + hipGetErrorString(e); return SIMON_ENOMEM; }
     auto body = [&]() -> int {
@@ -2221,6 +2229,11 @@ int wide_replay(WideDevice& w, const HostInputs& in, const WideReplay& job, int 
                 TRY(hipMemcpyAsync(d + o_inv + (size_t)k * N * 4, job.d_node_inv + (size_t)job.rank_row[k] * N, N * 4, hipMemcpyDeviceToDevice, st));
             }
             L.ranks((const int32_t*)(d + o_rank), (const int32_t*)(d + o_inv));
+        }
+        if (podsets) {                                       // (behind the clear above: o_pods lies after o_nf)
+            for (int k = 0; k < S; ++k)
+                TRY(hipMemcpyAsync(d + o_pods + (size_t)k * job.pp_words * 4, job.d_pod_present + (size_t)job.pod_row[k] * job.pp_words, (size_t)job.pp_words * 4, hipMemcpyDeviceToDevice, st));
+            c.pod_present = (const uint32_t*)(d + o_pods); c.pp_words = job.pp_words; a.flags |= kArgPodSets;
         }
         a.scen = (const WideScenario*)(d + o_scen);
         a.orders = job.d_orders ? job.d_orders : (const int32_t*)(d + o_order);

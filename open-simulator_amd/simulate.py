@@ -27,13 +27,17 @@ class HipEngine:
     supports_scenario_segments = True         # pool segments (simon_set_scenario_segments): sweep_mix() batches node-type mixes
     supports_scenario_subsets = True          # node subsets (simon_set_scenario_nodes): sweep_failures() batches the loss of every failure domain
     supports_pod_eviction = True              # ... and reschedules the pods of the lost nodes (simon_set_pod_eviction): sweep_failures(reschedule=...)
+    supports_pod_subsets = True               # pod subsets (simon_set_scenario_pods): sweep_apps() batches the combinations of apps
 
     def __init__(self, device_id: int = 0):
         self.device_id = device_id
 
     def run(self, prob: capi.Problem, scen, orders, want_placement=True, node_ranks=None, want_gpu_slices=False,
-            segments=None, present=None, evict=None) -> capi.BatchResult:
-        """segments: (seg_start [G], counts [S][G]) -- scenario s holds the pool nodes before seg_start[0] and the first counts[s][g] of every
+            segments=None, present=None, evict=None, pod_present=None, pod_groups=None) -> capi.BatchResult:
+        """pod_present: bool [S][P] (or packed words) -- scenario s holds the pods of its row and no others (simon_set_scenario_pods; with
+        any of the node dimensions below).  pod_groups: int [P] in [0, G) or -1 -- the result carries group_unscheduled / group_placed
+        [S][G], counted on the device (simon_fetch_group_counts), and with want_placement=False no placement matrix comes back.
+        segments: (seg_start [G], counts [S][G]) -- scenario s holds the pool nodes before seg_start[0] and the first counts[s][g] of every
         segment g (sweep_mix).  present: (mask bool [S][N], node_zone [N] or None) -- scenario s holds exactly the pool nodes of its row, in
         the nodeTree order of those nodes (sweep_failures).  Neither = every scenario is a prefix of the pool; both = ValueError.
         evict: bool [P], with present only -- the node-bound pods that the scenarios without their node schedule like fresh pods."""
@@ -45,18 +49,23 @@ class HipEngine:
             ctx.load_problem(prob)
             if evict is not None:
                 ctx.set_pod_eviction(evict)
-            if node_ranks is None and segments is None and present is None:
+            if node_ranks is None and segments is None and present is None and pod_present is None and pod_groups is None:
                 res = ctx.run_batch(scen, orders, want_placement, want_gpu_slices)
             else:
                 ctx.load_scenarios(scen, orders)
+                if pod_present is not None:
+                    ctx.set_scenario_pods(pod_present)
                 if segments is not None:
                     ctx.set_scenario_segments(*segments)
                 if present is not None:
                     ctx.set_scenario_nodes(*present)
                 if node_ranks is not None:
                     ctx.set_node_ranks(node_ranks)    # per-scenario nodeTree order (clusters with several zones)
-                ctx.run_loaded(want_placement, want_gpu_slices)
+                ctx.run_loaded(want_placement or pod_groups is not None, want_gpu_slices)
                 res = ctx.fetch(want_placement, want_gpu_slices)
+                if pod_groups is not None:
+                    g = np.asarray(pod_groups, np.int32)
+                    res.group_unscheduled, res.group_placed = ctx.fetch_group_counts(g, max(int(g.max(initial=-1)) + 1, 1), placed=True)
             self.last_stats = ctx.stats()             # which kernel ran (simon_get_stats)
             if prob.priority is not None:             # pods of unequal priority: where DefaultPreemption could have acted (ABI v6)
                 res.preempt_risk = ctx.fetch_preempt_risk()
@@ -69,7 +78,8 @@ class HipEngine:
             nf, failed, codes = ctx.explain(n_nodes, order, max_failed)
             return nf, failed, codes, ctx.explain_local_detail(len(failed), n_nodes)
 
-    def explain_batch(self, prob: capi.Problem, scen, orders, node_ranks, ids, max_failed: int, max_bins: int = 32) -> List["ExplainedScenario"]:
+    def explain_batch(self, prob: capi.Problem, scen, orders, node_ranks, ids, max_failed: int, max_bins: int = 32, *,
+                      pod_present=None) -> List["ExplainedScenario"]:
         """Why the pods of scenarios `ids` of the batch (scen, orders, node_ranks) fail, many scenarios per launch (simon_explain_batch):
         per failed pod the (code, node count) histogram.  Scenarios with a pod whose histogram cannot be turned into text -- a code that
         names the node (fiterror.NODE_SPECIFIC_CODES) or more distinct codes than fit -- are listed once more for their full code rows,
@@ -81,6 +91,8 @@ class HipEngine:
         with capi.Context(self.device_id) as ctx:
             ctx.load_problem(prob)
             ctx.load_scenarios(scen, orders)
+            if pod_present is not None:              # (every listed scenario is replayed with its own pod row)
+                ctx.set_scenario_pods(pod_present)
             if node_ranks is not None:
                 ctx.set_node_ranks(node_ranks)
             out, again = [], []
@@ -104,7 +116,7 @@ class HipEngine:
             return out
 
     def explain_own_batch(self, prob: capi.Problem, scen, orders, node_ranks, ids, max_failed: int, max_bins: int = 32, *, present=None,
-                          segments=None, evict=None) -> List["ExplainedScenario"]:
+                          segments=None, evict=None, pod_present=None) -> List["ExplainedScenario"]:
         """explain_batch for a batch with pool segments or node subsets (simon_explain_own_batch), on the context shape run() gives such a
         batch: `segments` / `present` / `evict` / `node_ranks` as run() takes them.  Bins count each scenario's own nodes; the rows of the
         second pass are [failed][N], indexed by POOL node, 0 on the nodes the scenario lacks.  capi.SimonError (ESTATE) where the
@@ -124,6 +136,8 @@ class HipEngine:
                 ctx.set_scenario_segments(*segments)
             if present is not None:
                 ctx.set_scenario_nodes(*present)
+            if pod_present is not None:
+                ctx.set_scenario_pods(pod_present)
             if node_ranks is not None:
                 ctx.set_node_ranks(node_ranks)
             out, again = [], []
@@ -1226,6 +1240,259 @@ def _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why: str, r
         if reasons and names:
             lists.append(_failure_replay(cluster, apps, names, engine, reschedule) if rows[-1][0] > 0 else [])
     return _failure_result(doms, rows, caps, where, lists, False, why, moved)
+
+
+@dataclass
+class AppSweepResult:
+    """sweep_apps: which combinations of apps fit.  Scenario (u, k) = the cluster with the apps of subsets[u] and counts[k] new nodes."""
+    apps: List[str]                       # app names, in the order given
+    subsets: List[tuple]                  # per subset: indices into apps, ascending
+    counts: List[int]                     # new nodes per column
+    unscheduled: List[List[int]]          # [U][K]
+    unscheduled_by_app: List[List[List[int]]]   # [U][K][A] pods of app a left unscheduled (0 for the apps the subset lacks)
+    cpu_pct: List[List[int]]              # [U][K] occupancies (satisfyResourceSetting)
+    mem_pct: List[List[int]]
+    vg_pct: List[List[int]]
+    fits: List[List[bool]]                # [U][K] no unscheduled pod and the caps hold
+    min_count: List[Optional[int]]        # [U] the smallest count that fits, or None
+    needs_reference: List[List[bool]]     # [U][K] DefaultPreemption could have acted there (simon_fetch_preempt_risk)
+    best: Optional[int]                   # the subset of largest weight that fits with counts[0] (lowest index among equals), or None
+    maximal: List[int]                    # the subsets that fit with counts[0] and are contained in no other subset that does
+    unscheduled_pods: List[List[List[dict]]] = field(default_factory=list)   # reasons=True: [U][K] simulate()'s list of that scenario
+    batched: bool = True                  # pod-subset engine batches (False: every scenario ran as its own simulate())
+    fallback: Optional[str] = None        # why the scenarios ran one by one (None when batched); sweep_apps also warns
+
+
+class AppFallbackWarning(UserWarning):
+    """sweep_apps could not batch the scenarios and runs each as its own problem: one flatten, upload and launch per combination.  The
+    reason names what refused: an engine without pod subsets, an app whose pod list depends on the cluster size (a DaemonSet) in a way
+    that makes some scenario's own stream differ from the restricted one, an app whose pods use a StorageClass that only another app
+    defines, or an engine that refused the batch."""
+
+
+def _app_subsets(apps, subsets) -> List[tuple]:
+    A = len(apps)
+    if subsets is None:
+        if A > 12:
+            raise ValueError(f"{A} apps have 2^{A} subsets: pass the subsets to sweep (at most 12 apps are enumerated)")
+        return [tuple(a for a in range(A) if (u >> a) & 1) for u in range(1 << A)]
+    names = {a.name: i for i, a in enumerate(apps)}
+    out = []
+    for row in subsets:
+        row = list(row)
+        if len(row) == A and all(isinstance(x, (bool, np.bool_)) for x in row):
+            out.append(tuple(a for a in range(A) if row[a]))
+        else:
+            for x in row:
+                if x not in names:
+                    raise ValueError(f"subset names app {x!r}: the apps are {sorted(names)}")
+            out.append(tuple(sorted({names[x] for x in row})))
+    return out
+
+
+def _app_summary(apps, subs, counts, rows, by_app, caps, weights, why_lists, batched, fallback) -> AppSweepResult:
+    """rows[u][k] = (unscheduled, cpu_pct, mem_pct, vg_pct, needs_reference)."""
+    max_cpu, max_mem, max_vg = caps
+    fits = [[r[0] == 0 and r[1] <= max_cpu and r[2] <= max_mem and r[3] <= max_vg for r in row] for row in rows]
+    min_count = [min((counts[k] for k in range(len(counts)) if f[k]), default=None) for f in fits]
+    weight = [sum(weights[a] for a in sub) for sub in subs]
+    ok = [u for u in range(len(subs)) if fits[u][0]]
+    best = max(ok, key=lambda u: (weight[u], -u)) if ok else None
+    sets = [frozenset(s) for s in subs]
+    maximal = [u for u in ok if not any(v != u and sets[u] < sets[v] for v in ok)]
+    return AppSweepResult([a.name for a in apps], subs, list(counts), [[r[0] for r in row] for row in rows], by_app,
+                          [[r[1] for r in row] for row in rows], [[r[2] for r in row] for row in rows], [[r[3] for r in row] for row in rows],
+                          fits, min_count, [[bool(r[4]) for r in row] for row in rows], best, maximal, why_lists, batched, fallback)
+
+
+def _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, weights, reasons, why: str) -> AppSweepResult:
+    """Every scenario as its own Simulate(): the cluster, the subset's apps and its new nodes, canonical nodeTree order."""
+    import warnings
+    warnings.warn(f"sweep_apps runs {len(subs) * len(counts)} scenarios one by one ({why})", AppFallbackWarning, stacklevel=3)
+    base = list(cluster.get("Node", []))
+    rows, by_app, lists = [], [], []
+    for sub in subs:
+        mine = [apps[a] for a in sub]
+        rows.append([])
+        by_app.append([])
+        lists.append([])
+        for k in counts:
+            if k > 0 and new_node is None:
+                raise ValueError("new node is nil when adding node to cluster")
+            nodes = base + (wl.new_fake_nodes(new_node, k) if k > 0 else [])
+            pods, _ = build_stream(cluster, mine, nodes, len(nodes))
+            own = [len(wl.app_pods(apps[a].name, apps[a].resource, nodes)) for a in sub]      # (the stream: cluster pods, then app by app)
+            group = np.full(len(pods), -1, np.int64)
+            at = len(pods) - sum(own)
+            for a, n_a in zip(sub, own):
+                group[at:at + n_a] = a
+                at += n_a
+            arrival = [n["metadata"]["name"] for n in nodes]
+            nodes = [nodes[j] for j in k8s.canonical_node_order(nodes)]
+            flat = fl.flatten(nodes, pods, cluster.get("Service", []), cluster.get("ReplicaSet", []), cluster.get("StatefulSet", []),
+                              storage_classes=_storage_classes(cluster, mine), image_total=len(nodes), node_arrival_order=arrival)
+            pr = flat.problem
+            per = [0] * len(apps)
+            if not pods:
+                rows[-1].append((0, 0, 0, 0, False))
+                by_app[-1].append(per)
+                lists[-1].append([])
+                continue
+            out = engine.run(pr, np.array([[len(nodes), 0]], np.int32), np.arange(len(pods), dtype=np.int32)[None, :])
+            vg_cap = _vg_caps(pr, out)
+            rows[-1].append((int(out.unscheduled[0]), occupancy_pct(int(out.used_cpu[0]), int(pr.alloc_cpu.sum())),
+                             occupancy_pct(int(out.used_mem[0]) * 1000, int(pr.alloc_mem.sum()) * 1000),
+                             occupancy_pct(int(out.used_vg[0]), int(vg_cap.sum())) if vg_cap is not None else 0, _risk(out, 0)))
+            for a in group[(out.placement[0] == capi.UNSCHEDULED) & (group >= 0)].tolist():
+                per[a] += 1
+            by_app[-1].append(per)
+            texts = {}
+            if reasons and out.unscheduled[0] > 0 and not _risk(out, 0):
+                nf, failed, codes, detail = engine.explain(pr, len(nodes), np.arange(len(pods), dtype=np.int32), int(out.unscheduled[0]))
+                texts = _reason_texts(flat, failed, codes, detail)
+            lists[-1].append(_unscheduled_list(flat, out.placement[0], texts) if reasons else [])
+    return _app_summary(apps, subs, counts, rows, by_app, caps, weights, lists if reasons else [], False, why)
+
+
+@_gc_paused
+def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subsets=None, new_node: Optional[dict] = None,
+               counts: Sequence[int] = (0,), weights: Optional[Sequence[float]] = None, engine=None, max_cpu: int = 100, max_mem: int = 100,
+               max_vg: int = 100, reasons: bool = False, batch_scenarios: int = 4096) -> AppSweepResult:
+    """Which of these apps fit on the cluster together, what has to be left out, and how many new nodes each combination costs: scenario
+    (u, k) is simulate(cluster, [apps[a] for a in subsets[u]], new_nodes = counts[k] clones of new_node); the cluster's own pods are part
+    of every scenario.  subsets: bool rows [U][len(apps)] or lists of app names; None = every subset of at most 12 apps (4 096 scenarios per
+    count, bit a of u = app a; more apps: ValueError, name the subsets).  weights: per app, default its pod count.
+
+    All scenarios run as pod-subset batches of ONE problem -- the whole node pool and every app (sweep_batch), one presence row per
+    scenario from app membership, pod groups = apps (simon_set_scenario_pods, simon_fetch_group_counts) -- batch_scenarios per launch.
+    Why that is exact: workloads.app_pods(app.name, app.resource, pool) depends on the app and the pool only, so the stream of a subset
+    is the full stream restricted to its pods, in order; every topology term and counter counts PLACED pods only, so the pods of an
+    absent app, which are never placed, leave them alone; and the classes and signatures those pods bring cost table rows and nothing
+    else.  Where the argument does not hold the scenarios run one by one, each as its own simulate() (AppFallbackWarning, batched =
+    False): an engine without supports_pod_subsets; an app with a DaemonSet whose pod list at some size is not the pool's restricted
+    to that size (_same_stream's case); an app whose pods use a StorageClass that only another app defines (_storage_classes registers
+    them all up front); an engine that refuses the batch (SIMON_ESTATE).  Not covered: subsets of the replicas WITHIN one app --
+    ScheduleApp's unstable sorts order an app's pods by the length of the list, so a shorter replica list is not a restriction of the
+    longer one's stream."""
+    engine = engine or HipEngine()
+    apps, counts = list(apps), list(counts)
+    if not counts:
+        raise ValueError("sweep_apps needs one count at least")
+    subs = _app_subsets(apps, subsets)
+    caps = _caps(max_cpu, max_mem, max_vg)
+    base = list(cluster.get("Node", []))
+    if max(counts) > 0 and new_node is None:
+        raise ValueError("new node is nil when adding node to cluster")
+    pool = base + (wl.new_fake_nodes(new_node, max(counts)) if max(counts) > 0 else [])
+    lens = [len(wl.app_pods(a.name, a.resource, pool)) for a in apps]
+    w = [float(x) for x in weights] if weights is not None else [float(n) for n in lens]
+    if len(w) != len(apps):
+        raise ValueError(f"{len(w)} weights for {len(apps)} apps")
+    each = lambda why: _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, w, reasons, why)   # noqa: E731
+    if not getattr(engine, "supports_pod_subsets", False):
+        return each("the engine has no pod subsets")
+    # a StorageClass that one app defines and another app's pods use: in a subset without the first app the class is unknown
+    own_sc = [{sc["metadata"]["name"] for sc in a.resource.get("StorageClass", [])} for a in apps]
+    shared = {sc["metadata"]["name"] for sc in cluster.get("StorageClass", [])}
+    for a, app in enumerate(apps):
+        others = set().union(*(own_sc[b] for b in range(len(apps)) if b != a)) - own_sc[a] - shared if len(apps) > 1 else set()
+        if others and any(n in others for n in _claimed_storage_classes(app)):
+            return each(f"app {app.name} uses a StorageClass that only another app defines")
+    try:
+        batch = sweep_batch(cluster, apps, new_node, counts, ranks_ok=getattr(engine, "supports_node_ranks", True),
+                            image_batch=getattr(engine, "supports_image_locality", False))
+    except fl.Unsupported as e:
+        if "ImageLocality" not in str(e) and "node ranks" not in str(e):
+            raise
+        return each(str(e))
+    flat, pr = batch.flat, batch.flat.problem
+    P, K, A = len(flat.pods), len(counts), len(apps)
+    if P == 0:
+        return each("no pods")
+    group = np.full(P, -1, np.int32)
+    at = P - sum(lens)
+    for a, n_a in enumerate(lens):
+        group[at:at + n_a] = a
+        at += n_a
+    if any(a.resource.get("DaemonSet") for a in apps):
+        # such an app makes one pod per pool node, and ScheduleApp's unstable sorts order its pods by the length of that list: the batch
+        # stands only if at every size the app's own list is the pool's list without the pods gated at that size
+        ref = lambda p: (p["metadata"].get("namespace"), p["metadata"]["name"])                # noqa: E731
+        gate = np.asarray(pr.gate_node) if pr.gate_node is not None else np.full(P, -1)
+        for a, app in enumerate(apps):
+            if not app.resource.get("DaemonSet"):
+                continue
+            for k in counts:
+                n = len(base) + k
+                mine = [ref(flat.pods[pid]) for pid in np.flatnonzero((group == a) & (gate < n)).tolist()]
+                if mine != [ref(p) for p in wl.app_pods(app.name, app.resource, pool[:n])]:
+                    return each(f"app {app.name} holds a DaemonSet, and its pod order with {k} new nodes is not the pool's")
+    member = np.zeros((len(subs), A), bool)
+    for u, sub in enumerate(subs):
+        member[u, list(sub)] = True
+    rows_of = lambda us: np.where(group[None, :] >= 0, member[us][:, np.maximum(group, 0)], True)   # noqa: E731  (cluster pods: always present)
+    pc, pm = np.cumsum(pr.alloc_cpu), np.cumsum(pr.alloc_mem)
+    rows = [[None] * K for _ in subs]
+    by_app = [[None] * K for _ in subs]
+    lists = [[[] for _ in counts] for _ in subs]
+    per_launch = max(1, int(batch_scenarios) // K)                  # whole subsets per launch: K scenarios each
+    for lo in range(0, len(subs), per_launch):
+        us = np.arange(lo, min(lo + per_launch, len(subs)))
+        scen = np.array([[len(base) + k, 0] for _ in us for k in counts], np.int32)
+        present = np.repeat(rows_of(us), K, axis=0)
+        kw = {}
+        if batch.node_ranks is not None:
+            kw["node_ranks"] = np.tile(batch.node_ranks, (len(us), 1))
+        try:
+            out = engine.run(pr, scen, batch.orders, want_placement=reasons, pod_present=present, pod_groups=group, **kw)
+        except capi.SimonError as e:
+            if getattr(e, "code", None) != capi.ESTATE:
+                raise
+            return each(f"the engine refused the pod-subset batch: {e}")
+        vg_cap = _vg_caps(pr, out)
+        cv = np.cumsum(vg_cap) if vg_cap is not None else None
+        told: Dict[int, Dict[int, str]] = {}
+        failing = [s for s in range(len(scen)) if out.unscheduled[s] > 0 and not _risk(out, s)] if reasons else []
+        if failing and not getattr(engine, "supports_explain_batch", False):
+            # no batched explain: each failing scenario's own simulate() tells its pods and texts
+            for s in failing:
+                u, k = int(us[s // K]), s % K
+                try:
+                    lists[u][k] = simulate(cluster, [apps[a] for a in subs[u]], engine, wl.new_fake_nodes(new_node, counts[k]) if counts[k] > 0 else ()).unscheduled_pods
+                except NeedsReference:
+                    lists[u][k] = _unscheduled_list(flat, out.placement[s], {})
+            replayed = set(failing)
+            failing = []
+        else:
+            replayed = set()
+        if failing:
+            # the failing scenarios of this launch in one explain_batch call, each replayed with its own pod row
+            for e in engine.explain_batch(pr, scen, batch.orders, kw.get("node_ranks"), failing, int(max(out.unscheduled[s] for s in failing)),
+                                          pod_present=present):
+                told[e.scenario] = _reason_texts(flat, e.failed, e.rows, e.detail, [(e.n_nodes, b) for b in e.bins])
+        for i, u in enumerate(us.tolist()):
+            for k in range(K):
+                s, n = i * K + k, int(scen[i * K + k, 0])
+                rows[u][k] = (int(out.unscheduled[s]), occupancy_pct(int(out.used_cpu[s]), int(pc[n - 1])),
+                              occupancy_pct(int(out.used_mem[s]) * 1000, int(pm[n - 1]) * 1000),
+                              occupancy_pct(int(out.used_vg[s]), int(cv[n - 1])) if cv is not None else 0, _risk(out, s))
+                g = out.group_unscheduled[s]
+                by_app[u][k] = [int(g[a]) if a < len(g) else 0 for a in range(A)]
+                if reasons and s not in replayed:
+                    lists[u][k] = _unscheduled_list(flat, out.placement[s], told.get(s, {}))
+    return _app_summary(apps, subs, counts, rows, by_app, caps, w, lists if reasons else [], True, None)
+
+
+def _claimed_storage_classes(app: AppResource) -> set:
+    """StorageClass names the app's PersistentVolumeClaims and volumeClaimTemplates ask for."""
+    names = set()
+    for pvc in app.resource.get("PersistentVolumeClaim", []):
+        names.add((pvc.get("spec") or {}).get("storageClassName"))
+    for obj in app.resource.get("StatefulSet", []):
+        for t in (obj.get("spec") or {}).get("volumeClaimTemplates") or []:
+            names.add((t.get("spec") or {}).get("storageClassName"))
+    names.discard(None)
+    return names
 
 
 def load_config(path: str, base_dir: str = ".") -> dict:
