@@ -112,6 +112,7 @@ struct simon_ctx : simon::HostInputs {
     size_t pro_bytes = 0;
     int pro_nb = 0;
     bool no_shared_prologue = false;              // env SIMON_NO_SHARED_PROLOGUE: every scenario evaluates its own initial table (A/B + tests)
+    bool no_size_dispatch = false;                // env SIMON_NO_SIZE_DISPATCH: every scenario scans the launch's entries-per-lane, not its own size's (A/B + tests)
     // REST path of the score-table kernel (Open-Gpu-Share + node-level required anti-affinity): decided by choose_variant
     std::vector<int32_t> h_ncls_t, h_cls_off;    // internal node class of every node; class offsets into the per-class node lists
     DevBuf<int32_t> d_rk_ids, d_rk_pos;          // per-scenario node order for the score-table kernel (simon_set_node_ranks)
@@ -1654,6 +1655,7 @@ simon_ctx* simon_ctx_create(int device_id) {
     c->no_class_content = getenv("SIMON_TABLE_NO_CLASS_CONTENT") != nullptr;
     c->no_gpu_fold = getenv("SIMON_NO_GPU_FOLD") != nullptr;
     c->no_shared_prologue = getenv("SIMON_NO_SHARED_PROLOGUE") != nullptr;
+    c->no_size_dispatch = getenv("SIMON_NO_SIZE_DISPATCH") != nullptr;
     if (const char* e = getenv("SIMON_SUBSET_STAGE")) c->subset_host = strcmp(e, "host") == 0;   // A/B + tests: node-subset staging in host loops
     c->debug_route = getenv("SIMON_DEBUG_ROUTE") != nullptr;
     c->force_table = getenv("SIMON_FORCE_TABLE") != nullptr;         // A/B + tests: keep 257 .. 384 signatures on the score-table kernel   // A/B: node classes not split into with / without devices
@@ -2631,7 +2633,7 @@ static TableCold table_cold(const simon_ctx* c, bool want_slices) {
 static int32_t table_static_bits(const simon_ctx* c, bool want_slices) {
     return (c->has_na ? kStNa : 0) | (c->has_tt ? kStTt : 0) | (c->has_add ? kStAdd : 0) | (want_slices ? kStGpuSlices : 0) | (c->sig_twins ? kStTwins : 0) |
            (c->fold ? kStFold : 0) | ((c->spread && (c->ipa_fold || c->hard_fold)) ? kStSpreadAff : 0) | (c->gfold ? kStGpuFold : 0) | (c->img_R > 0 ? kStImg : 0) |
-           (own_nodes(c) ? kStSegments : 0) | (c->pods_on ? kStPodSets : 0);
+           (own_nodes(c) ? kStSegments : 0) | (c->pods_on ? kStPodSets : 0) | (c->no_size_dispatch ? kStOneSize : 0);
 }
 
 static TableScalars table_scalars(const simon_ctx* c, bool want_slices) {
@@ -2711,7 +2713,18 @@ static int run_table_batch(simon_ctx* c, const BatchRoute& r, bool want_placemen
     f.cls_list = c->has_ranks ? c->d_rk_ids.p : c->d_cls_list.p; f.pods = c->d_podsC.p; f.orders = c->d_orders.p; f.perm = c->d_perm.p;
     f.place_step = want_placement ? c->d_place_step.p : nullptr;
     f.ws_off = c->d_ws_off.p; f.ws = c->d_ws.p;
-    if (c->debug_route) fprintf(stderr, "[route] unit %s nzeq %d team %d prologue %s\n", table_unit_name(f), (int)f.nzeq, f.team, shared_pro ? "shared-image" : "per-scenario");
+    if (c->debug_route) {
+        // entries per lane of the launch, and the scenarios that scan fewer because their own padded size fits (table_kernel: LO)
+        char own[64] = "none";
+        if (const int lo = table_entries_own_size(f)) {
+            int fits = 0;
+            for (int s = 0; s < S; ++s) fits += c->scen_ni[s] <= 1024 * lo;
+            if (c->no_size_dispatch) snprintf(own, sizeof own, "off");
+            else snprintf(own, sizeof own, "%d of %d scenarios at %d", fits, S, lo);
+        }
+        fprintf(stderr, "[route] unit %s nzeq %d team %d prologue %s entries/lane %d (own size: %s)\n", table_unit_name(f), (int)f.nzeq, f.team,
+                shared_pro ? "shared-image" : "per-scenario", table_entries_per_lane(f), own);
+    }
     trace_segmented(c, "score-table kernel, ranked instantiation");
     if (int rc = timed_launch(c, [&] {
             if (shared_pro) HIP_TRY(c, launch_table_image(f, c->pro_nb, c->stream));

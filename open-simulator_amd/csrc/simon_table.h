@@ -43,6 +43,7 @@ enum TableStatic : int32_t {
     kStImg = 256,        // TableCold::img present (ImageLocality)
     kStSegments = 512,   // segmented batch (TableCold::scls, ranked instantiations only)
     kStPodSets = 1024,   // pod-subset batch (simon_set_scenario_pods): TableCold::pod_present decides, next to the gate, which pods a scenario holds
+    kStOneSize = 2048,   // env SIMON_NO_SIZE_DISPATCH: every scenario takes the launch's entries-per-lane, also where its kernel holds a body for fewer (table_kernel: LO)
     kStClassTerms = kStNa | kStTt | kStAdd | kStImg,   // any static score table next to the Simon raw scores in the class term
 };
 
@@ -179,6 +180,10 @@ size_t table_ws_bytes(int K, int ni, bool nzeq, bool coarse, int Cn, int M, int 
 // serves the launch (simon_table.hip: table_route)
 hipError_t launch_table(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st);
 const char* table_unit_name(const TableLaunch& a);   // the unit launch_table sends `a` to, by file name (SIMON_DEBUG_ROUTE)
+int table_entries_per_lane(const TableLaunch& a);    // summary entries per lane of the kernel launch_table picks (NBQ), from the batch's largest scenario
+// The smaller entries-per-lane the same kernel also serves, each scenario by its own padded size (table_kernel: LO); 0: none.  A scenario takes it iff
+// its padded size is at most 64 x 16 x that many positions, unless TableScalars::static_tables holds kStOneSize.
+int table_entries_own_size(const TableLaunch& a);
 // Can the launch take its initial table from the shared image (a.cold's pro_image)?  The one-level instantiations of simon_table.hip on prefix scenarios in
 // canonical order: neither ranked nor segmented.  launch_table_image fills the image (the batch's largest scenario, `nb` blocks) on `st`, ahead of launch_table.
 bool table_shared_prologue(const TableLaunch& a);

@@ -1,3 +1,5 @@
+// (Read twice: SIMON_TABLE_BODY_PASS keeps the body of table_kernel alone -- the text between the two marks inside it -- for table_body, see there.)
+#ifndef SIMON_TABLE_BODY_PASS
 // simon_table.hip -- cpu+memory scenario kernel, generations 4 to 6: one WAVE = one capacity-planning scenario over a
 // (signature, node) score table, with the class term folded into the block summaries.
 //
@@ -347,7 +349,9 @@ __device__ __forceinline__ unsigned eval_node_t(double q_req_c, double q_req_m, 
 // KQ: signatures per lane (1: K <= 64, 2: K <= 128).  HAS_PIN: the stream holds pinned pods (own instantiation: the extra
 // branch costs the common kernel time).
 // NBQ: blocks per lane (1, 2 or 4: padded scenario sizes up to 1024 / 2048 / 4096 positions) -- a template parameter so that the
-// scan is straight-line code (as run-time conditions the four reads became four dependent LDS round trips).
+// scan is straight-line code (as run-time conditions the four reads became four dependent LDS round trips).  The launch picks it from its
+// largest scenario; since round 11 the unranked one-level kernels with two entries per lane have a twin that also holds the one-entry body,
+// and a wave takes the one its own scenario fits (table_kernel with LO, behind this one) -- a choice per wave ahead of the prologue.
 // fitsRequest's ephemeral-storage and extended-resource checks (fit.go:264-299) of one request on one node: component 0 is checked
 // whatever the request, an extended resource only when the pod names it (non-zero)
 __device__ __forceinline__ bool xres_fits_t(const unsigned (&req)[5], const unsigned (&used)[5], const unsigned (&alloc)[5]) {
@@ -422,6 +426,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     const TableCold* __restrict__ cold_, const int32_t* __restrict__ cls_list_pool, const PodRowC* __restrict__ pods,
     const int32_t* __restrict__ orders, const int32_t* __restrict__ perm, const unsigned long long* __restrict__ ws_off,
     int32_t* __restrict__ place_step, unsigned char* ws, const TableScalars sc) {
+#endif  // !SIMON_TABLE_BODY_PASS: from here to the mark at the end of the function, the body
     // Pointers the hot loop never touches live in a device-resident struct: as kernel arguments (24 pointers) they kept the
     // loop at the SGPR limit and spilled into VGPR lanes.
     GPtr<const TableCold> const cold = gp(cold_);
@@ -2225,6 +2230,52 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         gp(cold->used_cpu)[s] = uc * (long long)sc.g_cpu;
         gp(cold->used_mem)[s] = um * (long long)sc.g_mem;
     }
+#ifndef SIMON_TABLE_BODY_PASS   // the end of the body
+}
+
+// The same body as a function, for the entries that hold TWO bodies (below): this file read once more, the body alone.  Not a function under every
+// kernel: built that way, the same text compiled to another schedule and other register figures in half of the base unit's kernels.
+template <bool HAS_MASK, bool NZEQ, bool HAS_PIN, int KQ, int NBQ, bool COARSE, bool REST, bool RANKED, bool AFF, bool MANY, bool SPREAD, int NW, bool LDSWS, bool LDSX, bool CN2>
+__device__ __forceinline__ void table_body(
+    const TableCold* __restrict__ cold_, const int32_t* __restrict__ cls_list_pool, const PodRowC* __restrict__ pods,
+    const int32_t* __restrict__ orders, const int32_t* __restrict__ perm, const unsigned long long* __restrict__ ws_off,
+    int32_t* __restrict__ place_step, unsigned char* ws, const TableScalars sc) {
+#define SIMON_TABLE_BODY_PASS
+#include "simon_table.hip"
+#undef SIMON_TABLE_BODY_PASS
+}
+
+// The smaller entries-per-lane a one-level launch of NBQ entries per lane also serves (0: none).  Round 11: NBQ is picked once per launch, from the
+// batch's largest scenario, and a sweep over cluster sizes that crosses 1 024 padded positions used to run the two-entry scan -- a second LDS read,
+// key and tie-check term per cycle, all of them on the duplicate of entry 0 -- on every smaller scenario as well.  The unranked one-level kernels of
+// the base unit alone (the flagship's route): every other launch keeps the kernel above.
+constexpr int table_lo_entries(bool coarse, bool ranked, int nbq) { return (!coarse && !ranked && nbq == 2) ? 1 : 0; }
+
+// table_kernel with two bodies (LO: a further template argument, no default -- the kernels above keep their names).  The wave first derives its
+// scenario's padded size (prologue 1's class counts, summed; the body repeats the scan for the segment offsets) and runs the body instantiated for LO
+// entries per lane when the scenario fits it (nblk <= 64 LO), else the NBQ body.  Wave-uniform, once per wave; the two bodies share the kernel
+// arguments and nothing else.  The LDS carve (tcarve: row pitch nbp), the workspace offsets and the launch order stay those of ni_max for either body.
+// kStOneSize (SIMON_NO_SIZE_DISPATCH) sends every scenario to the NBQ body.
+template <bool HAS_MASK, bool NZEQ, bool HAS_PIN, int KQ, int NBQ, bool COARSE, bool REST, bool RANKED, bool AFF, bool MANY, bool SPREAD, int NW, bool LDSWS, bool LDSX, bool CN2, int LO>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1))) void table_kernel(
+    const TableCold* __restrict__ cold_, const int32_t* __restrict__ cls_list_pool, const PodRowC* __restrict__ pods,
+    const int32_t* __restrict__ orders, const int32_t* __restrict__ perm, const unsigned long long* __restrict__ ws_off,
+    int32_t* __restrict__ place_step, unsigned char* ws, const TableScalars sc) {
+    static_assert(LO > 0 && LO < NBQ && !COARSE && !RANKED && !REST && !SPREAD && !MANY && !LDSWS && !LDSX && !CN2 && NW == 1, "a second body: the unranked one-level kernels of the base unit");
+    if (!(sc.static_tables & kStOneSize)) {
+        GPtr<const TableCold> const cold = gp(cold_);
+        const int lane = threadIdx.x, Cn = sc.Cn;
+        const int s = __builtin_amdgcn_readfirstlane(perm[blockIdx.x]);
+        const int n = __builtin_amdgcn_readfirstlane(cold->scen[s].n_nodes);
+        GPtr<const int32_t> const clsprefix = gp(cold->clsprefix);
+        int pad = lane < Cn ? (clsprefix[(size_t)n * Cn + lane] + 15) & ~15 : 0;          // (unranked: a prefix scenario's class counts)
+        if (Cn > 64) pad += 64 + lane < Cn ? (clsprefix[(size_t)n * Cn + 64 + lane] + 15) & ~15 : 0;
+        if ((wave_sum_i32_t(pad) >> 4) <= 64 * LO) {
+            table_body<HAS_MASK, NZEQ, HAS_PIN, KQ, LO, COARSE, REST, RANKED, AFF, MANY, SPREAD, NW, LDSWS, LDSX, CN2>(cold_, cls_list_pool, pods, orders, perm, ws_off, place_step, ws, sc);
+            return;
+        }
+    }
+    table_body<HAS_MASK, NZEQ, HAS_PIN, KQ, NBQ, COARSE, REST, RANKED, AFF, MANY, SPREAD, NW, LDSWS, LDSX, CN2>(cold_, cls_list_pool, pods, orders, perm, ws_off, place_step, ws, sc);
 }
 
 // ---- host side: from a TableLaunch to one table_kernel<...> instantiation ------------------------------------------------------------
@@ -2269,7 +2320,9 @@ template <class F, class... Rest> static hipError_t with_consts(F&& f, bool b, R
 // The flags every unit derives the same way
 static OneOf<1, 2> table_kq(const TableLaunch& a) { return {a.sc.K > 64 ? 2 : 1}; }                        // signatures per lane in registers
 static OneOf<1, 2> table_nbq64(const TableLaunch& a) { return {a.sc.ni_max / 64 <= 64 ? 1 : 2}; }           // two-level: LDS entries of 64 positions per lane
-static OneOf<1, 2, 4> table_nbq16(const TableLaunch& a) { const int nblk = a.sc.ni_max / 16; return {nblk <= 64 ? 1 : nblk <= 128 ? 2 : 4}; }   // one-level: entries of 16 positions per lane
+// one-level: entries of 16 positions per lane, by the LARGEST scenario of the launch (the LDS carve and the kernel are the launch's; a scenario of at
+// most 1 024 padded positions in a two-entry launch runs that kernel's one-entry body: table_lo_entries)
+static OneOf<1, 2, 4> table_nbq16(const TableLaunch& a) { const int nblk = a.sc.ni_max / 16; return {nblk <= 64 ? 1 : nblk <= 128 ? 2 : 4}; }
 static bool table_ranked(const TableLaunch& a) { return a.sc.rk_stride != 0; }                             // per-scenario node order (a sweep over several zones)
 static bool table_folds(const TableLaunch& a) { return (a.sc.static_tables & (kStFold | kStGpuFold)) != 0; }   // (the folds are carried by COARSE && !REST && HAS_PIN: the base unit alone)
 static bool table_spread_aff(const TableLaunch& a) { return (a.sc.static_tables & kStSpreadAff) != 0; }    // preferred pod (anti-)affinity / hard zone constraints in spread_select: SPREAD && AFF
@@ -2511,6 +2564,7 @@ static hipError_t launch_table_base(const TableLaunch& a, int n_blocks, size_t l
     const OneOf<1, 2, 4> nbq = a.coarse ? OneOf<1, 2, 4>{table_nbq64(a).v} : table_nbq16(a);   // entries of 64 positions: <= 8192 padded positions; of 16: <= 4096
     return with_consts([&](auto Z, auto PIN, auto KQ, auto COARSE, auto NBQ, auto RANKED, auto MANY) -> hipError_t {
         if constexpr ((COARSE && NBQ == 4) || (MANY && !(COARSE && KQ == 2))) return hipErrorInvalidValue;
+        else if constexpr (table_lo_entries(COARSE, RANKED, NBQ) != 0) return launch_kernel(table_kernel<true, Z, PIN, KQ, NBQ, COARSE, false, RANKED, false, MANY, false, 1, false, false, false, table_lo_entries(COARSE, RANKED, NBQ)>, a, n_blocks, 1, lds_bytes, st);
         else return launch_kernel(table_kernel<true, Z, PIN, KQ, NBQ, COARSE, false, RANKED, false, MANY, false>, a, n_blocks, 1, lds_bytes, st);
     }, a.nzeq, pin, table_kq(a), a.coarse, nbq, table_ranked(a), many);
 }
@@ -2538,6 +2592,17 @@ const char* table_unit_name(const TableLaunch& a) {
     return names[(int)table_route(a)];
 }
 
+// (SIMON_DEBUG_ROUTE; the units restate their own choice of NBQ)
+int table_entries_per_lane(const TableLaunch& a) {
+    const TableUnit u = table_route(a);
+    if (u == TableUnit::Cls4) return 4;
+    if ((u == TableUnit::Team || u == TableUnit::Rs || u == TableUnit::Spread) && table_many(a)) return 2;
+    return a.coarse ? table_nbq64(a).v : table_nbq16(a).v;
+}
+int table_entries_own_size(const TableLaunch& a) {
+    return table_base_unit(a) ? table_lo_entries(a.coarse, table_ranked(a), table_entries_per_lane(a)) : 0;
+}
+
 hipError_t launch_table(const TableLaunch& a, int n_blocks, size_t lds_bytes, hipStream_t st) {
     switch (table_route(a)) {
         case TableUnit::Team: return a.team == kTeamWaves ? launch_table_team4(a, n_blocks, lds_bytes, st) : hipErrorInvalidValue;
@@ -2556,3 +2621,4 @@ hipError_t launch_table(const TableLaunch& a, int n_blocks, size_t lds_bytes, hi
 #endif  // SIMON_TABLE_TEAM_TU
 
 }  // namespace simon
+#endif  // !SIMON_TABLE_BODY_PASS
