@@ -478,6 +478,48 @@ int simon_set_scenario_pods(simon_ctx* ctx, const uint32_t* present /* [S][(P+31
 int simon_fetch_group_counts(simon_ctx* ctx, const int32_t* pod_group /* [P] */, int32_t G,
                              int32_t* unscheduled /* [S][G] */, int32_t* placed /* [S][G], may be NULL */);
 
+/* Per-node usage and headroom of the last run's scenarios, reduced on the device from the placement matrix (which stays there).  Both
+ * calls require what simon_fetch_group_counts requires: a run that stored placements (otherwise SIMON_ESTATE) and the pods, nodes and
+ * class tables that run used, still loaded (a reload since the run: SIMON_ESTATE).  A scenario HOLDS pool node j when j < n_nodes
+ * (prefix batch) or rank[s][j] < N in the rank rows in effect (segmented / node-subset batch, as simon_explain_own_batch reads them).
+ *
+ * simon_fetch_node_usage: the table `simon apply` ends with (pkg/apply/apply.go:315-400, reportClusterInfo), for the n listed scenarios
+ * (any order, repeats allowed, NULL = scenarios 0 .. n-1).  For a node j the scenario holds:
+ *   req_r[j] = init_req_r[j] + sum of req_r[p] over the pods with placement[s][p] == j (preset pods included: their placement is
+ *   their preset node), npods[j] = init_npods[j] + the number of those pods; pods that read SIMON_UNSCHEDULED or SIMON_GATED
+ *   contribute nothing.  For a node the scenario lacks the quantities are 0 and npods is -1.  Summed over a scenario's nodes, req_cpu /
+ *   req_mem give simon_batch_out.used_cpu / used_mem.
+ *
+ * simon_fetch_headroom: how many more pods like pod p_k would still fit in every scenario.  The probe uses that pod's request row (cpu,
+ * memory, ephemeral storage, scalars and its simon_set_scalar_entries bits) and its class's static_mask row:
+ *   fit[s][k] = sum of cap(s, j, k) over the nodes j that scenario s holds and whose static_mask[class(p_k)][j] bit is set,
+ *   cap = the largest m >= 0 such that m further pods of that request pass fitsRequest (V/framework/plugins/noderesources/fit.go:230-302)
+ *   on the node's end state: pod slots alloc_pods - npods; per requested resource floor((alloc_r - req_r) / q_r); a resource of
+ *   quantity 0 (past the all-zero shortcut) only demands alloc_r >= req_r, so an over-committed node has cap 0; with the all-zero
+ *   shortcut (no cpu, memory, ephemeral storage and no scalar ENTRY) the pod slots are the only bound; a scalar entry of quantity 0
+ *   disables the shortcut (the ABI v6 rule).  fit_nodes[s][k] counts the nodes with cap > 0.  All arithmetic is exact int64.
+ * exact[k] = 1 iff the probe pod has no GPU request, pin or preset and its class has empty match, anti, port, aff and spread_hard
+ * lists and no Open-Local spec.  When exact is 1, fit is the number of such pods the scheduler would place after the stream (nodes are
+ * independent and scores cannot change a count).  When exact is 0, fit is the resource-and-static-filter upper bound.
+ * SIMON_EINVAL: n < 1, a scenario id outside [0, S), a missing required output array (req_cpu, req_mem, npods, fit), a wrong
+ * struct_size, K outside [1, SIMON_MAX_PROBES], a pod id outside [0, P).  A failed call leaves results and batch alone.
+ * The node range is tiled to the LDS budget (env SIMON_USAGE_TILE=<nodes> overrides the tile, read once in simon_ctx_create).
+ * Not covered: GPU-share device usage (gpu_slices x gpu_mem per device) and Open-Local VG / device usage per node (exact is 0 for such
+ * probes); probes that are not pods of the loaded stream; no simon_group_* forward and no Go shim.  (additive: the ABI stays 7) */
+typedef struct simon_node_usage {
+    uint32_t struct_size;
+    int64_t* req_cpu;      /* [n][N] Requested.MilliCPU of pool node j at the end of listed scenario i */
+    int64_t* req_mem;      /* [n][N] */
+    int64_t* req_eph;      /* [n][N] optional */
+    int64_t* scalar_req;   /* [n][K][N] optional */
+    int32_t* npods;        /* [n][N] len(NodeInfo.Pods); -1 = the scenario does not hold node j */
+} simon_node_usage;
+int simon_fetch_node_usage(simon_ctx* ctx, const int32_t* scen_ids /* [n], NULL = 0..n-1 */, int32_t n, simon_node_usage* out);
+
+int simon_fetch_headroom(simon_ctx* ctx, const int32_t* probe_pod /* [K] pod ids */, int32_t K,
+                         int64_t* fit /* [S][K] */, int32_t* fit_nodes /* [S][K], may be NULL */, uint8_t* exact /* [K], may be NULL */);
+#define SIMON_MAX_PROBES 64
+
 /* The rank rows in effect, rank[s][j] = position of pool node j in scenario s's canonical order: the caller's (simon_set_node_ranks) or
  * those of a segmented / node-subset batch, where nodes a scenario lacks read N.  SIMON_ESTATE for a batch without rank rows. */
 int simon_fetch_node_ranks(simon_ctx* ctx, int32_t* rank /* [S][N] */);

@@ -27,6 +27,7 @@ EINVAL = -22     # SIMON_EINVAL
 MAX_SEGMENTS = 8 # SIMON_MAX_SEGMENTS
 MAX_ZONES = 64 # SIMON_MAX_ZONES
 MAX_POD_GROUPS = 1024 # SIMON_MAX_POD_GROUPS
+MAX_PROBES = 64 # SIMON_MAX_PROBES
 
 FAIL_STATIC = 0x8000
 REASON_NODE_AFFINITY = 3
@@ -477,6 +478,9 @@ class BatchResult:
     preempt_risk: Optional[np.ndarray] = None      # [S] uint8 (oracle runs; the library: Context.fetch_preempt_risk)
     group_unscheduled: Optional[np.ndarray] = None # [S][G] int32: pods of group g left unscheduled (Context.fetch_group_counts; engines fill it on request)
     group_placed: Optional[np.ndarray] = None      # [S][G] int32: pods of group g placed
+    headroom: Optional[np.ndarray] = None          # [S][K] int64: further pods like probe k that fit (Context.fetch_headroom; engines fill it on request)
+    headroom_exact: Optional[np.ndarray] = None    # [K] bool: headroom[:, k] is what the scheduler would place, not an upper bound
+    node_usage: Optional["NodeUsage"] = None       # per-node end state of the listed scenarios (Context.fetch_node_usage; on request)
 
     def c_out(self) -> BatchOut:
         o = BatchOut()
@@ -495,6 +499,21 @@ class BatchResult:
         return BatchResult(np.zeros(S, np.int32), np.zeros(S, np.int64), np.zeros(S, np.int64),
                            np.full((S, P), -9, np.int32) if want_placement else None, np.zeros(S, np.int64),
                            np.zeros((S, P), np.uint64) if want_gpu_slices else None)
+
+
+@dataclass
+class NodeUsage:
+    """simon_fetch_node_usage: the per-node end state of the listed scenarios (row i = scenarios[i], column j = pool node j)."""
+    scenarios: np.ndarray               # [n] the indices as listed
+    req_cpu: np.ndarray                 # [n][N] int64 Requested.MilliCPU
+    req_mem: np.ndarray                 # [n][N] int64
+    npods: np.ndarray                   # [n][N] int32 len(NodeInfo.Pods); -1 = the scenario does not hold node j
+    req_eph: Optional[np.ndarray] = None      # [n][N] int64, on request
+    scalar_req: Optional[np.ndarray] = None   # [n][K][N] int64, on request
+
+
+class NodeUsageC(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("req_cpu", _p64), ("req_mem", _p64), ("req_eph", _p64), ("scalar_req", _p64), ("npods", _p32)]
 
 
 WANT_PLACEMENT, WANT_GPU_SLICES = 1, 2
@@ -543,7 +562,7 @@ EXPORTS = [
     "simon_group_set_scalar_entries", "simon_group_set_pod_priorities", "simon_group_fetch_preempt_risk",
     "simon_set_image_locality", "simon_group_set_image_locality",
     "simon_set_scenario_segments", "simon_set_scenario_nodes", "simon_fetch_node_ranks", "simon_set_pod_eviction",
-    "simon_set_scenario_pods", "simon_fetch_group_counts",
+    "simon_set_scenario_pods", "simon_fetch_group_counts", "simon_fetch_node_usage", "simon_fetch_headroom",
     "simon_group_create", "simon_group_destroy", "simon_group_last_error", "simon_group_size", "simon_group_member",
     "simon_group_load_nodes", "simon_group_load_pods", "simon_group_load_class_tables", "simon_group_load_scenarios",
     "simon_group_run_loaded", "simon_group_fetch_results", "simon_group_run_batch", "simon_group_fetch_placement", "simon_group_fetch_gpu_slices",
@@ -591,6 +610,10 @@ def load_library(path: Optional[str] = None):
     lib.simon_set_scenario_pods.restype = C.c_int
     lib.simon_fetch_group_counts.argtypes = [vp, _p32, C.c_int32, _p32, _p32]
     lib.simon_fetch_group_counts.restype = C.c_int
+    lib.simon_fetch_node_usage.argtypes = [vp, _p32, C.c_int32, C.POINTER(NodeUsageC)]
+    lib.simon_fetch_node_usage.restype = C.c_int
+    lib.simon_fetch_headroom.argtypes = [vp, _p32, C.c_int32, _p64, _p32, C.POINTER(C.c_uint8)]
+    lib.simon_fetch_headroom.restype = C.c_int
     lib.simon_min_plan.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(Plan)]
     lib.simon_min_plan_vg.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Plan), C.POINTER(C.c_int32)]
     lib.simon_explain.argtypes = [vp, Scenario, _p32, _p32, _pu16, C.c_int32]
@@ -870,6 +893,35 @@ class Context:
         self._check(self.lib.simon_fetch_group_counts(self.h, _ptr(g, C.c_int32), int(G), _ptr(uns, C.c_int32), _ptr(pl, C.c_int32)),
                     "simon_fetch_group_counts")
         return (uns, pl) if placed else uns
+
+    def fetch_node_usage(self, scen_ids=None, eph: bool = False, scalars: bool = False) -> NodeUsage:
+        """simon_fetch_node_usage: requested cpu / memory (ephemeral storage, scalars on request) and pod count of every pool node at the
+        end of the listed scenarios of the last run (None: all of them), reduced on the device from the placement matrix."""
+        ids = np.arange(self.S, dtype=np.int32) if scen_ids is None else np.ascontiguousarray(scen_ids, dtype=np.int32).reshape(-1)
+        n, N, K = len(ids), self.problem.n_nodes, 0 if self.problem.scalar_alloc is None else int(np.asarray(self.problem.scalar_alloc).shape[0])
+        res = NodeUsage(ids, np.zeros((n, N), np.int64), np.zeros((n, N), np.int64), np.zeros((n, N), np.int32),
+                        np.zeros((n, N), np.int64) if eph else None, np.zeros((n, K, N), np.int64) if scalars else None)
+        o = NodeUsageC()
+        o.struct_size = C.sizeof(NodeUsageC)
+        o.req_cpu, o.req_mem, o.npods = _ptr(res.req_cpu, C.c_int64), _ptr(res.req_mem, C.c_int64), _ptr(res.npods, C.c_int32)
+        o.req_eph = _ptr(res.req_eph, C.c_int64)
+        o.scalar_req = _ptr(res.scalar_req if scalars and K else None, C.c_int64)
+        self._check(self.lib.simon_fetch_node_usage(self.h, None if scen_ids is None else _ptr(ids, C.c_int32), n, C.byref(o)),
+                    "simon_fetch_node_usage")
+        return res
+
+    def fetch_headroom(self, probe_pods, nodes: bool = False):
+        """simon_fetch_headroom: (fit [S][K] int64, fit_nodes [S][K] int32 or None, exact [K] bool) -- how many more pods like pod
+        probe_pods[k] fit in every scenario of the last run, on how many nodes, and whether that count is what the scheduler would place
+        (exact) or the resource-and-static-filter upper bound."""
+        pp = np.ascontiguousarray(probe_pods, dtype=np.int32).reshape(-1)
+        K = len(pp)
+        fit = np.zeros((self.S, K), np.int64)
+        fn = np.zeros((self.S, K), np.int32) if nodes else None
+        ex = np.zeros(K, np.uint8)
+        self._check(self.lib.simon_fetch_headroom(self.h, _ptr(pp, C.c_int32), K, _ptr(fit, C.c_int64), _ptr(fn, C.c_int32), _ptr(ex, C.c_uint8)),
+                    "simon_fetch_headroom")
+        return fit, fn, ex.astype(bool)
 
     def fetch_node_ranks(self) -> np.ndarray:
         """[S][N] the rank rows in effect (nodes a segmented / node-subset scenario lacks: N); SIMON_ESTATE for a batch without rows."""

@@ -211,6 +211,16 @@ struct simon_ctx : simon::HostInputs {
     int pod_W = 0;
     DevBuf<uint32_t> d_pod_words;
     DevBuf<int32_t> d_pod_group, d_grp_uns, d_grp_placed;
+    // simon_fetch_node_usage / simon_fetch_headroom: compact int64 copies of the pod requests and the node rows ([kUsageRows][P] / [N]),
+    // uploaded on the first call after simon_load_pods / simon_load_nodes; usage_rows: bit r = some pod requests resource row r (cpu and
+    // memory always), the rows the kernels accumulate.  usage_tile: env SIMON_USAGE_TILE (nodes per LDS tile; 0 = from the LDS budget)
+    bool usage_pods_staged = false, usage_nodes_staged = false;
+    uint32_t usage_rows = 3;
+    int usage_tile = 0;
+    DevBuf<int64_t> d_u_pod_req, d_u_node_init, d_u_node_alloc, d_u_out64, d_u_fit;
+    DevBuf<int32_t> d_u_init_npods, d_u_alloc_pods, d_u_ids, d_u_npods, d_u_fit_nodes;
+    DevBuf<ProbeRow> d_u_probes;
+    DevBuf<uint64_t> d_u_probe_mask;
     bool orders_perm = false;                     // every loaded order is a permutation of [0, P) (the score-table kernel's placement gather)
     std::vector<int64_t> prefix_cpu, prefix_mem;   // [N+1] allocatable of the first n nodes
     std::vector<int64_t> prefix_vg;   // [N+1] Open-Local VG capacity of the first n nodes (0 without local storage)
@@ -1657,6 +1667,7 @@ simon_ctx* simon_ctx_create(int device_id) {
     c->no_shared_prologue = getenv("SIMON_NO_SHARED_PROLOGUE") != nullptr;
     c->no_size_dispatch = getenv("SIMON_NO_SIZE_DISPATCH") != nullptr;
     if (const char* e = getenv("SIMON_SUBSET_STAGE")) c->subset_host = strcmp(e, "host") == 0;   // A/B + tests: node-subset staging in host loops
+    if (const char* e = getenv("SIMON_USAGE_TILE")) c->usage_tile = std::max(atoi(e), 0);        // tests: node tiles of simon_fetch_node_usage / _headroom
     c->debug_route = getenv("SIMON_DEBUG_ROUTE") != nullptr;
     c->force_table = getenv("SIMON_FORCE_TABLE") != nullptr;         // A/B + tests: keep 257 .. 384 signatures on the score-table kernel   // A/B: node classes not split into with / without devices
 #ifdef SIMON_TABLE_PROFILE
@@ -1739,6 +1750,7 @@ int simon_load_nodes(simon_ctx* c, const simon_nodes_soa* nd) {
             if (d < -1 || d >= c->topo_n_dom[k]) return fail(c, SIMON_EINVAL, "topo_dom[%d][%d] out of range", k, j);
         }
     c->have_nodes = true; c->staged = false; c->have_results = false;
+    c->usage_nodes_staged = false;
     return SIMON_OK;
 }
 
@@ -1781,6 +1793,7 @@ int simon_load_pods(simon_ctx* c, const simon_pods_soa* pd) {
     c->p_evict.clear(); c->evict_short = -1;
     c->pods_on = false;
     c->have_pods = true; c->staged = false; c->have_results = false;
+    c->usage_pods_staged = false;
     return SIMON_OK;
 }
 
@@ -2484,6 +2497,152 @@ int simon_fetch_group_counts(simon_ctx* c, const int32_t* pod_group, int32_t G, 
     HIP_TRY(c, hipMemcpyAsync(unscheduled, c->d_grp_uns.p, cells * 4, hipMemcpyDeviceToHost, c->stream));
     if (placed) HIP_TRY(c, hipMemcpyAsync(placed, c->d_grp_placed.p, cells * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));                 // (simon_stats is left alone: d2h_ms stays the last result fetch's)
+    return SIMON_OK;
+}
+
+// ---- simon_fetch_node_usage / simon_fetch_headroom ----
+// The compact int64 copies both kernels read (the per-family pod rows are normalised: not usable here), uploaded on the first call after
+// a reload, and the launch arguments the two calls share.
+static int usage_stage(simon_ctx* c, UsageCommon& a) {
+    const size_t P = c->P, N = c->N;
+    const int K = c->K;
+    if (!c->usage_pods_staged) {
+        std::vector<int64_t> h((size_t)kUsageRows * std::max<size_t>(P, 1), 0);
+        c->usage_rows = 3;
+        for (size_t p = 0; p < P; ++p) {
+            h[p] = c->p_req_cpu[p]; h[P + p] = c->p_req_mem[p]; h[2 * P + p] = c->p_req_eph[p];
+            if (c->p_req_eph[p] != 0) c->usage_rows |= 4u;
+            for (int k = 0; k < K; ++k)
+                if ((h[(3 + k) * P + p] = c->p_scalar[(size_t)k * P + p]) != 0) c->usage_rows |= 8u << k;
+        }
+        HIP_TRY(c, c->d_u_pod_req.upload(h, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));             // (h leaves scope)
+        c->usage_pods_staged = true;
+    }
+    if (!c->usage_nodes_staged) {
+        std::vector<int64_t> init((size_t)kUsageRows * N, 0), alloc((size_t)kUsageRows * N, 0);
+        for (size_t j = 0; j < N; ++j) {
+            init[j] = c->i_req_cpu[j]; init[N + j] = c->i_req_mem[j]; init[2 * N + j] = c->i_req_eph[j];
+            alloc[j] = c->alloc_cpu[j]; alloc[N + j] = c->alloc_mem[j]; alloc[2 * N + j] = c->alloc_eph[j];
+            for (int k = 0; k < K; ++k) {
+                init[(3 + k) * N + j] = c->i_scalar_req[(size_t)k * N + j];
+                alloc[(3 + k) * N + j] = c->scalar_alloc[(size_t)k * N + j];
+            }
+        }
+        HIP_TRY(c, c->d_u_node_init.upload(init, c->stream));
+        HIP_TRY(c, c->d_u_node_alloc.upload(alloc, c->stream));
+        HIP_TRY(c, c->d_u_init_npods.upload(c->i_npods, c->stream));
+        HIP_TRY(c, c->d_u_alloc_pods.upload(c->alloc_pods, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->usage_nodes_staged = true;
+    }
+    a.placement = c->d_place.p; a.scen = reinterpret_cast<const int32_t*>(c->d_scen.p);
+    a.rank = own_nodes(c) && c->has_ranks ? c->d_node_rank.p : nullptr;
+    a.pod_req = c->d_u_pod_req.p; a.node_init = c->d_u_node_init.p; a.init_npods = c->d_u_init_npods.p;
+    a.P = c->P; a.N = c->N;
+    return SIMON_OK;
+}
+
+// the rows a launch of `blocks` workgroups accumulates: `rows` (bits over the resource rows) in ascending order, and the node tile for
+// them -- the LDS budget's (four workgroups per CU), or, where the launch puts at most one workgroup on a CU anyway, the largest that
+// fits a workgroup (fewer passes over the placement row: config 5's 256 scenarios, profiles/usage/README.md)
+static void usage_rows_of(const simon_ctx* c, uint32_t rows, UsageCommon& a, int blocks) {
+    a.nrows = 0;
+    for (int r = 0; r < kUsageRows; ++r)
+        if ((rows >> r) & 1u) a.row_src[a.nrows++] = r;
+    for (int i = a.nrows; i < kUsageRows; ++i) a.row_src[i] = -1;
+    a.tile = usage_tile(c->N, a.nrows, c->usage_tile ? c->usage_tile : blocks <= c->n_cus ? 1 << 30 : 0);
+}
+
+static_assert(sizeof(ScenarioDesc) == 8, "the usage kernels read ScenarioDesc as int32 pairs");
+
+int simon_fetch_node_usage(simon_ctx* c, const int32_t* scen_ids, int32_t n, simon_node_usage* out) {
+    if (!c) return SIMON_EINVAL;
+    if (!out) return fail(c, SIMON_EINVAL, "fetch_node_usage: bad arguments");
+    if (out->struct_size != sizeof(simon_node_usage)) return fail(c, SIMON_EINVAL, "fetch_node_usage: simon_node_usage size mismatch");
+    if (!out->req_cpu || !out->req_mem || !out->npods) return fail(c, SIMON_EINVAL, "fetch_node_usage: missing required arrays (req_cpu, req_mem, npods)");
+    if (n < 1) return fail(c, SIMON_EINVAL, "fetch_node_usage: %d scenarios listed", n);
+    if (!c->have_results || !c->have_placement) return fail(c, SIMON_ESTATE, "fetch_node_usage: no placements on device (run with SIMON_WANT_PLACEMENT)");
+    if (!scen_ids && n > c->S) return fail(c, SIMON_EINVAL, "fetch_node_usage: scenario %d outside [0,%d)", c->S, c->S);
+    for (int i = 0; scen_ids && i < n; ++i)
+        if (scen_ids[i] < 0 || scen_ids[i] >= c->S) return fail(c, SIMON_EINVAL, "fetch_node_usage: scenario %d outside [0,%d)", scen_ids[i], c->S);
+    HIP_TRY(c, hipSetDevice(c->device));
+    UsageCommon a{};
+    if (const int rc = usage_stage(c, a)) return rc;
+    const size_t N = c->N, K = c->K, cells = (size_t)n * N;
+    const bool eph = out->req_eph != nullptr, sc = out->scalar_req != nullptr && K > 0;
+    usage_rows_of(c, 3u | (eph ? 4u : 0u) | (sc ? ((1u << K) - 1u) << 3 : 0u), a, n);
+    HIP_TRY(c, c->d_u_out64.ensure(cells * (size_t)a.nrows));
+    HIP_TRY(c, c->d_u_npods.ensure(cells));
+    UsageOut o{};
+    o.npods = c->d_u_npods.p;
+    int64_t* const d_sc = c->d_u_out64.p + cells * (2 + (eph ? 1 : 0));          // [n][K][N]
+    for (int i = 0; i < a.nrows; ++i) {
+        const int r = a.row_src[i];
+        if (r < 3) { o.rows[i] = c->d_u_out64.p + cells * i; o.row_stride[i] = N; }
+        else { o.rows[i] = d_sc + (size_t)(r - 3) * N; o.row_stride[i] = K * N; }
+    }
+    if (scen_ids) {
+        HIP_TRY(c, c->d_u_ids.ensure((size_t)n));
+        HIP_TRY(c, hipMemcpyAsync(c->d_u_ids.p, scen_ids, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        o.scen_ids = c->d_u_ids.p;
+    }
+    HIP_TRY(c, launch_node_usage(a, o, n, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out->req_cpu, o.rows[0], cells * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out->req_mem, o.rows[1], cells * 8, hipMemcpyDeviceToHost, c->stream));
+    if (eph) HIP_TRY(c, hipMemcpyAsync(out->req_eph, o.rows[2], cells * 8, hipMemcpyDeviceToHost, c->stream));
+    if (sc) HIP_TRY(c, hipMemcpyAsync(out->scalar_req, d_sc, cells * K * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out->npods, c->d_u_npods.p, cells * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));                 // (simon_stats is left alone, as in simon_fetch_group_counts)
+    return SIMON_OK;
+}
+
+int simon_fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int64_t* fit, int32_t* fit_nodes, uint8_t* exact) {
+    if (!c) return SIMON_EINVAL;
+    if (!probe_pod || !fit) return fail(c, SIMON_EINVAL, "fetch_headroom: missing required arrays (probe_pod, fit)");
+    if (K < 1 || K > SIMON_MAX_PROBES) return fail(c, SIMON_EINVAL, "fetch_headroom: %d probes outside [1, %d]", K, SIMON_MAX_PROBES);
+    if (!c->have_results || !c->have_placement) return fail(c, SIMON_ESTATE, "fetch_headroom: no placements on device (run with SIMON_WANT_PLACEMENT)");
+    for (int k = 0; k < K; ++k)
+        if (probe_pod[k] < 0 || probe_pod[k] >= c->P) return fail(c, SIMON_EINVAL, "fetch_headroom: probe %d: pod %d outside [0,%d)", k, probe_pod[k], c->P);
+    HIP_TRY(c, hipSetDevice(c->device));
+    UsageCommon a{};
+    if (const int rc = usage_stage(c, a)) return rc;
+    usage_rows_of(c, c->usage_rows, a, c->S);
+    // the probe rows: request, the resources fitsRequest compares (fit.go:244-299), the class's static mask
+    const size_t S = c->S, N = c->N, W = (N + 63) / 64, P = c->P;
+    std::vector<ProbeRow> rows((size_t)K);
+    std::vector<uint64_t> mask((size_t)K * W, ~0ull);
+    auto none = [](const std::vector<int32_t>& off, int cls) { return (size_t)cls + 1 >= off.size() || off[cls + 1] == off[cls]; };
+    for (int k = 0; k < K; ++k) {
+        const int p = probe_pod[k], cls = c->p_cls[p];
+        ProbeRow& r = rows[k];
+        r = ProbeRow{};
+        r.q[0] = c->p_req_cpu[p]; r.q[1] = c->p_req_mem[p]; r.q[2] = c->p_req_eph[p];
+        uint32_t entries = c->p_entries.empty() ? 0u : c->p_entries[p];
+        for (int i = 0; i < c->K; ++i) {
+            r.q[3 + i] = c->p_scalar[(size_t)i * P + p];
+            if (r.q[3 + i] != 0) entries |= 1u << i;             // a non-zero quantity IS an entry
+        }
+        const bool shortcut = r.q[0] == 0 && r.q[1] == 0 && r.q[2] == 0 && entries == 0;
+        r.checked = shortcut ? 0u : 7u | ((entries & ((1u << c->K) - 1u)) << 3);
+        if (c->has_mask) std::copy_n(c->static_mask.data() + (size_t)cls * W, W, mask.data() + (size_t)k * W);
+        if (exact)
+            exact[k] = c->p_gpu_mem[p] == 0 && c->p_gpu_cnt[p] == 0 && c->p_gpu_index[p] == 0 && c->p_pin[p] < 0 && c->p_preset[p] < 0 &&
+                       none(c->match_off, cls) && none(c->anti_off, cls) && none(c->port_off, cls) && none(c->aff_off, cls) && none(c->sh_off, cls) &&
+                       ((size_t)cls >= c->l_spec_of.size() || c->l_spec_of[cls] < 0);
+    }
+    HeadroomArgs h{};
+    const size_t cells = S * (size_t)K;
+    HIP_TRY(c, c->d_u_probes.upload(rows, c->stream));
+    HIP_TRY(c, c->d_u_probe_mask.upload(mask, c->stream));
+    HIP_TRY(c, c->d_u_fit.ensure(cells));
+    if (fit_nodes) HIP_TRY(c, c->d_u_fit_nodes.ensure(cells));
+    h.node_alloc = c->d_u_node_alloc.p; h.alloc_pods = c->d_u_alloc_pods.p; h.probes = c->d_u_probes.p; h.probe_mask = c->d_u_probe_mask.p;
+    h.K = K; h.fit = c->d_u_fit.p; h.fit_nodes = fit_nodes ? c->d_u_fit_nodes.p : nullptr;
+    HIP_TRY(c, launch_headroom(a, h, (int)S, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(fit, c->d_u_fit.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
+    if (fit_nodes) HIP_TRY(c, hipMemcpyAsync(fit_nodes, c->d_u_fit_nodes.p, cells * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));                 // (also: rows and mask outlive their uploads)
     return SIMON_OK;
 }
 

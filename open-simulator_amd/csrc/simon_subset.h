@@ -34,4 +34,60 @@ constexpr int kMaxPodGroups = 1024;          // SIMON_MAX_POD_GROUPS
 hipError_t launch_group_counts(const int32_t* placement, const int32_t* pod_group, int S, int P, int G, int32_t* unscheduled, int32_t* placed,
                                hipStream_t st);
 
+// simon_fetch_node_usage / simon_fetch_headroom: the placement matrix reduced over the node dimension.  One 256-thread workgroup per
+// scenario accumulates, per tile of `tile` pool nodes, the request sums and pod counts of the pods placed on the tile's nodes in LDS
+// (LDS atomics; integer sums, so the result does not depend on the order), re-reading the placement row per tile.  Resource rows:
+// 0 cpu, 1 memory, 2 ephemeral storage, 3 + k scalar k; pod_req [kUsageRows][P] and node_init / node_alloc [kUsageRows][N] are compact
+// int64 copies of the caller's arrays (rows the problem lacks are zero).  A scenario holds node j iff rank ? rank[s][j] < N : j < n_nodes.
+constexpr int kUsageMaxScalar = 4;           // SIMON_MAX_SCALAR
+constexpr int kUsageRows = 3 + kUsageMaxScalar;
+constexpr int kMaxProbes = 64;               // SIMON_MAX_PROBES
+constexpr size_t kUsageLdsBudget = 40 * 1024;   // default tile: the largest multiple of 64 nodes whose rows fit (four workgroups per CU)
+
+struct UsageCommon {
+    const int32_t* placement;                // [S][P] by pod id
+    const int32_t* scen;                     // [S][2] ScenarioDesc: n_nodes, order_id
+    const int32_t* rank;                     // [S][N] rank rows of an own-nodes batch, or nullptr = prefix scenarios
+    const int64_t* pod_req;                  // [kUsageRows][P]
+    const int64_t* node_init;                // [kUsageRows][N] requested before the stream
+    const int32_t* init_npods;               // [N]
+    int32_t P, N, tile;
+    int32_t nrows;                           // accumulated rows
+    int32_t row_src[kUsageRows];             // their resource row (ascending)
+};
+
+struct UsageOut {
+    const int32_t* scen_ids;                 // [n] listed scenarios, or nullptr = 0 .. n-1
+    int64_t* rows[kUsageRows];               // per accumulated row i: [n][N]  (scalars: the caller's [n][K][N] is written with stride_n)
+    size_t row_stride[kUsageRows];           // elements between two listed scenarios of row i
+    int32_t* npods;                          // [n][N]
+};
+
+struct ProbeRow {                            // one probe of simon_fetch_headroom
+    int64_t q[kUsageRows];                   // its request
+    uint32_t checked;                        // bit r: fitsRequest compares resource row r (0 = the all-zero shortcut: pod slots only)
+    uint32_t pad;
+};
+
+struct HeadroomArgs {
+    const int64_t* node_alloc;               // [kUsageRows][N]
+    const int32_t* alloc_pods;               // [N]
+    const ProbeRow* probes;                  // [K]
+    const uint64_t* probe_mask;              // [K][ceil(N / 64)] static_mask row of every probe's class
+    int32_t K;
+    int64_t* fit;                            // [S][K]
+    int32_t* fit_nodes;                      // [S][K] or nullptr
+};
+
+// bytes of LDS one node of a tile costs, and the tile the launchers use for N nodes (`forced` > 0: SIMON_USAGE_TILE)
+inline size_t usage_node_bytes(int nrows) { return (size_t)nrows * 8 + 4; }
+inline int usage_tile(int N, int nrows, int forced) {
+    int t = forced > 0 ? forced : (int)(kUsageLdsBudget / usage_node_bytes(nrows)) / 64 * 64;
+    const int cap = (int)((64 * 1024 - 2 * kMaxProbes * 8) / usage_node_bytes(nrows));   // (one workgroup's 64 KB, less the headroom counters)
+    t = t > cap ? cap : t;
+    return t < 1 ? 1 : (t > N ? N : t);
+}
+hipError_t launch_node_usage(const UsageCommon& a, const UsageOut& o, int n, hipStream_t st);
+hipError_t launch_headroom(const UsageCommon& a, const HeadroomArgs& h, int S, hipStream_t st);
+
 }  // namespace simon

@@ -139,7 +139,120 @@ __global__ __launch_bounds__(256) void group_counts_kernel(const int32_t* __rest
     }
 }
 
+// ---- simon_fetch_node_usage / simon_fetch_headroom ----------------------------------------------------------------------------------
+// One tile of the node range [t0, t1): s_req[i][j - t0] = request sum of accumulated row i over the pods placed on node j, s_cnt[j - t0]
+// their number.  The placement row is read coalesced; a pod whose node lies outside the tile (SIMON_UNSCHEDULED / SIMON_GATED: below 0)
+// adds nothing.  Ends behind a barrier: every thread may read the tile.
+__device__ __forceinline__ void usage_accumulate(const UsageCommon& a, const int32_t* __restrict__ row, int t0, int t1,
+                                                 unsigned long long* s_req, int32_t* s_cnt) {
+    const int tid = threadIdx.x, tile = a.tile;
+    for (int i = tid; i < a.nrows * tile; i += 256) s_req[i] = 0;
+    for (int i = tid; i < tile; i += 256) s_cnt[i] = 0;
+    __syncthreads();
+    for (int p = tid; p < a.P; p += 256) {
+        const int v = row[p];
+        if (v < t0 || v >= t1) continue;
+        atomicAdd(&s_cnt[v - t0], 1);
+        for (int i = 0; i < a.nrows; ++i) {
+            const long long q = a.pod_req[(size_t)a.row_src[i] * a.P + p];
+            if (q != 0) atomicAdd(&s_req[i * tile + (v - t0)], (unsigned long long)q);
+        }
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ bool usage_holds(const UsageCommon& a, int s, int j) {
+    return a.rank ? a.rank[(size_t)s * a.N + j] < a.N : j < a.scen[2 * s];
+}
+
+// node_usage_kernel: workgroup b = listed scenario b.  Rows leave coalesced; a node the scenario lacks reads 0 / npods -1.
+__global__ __launch_bounds__(256) void node_usage_kernel(UsageCommon a, UsageOut o) {
+    extern __shared__ unsigned long long usage_smem[];
+    unsigned long long* const s_req = usage_smem;                       // [nrows][tile]
+    int32_t* const s_cnt = (int32_t*)(usage_smem + (size_t)a.nrows * a.tile);   // [tile]
+    const int b = blockIdx.x, tid = threadIdx.x, N = a.N;
+    const int s = o.scen_ids ? o.scen_ids[b] : b;
+    const int32_t* __restrict__ const row = a.placement + (size_t)s * a.P;
+    for (int t0 = 0; t0 < N; t0 += a.tile) {
+        const int t1 = min(t0 + a.tile, N);
+        usage_accumulate(a, row, t0, t1, s_req, s_cnt);
+        for (int j = t0 + tid; j < t1; j += 256) {
+            const bool in = usage_holds(a, s, j);
+            for (int i = 0; i < a.nrows; ++i)
+                o.rows[i][(size_t)b * o.row_stride[i] + j] = in ? a.node_init[(size_t)a.row_src[i] * N + j] + (long long)s_req[i * a.tile + (j - t0)] : 0;
+            o.npods[(size_t)b * N + j] = in ? a.init_npods[j] + s_cnt[j - t0] : -1;
+        }
+        __syncthreads();                                                // (the next tile zeroes what this one read)
+    }
+}
+
+// headroom_kernel: workgroup s = scenario s of the batch.  Per tile the same accumulation; then, per probe, every thread takes the cap
+// of its nodes of the tile and the workgroup adds them up in LDS.  Only [S][K] counters leave.
+__global__ __launch_bounds__(256) void headroom_kernel(UsageCommon a, HeadroomArgs h) {
+    extern __shared__ unsigned long long usage_smem[];
+    unsigned long long* const s_req = usage_smem;                       // [nrows][tile]
+    unsigned long long* const s_fit = s_req + (size_t)a.nrows * a.tile; // [K]
+    int32_t* const s_cnt = (int32_t*)(s_fit + h.K);                     // [tile]
+    int32_t* const s_nodes = s_cnt + a.tile;                            // [K]
+    const int s = blockIdx.x, tid = threadIdx.x, N = a.N, K = h.K, W = (N + 63) >> 6;
+    const int32_t* __restrict__ const row = a.placement + (size_t)s * a.P;
+    for (int k = tid; k < K; k += 256) { s_fit[k] = 0; s_nodes[k] = 0; }
+    for (int t0 = 0; t0 < N; t0 += a.tile) {
+        const int t1 = min(t0 + a.tile, N);
+        usage_accumulate(a, row, t0, t1, s_req, s_cnt);                 // (its first barrier also covers s_fit / s_nodes)
+        for (int k = 0; k < K; ++k) {
+            const ProbeRow& pr = h.probes[k];
+            const uint64_t* __restrict__ const mask = h.probe_mask + (size_t)k * W;
+            long long fit = 0;
+            int nodes = 0;
+            for (int j = t0 + tid; j < t1; j += 256) {
+                if (!((mask[j >> 6] >> (j & 63)) & 1ull) || !usage_holds(a, s, j)) continue;
+                long long cap = (long long)h.alloc_pods[j] - a.init_npods[j] - s_cnt[j - t0];      // pod slots
+                int ai = 0;                                             // (the accumulated rows are an ascending subset of the resource rows)
+                for (int r = 0; r < kUsageRows && cap > 0; ++r) {
+                    long long used = a.node_init[(size_t)r * N + j];
+                    if (ai < a.nrows && a.row_src[ai] == r) used += (long long)s_req[ai++ * a.tile + (j - t0)];
+                    if (!((pr.checked >> r) & 1u)) continue;
+                    const long long room = h.node_alloc[(size_t)r * N + j] - used, q = pr.q[r];
+                    if (room < 0) cap = 0;                              // over-committed: Allocatable < request + Requested whatever the request
+                    else if (q > 0) cap = min(cap, room / q);
+                }
+                if (cap > 0) { fit += cap; ++nodes; }
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                fit += __shfl_xor(fit, off, 64);
+                nodes += __shfl_xor(nodes, off, 64);
+            }
+            if ((tid & 63) == 0 && nodes) {
+                atomicAdd(&s_fit[k], (unsigned long long)fit);
+                atomicAdd(&s_nodes[k], nodes);
+            }
+        }
+        __syncthreads();
+    }
+    for (int k = tid; k < K; k += 256) {
+        h.fit[(size_t)s * K + k] = (long long)s_fit[k];
+        if (h.fit_nodes) h.fit_nodes[(size_t)s * K + k] = s_nodes[k];
+    }
+}
+
 }  // namespace
+
+hipError_t launch_node_usage(const UsageCommon& a, const UsageOut& o, int n, hipStream_t st) {
+    if (n <= 0 || a.N <= 0 || a.tile <= 0 || a.nrows < 2 || a.nrows > kUsageRows) return hipErrorInvalidValue;
+    const size_t lds = (size_t)a.tile * usage_node_bytes(a.nrows);
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(node_usage_kernel, dim3((unsigned)n), dim3(256), lds, st, a, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_headroom(const UsageCommon& a, const HeadroomArgs& h, int S, hipStream_t st) {
+    if (S <= 0 || a.N <= 0 || a.tile <= 0 || a.nrows < 2 || a.nrows > kUsageRows || h.K < 1 || h.K > kMaxProbes) return hipErrorInvalidValue;
+    const size_t lds = (size_t)a.tile * usage_node_bytes(a.nrows) + (size_t)h.K * 12;
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(headroom_kernel, dim3((unsigned)S), dim3(256), lds, st, a, h);
+    return hipGetLastError();
+}
 
 hipError_t launch_group_counts(const int32_t* placement, const int32_t* pod_group, int S, int P, int G, int32_t* unscheduled, int32_t* placed,
                                hipStream_t st) {

@@ -28,13 +28,17 @@ class HipEngine:
     supports_scenario_subsets = True          # node subsets (simon_set_scenario_nodes): sweep_failures() batches the loss of every failure domain
     supports_pod_eviction = True              # ... and reschedules the pods of the lost nodes (simon_set_pod_eviction): sweep_failures(reschedule=...)
     supports_pod_subsets = True               # pod subsets (simon_set_scenario_pods): sweep_apps() batches the combinations of apps
+    supports_node_usage = True                # per-node usage and headroom reduced on the device (simon_fetch_node_usage / simon_fetch_headroom)
 
     def __init__(self, device_id: int = 0):
         self.device_id = device_id
 
     def run(self, prob: capi.Problem, scen, orders, want_placement=True, node_ranks=None, want_gpu_slices=False,
-            segments=None, present=None, evict=None, pod_present=None, pod_groups=None) -> capi.BatchResult:
-        """pod_present: bool [S][P] (or packed words) -- scenario s holds the pods of its row and no others (simon_set_scenario_pods; with
+            segments=None, present=None, evict=None, pod_present=None, pod_groups=None, headroom_pods=None, usage_of=None) -> capi.BatchResult:
+        """headroom_pods: pod ids [K] -- the result carries headroom [S][K] (how many more pods like each fit in every scenario) and
+        headroom_exact [K] (simon_fetch_headroom).  usage_of: scenario indices -- the result carries node_usage, the per-node requests and
+        pod counts at the end of those scenarios (simon_fetch_node_usage).  Both are reduced on the device from the placement matrix.
+        pod_present: bool [S][P] (or packed words) -- scenario s holds the pods of its row and no others (simon_set_scenario_pods; with
         any of the node dimensions below).  pod_groups: int [P] in [0, G) or -1 -- the result carries group_unscheduled / group_placed
         [S][G], counted on the device (simon_fetch_group_counts), and with want_placement=False no placement matrix comes back.
         segments: (seg_start [G], counts [S][G]) -- scenario s holds the pool nodes before seg_start[0] and the first counts[s][g] of every
@@ -49,7 +53,8 @@ class HipEngine:
             ctx.load_problem(prob)
             if evict is not None:
                 ctx.set_pod_eviction(evict)
-            if node_ranks is None and segments is None and present is None and pod_present is None and pod_groups is None:
+            usage = headroom_pods is not None or usage_of is not None
+            if node_ranks is None and segments is None and present is None and pod_present is None and pod_groups is None and not usage:
                 res = ctx.run_batch(scen, orders, want_placement, want_gpu_slices)
             else:
                 ctx.load_scenarios(scen, orders)
@@ -61,8 +66,12 @@ class HipEngine:
                     ctx.set_scenario_nodes(*present)
                 if node_ranks is not None:
                     ctx.set_node_ranks(node_ranks)    # per-scenario nodeTree order (clusters with several zones)
-                ctx.run_loaded(want_placement or pod_groups is not None, want_gpu_slices)
+                ctx.run_loaded(want_placement or pod_groups is not None or usage, want_gpu_slices)
                 res = ctx.fetch(want_placement, want_gpu_slices)
+                if headroom_pods is not None:
+                    res.headroom, _, res.headroom_exact = ctx.fetch_headroom(headroom_pods)
+                if usage_of is not None:
+                    res.node_usage = ctx.fetch_node_usage(usage_of)
                 if pod_groups is not None:
                     g = np.asarray(pod_groups, np.int32)
                     res.group_unscheduled, res.group_placed = ctx.fetch_group_counts(g, max(int(g.max(initial=-1)) + 1, 1), placed=True)
@@ -424,6 +433,150 @@ def simulate(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], engine
     return res
 
 
+class UsageFallbackWarning(UserWarning):
+    """sweep(..., headroom=..., node_table=True) computes the figures on the host from the placement rows: the engine has no
+    supports_node_usage, or the sizes ran one by one (ImageLocality, several zones without node ranks)."""
+
+
+def probe_ids(flat: fl.Flat, headroom) -> Optional[np.ndarray]:
+    """Pod ids of the sweeps' headroom=[pod id or (namespace, name) from Flat.pod_refs, ...]."""
+    if headroom is None:
+        return None
+    ids = []
+    for h in headroom:
+        if isinstance(h, (int, np.integer)):
+            if not 0 <= int(h) < len(flat.pod_refs):
+                raise ValueError(f"headroom probe {h}: the stream has {len(flat.pod_refs)} pods")
+            ids.append(int(h))
+        else:
+            try:
+                ids.append(flat.pod_refs.index(tuple(h)))
+            except ValueError:
+                raise ValueError(f"headroom probe {tuple(h)} is not a pod of the stream") from None
+    if not 1 <= len(ids) <= capi.MAX_PROBES:
+        raise ValueError(f"headroom takes 1..{capi.MAX_PROBES} probe pods, got {len(ids)}")
+    return np.array(ids, np.int32)
+
+
+def _usage_sums(prob: capi.Problem, placement, held):
+    """Per scenario and pool node the requested quantities [S][3 + K][N] (cpu, memory, ephemeral storage, scalars) and pod counts [S][N]
+    at the end of the run, from the placement rows: what simon_fetch_node_usage defines, restated with numpy on the host."""
+    placement, held = np.asarray(placement), np.asarray(held, bool)
+    S, N = held.shape
+    z = lambda v, n: np.zeros(n, np.int64) if v is None else np.asarray(v, np.int64)                      # noqa: E731
+    P = placement.shape[1]
+    K = 0 if prob.scalar_alloc is None else len(prob.scalar_alloc)
+    q = [z(prob.req_cpu, P), z(prob.req_mem, P), z(prob.req_eph, P)] + [z(None if prob.scalar_req is None else prob.scalar_req[k], P) for k in range(K)]
+    i = [z(prob.init_req_cpu, N), z(prob.init_req_mem, N), z(prob.init_req_eph, N)] + [z(None if prob.init_scalar_req is None else prob.init_scalar_req[k], N) for k in range(K)]
+    req = np.zeros((S, 3 + K, N), np.int64)
+    cnt = np.zeros((S, N), np.int64)
+    for s in range(S):
+        on = placement[s] >= 0
+        idx = placement[s][on]
+        for r in range(3 + K):
+            req[s, r] = i[r]
+            np.add.at(req[s, r], idx, q[r][on])
+        cnt[s] = z(prob.init_npods, N)
+        np.add.at(cnt[s], idx, 1)
+    req *= held[:, None, :]
+    return req, np.where(held, cnt, -1).astype(np.int32)
+
+
+def host_node_usage(prob: capi.Problem, placement, held, scen_ids=None) -> capi.NodeUsage:
+    """capi.Context.fetch_node_usage on the host, from placement rows [S][P] and the nodes every scenario holds (bool [S][N])."""
+    ids = np.arange(len(held), dtype=np.int32) if scen_ids is None else np.asarray(scen_ids, np.int32)
+    req, cnt = _usage_sums(prob, np.asarray(placement)[ids], np.asarray(held)[ids])
+    return capi.NodeUsage(ids, req[:, 0].copy(), req[:, 1].copy(), cnt, req[:, 2].copy(), req[:, 3:].copy())
+
+
+def host_headroom(prob: capi.Problem, placement, held, probes):
+    """capi.Context.fetch_headroom on the host: (fit [S][K] int64, fit_nodes [S][K] int32, exact [K] bool)."""
+    held = np.asarray(held, bool)
+    S, N = held.shape
+    req, cnt = _usage_sums(prob, placement, held)
+    K = req.shape[1] - 3
+    z = lambda v: np.zeros(N, np.int64) if v is None else np.asarray(v, np.int64)                         # noqa: E731
+    alloc = [z(prob.alloc_cpu), z(prob.alloc_mem), z(prob.alloc_eph)] + [z(prob.scalar_alloc[k]) for k in range(K)]
+    probes = np.asarray(probes, np.int64).reshape(-1)
+    fit, nodes, exact = np.zeros((S, len(probes)), np.int64), np.zeros((S, len(probes)), np.int32), np.zeros(len(probes), bool)
+    j = np.arange(N)
+    of = lambda v, p, d=0: d if v is None else int(np.asarray(v)[p])                                      # noqa: E731
+    for k, p in enumerate(probes.tolist()):
+        cls = of(prob.pod_class, p)
+        q = [of(prob.req_cpu, p), of(prob.req_mem, p), of(prob.req_eph, p)] + [of(None if prob.scalar_req is None else prob.scalar_req[i], p) for i in range(K)]
+        entries = of(prob.scalar_entries, p)
+        for i in range(K):
+            entries |= (1 << i) if q[3 + i] else 0
+        checked = [] if not any(q[:3]) and not entries else [0, 1, 2] + [3 + i for i in range(K) if (entries >> i) & 1]
+        ok = held if prob.static_mask is None else held & (((np.asarray(prob.static_mask, np.uint64)[cls][j >> 6] >> (j & 63).astype(np.uint64)) & np.uint64(1)) != 0)[None, :]
+        cap = z(prob.alloc_pods)[None, :] - cnt
+        for r in checked:
+            room = alloc[r][None, :] - req[:, r]
+            cap = np.where(room < 0, 0, cap if q[r] <= 0 else np.minimum(cap, np.maximum(room, 0) // max(q[r], 1)))
+        cap = np.where(ok, np.maximum(cap, 0), 0)
+        fit[:, k], nodes[:, k] = cap.sum(1), (cap > 0).sum(1)
+        none = lambda off: prob.term_topo_key is None or len(prob.term_topo_key) == 0 or off is None or off[cls + 1] == off[cls]   # noqa: E731
+        exact[k] = (not of(prob.gpu_mem, p) and not of(prob.pod_gpu_cnt, p) and not of(prob.gpu_index, p) and of(prob.pin_node, p, -1) < 0
+                    and of(prob.preset_node, p, -1) < 0 and all(none(o) for o in (prob.match_off, prob.anti_off, prob.port_off, prob.aff_off, prob.spread_hard_off))
+                    and (prob.local_spec_of is None or int(prob.local_spec_of[cls]) < 0))
+    return fit, nodes, exact
+
+
+def _usage_kw(engine, probes, node_table: bool, S: int) -> dict:
+    """engine.run's keywords for a batch whose sweep asked for headroom / the node table (nothing for an engine without the calls)."""
+    if not getattr(engine, "supports_node_usage", False):
+        return {}
+    return {**({"headroom_pods": probes} if probes is not None else {}), **({"usage_of": np.arange(S, dtype=np.int32)} if node_table else {})}
+
+
+def _node_rows(nodes: List[dict], prob: capi.Problem, usage: capi.NodeUsage, i: int) -> List[dict]:
+    """reportClusterInfo's columns (pkg/apply/apply.go:315-400) for the nodes scenario row i of `usage` holds, in pool order."""
+    return [{"node": nodes[j]["metadata"]["name"], "cpu_allocatable": int(prob.alloc_cpu[j]), "cpu_requests": int(usage.req_cpu[i, j]),
+             "memory_allocatable": int(prob.alloc_mem[j]), "memory_requests": int(usage.req_mem[i, j]), "pods": int(usage.npods[i, j]),
+             "new": wl.LABEL_NEW_NODE in (nodes[j]["metadata"].get("labels") or {})}
+            for j in np.flatnonzero(usage.npods[i] >= 0).tolist()]
+
+
+def _usage_fill(engine, out, nodes, prob, held, probes, node_table: bool, warn, what: str):
+    """(headroom [S][K] lists, headroom_exact [K], node_table [S] lists of rows) of one engine batch -- None where not asked for: from the
+    engine's own reduction, or, for an engine without supports_node_usage, the same figures on the host from the placement rows (warns)."""
+    if probes is None and not node_table:
+        return None, None, None
+    hr, hx, usage = out.headroom, out.headroom_exact, out.node_usage
+    if not getattr(engine, "supports_node_usage", False):
+        import warnings
+        warnings.warn(f"{what} computes headroom / the node table on the host from the placement matrix (the engine has no supports_node_usage)", warn, stacklevel=4)
+        if probes is not None:
+            hr, _, hx = host_headroom(prob, out.placement, held, probes)
+        if node_table:
+            usage = host_node_usage(prob, out.placement, held)
+    return (None if probes is None else np.asarray(hr).tolist(), None if probes is None else [bool(x) for x in hx],
+            [_node_rows(nodes, prob, usage, i) for i in range(len(held))] if node_table else None)
+
+
+def _usage_each(flat: fl.Flat, nodes: List[dict], out, headroom, node_table: bool, pool_order: Sequence[str]):
+    """_usage_fill for ONE scenario that ran as its own problem (the sweeps' fallback roads; `nodes` = its nodes in the problem's order,
+    pool_order = their names in pool order): on the host from its placement row.  Probes are named (namespace, name) there: a pod id
+    belongs to the batch's stream, which these roads do not build."""
+    hr = hx = tab = None
+    held = np.ones((1, len(nodes)), bool)
+    if headroom is not None:
+        if any(isinstance(h, (int, np.integer)) for h in headroom):
+            raise ValueError("the scenarios run one by one, each with its own pod stream: name the headroom probes by (namespace, name)")
+        fit, _, ex = host_headroom(flat.problem, out.placement[:1], held, probe_ids(flat, headroom))
+        hr, hx = fit[0].tolist(), [bool(x) for x in ex]
+    if node_table:
+        rows = {r["node"]: r for r in _node_rows(nodes, flat.problem, host_node_usage(flat.problem, out.placement[:1], held), 0)}
+        tab = [rows[n] for n in pool_order]
+    return hr, hx, tab
+
+
+def _and_exact(rows):
+    """headroom_exact over scenarios that ran as their own problems: exact where every one of them says so."""
+    rows = [r for r in rows if r is not None]
+    return [all(r[k] for r in rows) for k in range(len(rows[0]))] if rows else None
+
+
 @dataclass
 class SweepResult:
     counts: List[int]                    # new nodes added per scenario
@@ -439,6 +592,11 @@ class SweepResult:
     # SimulateResult.unscheduled_pods ("show results" of the add-nodes loop, pkg/apply/apply.go:229-232); empty without reasons.  With an
     # app DaemonSet a size may be listed from its own simulate() run (_same_stream): len(unscheduled_pods[s]) may then differ from unscheduled[s]
     unscheduled_pods: List[List[dict]] = field(default_factory=list)
+    # sweep(..., headroom=[...], node_table=True): per count, how many more pods like each probe fit; per probe, whether that is the count
+    # the scheduler would place (else the resource-and-static-filter upper bound); per count, reportClusterInfo's table over its nodes
+    headroom: Optional[List[List[int]]] = None
+    headroom_exact: Optional[List[bool]] = None
+    node_table: Optional[List[List[dict]]] = None
 
 
 def occupancy_pct(used: int, alloc: int) -> int:
@@ -556,11 +714,17 @@ def _sweep_reasons(engine, batch: "SweepBatch", out, replay, same_stream) -> Lis
 
 @_gc_paused
 def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node: Optional[dict], counts: Sequence[int],
-          engine=None, max_cpu: int = 100, max_mem: int = 100, max_vg: int = 100, reasons: bool = False) -> SweepResult:
+          engine=None, max_cpu: int = 100, max_mem: int = 100, max_vg: int = 100, reasons: bool = False, headroom=None,
+          node_table: bool = False) -> SweepResult:
     """The add-nodes loop of Applier.Run (pkg/apply/apply.go:203-259) as ONE scenario batch: scenario k = the cluster plus
     counts[k] clones of new_node (utils.NewFakeNodes); the answer is the smallest count with no unscheduled pod whose
     occupancy satisfies MaxCPU / MaxMemory (satisfyResourceSetting, :689-775).  reasons=True: SweepResult.unscheduled_pods lists, per
-    count, the pods that stay unscheduled with their FitError text (what the loop prints under "show results", :229-232)."""
+    count, the pods that stay unscheduled with their FitError text (what the loop prints under "show results", :229-232).
+    headroom=[pod id or (namespace, name) from Flat.pod_refs, ...]: SweepResult.headroom[s][k] = how many more pods like probe k still fit
+    at count s (headroom_exact[k]: that is the scheduler's own count, else the resource-and-static-filter upper bound).  node_table=True:
+    SweepResult.node_table[s] = the table `simon apply` ends with (reportClusterInfo, :315-400) over the nodes of count s.  Both are reduced
+    on the device from the placement matrix; an engine without supports_node_usage and the size-by-size road compute the same figures on
+    the host (UsageFallbackWarning)."""
     engine = engine or HipEngine()
     counts = list(counts)
     if max_cpu > 100 or max_cpu < 0:
@@ -575,13 +739,16 @@ def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node:
             raise
         # ImageLocality scores depend on the cluster size: an engine without the per-size image scores runs every size as its own
         # problem with its own static scores (and an engine without per-scenario node ranks runs a pool of several zones size by size)
-        return _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg, reasons)
+        return _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg, reasons, headroom, node_table)
     flat, scen, orders, node_ranks, pool, base = batch.flat, batch.scen, batch.orders, batch.node_ranks, batch.pool, batch.base
     want_gpu = flat.problem.gpu_mem is not None
     kw = {"want_gpu_slices": True} if want_gpu else {}
     if node_ranks is not None:
         kw["node_ranks"] = node_ranks
-    out = engine.run(flat.problem, scen, orders, **kw)
+    probes = probe_ids(flat, headroom)
+    out = engine.run(flat.problem, scen, orders, **kw, **_usage_kw(engine, probes, node_table, len(scen)))
+    hr, hx, tab = _usage_fill(engine, out, pool, flat.problem, np.arange(len(pool))[None, :] < scen[:, :1], probes, node_table,
+                              UsageFallbackWarning, "sweep")
     pc, pm = np.cumsum(flat.problem.alloc_cpu), np.cumsum(flat.problem.alloc_mem)
     cpu_pct = [occupancy_pct(int(out.used_cpu[s]), int(pc[scen[s, 0] - 1])) for s in range(len(counts))]
     mem_pct = [occupancy_pct(int(out.used_mem[s]) * 1000, int(pm[scen[s, 0] - 1]) * 1000) for s in range(len(counts))]
@@ -609,11 +776,17 @@ def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node:
                 return _unscheduled_list(flat, out.placement[s], {})
         why = _sweep_reasons(engine, batch, out, replay, lambda s: _same_stream(cluster, apps, batch, out, s))
     return SweepResult(counts, out.unscheduled.tolist(), cpu_pct, mem_pct, None if best is None else counts[best], result, vg_pct,
-                       [_risk(out, s) for s in range(len(counts))], why)
+                       [_risk(out, s) for s in range(len(counts))], why, hr, hx, tab)
 
 
-def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg, reasons: bool = False) -> SweepResult:
+def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg, reasons: bool = False, headroom=None,
+                    node_table: bool = False) -> SweepResult:
     base = list(cluster.get("Node", []))
+    hrs, hxs, tabs = [], [], []
+    if headroom is not None or node_table:
+        import warnings
+        warnings.warn("sweep runs the sizes one by one and computes headroom / the node table on the host from each placement row",
+                      UsageFallbackWarning, stacklevel=3)
     if max_vg > 100 or max_vg < 0:
         max_vg = 100
     uns, cpu_pct, mem_pct, vg_pct, kept, risks = [], [], [], [], {}, []
@@ -630,6 +803,8 @@ def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, m
                          **({"want_gpu_slices": True} if want_gpu else {}))
         uns.append(int(out.unscheduled[0]))
         risks.append(_risk(out, 0))
+        for acc, v in zip((hrs, hxs, tabs), _usage_each(flat, nodes, out, headroom, node_table, arrival)):
+            acc.append(v)
         if reasons:
             texts = {}
             if uns[-1] > 0:
@@ -652,7 +827,8 @@ def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, m
         res, per_node, per_dev = _unflatten(flat, out.placement[0], len(nodes), {}, out.gpu_slices[0] if out.gpu_slices is not None else None)
         res.node_status = [{"node": _gpu_node_status(n, per_dev[j]) if j in per_dev else _node_out(n), "pods": per_node[j]} for j, n in enumerate(nodes)]
         result = res
-    return SweepResult(list(counts), uns, cpu_pct, mem_pct, None if best is None else counts[best], result, vg_pct, risks, why)
+    return SweepResult(list(counts), uns, cpu_pct, mem_pct, None if best is None else counts[best], result, vg_pct, risks, why,
+                       hrs if headroom is not None else None, _and_exact(hxs), tabs if node_table else None)
 
 
 @dataclass
@@ -670,6 +846,9 @@ class MixSweepResult:
     batched: bool = True                 # one segmented engine batch (False: every mix ran as its own problem)
     fallback: Optional[str] = None       # why the mixes ran one by one (None when batched); sweep_mix also warns (MixFallbackWarning)
     unscheduled_pods: List[List[dict]] = field(default_factory=list)   # reasons=True: per mix, simulate()'s list of that mix
+    headroom: Optional[List[List[int]]] = None      # headroom=[...]: per mix and probe, how many more such pods fit
+    headroom_exact: Optional[List[bool]] = None     # per probe: the scheduler's own count (else an upper bound)
+    node_table: Optional[List[List[dict]]] = None   # node_table=True: per mix, reportClusterInfo's table over its own nodes, pool order
 
 
 class MixFallbackWarning(UserWarning):
@@ -737,7 +916,7 @@ def _caps(max_cpu, max_mem, max_vg):
 @_gc_paused
 def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_nodes: Sequence[dict], counts: Sequence[Sequence[int]],
               costs: Optional[Sequence[float]] = None, engine=None, max_cpu: int = 100, max_mem: int = 100, max_vg: int = 100,
-              reasons: bool = False) -> MixSweepResult:
+              reasons: bool = False, headroom=None, node_table: bool = False) -> MixSweepResult:
     """The add-nodes search over mixes of several new-node types (Applier.Run clones ONE template, pkg/apply/apply.go:155-166): mix
     (c_1 .. c_T) = Simulate(cluster + NewFakeNodes(type_1, c_1) + ... + NewFakeNodes(type_T, c_T)), the grid = the Cartesian product of
     counts (one iterable per type).  The answer is the mix of least total cost sum_t costs[t] * c_t (default 1 per node) with no
@@ -746,7 +925,8 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
     segment per type (simon_set_scenario_segments); engines without segments, clusters whose nodes list the pods' images and problems
     the segmented kernel does not take run every mix as its own problem.  reasons=True: MixSweepResult.unscheduled_pods lists, per mix,
     the pods that stay unscheduled with their FitError text, as sweep() does per count -- every failing mix of the batch explained in
-    one engine.explain_own_batch call (engines without it, and mixes whose pod stream is not the pool's: simulate() of the mix)."""
+    one engine.explain_own_batch call (engines without it, and mixes whose pod stream is not the pool's: simulate() of the mix).
+    headroom=[...] / node_table=True: as sweep() takes them, per mix (MixSweepResult.headroom / headroom_exact / node_table)."""
     import itertools
     engine = engine or HipEngine()
     new_nodes = list(new_nodes)
@@ -765,7 +945,7 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
     mixes = [tuple(int(k) for k in m) for m in itertools.product(*counts)]
     caps = _caps(max_cpu, max_mem, max_vg)
     if not getattr(engine, "supports_scenario_segments", False):
-        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, "the engine has no pool segments", reasons)
+        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, "the engine has no pool segments", reasons, headroom, node_table)
     base = list(cluster.get("Node", []))
     if not base and any(sum(m) == 0 for m in mixes):   # (a scenario holds one node at least: simon_set_scenario_segments, and flatten)
         raise ValueError("sweep_mix: a cluster without nodes needs at least one new node in every mix")
@@ -786,20 +966,21 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
         if "ImageLocality" not in str(e):
             raise
         return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps,
-                                  "nodes list the pods' images: ImageLocality depends on the node set", reasons)
+                                  "nodes list the pods' images: ImageLocality depends on the node set", reasons, headroom, node_table)
     scen = np.stack([len(base) + cnt.sum(1), np.zeros(len(mixes), np.int64)], 1).astype(np.int32)
     orders = np.arange(len(pods), dtype=np.int32)[None, :]
     want_gpu = flat.problem.gpu_mem is not None
     kw = {"want_gpu_slices": True} if want_gpu else {}
     if node_ranks is not None:
         kw["node_ranks"] = node_ranks
+    probes = probe_ids(flat, headroom)
     try:
-        out = engine.run(flat.problem, scen, orders, segments=(seg_start, cnt), **kw)
+        out = engine.run(flat.problem, scen, orders, segments=(seg_start, cnt), **kw, **_usage_kw(engine, probes, node_table, len(scen)))
     except capi.SimonError as e:
         if getattr(e, "code", None) != capi.ESTATE:
             raise
         # a problem on the all-feature kernel (prefix scenarios only): every mix as its own problem
-        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, f"the engine refused the segmented batch: {e}", reasons)
+        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, f"the engine refused the segmented batch: {e}", reasons, headroom, node_table)
     # satisfyResourceSetting over each mix's own nodes: the fixed nodes + a prefix of every segment
     pr = flat.problem
     vg_cap = None
@@ -829,7 +1010,8 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
         why = _mix_reasons(engine, cluster, apps, flat, pool, len(base), present, scen, orders, node_ranks, (seg_start, cnt), out)
     return MixSweepResult(mixes, out.unscheduled.tolist(), cpu_pct, mem_pct, vg_pct, [_risk(out, s) for s in range(len(mixes))],
                           None if best is None else mixes[best], None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result,
-                          unscheduled_pods=why)
+                          unscheduled_pods=why, **dict(zip(("headroom", "headroom_exact", "node_table"), _usage_fill(
+                              engine, out, pool, flat.problem, present, probes, node_table, MixFallbackWarning, "sweep_mix"))))
 
 
 def _mix_reasons(engine, cluster, apps, flat, pool, n_base, present, scen, orders, node_ranks, segments, out) -> List[List[dict]]:
@@ -872,13 +1054,15 @@ def _mix_reasons(engine, cluster, apps, flat, pool, n_base, present, scen, order
     return [lists[s] if s in lists else _unscheduled_list(flat, out.placement[s], texts.get(s, {})) for s in range(len(scen))]
 
 
-def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why: str, reasons: bool = False) -> MixSweepResult:
+def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why: str, reasons: bool = False, headroom=None,
+                       node_table: bool = False) -> MixSweepResult:
     """Every mix as its own Simulate(): cluster + each type's clones in type order, canonical nodeTree order."""
     import warnings
     warnings.warn(f"sweep_mix runs {len(mixes)} mixes one by one ({why})", MixFallbackWarning, stacklevel=3)
     base = list(cluster.get("Node", []))
     uns, cpu_pct, mem_pct, vg_pct, risks, kept = [], [], [], [], [], {}
     lists: List[List[dict]] = []
+    hrs, hxs, tabs = [], [], []
     for s, mix in enumerate(mixes):
         nodes = base + [n for nodes in mix_fake_nodes(new_nodes, mix) for n in nodes]
         pods, _ = build_stream(cluster, apps, nodes, len(nodes))
@@ -891,6 +1075,8 @@ def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why
                          **({"want_gpu_slices": True} if want_gpu else {}))
         uns.append(int(out.unscheduled[0]))
         risks.append(_risk(out, 0))
+        for acc, v in zip((hrs, hxs, tabs), _usage_each(flat, nodes, out, headroom, node_table, arrival)):
+            acc.append(v)
         if reasons:
             texts = {}
             if uns[-1] > 0:
@@ -915,7 +1101,8 @@ def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why
         result = res
     return MixSweepResult(mixes, uns, cpu_pct, mem_pct, vg_pct, risks, None if best is None else mixes[best],
                           None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result, batched=False, fallback=why,
-                          unscheduled_pods=lists)
+                          unscheduled_pods=lists, headroom=hrs if headroom is not None else None, headroom_exact=_and_exact(hxs),
+                          node_table=tabs if node_table else None)
 
 
 @dataclass
@@ -937,6 +1124,11 @@ class FailureSweepResult:
     fallback: Optional[str] = None       # why the scenarios ran one by one (None when batched); sweep_failures also warns
     evicted: List[int] = field(default_factory=list)                # reschedule: pods of the domain's nodes that were scheduled again (else 0s)
     evicted_unscheduled: List[int] = field(default_factory=list)    # ... and how many of them found no room
+    # headroom=[...] / node_table=True, per SCENARIO like `rows` ([0] the whole cluster, [d + 1] without domain d): how many more pods like
+    # each probe fit; per probe whether that is the scheduler's own count; reportClusterInfo's table over the scenario's nodes, pool order
+    headroom: Optional[List[List[int]]] = None
+    headroom_exact: Optional[List[bool]] = None
+    node_table: Optional[List[List[dict]]] = None
 
     @property
     def removable(self) -> List[int]:
@@ -1096,7 +1288,7 @@ def _failure_replay(cluster, apps, names, engine, reschedule=False) -> List[dict
 @_gc_paused
 def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], domains="node", engine=None, max_cpu: int = 100,
                    max_mem: int = 100, max_vg: int = 100, reasons: bool = False, batch_scenarios: int = 4096,
-                   reschedule=False) -> FailureSweepResult:
+                   reschedule=False, headroom=None, node_table: bool = False) -> FailureSweepResult:
     """The node-failure what-if sweep: does the cluster still hold its workloads when a node, a rack or a zone is lost?  Scenario 0 is
     the whole cluster; scenario d + 1 is simulate() of the cluster without failure domain d (failure_domains: "node", a label key, or
     lists of node names), without the pods bound to its nodes and without their DaemonSet pods (cluster_without) -- lost pods are
@@ -1112,7 +1304,8 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     pods without spec.nodeName.  In the batch they are flagged (simon_set_pod_eviction): bound where their node is present, scheduled
     where it is not.  `evicted` / `evicted_unscheduled` count them per domain, `removable` lists the domains the cluster survives.
     Pods that a workload TEMPLATE binds to a node stay Unsupported (their controller would bind the new pod to the same node); an
-    engine without supports_pod_eviction and evicted pods that carry a gpu-index annotation run scenario by scenario."""
+    engine without supports_pod_eviction and evicted pods that carry a gpu-index annotation run scenario by scenario.
+    headroom=[...] / node_table=True: as sweep() takes them, per SCENARIO ([0] the whole cluster, [d + 1] without domain d)."""
     engine = engine or HipEngine()
     reschedule = reschedule or False
     evictable({}, reschedule or "all")
@@ -1125,7 +1318,7 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     if not present.any(axis=1).all():
         raise ValueError("sweep_failures: a failure domain holds every node of the cluster")
     caps = _caps(max_cpu, max_mem, max_vg)
-    each = lambda why: _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why, reschedule)   # noqa: E731
+    each = lambda why: _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why, reschedule, headroom, node_table)   # noqa: E731
     if not getattr(engine, "supports_scenario_subsets", False):
         return each("the engine has no node subsets")
     if reschedule and not getattr(engine, "supports_pod_eviction", False):
@@ -1164,6 +1357,8 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     orders = np.arange(len(pods), dtype=np.int32)[None, :]
     want_gpu = pr.gpu_mem is not None
     rows, where = [], []
+    probes = probe_ids(flat, headroom)
+    hr, hx, tab = ([] if headroom is not None else None), None, ([] if node_table else None)
     told: Dict[int, List[dict]] = {}             # reasons: scenario -> its unscheduled_pods, from the batch's own explain
     for lo in range(0, len(present), max(1, int(batch_scenarios))):
         part = present[lo:lo + max(1, int(batch_scenarios))]
@@ -1174,11 +1369,18 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
         try:
             if evict.any():
                 kw["evict"] = evict
-            out = engine.run(pr, scen, orders, present=(part, zone if 1 < len(zid) <= capi.MAX_ZONES else None), **kw)
+            out = engine.run(pr, scen, orders, present=(part, zone if 1 < len(zid) <= capi.MAX_ZONES else None), **kw,
+                             **_usage_kw(engine, probes, node_table, len(scen)))
         except capi.SimonError as e:
             if getattr(e, "code", None) != capi.ESTATE:
                 raise
             return each(f"the engine refused the node-subset batch: {e}")
+        h1, x1, t1 = _usage_fill(engine, out, pool, pr, part, probes, node_table, FailureFallbackWarning, "sweep_failures")
+        if h1 is not None:
+            hr += h1
+            hx = x1
+        if t1 is not None:
+            tab += t1
         failing = [s for s in range(len(part)) if lo + s > 0 and out.unscheduled[s] > 0 and not _risk(out, s)] if reasons else []
         if failing and getattr(engine, "supports_explain_own", False):
             # the failing scenarios of this launch on the context shape it ran with; a pod evicted in a scenario is listed as its
@@ -1210,14 +1412,18 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     if evict.any():
         preset = np.asarray(pr.preset_node)
         moved = [np.flatnonzero(evict & ~present[d + 1][np.maximum(preset, 0)]) for d in range(len(doms))]
-    return _failure_result(doms, rows, caps, where, why, True, None, moved)
+    res = _failure_result(doms, rows, caps, where, why, True, None, moved)
+    res.headroom, res.headroom_exact, res.node_table = hr, hx, tab
+    return res
 
 
-def _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why: str, reschedule=False) -> FailureSweepResult:
+def _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why: str, reschedule=False, headroom=None,
+                         node_table: bool = False) -> FailureSweepResult:
     """Every scenario as its own Simulate(): the cluster without the domain, canonical nodeTree order."""
     import warnings
     warnings.warn(f"sweep_failures runs {len(doms) + 1} scenarios one by one ({why})", FailureFallbackWarning, stacklevel=3)
     rows, where, lists, moved = [], [], [], []
+    hrs, hxs, tabs = [], [], []
     for names in [[]] + doms:
         cl, ap = _reduced(cluster, apps, names, reschedule)
         nodes = list(cl.get("Node", []))
@@ -1234,12 +1440,16 @@ def _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why: str, r
                      occupancy_pct(int(out.used_mem[0]) * 1000, int(pr.alloc_mem.sum()) * 1000),
                      occupancy_pct(int(out.used_vg[0]), int(vg_cap.sum())) if vg_cap is not None else 0, _risk(out, 0)))
         where.append((flat, out.placement[0]))
+        for acc, v in zip((hrs, hxs, tabs), _usage_each(flat, nodes, out, headroom, node_table, arrival)):
+            acc.append(v)
         if reschedule and names:
             refs = _evicted_refs(cluster, apps, names, reschedule)
             moved.append(np.array([pid for pid, r in enumerate(flat.pod_refs) if r in refs], np.int64))
         if reasons and names:
             lists.append(_failure_replay(cluster, apps, names, engine, reschedule) if rows[-1][0] > 0 else [])
-    return _failure_result(doms, rows, caps, where, lists, False, why, moved)
+    res = _failure_result(doms, rows, caps, where, lists, False, why, moved)
+    res.headroom, res.headroom_exact, res.node_table = hrs if headroom is not None else None, _and_exact(hxs), tabs if node_table else None
+    return res
 
 
 @dataclass
@@ -1261,6 +1471,9 @@ class AppSweepResult:
     unscheduled_pods: List[List[List[dict]]] = field(default_factory=list)   # reasons=True: [U][K] simulate()'s list of that scenario
     batched: bool = True                  # pod-subset engine batches (False: every scenario ran as its own simulate())
     fallback: Optional[str] = None        # why the scenarios ran one by one (None when batched); sweep_apps also warns
+    headroom: Optional[List[List[List[int]]]] = None    # headroom=[...]: [U][K][probe] how many more pods like the probe fit
+    headroom_exact: Optional[List[bool]] = None         # per probe: the scheduler's own count (else an upper bound)
+    node_table: Optional[List[List[List[dict]]]] = None # node_table=True: [U][K] reportClusterInfo's table over the scenario's nodes
 
 
 class AppFallbackWarning(UserWarning):
@@ -1305,14 +1518,18 @@ def _app_summary(apps, subs, counts, rows, by_app, caps, weights, why_lists, bat
                           fits, min_count, [[bool(r[4]) for r in row] for row in rows], best, maximal, why_lists, batched, fallback)
 
 
-def _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, weights, reasons, why: str) -> AppSweepResult:
+def _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, weights, reasons, why: str, headroom=None,
+                     node_table: bool = False) -> AppSweepResult:
     """Every scenario as its own Simulate(): the cluster, the subset's apps and its new nodes, canonical nodeTree order."""
     import warnings
     warnings.warn(f"sweep_apps runs {len(subs) * len(counts)} scenarios one by one ({why})", AppFallbackWarning, stacklevel=3)
     base = list(cluster.get("Node", []))
     rows, by_app, lists = [], [], []
+    hrs, hxs, tabs = [], [], []
     for sub in subs:
         mine = [apps[a] for a in sub]
+        hrs.append([])
+        tabs.append([])
         rows.append([])
         by_app.append([])
         lists.append([])
@@ -1334,11 +1551,17 @@ def _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, weight
             pr = flat.problem
             per = [0] * len(apps)
             if not pods:
+                if headroom is not None or node_table:
+                    raise ValueError("sweep_apps: headroom / node_table of a scenario without any pod, run on its own")
                 rows[-1].append((0, 0, 0, 0, False))
                 by_app[-1].append(per)
                 lists[-1].append([])
                 continue
             out = engine.run(pr, np.array([[len(nodes), 0]], np.int32), np.arange(len(pods), dtype=np.int32)[None, :])
+            h1, x1, t1 = _usage_each(flat, nodes, out, headroom, node_table, arrival)
+            hrs[-1].append(h1)
+            hxs.append(x1)
+            tabs[-1].append(t1)
             vg_cap = _vg_caps(pr, out)
             rows[-1].append((int(out.unscheduled[0]), occupancy_pct(int(out.used_cpu[0]), int(pr.alloc_cpu.sum())),
                              occupancy_pct(int(out.used_mem[0]) * 1000, int(pr.alloc_mem.sum()) * 1000),
@@ -1351,13 +1574,15 @@ def _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, weight
                 nf, failed, codes, detail = engine.explain(pr, len(nodes), np.arange(len(pods), dtype=np.int32), int(out.unscheduled[0]))
                 texts = _reason_texts(flat, failed, codes, detail)
             lists[-1].append(_unscheduled_list(flat, out.placement[0], texts) if reasons else [])
-    return _app_summary(apps, subs, counts, rows, by_app, caps, weights, lists if reasons else [], False, why)
+    res = _app_summary(apps, subs, counts, rows, by_app, caps, weights, lists if reasons else [], False, why)
+    res.headroom, res.headroom_exact, res.node_table = hrs if headroom is not None else None, _and_exact(hxs), tabs if node_table else None
+    return res
 
 
 @_gc_paused
 def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subsets=None, new_node: Optional[dict] = None,
                counts: Sequence[int] = (0,), weights: Optional[Sequence[float]] = None, engine=None, max_cpu: int = 100, max_mem: int = 100,
-               max_vg: int = 100, reasons: bool = False, batch_scenarios: int = 4096) -> AppSweepResult:
+               max_vg: int = 100, reasons: bool = False, batch_scenarios: int = 4096, headroom=None, node_table: bool = False) -> AppSweepResult:
     """Which of these apps fit on the cluster together, what has to be left out, and how many new nodes each combination costs: scenario
     (u, k) is simulate(cluster, [apps[a] for a in subsets[u]], new_nodes = counts[k] clones of new_node); the cluster's own pods are part
     of every scenario.  subsets: bool rows [U][len(apps)] or lists of app names; None = every subset of at most 12 apps (4 096 scenarios per
@@ -1373,7 +1598,9 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
     to that size (_same_stream's case); an app whose pods use a StorageClass that only another app defines (_storage_classes registers
     them all up front); an engine that refuses the batch (SIMON_ESTATE).  Not covered: subsets of the replicas WITHIN one app --
     ScheduleApp's unstable sorts order an app's pods by the length of the list, so a shorter replica list is not a restriction of the
-    longer one's stream."""
+    longer one's stream.
+    headroom=[...] / node_table=True: as sweep() takes them, per scenario (u, k) (AppSweepResult.headroom[u][k] etc.); a probe may be a
+    pod of an app the scenario lacks -- its request and class stand for "one more such pod"."""
     engine = engine or HipEngine()
     apps, counts = list(apps), list(counts)
     if not counts:
@@ -1388,7 +1615,7 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
     w = [float(x) for x in weights] if weights is not None else [float(n) for n in lens]
     if len(w) != len(apps):
         raise ValueError(f"{len(w)} weights for {len(apps)} apps")
-    each = lambda why: _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, w, reasons, why)   # noqa: E731
+    each = lambda why: _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, w, reasons, why, headroom, node_table)   # noqa: E731
     if not getattr(engine, "supports_pod_subsets", False):
         return each("the engine has no pod subsets")
     # a StorageClass that one app defines and another app's pods use: in a subset without the first app the class is unknown
@@ -1435,6 +1662,11 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
     rows = [[None] * K for _ in subs]
     by_app = [[None] * K for _ in subs]
     lists = [[[] for _ in counts] for _ in subs]
+    probes = probe_ids(flat, headroom)
+    hr = [[None] * K for _ in subs] if headroom is not None else None
+    hx = None
+    tab = [[None] * K for _ in subs] if node_table else None
+    on_host = (headroom is not None or node_table) and not getattr(engine, "supports_node_usage", False)     # (the host figures need the rows)
     per_launch = max(1, int(batch_scenarios) // K)                  # whole subsets per launch: K scenarios each
     for lo in range(0, len(subs), per_launch):
         us = np.arange(lo, min(lo + per_launch, len(subs)))
@@ -1444,11 +1676,15 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
         if batch.node_ranks is not None:
             kw["node_ranks"] = np.tile(batch.node_ranks, (len(us), 1))
         try:
-            out = engine.run(pr, scen, batch.orders, want_placement=reasons, pod_present=present, pod_groups=group, **kw)
+            out = engine.run(pr, scen, batch.orders, want_placement=reasons or on_host, pod_present=present, pod_groups=group, **kw,
+                             **_usage_kw(engine, probes, node_table, len(scen)))
         except capi.SimonError as e:
             if getattr(e, "code", None) != capi.ESTATE:
                 raise
             return each(f"the engine refused the pod-subset batch: {e}")
+        h1, x1, t1 = _usage_fill(engine, out, batch.pool, pr, np.arange(len(batch.pool))[None, :] < scen[:, :1], probes, node_table,
+                                 AppFallbackWarning, "sweep_apps")
+        hx = x1 if x1 is not None else hx
         vg_cap = _vg_caps(pr, out)
         cv = np.cumsum(vg_cap) if vg_cap is not None else None
         told: Dict[int, Dict[int, str]] = {}
@@ -1478,9 +1714,15 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
                               occupancy_pct(int(out.used_vg[s]), int(cv[n - 1])) if cv is not None else 0, _risk(out, s))
                 g = out.group_unscheduled[s]
                 by_app[u][k] = [int(g[a]) if a < len(g) else 0 for a in range(A)]
+                if h1 is not None:
+                    hr[u][k] = h1[s]
+                if t1 is not None:
+                    tab[u][k] = t1[s]
                 if reasons and s not in replayed:
                     lists[u][k] = _unscheduled_list(flat, out.placement[s], told.get(s, {}))
-    return _app_summary(apps, subs, counts, rows, by_app, caps, w, lists if reasons else [], True, None)
+    res = _app_summary(apps, subs, counts, rows, by_app, caps, w, lists if reasons else [], True, None)
+    res.headroom, res.headroom_exact, res.node_table = hr, hx, tab
+    return res
 
 
 def _claimed_storage_classes(app: AppResource) -> set:
