@@ -504,8 +504,9 @@ int simon_fetch_group_counts(simon_ctx* ctx, const int32_t* pod_group /* [P] */,
  * SIMON_EINVAL: n < 1, a scenario id outside [0, S), a missing required output array (req_cpu, req_mem, npods, fit), a wrong
  * struct_size, K outside [1, SIMON_MAX_PROBES], a pod id outside [0, P).  A failed call leaves results and batch alone.
  * The node range is tiled to the LDS budget (env SIMON_USAGE_TILE=<nodes> overrides the tile, read once in simon_ctx_create).
- * Not covered: GPU-share device usage (gpu_slices x gpu_mem per device) and Open-Local VG / device usage per node (exact is 0 for such
- * probes); probes that are not pods of the loaded stream; no simon_group_* forward and no Go shim.  (additive: the ABI stays 7) */
+ * Not covered: Open-Local VG / device usage per node (exact is 0 for such probes); probes that are not pods of the loaded stream; no
+ * simon_group_* forward and no Go shim.  GPU-share devices: simon_fetch_gpu_usage / simon_fetch_headroom_gpu below (simon_fetch_headroom
+ * itself keeps exact = 0 for a probe with a GPU request).  (additive: the ABI stays 7) */
 typedef struct simon_node_usage {
     uint32_t struct_size;
     int64_t* req_cpu;      /* [n][N] Requested.MilliCPU of pool node j at the end of listed scenario i */
@@ -519,6 +520,42 @@ int simon_fetch_node_usage(simon_ctx* ctx, const int32_t* scen_ids /* [n], NULL 
 int simon_fetch_headroom(simon_ctx* ctx, const int32_t* probe_pod /* [K] pod ids */, int32_t K,
                          int64_t* fit /* [S][K] */, int32_t* fit_nodes /* [S][K], may be NULL */, uint8_t* exact /* [K], may be NULL */);
 #define SIMON_MAX_PROBES 64
+
+/* GPU-share devices of the last run's scenarios, reduced on the device from the placement matrix and the recorded devices (both stay
+ * there).  Requirements and refusals are those of simon_fetch_node_usage / simon_fetch_headroom, and one more: a problem with GPU
+ * requests or GPU nodes must have run with SIMON_WANT_GPU_SLICES (otherwise SIMON_ESTATE, the message names the flag).  A problem
+ * without any GPU request is answered: its slices are zero by definition, the result is the state before the stream.
+ *
+ * simon_fetch_gpu_usage: the "GPU Node Resource" table `simon apply` ends with (pkg/apply/apply.go:456-500), for the n listed scenarios
+ * (any order, repeats allowed, NULL = scenarios 0 .. n-1).  For a node j the scenario holds and a device d < min(gpu_cnt[j],
+ * SIMON_MAX_GPU_DEV):
+ *   dev_used[i][j][d] = init_gpu_used[j][d] + sum over the pods p with placement[s][p] == j of byte_d(gpu_slices[s][p]) * gpu_mem[p]
+ *   (GpuSharePlugin.Reserve books gpu_mem once per slice; a pod bound by Spec.NodeName never reaches Reserve and reads 0 slices),
+ *   dev_pods[i][j][d] = the number of those pods with byte_d > 0 -- pods of the STREAM only: init_gpu_used carries no pod count.
+ * For a node the scenario lacks dev_used is 0 and dev_pods is -1; for a device the node lacks (d >= gpu_cnt[j], nodes without GPUs)
+ * both are 0.  The sum of dev_used over a node's devices is the "GPU Mem Requests" column of reportClusterInfo (:328-329, 380).
+ *
+ * simon_fetch_headroom_gpu: simon_fetch_headroom with the device bound.  For a probe pod with gpu_mem > 0 that arrives without a
+ * gpu-index annotation, cap(s, j, k) = min(cap of simon_fetch_headroom, cap_gpu) with, on a node of cnt = min(gpu_cnt[j],
+ * SIMON_MAX_GPU_DEV) devices of per = gpu_mem_total[j] / gpu_cnt[j] bytes each,
+ *   T = sum over d < cnt of max(per - dev_used[d], 0) / gpu_mem   (integer division),   cap_gpu = T / min(gpu_cnt of the pod, 64);
+ *   cap_gpu = 0 on a node without devices and for a pod whose gpu_cnt is <= 0 (GpuNodeInfo.AllocateGpuId returns nothing there).
+ * This is the number of further such pods AllocateGpuId + Reserve accept on the node: the tightest-fit rule (one device) and the
+ * two-pointer greedy (several) both succeed iff T >= count, and every success lowers T by exactly count, whichever devices it takes.
+ * exact[k] is 1 under simon_fetch_headroom's conditions, except that such a GPU request no longer disqualifies.  A probe without
+ * gpu_mem gives simon_fetch_headroom's result bit for bit.  A probe that arrives WITH a gpu-index annotation short-cuts AllocateGpuId:
+ * no device bound is applied and exact is 0.  SIMON_EINVAL as for the two calls above (dev_used is the one required array).
+ * Not covered: Open-Local VG / device usage; probes that are not pods of the loaded stream; no simon_group_* forward and no Go shim.
+ * (additive: the ABI stays 7) */
+typedef struct simon_gpu_usage {
+    uint32_t struct_size;
+    int64_t* dev_used;     /* [n][N][SIMON_MAX_GPU_DEV] GPU memory booked on device d of pool node j at the end of listed scenario i */
+    int32_t* dev_pods;     /* [n][N][SIMON_MAX_GPU_DEV] optional: stream pods holding a slice of the device; -1 = the scenario lacks node j */
+} simon_gpu_usage;
+int simon_fetch_gpu_usage(simon_ctx* ctx, const int32_t* scen_ids /* [n], NULL = 0..n-1 */, int32_t n, simon_gpu_usage* out);
+
+int simon_fetch_headroom_gpu(simon_ctx* ctx, const int32_t* probe_pod /* [K] pod ids */, int32_t K,
+                             int64_t* fit /* [S][K] */, int32_t* fit_nodes /* [S][K], may be NULL */, uint8_t* exact /* [K], may be NULL */);
 
 /* The rank rows in effect, rank[s][j] = position of pool node j in scenario s's canonical order: the caller's (simon_set_node_ranks) or
  * those of a segmented / node-subset batch, where nodes a scenario lacks read N.  SIMON_ESTATE for a batch without rank rows. */

@@ -481,6 +481,7 @@ class BatchResult:
     headroom: Optional[np.ndarray] = None          # [S][K] int64: further pods like probe k that fit (Context.fetch_headroom; engines fill it on request)
     headroom_exact: Optional[np.ndarray] = None    # [K] bool: headroom[:, k] is what the scheduler would place, not an upper bound
     node_usage: Optional["NodeUsage"] = None       # per-node end state of the listed scenarios (Context.fetch_node_usage; on request)
+    gpu_usage: Optional["GpuUsage"] = None         # per-device end state of the listed scenarios (Context.fetch_gpu_usage; on request)
 
     def c_out(self) -> BatchOut:
         o = BatchOut()
@@ -514,6 +515,18 @@ class NodeUsage:
 
 class NodeUsageC(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("req_cpu", _p64), ("req_mem", _p64), ("req_eph", _p64), ("scalar_req", _p64), ("npods", _p32)]
+
+
+@dataclass
+class GpuUsage:
+    """simon_fetch_gpu_usage: the GPU-share devices at the end of the listed scenarios (row i = scenarios[i], pool node j, device d)."""
+    scenarios: np.ndarray               # [n] the indices as listed
+    dev_used: np.ndarray                # [n][N][MAX_GPU_DEV] int64 GPU memory booked on the device (state before the stream included)
+    dev_pods: Optional[np.ndarray] = None     # [n][N][MAX_GPU_DEV] int32 stream pods holding a slice of the device, on request; -1 = the scenario lacks node j
+
+
+class GpuUsageC(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("dev_used", _p64), ("dev_pods", _p32)]
 
 
 WANT_PLACEMENT, WANT_GPU_SLICES = 1, 2
@@ -563,6 +576,7 @@ EXPORTS = [
     "simon_set_image_locality", "simon_group_set_image_locality",
     "simon_set_scenario_segments", "simon_set_scenario_nodes", "simon_fetch_node_ranks", "simon_set_pod_eviction",
     "simon_set_scenario_pods", "simon_fetch_group_counts", "simon_fetch_node_usage", "simon_fetch_headroom",
+    "simon_fetch_gpu_usage", "simon_fetch_headroom_gpu",
     "simon_group_create", "simon_group_destroy", "simon_group_last_error", "simon_group_size", "simon_group_member",
     "simon_group_load_nodes", "simon_group_load_pods", "simon_group_load_class_tables", "simon_group_load_scenarios",
     "simon_group_run_loaded", "simon_group_fetch_results", "simon_group_run_batch", "simon_group_fetch_placement", "simon_group_fetch_gpu_slices",
@@ -614,6 +628,10 @@ def load_library(path: Optional[str] = None):
     lib.simon_fetch_node_usage.restype = C.c_int
     lib.simon_fetch_headroom.argtypes = [vp, _p32, C.c_int32, _p64, _p32, C.POINTER(C.c_uint8)]
     lib.simon_fetch_headroom.restype = C.c_int
+    lib.simon_fetch_gpu_usage.argtypes = [vp, _p32, C.c_int32, C.POINTER(GpuUsageC)]
+    lib.simon_fetch_gpu_usage.restype = C.c_int
+    lib.simon_fetch_headroom_gpu.argtypes = [vp, _p32, C.c_int32, _p64, _p32, C.POINTER(C.c_uint8)]
+    lib.simon_fetch_headroom_gpu.restype = C.c_int
     lib.simon_min_plan.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(Plan)]
     lib.simon_min_plan_vg.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Plan), C.POINTER(C.c_int32)]
     lib.simon_explain.argtypes = [vp, Scenario, _p32, _p32, _pu16, C.c_int32]
@@ -910,17 +928,32 @@ class Context:
                     "simon_fetch_node_usage")
         return res
 
-    def fetch_headroom(self, probe_pods, nodes: bool = False):
+    def fetch_gpu_usage(self, scen_ids=None, pods: bool = False) -> GpuUsage:
+        """simon_fetch_gpu_usage: GPU memory booked on every device of every pool node at the end of the listed scenarios of the last run
+        (None: all of them; pods=True: also the stream pods per device), reduced on the device from the placement matrix and the recorded
+        devices (run with want_gpu_slices)."""
+        ids = np.arange(self.S, dtype=np.int32) if scen_ids is None else np.ascontiguousarray(scen_ids, dtype=np.int32).reshape(-1)
+        n, N = len(ids), self.problem.n_nodes
+        res = GpuUsage(ids, np.zeros((n, N, MAX_GPU_DEV), np.int64), np.zeros((n, N, MAX_GPU_DEV), np.int32) if pods else None)
+        o = GpuUsageC()
+        o.struct_size = C.sizeof(GpuUsageC)
+        o.dev_used, o.dev_pods = _ptr(res.dev_used, C.c_int64), _ptr(res.dev_pods, C.c_int32)
+        self._check(self.lib.simon_fetch_gpu_usage(self.h, None if scen_ids is None else _ptr(ids, C.c_int32), n, C.byref(o)),
+                    "simon_fetch_gpu_usage")
+        return res
+
+    def fetch_headroom(self, probe_pods, nodes: bool = False, devices: bool = False):
         """simon_fetch_headroom: (fit [S][K] int64, fit_nodes [S][K] int32 or None, exact [K] bool) -- how many more pods like pod
         probe_pods[k] fit in every scenario of the last run, on how many nodes, and whether that count is what the scheduler would place
-        (exact) or the resource-and-static-filter upper bound."""
+        (exact) or the resource-and-static-filter upper bound.  devices=True: simon_fetch_headroom_gpu -- a probe with a GPU request is
+        also bounded by the slices the nodes' devices still hold, and is exact (run with want_gpu_slices)."""
         pp = np.ascontiguousarray(probe_pods, dtype=np.int32).reshape(-1)
         K = len(pp)
         fit = np.zeros((self.S, K), np.int64)
         fn = np.zeros((self.S, K), np.int32) if nodes else None
         ex = np.zeros(K, np.uint8)
-        self._check(self.lib.simon_fetch_headroom(self.h, _ptr(pp, C.c_int32), K, _ptr(fit, C.c_int64), _ptr(fn, C.c_int32), _ptr(ex, C.c_uint8)),
-                    "simon_fetch_headroom")
+        call, name = (self.lib.simon_fetch_headroom_gpu, "simon_fetch_headroom_gpu") if devices else (self.lib.simon_fetch_headroom, "simon_fetch_headroom")
+        self._check(call(self.h, _ptr(pp, C.c_int32), K, _ptr(fit, C.c_int64), _ptr(fn, C.c_int32), _ptr(ex, C.c_uint8)), name)
         return fit, fn, ex.astype(bool)
 
     def fetch_node_ranks(self) -> np.ndarray:

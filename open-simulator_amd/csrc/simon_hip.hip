@@ -221,6 +221,11 @@ struct simon_ctx : simon::HostInputs {
     DevBuf<int32_t> d_u_init_npods, d_u_alloc_pods, d_u_ids, d_u_npods, d_u_fit_nodes;
     DevBuf<ProbeRow> d_u_probes;
     DevBuf<uint64_t> d_u_probe_mask;
+    // simon_fetch_gpu_usage / simon_fetch_headroom_gpu: the GPU-share arrays the kernels read, staged likewise (gpu_mem [P]; devices per
+    // node, bytes per device [N] and the state before the stream [N][8]); the probes' device requests per call
+    bool usage_gpu_pods_staged = false, usage_gpu_nodes_staged = false;
+    DevBuf<int64_t> d_g_pod_mem, d_g_per_dev, d_g_init_used, d_g_out_used, d_g_probe_mem;
+    DevBuf<int32_t> d_g_node_cnt, d_g_out_pods, d_g_probe_cnt;
     bool orders_perm = false;                     // every loaded order is a permutation of [0, P) (the score-table kernel's placement gather)
     std::vector<int64_t> prefix_cpu, prefix_mem;   // [N+1] allocatable of the first n nodes
     std::vector<int64_t> prefix_vg;   // [N+1] Open-Local VG capacity of the first n nodes (0 without local storage)
@@ -1750,7 +1755,7 @@ int simon_load_nodes(simon_ctx* c, const simon_nodes_soa* nd) {
             if (d < -1 || d >= c->topo_n_dom[k]) return fail(c, SIMON_EINVAL, "topo_dom[%d][%d] out of range", k, j);
         }
     c->have_nodes = true; c->staged = false; c->have_results = false;
-    c->usage_nodes_staged = false;
+    c->usage_nodes_staged = false; c->usage_gpu_nodes_staged = false;
     return SIMON_OK;
 }
 
@@ -1793,7 +1798,7 @@ int simon_load_pods(simon_ctx* c, const simon_pods_soa* pd) {
     c->p_evict.clear(); c->evict_short = -1;
     c->pods_on = false;
     c->have_pods = true; c->staged = false; c->have_results = false;
-    c->usage_pods_staged = false;
+    c->usage_pods_staged = false; c->usage_gpu_pods_staged = false;
     return SIMON_OK;
 }
 
@@ -2546,12 +2551,12 @@ static int usage_stage(simon_ctx* c, UsageCommon& a) {
 // the rows a launch of `blocks` workgroups accumulates: `rows` (bits over the resource rows) in ascending order, and the node tile for
 // them -- the LDS budget's (four workgroups per CU), or, where the launch puts at most one workgroup on a CU anyway, the largest that
 // fits a workgroup (fewer passes over the placement row: config 5's 256 scenarios, profiles/usage/README.md)
-static void usage_rows_of(const simon_ctx* c, uint32_t rows, UsageCommon& a, int blocks) {
+static void usage_rows_of(const simon_ctx* c, uint32_t rows, UsageCommon& a, int blocks, int dev = 0) {
     a.nrows = 0;
     for (int r = 0; r < kUsageRows; ++r)
         if ((rows >> r) & 1u) a.row_src[a.nrows++] = r;
     for (int i = a.nrows; i < kUsageRows; ++i) a.row_src[i] = -1;
-    a.tile = usage_tile(c->N, a.nrows, c->usage_tile ? c->usage_tile : blocks <= c->n_cus ? 1 << 30 : 0);
+    a.tile = usage_tile(c->N, a.nrows, c->usage_tile ? c->usage_tile : blocks <= c->n_cus ? 1 << 30 : 0, dev);
 }
 
 static_assert(sizeof(ScenarioDesc) == 8, "the usage kernels read ScenarioDesc as int32 pairs");
@@ -2597,21 +2602,97 @@ int simon_fetch_node_usage(simon_ctx* c, const int32_t* scen_ids, int32_t n, sim
     return SIMON_OK;
 }
 
-int simon_fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int64_t* fit, int32_t* fit_nodes, uint8_t* exact) {
+// The GPU-share arrays of both device calls, uploaded on the first call after a reload; g.slices = the last run's record (nullptr for a
+// problem without any GPU request: nothing was booked).
+static int usage_stage_gpu(simon_ctx* c, DevUsage& g) {
+    const size_t N = c->N;
+    if (!c->usage_gpu_pods_staged) {
+        HIP_TRY(c, c->d_g_pod_mem.upload(c->p_gpu_mem, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->usage_gpu_pods_staged = true;
+    }
+    if (!c->usage_gpu_nodes_staged) {
+        std::vector<int32_t> cnt(N, 0);
+        std::vector<int64_t> per(N, 0), init(N * SIMON_MAX_GPU_DEV, 0);
+        for (size_t j = 0; j < N && c->has_gpu_nodes; ++j) {
+            if (c->gpu_cnt[j] <= 0) continue;
+            cnt[j] = std::min(c->gpu_cnt[j], SIMON_MAX_GPU_DEV);
+            per[j] = c->gpu_mem_total[j] / c->gpu_cnt[j];         // (by the unclamped count, as AllocateGpuId's per-device total)
+            std::copy_n(c->i_gpu_used.data() + j * SIMON_MAX_GPU_DEV, SIMON_MAX_GPU_DEV, init.data() + j * SIMON_MAX_GPU_DEV);
+        }
+        HIP_TRY(c, c->d_g_node_cnt.upload(cnt, c->stream));
+        HIP_TRY(c, c->d_g_per_dev.upload(per, c->stream));
+        HIP_TRY(c, c->d_g_init_used.upload(init, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));             // (the vectors leave scope)
+        c->usage_gpu_nodes_staged = true;
+    }
+    g.slices = c->has_gpu ? c->d_gpu_slices.p : nullptr;
+    g.gpu_mem = c->d_g_pod_mem.p; g.node_cnt = c->d_g_node_cnt.p; g.per_dev = c->d_g_per_dev.p; g.init_used = c->d_g_init_used.p;
+    return SIMON_OK;
+}
+
+static_assert(SIMON_MAX_GPU_DEV == kGpuDev, "the device kernels unpack one slices byte per device");
+
+int simon_fetch_gpu_usage(simon_ctx* c, const int32_t* scen_ids, int32_t n, simon_gpu_usage* out) {
     if (!c) return SIMON_EINVAL;
-    if (!probe_pod || !fit) return fail(c, SIMON_EINVAL, "fetch_headroom: missing required arrays (probe_pod, fit)");
-    if (K < 1 || K > SIMON_MAX_PROBES) return fail(c, SIMON_EINVAL, "fetch_headroom: %d probes outside [1, %d]", K, SIMON_MAX_PROBES);
-    if (!c->have_results || !c->have_placement) return fail(c, SIMON_ESTATE, "fetch_headroom: no placements on device (run with SIMON_WANT_PLACEMENT)");
+    if (!out) return fail(c, SIMON_EINVAL, "fetch_gpu_usage: bad arguments");
+    if (out->struct_size != sizeof(simon_gpu_usage)) return fail(c, SIMON_EINVAL, "fetch_gpu_usage: simon_gpu_usage size mismatch");
+    if (!out->dev_used) return fail(c, SIMON_EINVAL, "fetch_gpu_usage: missing required arrays (dev_used)");
+    if (n < 1) return fail(c, SIMON_EINVAL, "fetch_gpu_usage: %d scenarios listed", n);
+    if (!c->have_results || !c->have_placement) return fail(c, SIMON_ESTATE, "fetch_gpu_usage: no placements on device (run with SIMON_WANT_PLACEMENT)");
+    if (!scen_ids && n > c->S) return fail(c, SIMON_EINVAL, "fetch_gpu_usage: scenario %d outside [0,%d)", c->S, c->S);
+    for (int i = 0; scen_ids && i < n; ++i)
+        if (scen_ids[i] < 0 || scen_ids[i] >= c->S) return fail(c, SIMON_EINVAL, "fetch_gpu_usage: scenario %d outside [0,%d)", scen_ids[i], c->S);
+    if (c->has_gpu && !c->have_slices) return fail(c, SIMON_ESTATE, "fetch_gpu_usage: the last run did not record GPU devices (SIMON_WANT_GPU_SLICES)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    UsageCommon a{};
+    a.placement = c->d_place.p; a.scen = reinterpret_cast<const int32_t*>(c->d_scen.p);
+    a.rank = own_nodes(c) && c->has_ranks ? c->d_node_rank.p : nullptr;
+    a.P = c->P; a.N = c->N;
+    DevUsage g{};
+    if (const int rc = usage_stage_gpu(c, g)) return rc;
+    const int dev = kDevBytes + (out->dev_pods ? kDevPodsBytes : 0);
+    a.tile = usage_tile(c->N, 0, c->usage_tile ? c->usage_tile : n <= c->n_cus ? 1 << 30 : 0, dev);
+    const size_t cells = (size_t)n * c->N * SIMON_MAX_GPU_DEV;
+    GpuUsageOut o{};
+    HIP_TRY(c, c->d_g_out_used.ensure(cells));
+    o.dev_used = c->d_g_out_used.p;
+    if (out->dev_pods) { HIP_TRY(c, c->d_g_out_pods.ensure(cells)); o.dev_pods = c->d_g_out_pods.p; }
+    if (scen_ids) {
+        HIP_TRY(c, c->d_u_ids.ensure((size_t)n));
+        HIP_TRY(c, hipMemcpyAsync(c->d_u_ids.p, scen_ids, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        o.scen_ids = c->d_u_ids.p;
+    }
+    HIP_TRY(c, launch_gpu_usage(a, g, o, n, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out->dev_used, o.dev_used, cells * 8, hipMemcpyDeviceToHost, c->stream));
+    if (out->dev_pods) HIP_TRY(c, hipMemcpyAsync(out->dev_pods, o.dev_pods, cells * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));                 // (simon_stats is left alone, as in simon_fetch_node_usage)
+    return SIMON_OK;
+}
+
+// simon_fetch_headroom and simon_fetch_headroom_gpu (`devices`: the device bound on top, `what` names the call in messages)
+static int fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int64_t* fit, int32_t* fit_nodes, uint8_t* exact, bool devices,
+                          const char* what) {
+    if (!c) return SIMON_EINVAL;
+    if (!probe_pod || !fit) return fail(c, SIMON_EINVAL, "%s: missing required arrays (probe_pod, fit)", what);
+    if (K < 1 || K > SIMON_MAX_PROBES) return fail(c, SIMON_EINVAL, "%s: %d probes outside [1, %d]", what, K, SIMON_MAX_PROBES);
+    if (!c->have_results || !c->have_placement) return fail(c, SIMON_ESTATE, "%s: no placements on device (run with SIMON_WANT_PLACEMENT)", what);
     for (int k = 0; k < K; ++k)
-        if (probe_pod[k] < 0 || probe_pod[k] >= c->P) return fail(c, SIMON_EINVAL, "fetch_headroom: probe %d: pod %d outside [0,%d)", k, probe_pod[k], c->P);
+        if (probe_pod[k] < 0 || probe_pod[k] >= c->P) return fail(c, SIMON_EINVAL, "%s: probe %d: pod %d outside [0,%d)", what, k, probe_pod[k], c->P);
+    if (devices && c->has_gpu && !c->have_slices) return fail(c, SIMON_ESTATE, "%s: the last run did not record GPU devices (SIMON_WANT_GPU_SLICES)", what);
     HIP_TRY(c, hipSetDevice(c->device));
     UsageCommon a{};
     if (const int rc = usage_stage(c, a)) return rc;
-    usage_rows_of(c, c->usage_rows, a, c->S);
+    DevUsage g{};
+    if (devices)
+        if (const int rc = usage_stage_gpu(c, g)) return rc;
+    usage_rows_of(c, c->usage_rows, a, c->S, devices ? kDevBytes : 0);
     // the probe rows: request, the resources fitsRequest compares (fit.go:244-299), the class's static mask
     const size_t S = c->S, N = c->N, W = (N + 63) / 64, P = c->P;
     std::vector<ProbeRow> rows((size_t)K);
     std::vector<uint64_t> mask((size_t)K * W, ~0ull);
+    std::vector<int64_t> gmem((size_t)K, 0);
+    std::vector<int32_t> gcnt((size_t)K, 0);
     auto none = [](const std::vector<int32_t>& off, int cls) { return (size_t)cls + 1 >= off.size() || off[cls + 1] == off[cls]; };
     for (int k = 0; k < K; ++k) {
         const int p = probe_pod[k], cls = c->p_cls[p];
@@ -2626,8 +2707,11 @@ int simon_fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int6
         const bool shortcut = r.q[0] == 0 && r.q[1] == 0 && r.q[2] == 0 && entries == 0;
         r.checked = shortcut ? 0u : 7u | ((entries & ((1u << c->K) - 1u)) << 3);
         if (c->has_mask) std::copy_n(c->static_mask.data() + (size_t)cls * W, W, mask.data() + (size_t)k * W);
+        // the device bound: a GPU request without a gpu-index annotation (such a pod short-cuts AllocateGpuId: no bound, not exact)
+        const bool bound = devices && c->p_gpu_mem[p] > 0 && c->p_gpu_index[p] == 0;
+        if (bound) { gmem[k] = c->p_gpu_mem[p]; gcnt[k] = std::min(c->p_gpu_cnt[p], 64); }
         if (exact)
-            exact[k] = c->p_gpu_mem[p] == 0 && c->p_gpu_cnt[p] == 0 && c->p_gpu_index[p] == 0 && c->p_pin[p] < 0 && c->p_preset[p] < 0 &&
+            exact[k] = (bound || (c->p_gpu_mem[p] == 0 && c->p_gpu_cnt[p] == 0 && c->p_gpu_index[p] == 0)) && c->p_pin[p] < 0 && c->p_preset[p] < 0 &&
                        none(c->match_off, cls) && none(c->anti_off, cls) && none(c->port_off, cls) && none(c->aff_off, cls) && none(c->sh_off, cls) &&
                        ((size_t)cls >= c->l_spec_of.size() || c->l_spec_of[cls] < 0);
     }
@@ -2639,11 +2723,25 @@ int simon_fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int6
     if (fit_nodes) HIP_TRY(c, c->d_u_fit_nodes.ensure(cells));
     h.node_alloc = c->d_u_node_alloc.p; h.alloc_pods = c->d_u_alloc_pods.p; h.probes = c->d_u_probes.p; h.probe_mask = c->d_u_probe_mask.p;
     h.K = K; h.fit = c->d_u_fit.p; h.fit_nodes = fit_nodes ? c->d_u_fit_nodes.p : nullptr;
-    HIP_TRY(c, launch_headroom(a, h, (int)S, c->stream));
+    if (devices) {
+        HIP_TRY(c, c->d_g_probe_mem.upload(gmem, c->stream));
+        HIP_TRY(c, c->d_g_probe_cnt.upload(gcnt, c->stream));
+        g.probe_mem = c->d_g_probe_mem.p; g.probe_cnt = c->d_g_probe_cnt.p;
+        HIP_TRY(c, launch_headroom_gpu(a, h, g, (int)S, c->stream));
+    } else
+        HIP_TRY(c, launch_headroom(a, h, (int)S, c->stream));
     HIP_TRY(c, hipMemcpyAsync(fit, c->d_u_fit.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
     if (fit_nodes) HIP_TRY(c, hipMemcpyAsync(fit_nodes, c->d_u_fit_nodes.p, cells * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));                 // (also: rows and mask outlive their uploads)
     return SIMON_OK;
+}
+
+int simon_fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int64_t* fit, int32_t* fit_nodes, uint8_t* exact) {
+    return fetch_headroom(c, probe_pod, K, fit, fit_nodes, exact, false, "fetch_headroom");
+}
+
+int simon_fetch_headroom_gpu(simon_ctx* c, const int32_t* probe_pod, int32_t K, int64_t* fit, int32_t* fit_nodes, uint8_t* exact) {
+    return fetch_headroom(c, probe_pod, K, fit, fit_nodes, exact, true, "fetch_headroom_gpu");
 }
 
 // The all-feature kernel gives every problem its failure codes and runs the batches no other kernel takes: staged on first use where

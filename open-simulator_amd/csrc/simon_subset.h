@@ -79,15 +79,46 @@ struct HeadroomArgs {
     int32_t* fit_nodes;                      // [S][K] or nullptr
 };
 
-// bytes of LDS one node of a tile costs, and the tile the launchers use for N nodes (`forced` > 0: SIMON_USAGE_TILE)
-inline size_t usage_node_bytes(int nrows) { return (size_t)nrows * 8 + 4; }
-inline int usage_tile(int N, int nrows, int forced) {
-    int t = forced > 0 ? forced : (int)(kUsageLdsBudget / usage_node_bytes(nrows)) / 64 * 64;
-    const int cap = (int)((64 * 1024 - 2 * kMaxProbes * 8) / usage_node_bytes(nrows));   // (one workgroup's 64 KB, less the headroom counters)
+// GPU-share devices (simon_fetch_gpu_usage, simon_fetch_headroom_gpu): the recorded slices reduced next to the placement matrix.  Per
+// tile the device sums sit in LDS as s_dev[tile][8] u64 (s_dpods[tile][8] i32 where asked for), 64 (96) bytes per node; device d of tile
+// node jj is slot dev_slot(jj, d): the eight devices of a node stay in the node's own 64 bytes, rotated by the node index, so that the
+// same device of neighbouring nodes (device 0 takes most bookings) does not fall on one pair of banks (docs/KERNELS.md).
+constexpr int kGpuDev = 8;                   // SIMON_MAX_GPU_DEV
+constexpr int kDevBytes = kGpuDev * 8, kDevPodsBytes = kGpuDev * 4;
+
+struct DevUsage {
+    const uint64_t* slices;                  // [S][P] byte d = slices booked on device d, or nullptr = no GPU request anywhere (nothing was booked)
+    const int64_t* gpu_mem;                  // [P] GPU memory per slice (0: the pod's slices word is not read)
+    const int32_t* node_cnt;                 // [N] devices of node j: min(gpu_cnt, kGpuDev), 0 = none
+    const int64_t* per_dev;                  // [N] bytes per device: gpu_mem_total / gpu_cnt (0 without devices)
+    const int64_t* init_used;                // [N][kGpuDev] booked before the stream
+    // headroom only: the device bound of every probe
+    const int64_t* probe_mem;                // [K] GPU memory per slice; 0 = no device bound for this probe
+    const int32_t* probe_cnt;                // [K] min(gpu_cnt, 64); <= 0 = the pod fits no device (cap 0)
+};
+
+struct GpuUsageOut {
+    const int32_t* scen_ids;                 // [n] listed scenarios, or nullptr = 0 .. n-1
+    int64_t* dev_used;                       // [n][N][kGpuDev]
+    int32_t* dev_pods;                       // [n][N][kGpuDev] or nullptr
+};
+
+__host__ __device__ inline int dev_slot(int jj, int d) { return jj * kGpuDev + ((d + (jj >> 1)) & (kGpuDev - 1)); }
+
+// bytes of LDS one node of a tile costs (`dev`: 0, kDevBytes or kDevBytes + kDevPodsBytes on top of the resource rows; nrows = 0: devices
+// only), and the tile the launchers use for N nodes (`forced` > 0: SIMON_USAGE_TILE)
+inline size_t usage_node_bytes(int nrows, int dev = 0) { return (nrows > 0 ? (size_t)nrows * 8 + 4 : 0) + (size_t)dev; }
+inline int usage_tile(int N, int nrows, int forced, int dev = 0) {
+    int t = forced > 0 ? forced : (int)(kUsageLdsBudget / usage_node_bytes(nrows, dev)) / 64 * 64;
+    const int cap = (int)((64 * 1024 - 2 * kMaxProbes * 8) / usage_node_bytes(nrows, dev));   // (one workgroup's 64 KB, less the headroom counters)
     t = t > cap ? cap : t;
     return t < 1 ? 1 : (t > N ? N : t);
 }
 hipError_t launch_node_usage(const UsageCommon& a, const UsageOut& o, int n, hipStream_t st);
 hipError_t launch_headroom(const UsageCommon& a, const HeadroomArgs& h, int S, hipStream_t st);
+// a.tile from usage_tile(N, 0, forced, kDevBytes (+ kDevPodsBytes with dev_pods)); a.pod_req / node_init / init_npods are not read
+hipError_t launch_gpu_usage(const UsageCommon& a, const DevUsage& g, const GpuUsageOut& o, int n, hipStream_t st);
+// headroom with the device bound: a.tile from usage_tile(N, nrows, forced, kDevBytes)
+hipError_t launch_headroom_gpu(const UsageCommon& a, const HeadroomArgs& h, const DevUsage& g, int S, hipStream_t st);
 
 }  // namespace simon

@@ -139,15 +139,37 @@ __global__ __launch_bounds__(256) void group_counts_kernel(const int32_t* __rest
     }
 }
 
-// ---- simon_fetch_node_usage / simon_fetch_headroom ----------------------------------------------------------------------------------
+// ---- simon_fetch_node_usage / simon_fetch_headroom / simon_fetch_gpu_usage / simon_fetch_headroom_gpu --------------------------------
+// One pod's recorded devices onto its node's eight sums: byte d of the slices word times the pod's GPU memory per slice, one LDS atomic
+// per non-zero byte (and 1 onto the device's pod count where kept).  A pod without a GPU request never touches the slices row.
+__device__ __forceinline__ void dev_add(const DevUsage& g, const uint64_t* __restrict__ srow, int p, int jj,
+                                        unsigned long long* s_dev, int32_t* s_dpods) {
+    const long long m = g.gpu_mem[p];
+    if (m <= 0) return;
+    const uint64_t w = srow[p];
+    if (w == 0) return;                                                 // (bound by Spec.NodeName: never reserved)
+#pragma unroll
+    for (int d = 0; d < kGpuDev; ++d) {
+        const unsigned b = (unsigned)(w >> (8 * d)) & 255u;
+        if (b == 0) continue;
+        atomicAdd(&s_dev[dev_slot(jj, d)], (unsigned long long)b * (unsigned long long)m);
+        if (s_dpods) atomicAdd(&s_dpods[dev_slot(jj, d)], 1);
+    }
+}
+
 // One tile of the node range [t0, t1): s_req[i][j - t0] = request sum of accumulated row i over the pods placed on node j, s_cnt[j - t0]
-// their number.  The placement row is read coalesced; a pod whose node lies outside the tile (SIMON_UNSCHEDULED / SIMON_GATED: below 0)
-// adds nothing.  Ends behind a barrier: every thread may read the tile.
+// their number; DEV: also s_dev[dev_slot(j - t0, d)] = GPU memory the stream booked on device d of node j (srow: the scenario's slices
+// row, nullptr = nothing booked).  The placement row is read coalesced; a pod whose node lies outside the tile (SIMON_UNSCHEDULED /
+// SIMON_GATED: below 0) adds nothing.  Ends behind a barrier: every thread may read the tile.
+template <bool DEV>
 __device__ __forceinline__ void usage_accumulate(const UsageCommon& a, const int32_t* __restrict__ row, int t0, int t1,
-                                                 unsigned long long* s_req, int32_t* s_cnt) {
+                                                 unsigned long long* s_req, int32_t* s_cnt, const DevUsage* g = nullptr,
+                                                 const uint64_t* __restrict__ srow = nullptr, unsigned long long* s_dev = nullptr) {
     const int tid = threadIdx.x, tile = a.tile;
     for (int i = tid; i < a.nrows * tile; i += 256) s_req[i] = 0;
     for (int i = tid; i < tile; i += 256) s_cnt[i] = 0;
+    if (DEV)
+        for (int i = tid; i < tile * kGpuDev; i += 256) s_dev[i] = 0;
     __syncthreads();
     for (int p = tid; p < a.P; p += 256) {
         const int v = row[p];
@@ -157,6 +179,22 @@ __device__ __forceinline__ void usage_accumulate(const UsageCommon& a, const int
             const long long q = a.pod_req[(size_t)a.row_src[i] * a.P + p];
             if (q != 0) atomicAdd(&s_req[i * tile + (v - t0)], (unsigned long long)q);
         }
+        if (DEV && srow) dev_add(*g, srow, p, v - t0, s_dev, nullptr);
+    }
+    __syncthreads();
+}
+
+// The device sums alone (gpu_usage_kernel): as above without the resource rows; s_dpods may be nullptr.
+__device__ __forceinline__ void dev_accumulate(const UsageCommon& a, const DevUsage& g, const int32_t* __restrict__ row,
+                                               const uint64_t* __restrict__ srow, int t0, int t1, unsigned long long* s_dev, int32_t* s_dpods) {
+    const int tid = threadIdx.x, cells = a.tile * kGpuDev;
+    for (int i = tid; i < cells; i += 256) s_dev[i] = 0;
+    for (int i = tid; s_dpods && i < cells; i += 256) s_dpods[i] = 0;
+    __syncthreads();
+    for (int p = tid; srow && p < a.P; p += 256) {
+        const int v = row[p];
+        if (v < t0 || v >= t1) continue;
+        dev_add(g, srow, p, v - t0, s_dev, s_dpods);
     }
     __syncthreads();
 }
@@ -175,7 +213,7 @@ __global__ __launch_bounds__(256) void node_usage_kernel(UsageCommon a, UsageOut
     const int32_t* __restrict__ const row = a.placement + (size_t)s * a.P;
     for (int t0 = 0; t0 < N; t0 += a.tile) {
         const int t1 = min(t0 + a.tile, N);
-        usage_accumulate(a, row, t0, t1, s_req, s_cnt);
+        usage_accumulate<false>(a, row, t0, t1, s_req, s_cnt);
         for (int j = t0 + tid; j < t1; j += 256) {
             const bool in = usage_holds(a, s, j);
             for (int i = 0; i < a.nrows; ++i)
@@ -186,23 +224,55 @@ __global__ __launch_bounds__(256) void node_usage_kernel(UsageCommon a, UsageOut
     }
 }
 
+// gpu_usage_kernel: workgroup b = listed scenario b.  [n][N][8] leaves coalesced (thread i of a pass = device i & 7 of tile node i >> 3);
+// a node the scenario lacks reads 0 / dev_pods -1, a device the node lacks 0 / 0.
+__global__ __launch_bounds__(256) void gpu_usage_kernel(UsageCommon a, DevUsage g, GpuUsageOut o) {
+    extern __shared__ unsigned long long usage_smem[];
+    unsigned long long* const s_dev = usage_smem;                       // [tile][8]
+    int32_t* const s_dpods = o.dev_pods ? (int32_t*)(usage_smem + (size_t)a.tile * kGpuDev) : nullptr;   // [tile][8]
+    const int b = blockIdx.x, tid = threadIdx.x, N = a.N;
+    const int s = o.scen_ids ? o.scen_ids[b] : b;
+    const int32_t* __restrict__ const row = a.placement + (size_t)s * a.P;
+    const uint64_t* __restrict__ const srow = g.slices ? g.slices + (size_t)s * a.P : nullptr;
+    for (int t0 = 0; t0 < N; t0 += a.tile) {
+        const int t1 = min(t0 + a.tile, N);
+        dev_accumulate(a, g, row, srow, t0, t1, s_dev, s_dpods);
+        for (int i = tid; i < (t1 - t0) * kGpuDev; i += 256) {
+            const int jj = i >> 3, d = i & 7, j = t0 + jj;
+            const bool in = usage_holds(a, s, j), live = d < g.node_cnt[j];
+            const size_t at = ((size_t)b * N + j) * kGpuDev + d;
+            o.dev_used[at] = in && live ? g.init_used[(size_t)j * kGpuDev + d] + (long long)s_dev[dev_slot(jj, d)] : 0;
+            if (o.dev_pods) o.dev_pods[at] = !in ? -1 : live ? s_dpods[dev_slot(jj, d)] : 0;
+        }
+        __syncthreads();                                                // (the next tile zeroes what this one read)
+    }
+}
+
 // headroom_kernel: workgroup s = scenario s of the batch.  Per tile the same accumulation; then, per probe, every thread takes the cap
-// of its nodes of the tile and the workgroup adds them up in LDS.  Only [S][K] counters leave.
-__global__ __launch_bounds__(256) void headroom_kernel(UsageCommon a, HeadroomArgs h) {
+// of its nodes of the tile and the workgroup adds them up in LDS.  Only [S][K] counters leave.  DEV (simon_fetch_headroom_gpu): the
+// tile also carries the device sums, and a probe with a GPU request is bounded by the slices the node's devices still hold:
+// T = sum over the node's devices of max(per_dev - used, 0) / mem, cap_gpu = T / count (GpuNodeInfo.AllocateGpuId accepts such a pod iff
+// T >= count, and every accepted pod lowers T by count).
+template <bool DEV>
+__global__ __launch_bounds__(256) void headroom_kernel(UsageCommon a, HeadroomArgs h, DevUsage g) {
     extern __shared__ unsigned long long usage_smem[];
     unsigned long long* const s_req = usage_smem;                       // [nrows][tile]
-    unsigned long long* const s_fit = s_req + (size_t)a.nrows * a.tile; // [K]
+    unsigned long long* const s_dev = s_req + (size_t)a.nrows * a.tile; // DEV: [tile][8]
+    unsigned long long* const s_fit = s_dev + (DEV ? (size_t)a.tile * kGpuDev : 0);   // [K]
     int32_t* const s_cnt = (int32_t*)(s_fit + h.K);                     // [tile]
     int32_t* const s_nodes = s_cnt + a.tile;                            // [K]
     const int s = blockIdx.x, tid = threadIdx.x, N = a.N, K = h.K, W = (N + 63) >> 6;
     const int32_t* __restrict__ const row = a.placement + (size_t)s * a.P;
+    const uint64_t* __restrict__ const srow = DEV && g.slices ? g.slices + (size_t)s * a.P : nullptr;
     for (int k = tid; k < K; k += 256) { s_fit[k] = 0; s_nodes[k] = 0; }
     for (int t0 = 0; t0 < N; t0 += a.tile) {
         const int t1 = min(t0 + a.tile, N);
-        usage_accumulate(a, row, t0, t1, s_req, s_cnt);                 // (its first barrier also covers s_fit / s_nodes)
+        usage_accumulate<DEV>(a, row, t0, t1, s_req, s_cnt, &g, srow, s_dev);   // (its first barrier also covers s_fit / s_nodes)
         for (int k = 0; k < K; ++k) {
             const ProbeRow& pr = h.probes[k];
             const uint64_t* __restrict__ const mask = h.probe_mask + (size_t)k * W;
+            const long long gm = DEV ? g.probe_mem[k] : 0;
+            const int gc = DEV ? g.probe_cnt[k] : 0;
             long long fit = 0;
             int nodes = 0;
             for (int j = t0 + tid; j < t1; j += 256) {
@@ -216,6 +286,16 @@ __global__ __launch_bounds__(256) void headroom_kernel(UsageCommon a, HeadroomAr
                     const long long room = h.node_alloc[(size_t)r * N + j] - used, q = pr.q[r];
                     if (room < 0) cap = 0;                              // over-committed: Allocatable < request + Requested whatever the request
                     else if (q > 0) cap = min(cap, room / q);
+                }
+                if (DEV && gm > 0 && cap > 0) {
+                    long long T = 0;
+                    const int cnt = gc > 0 ? g.node_cnt[j] : 0;
+                    const long long per = g.per_dev[j];
+                    for (int d = 0; d < cnt; ++d) {
+                        const long long idle = per - g.init_used[(size_t)j * kGpuDev + d] - (long long)s_dev[dev_slot(j - t0, d)];
+                        if (idle > 0) T += idle / gm;                   // (an over-booked device holds nothing)
+                    }
+                    cap = gc > 0 ? min(cap, T / gc) : 0;
                 }
                 if (cap > 0) { fit += cap; ++nodes; }
             }
@@ -250,7 +330,24 @@ hipError_t launch_headroom(const UsageCommon& a, const HeadroomArgs& h, int S, h
     if (S <= 0 || a.N <= 0 || a.tile <= 0 || a.nrows < 2 || a.nrows > kUsageRows || h.K < 1 || h.K > kMaxProbes) return hipErrorInvalidValue;
     const size_t lds = (size_t)a.tile * usage_node_bytes(a.nrows) + (size_t)h.K * 12;
     if (lds > 64 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(headroom_kernel, dim3((unsigned)S), dim3(256), lds, st, a, h);
+    hipLaunchKernelGGL(headroom_kernel<false>, dim3((unsigned)S), dim3(256), lds, st, a, h, DevUsage{});
+    return hipGetLastError();
+}
+
+hipError_t launch_gpu_usage(const UsageCommon& a, const DevUsage& g, const GpuUsageOut& o, int n, hipStream_t st) {
+    if (n <= 0 || a.N <= 0 || a.tile <= 0 || !o.dev_used || !g.gpu_mem || !g.node_cnt || !g.init_used) return hipErrorInvalidValue;
+    const size_t lds = (size_t)a.tile * usage_node_bytes(0, kDevBytes + (o.dev_pods ? kDevPodsBytes : 0));
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gpu_usage_kernel, dim3((unsigned)n), dim3(256), lds, st, a, g, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_headroom_gpu(const UsageCommon& a, const HeadroomArgs& h, const DevUsage& g, int S, hipStream_t st) {
+    if (S <= 0 || a.N <= 0 || a.tile <= 0 || a.nrows < 2 || a.nrows > kUsageRows || h.K < 1 || h.K > kMaxProbes) return hipErrorInvalidValue;
+    if (!g.gpu_mem || !g.node_cnt || !g.per_dev || !g.init_used || !g.probe_mem || !g.probe_cnt) return hipErrorInvalidValue;
+    const size_t lds = (size_t)a.tile * usage_node_bytes(a.nrows, kDevBytes) + (size_t)h.K * 12;
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(headroom_kernel<true>, dim3((unsigned)S), dim3(256), lds, st, a, h, g);
     return hipGetLastError();
 }
 

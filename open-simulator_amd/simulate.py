@@ -29,13 +29,18 @@ class HipEngine:
     supports_pod_eviction = True              # ... and reschedules the pods of the lost nodes (simon_set_pod_eviction): sweep_failures(reschedule=...)
     supports_pod_subsets = True               # pod subsets (simon_set_scenario_pods): sweep_apps() batches the combinations of apps
     supports_node_usage = True                # per-node usage and headroom reduced on the device (simon_fetch_node_usage / simon_fetch_headroom)
+    supports_gpu_usage = True                 # ... GPU-share devices and the device bound of headroom (simon_fetch_gpu_usage / simon_fetch_headroom_gpu)
 
     def __init__(self, device_id: int = 0):
         self.device_id = device_id
 
     def run(self, prob: capi.Problem, scen, orders, want_placement=True, node_ranks=None, want_gpu_slices=False,
-            segments=None, present=None, evict=None, pod_present=None, pod_groups=None, headroom_pods=None, usage_of=None) -> capi.BatchResult:
-        """headroom_pods: pod ids [K] -- the result carries headroom [S][K] (how many more pods like each fit in every scenario) and
+            segments=None, present=None, evict=None, pod_present=None, pod_groups=None, headroom_pods=None, usage_of=None,
+            gpu_usage_of=None, headroom_devices=False) -> capi.BatchResult:
+        """gpu_usage_of: scenario indices -- the result carries gpu_usage, GPU memory and stream pods per device at the end of those
+        scenarios (simon_fetch_gpu_usage).  headroom_devices: headroom_pods are answered with the device bound (simon_fetch_headroom_gpu:
+        GPU probes become exact).  Either one makes the run record the devices (want_gpu_slices) by itself.
+        headroom_pods: pod ids [K] -- the result carries headroom [S][K] (how many more pods like each fit in every scenario) and
         headroom_exact [K] (simon_fetch_headroom).  usage_of: scenario indices -- the result carries node_usage, the per-node requests and
         pod counts at the end of those scenarios (simon_fetch_node_usage).  Both are reduced on the device from the placement matrix.
         pod_present: bool [S][P] (or packed words) -- scenario s holds the pods of its row and no others (simon_set_scenario_pods; with
@@ -53,7 +58,8 @@ class HipEngine:
             ctx.load_problem(prob)
             if evict is not None:
                 ctx.set_pod_eviction(evict)
-            usage = headroom_pods is not None or usage_of is not None
+            usage = headroom_pods is not None or usage_of is not None or gpu_usage_of is not None
+            record = want_gpu_slices or gpu_usage_of is not None or (headroom_devices and headroom_pods is not None)
             if node_ranks is None and segments is None and present is None and pod_present is None and pod_groups is None and not usage:
                 res = ctx.run_batch(scen, orders, want_placement, want_gpu_slices)
             else:
@@ -66,10 +72,12 @@ class HipEngine:
                     ctx.set_scenario_nodes(*present)
                 if node_ranks is not None:
                     ctx.set_node_ranks(node_ranks)    # per-scenario nodeTree order (clusters with several zones)
-                ctx.run_loaded(want_placement or pod_groups is not None or usage, want_gpu_slices)
+                ctx.run_loaded(want_placement or pod_groups is not None or usage, record)
                 res = ctx.fetch(want_placement, want_gpu_slices)
                 if headroom_pods is not None:
-                    res.headroom, _, res.headroom_exact = ctx.fetch_headroom(headroom_pods)
+                    res.headroom, _, res.headroom_exact = ctx.fetch_headroom(headroom_pods, devices=bool(headroom_devices))
+                if gpu_usage_of is not None:
+                    res.gpu_usage = ctx.fetch_gpu_usage(gpu_usage_of, pods=True)
                 if usage_of is not None:
                     res.node_usage = ctx.fetch_node_usage(usage_of)
                 if pod_groups is not None:
@@ -489,11 +497,48 @@ def host_node_usage(prob: capi.Problem, placement, held, scen_ids=None) -> capi.
     return capi.NodeUsage(ids, req[:, 0].copy(), req[:, 1].copy(), cnt, req[:, 2].copy(), req[:, 3:].copy())
 
 
-def host_headroom(prob: capi.Problem, placement, held, probes):
-    """capi.Context.fetch_headroom on the host: (fit [S][K] int64, fit_nodes [S][K] int32, exact [K] bool)."""
+def _gpu_nodes(prob: capi.Problem):
+    """(devices per node min(gpu_cnt, 8) [N], bytes per device gpu_mem_total / gpu_cnt [N]) -- zeros for nodes without GPUs."""
+    N = prob.n_nodes
+    raw = np.zeros(N, np.int64) if prob.gpu_cnt is None else np.asarray(prob.gpu_cnt, np.int64)
+    tot = np.zeros(N, np.int64) if prob.gpu_mem_total is None else np.asarray(prob.gpu_mem_total, np.int64)
+    return np.minimum(np.maximum(raw, 0), capi.MAX_GPU_DEV), np.where(raw > 0, tot // np.maximum(raw, 1), 0)
+
+
+def host_gpu_usage(prob: capi.Problem, placement, slices, held, scen_ids=None) -> capi.GpuUsage:
+    """capi.Context.fetch_gpu_usage(pods=True) on the host, from placement rows [S][P], the recorded devices [S][P] (None: a problem
+    without GPU requests) and the nodes every scenario holds (bool [S][N])."""
+    ids = np.arange(len(held), dtype=np.int32) if scen_ids is None else np.asarray(scen_ids, np.int32)
+    placement, held = np.asarray(placement)[ids], np.asarray(held, bool)[ids]
+    n, N = held.shape
+    D = capi.MAX_GPU_DEV
+    used, pods = np.zeros((n, N, D), np.int64), np.zeros((n, N, D), np.int32)
+    gmem = None if prob.gpu_mem is None else np.asarray(prob.gpu_mem, np.int64)
+    if slices is not None and gmem is not None:
+        slices = np.asarray(slices, np.uint64)[ids]
+        for i in range(n):
+            on = (placement[i] >= 0) & (gmem > 0)
+            idx = placement[i][on]
+            for d in range(D):
+                b = ((slices[i][on] >> np.uint64(8 * d)) & np.uint64(255)).astype(np.int64)
+                np.add.at(used[i, :, d], idx, b * gmem[on])
+                np.add.at(pods[i, :, d], idx, (b > 0).astype(np.int32))
+    if prob.init_gpu_used is not None:
+        used += np.asarray(prob.init_gpu_used, np.int64).reshape(N, D)[None]
+    cnt, _ = _gpu_nodes(prob)
+    live = held[:, :, None] & (np.arange(D)[None, None, :] < cnt[None, :, None])
+    return capi.GpuUsage(ids, np.where(live, used, 0), np.where(held[:, :, None], np.where(live, pods, 0), -1).astype(np.int32))
+
+
+def host_headroom(prob: capi.Problem, placement, held, probes, slices=None, devices: bool = False):
+    """capi.Context.fetch_headroom on the host: (fit [S][K] int64, fit_nodes [S][K] int32, exact [K] bool).  devices=True: with the
+    device bound of simon_fetch_headroom_gpu, from the recorded devices `slices` [S][P]."""
     held = np.asarray(held, bool)
     S, N = held.shape
     req, cnt = _usage_sums(prob, placement, held)
+    if devices:
+        dev_used = host_gpu_usage(prob, placement, slices, np.ones_like(held)).dev_used
+        g_cnt, g_per = _gpu_nodes(prob)
     K = req.shape[1] - 3
     z = lambda v: np.zeros(N, np.int64) if v is None else np.asarray(v, np.int64)                         # noqa: E731
     alloc = [z(prob.alloc_cpu), z(prob.alloc_mem), z(prob.alloc_eph)] + [z(prob.scalar_alloc[k]) for k in range(K)]
@@ -514,61 +559,102 @@ def host_headroom(prob: capi.Problem, placement, held, probes):
             room = alloc[r][None, :] - req[:, r]
             cap = np.where(room < 0, 0, cap if q[r] <= 0 else np.minimum(cap, np.maximum(room, 0) // max(q[r], 1)))
         cap = np.where(ok, np.maximum(cap, 0), 0)
+        bound = devices and of(prob.gpu_mem, p) > 0 and not of(prob.gpu_index, p)
+        if bound:
+            # slices the node's devices still hold, over the pod's device count: what AllocateGpuId + Reserve accept (include/simon_hip.h)
+            idle = np.maximum(g_per[None, :, None] - dev_used, 0) // of(prob.gpu_mem, p)
+            idle *= np.arange(capi.MAX_GPU_DEV)[None, None, :] < g_cnt[None, :, None]
+            c = min(of(prob.pod_gpu_cnt, p), 64)
+            cap = np.minimum(cap, idle.sum(2) // c) if c > 0 else np.zeros_like(cap)
         fit[:, k], nodes[:, k] = cap.sum(1), (cap > 0).sum(1)
         none = lambda off: prob.term_topo_key is None or len(prob.term_topo_key) == 0 or off is None or off[cls + 1] == off[cls]   # noqa: E731
-        exact[k] = (not of(prob.gpu_mem, p) and not of(prob.pod_gpu_cnt, p) and not of(prob.gpu_index, p) and of(prob.pin_node, p, -1) < 0
+        exact[k] = ((bound or (not of(prob.gpu_mem, p) and not of(prob.pod_gpu_cnt, p) and not of(prob.gpu_index, p))) and of(prob.pin_node, p, -1) < 0
                     and of(prob.preset_node, p, -1) < 0 and all(none(o) for o in (prob.match_off, prob.anti_off, prob.port_off, prob.aff_off, prob.spread_hard_off))
                     and (prob.local_spec_of is None or int(prob.local_spec_of[cls]) < 0))
     return fit, nodes, exact
 
 
-def _usage_kw(engine, probes, node_table: bool, S: int) -> dict:
-    """engine.run's keywords for a batch whose sweep asked for headroom / the node table (nothing for an engine without the calls)."""
-    if not getattr(engine, "supports_node_usage", False):
+def _on_device(engine, devices: bool) -> bool:
+    """The engine reduces what the sweep asked for itself (with devices=True it needs both pairs of calls)."""
+    return getattr(engine, "supports_node_usage", False) and (not devices or getattr(engine, "supports_gpu_usage", False))
+
+
+def _usage_kw(engine, probes, node_table: bool, S: int, devices: bool = False) -> dict:
+    """engine.run's keywords for a batch whose sweep asked for headroom / the node table / the devices (nothing for an engine without
+    the calls)."""
+    if not _on_device(engine, devices):
         return {}
-    return {**({"headroom_pods": probes} if probes is not None else {}), **({"usage_of": np.arange(S, dtype=np.int32)} if node_table else {})}
+    ids = np.arange(S, dtype=np.int32)
+    return {**({"headroom_pods": probes} if probes is not None else {}), **({"usage_of": ids} if node_table else {}),
+            **({"gpu_usage_of": ids, "headroom_devices": True} if devices else {})}
 
 
-def _node_rows(nodes: List[dict], prob: capi.Problem, usage: capi.NodeUsage, i: int) -> List[dict]:
-    """reportClusterInfo's columns (pkg/apply/apply.go:315-400) for the nodes scenario row i of `usage` holds, in pool order."""
+def _node_rows(nodes: List[dict], prob: capi.Problem, usage: capi.NodeUsage, i: int, gpu: Optional[capi.GpuUsage] = None) -> List[dict]:
+    """reportClusterInfo's columns (pkg/apply/apply.go:315-400) for the nodes scenario row i of `usage` holds, in pool order; with `gpu`
+    also its "GPU Mem Allocatable / GPU Mem Requests" pair (:328-329, 380: the requests are the node's devices summed)."""
+    tot = None if gpu is None else (np.zeros(len(nodes), np.int64) if prob.gpu_mem_total is None else np.asarray(prob.gpu_mem_total, np.int64))
     return [{"node": nodes[j]["metadata"]["name"], "cpu_allocatable": int(prob.alloc_cpu[j]), "cpu_requests": int(usage.req_cpu[i, j]),
-             "memory_allocatable": int(prob.alloc_mem[j]), "memory_requests": int(usage.req_mem[i, j]), "pods": int(usage.npods[i, j]),
-             "new": wl.LABEL_NEW_NODE in (nodes[j]["metadata"].get("labels") or {})}
+             "memory_allocatable": int(prob.alloc_mem[j]), "memory_requests": int(usage.req_mem[i, j]),
+             **({} if gpu is None else {"gpu_mem_allocatable": int(tot[j]), "gpu_mem_requests": int(gpu.dev_used[i, j].sum())}),
+             "pods": int(usage.npods[i, j]), "new": wl.LABEL_NEW_NODE in (nodes[j]["metadata"].get("labels") or {})}
             for j in np.flatnonzero(usage.npods[i] >= 0).tolist()]
 
 
-def _usage_fill(engine, out, nodes, prob, held, probes, node_table: bool, warn, what: str):
+def _gpu_rows(nodes: List[dict], prob: capi.Problem, gpu: capi.GpuUsage, i: int) -> List[dict]:
+    """The "GPU Node Resource" table (pkg/apply/apply.go:456-500) for the GPU nodes scenario row i of `gpu` holds, in pool order: node,
+    GPU model label, and per device the memory booked, the device's total (node gpu-mem / gpu-count, as _gpu_node_status) and the
+    stream pods holding a slice of it."""
+    cnt, per = _gpu_nodes(prob)
+    return [{"node": nodes[j]["metadata"]["name"], "model": (nodes[j]["metadata"].get("labels") or {}).get(k8s.GPU_MODEL, "N/A"),
+             "devices": [{"id": d, "used": int(gpu.dev_used[i, j, d]), "total": int(per[j]), "pods": int(gpu.dev_pods[i, j, d])}
+                         for d in range(int(cnt[j]))]}
+            for j in np.flatnonzero((gpu.dev_pods[i, :, 0] >= 0) & (cnt > 0)).tolist()]
+
+
+def _usage_fill(engine, out, nodes, prob, held, probes, node_table: bool, warn, what: str, devices: bool = False):
     """(headroom [S][K] lists, headroom_exact [K], node_table [S] lists of rows) of one engine batch -- None where not asked for: from the
-    engine's own reduction, or, for an engine without supports_node_usage, the same figures on the host from the placement rows (warns)."""
-    if probes is None and not node_table:
-        return None, None, None
-    hr, hx, usage = out.headroom, out.headroom_exact, out.node_usage
-    if not getattr(engine, "supports_node_usage", False):
+    engine's own reduction, or, for an engine without supports_node_usage, the same figures on the host from the placement rows (warns).
+    The fourth entry is gpu_table [S] lists of rows (None without devices); with devices=True headroom carries the device bound and the node rows the GPU columns (an
+    engine without supports_gpu_usage: on the host from the placement rows and gpu_slices, warns)."""
+    if probes is None and not node_table and not devices:
+        return None, None, None, None
+    hr, hx, usage, gpu = out.headroom, out.headroom_exact, out.node_usage, out.gpu_usage
+    if not _on_device(engine, devices):
         import warnings
-        warnings.warn(f"{what} computes headroom / the node table on the host from the placement matrix (the engine has no supports_node_usage)", warn, stacklevel=4)
+        lacks = "supports_node_usage" if not getattr(engine, "supports_node_usage", False) else "supports_gpu_usage"
+        warnings.warn(f"{what} computes headroom / the node table on the host from the placement matrix (the engine has no {lacks})", warn, stacklevel=4)
         if probes is not None:
-            hr, _, hx = host_headroom(prob, out.placement, held, probes)
+            hr, _, hx = host_headroom(prob, out.placement, held, probes, out.gpu_slices, devices)
         if node_table:
             usage = host_node_usage(prob, out.placement, held)
+        if devices:
+            gpu = host_gpu_usage(prob, out.placement, out.gpu_slices, held)
     return (None if probes is None else np.asarray(hr).tolist(), None if probes is None else [bool(x) for x in hx],
-            [_node_rows(nodes, prob, usage, i) for i in range(len(held))] if node_table else None)
+            [_node_rows(nodes, prob, usage, i, gpu if devices else None) for i in range(len(held))] if node_table else None,
+            [_gpu_rows(nodes, prob, gpu, i) for i in range(len(held))] if devices else None)
 
 
-def _usage_each(flat: fl.Flat, nodes: List[dict], out, headroom, node_table: bool, pool_order: Sequence[str]):
+def _usage_each(flat: fl.Flat, nodes: List[dict], out, headroom, node_table: bool, pool_order: Sequence[str], devices: bool = False):
     """_usage_fill for ONE scenario that ran as its own problem (the sweeps' fallback roads; `nodes` = its nodes in the problem's order,
-    pool_order = their names in pool order): on the host from its placement row.  Probes are named (namespace, name) there: a pod id
-    belongs to the batch's stream, which these roads do not build."""
-    hr = hx = tab = None
+    pool_order = their names in pool order): on the host from its placement row (devices: and its gpu_slices row); always four entries,
+    the last the scenario's gpu_table (None without devices).  Probes are named (namespace, name) there: a pod id belongs to the batch's
+    stream, which these roads do not build."""
+    hr = hx = tab = gtab = None
     held = np.ones((1, len(nodes)), bool)
+    sl = out.gpu_slices[:1] if devices and out.gpu_slices is not None else None
+    gpu = host_gpu_usage(flat.problem, out.placement[:1], sl, held) if devices else None
     if headroom is not None:
         if any(isinstance(h, (int, np.integer)) for h in headroom):
             raise ValueError("the scenarios run one by one, each with its own pod stream: name the headroom probes by (namespace, name)")
-        fit, _, ex = host_headroom(flat.problem, out.placement[:1], held, probe_ids(flat, headroom))
+        fit, _, ex = host_headroom(flat.problem, out.placement[:1], held, probe_ids(flat, headroom), sl, devices)
         hr, hx = fit[0].tolist(), [bool(x) for x in ex]
     if node_table:
-        rows = {r["node"]: r for r in _node_rows(nodes, flat.problem, host_node_usage(flat.problem, out.placement[:1], held), 0)}
+        rows = {r["node"]: r for r in _node_rows(nodes, flat.problem, host_node_usage(flat.problem, out.placement[:1], held), 0, gpu)}
         tab = [rows[n] for n in pool_order]
-    return hr, hx, tab
+    if devices:
+        rows = {r["node"]: r for r in _gpu_rows(nodes, flat.problem, gpu, 0)}
+        gtab = [rows[n] for n in pool_order if n in rows]
+    return hr, hx, tab, gtab
 
 
 def _and_exact(rows):
@@ -597,6 +683,7 @@ class SweepResult:
     headroom: Optional[List[List[int]]] = None
     headroom_exact: Optional[List[bool]] = None
     node_table: Optional[List[List[dict]]] = None
+    gpu_table: Optional[List[List[dict]]] = None     # devices=True: per scenario the "GPU Node Resource" table (pkg/apply/apply.go:456-500): one row per GPU node it holds -- node, model, devices [{id, used, total, pods}]
 
 
 def occupancy_pct(used: int, alloc: int) -> int:
@@ -715,7 +802,7 @@ def _sweep_reasons(engine, batch: "SweepBatch", out, replay, same_stream) -> Lis
 @_gc_paused
 def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node: Optional[dict], counts: Sequence[int],
           engine=None, max_cpu: int = 100, max_mem: int = 100, max_vg: int = 100, reasons: bool = False, headroom=None,
-          node_table: bool = False) -> SweepResult:
+          node_table: bool = False, devices: bool = False) -> SweepResult:
     """The add-nodes loop of Applier.Run (pkg/apply/apply.go:203-259) as ONE scenario batch: scenario k = the cluster plus
     counts[k] clones of new_node (utils.NewFakeNodes); the answer is the smallest count with no unscheduled pod whose
     occupancy satisfies MaxCPU / MaxMemory (satisfyResourceSetting, :689-775).  reasons=True: SweepResult.unscheduled_pods lists, per
@@ -724,7 +811,12 @@ def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node:
     at count s (headroom_exact[k]: that is the scheduler's own count, else the resource-and-static-filter upper bound).  node_table=True:
     SweepResult.node_table[s] = the table `simon apply` ends with (reportClusterInfo, :315-400) over the nodes of count s.  Both are reduced
     on the device from the placement matrix; an engine without supports_node_usage and the size-by-size road compute the same figures on
-    the host (UsageFallbackWarning)."""
+    the host (UsageFallbackWarning).
+    devices=True (GPU-share clusters): headroom carries the device bound (a probe with a GPU request is bounded by the slices the nodes'
+    devices still hold, and headroom_exact is true for it), the result gains gpu_table (per scenario the "GPU Node Resource" table,
+    :456-500: one row per GPU node it holds, per device used / total / pods) and node_table rows gain gpu_mem_allocatable /
+    gpu_mem_requests -- reduced on the device (simon_fetch_gpu_usage / simon_fetch_headroom_gpu); an engine without supports_gpu_usage
+    and the one-by-one roads compute the same figures on the host from the placement rows and gpu_slices (the same fallback warning)."""
     engine = engine or HipEngine()
     counts = list(counts)
     if max_cpu > 100 or max_cpu < 0:
@@ -739,16 +831,16 @@ def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node:
             raise
         # ImageLocality scores depend on the cluster size: an engine without the per-size image scores runs every size as its own
         # problem with its own static scores (and an engine without per-scenario node ranks runs a pool of several zones size by size)
-        return _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg, reasons, headroom, node_table)
+        return _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg, reasons, headroom, node_table, devices)
     flat, scen, orders, node_ranks, pool, base = batch.flat, batch.scen, batch.orders, batch.node_ranks, batch.pool, batch.base
     want_gpu = flat.problem.gpu_mem is not None
     kw = {"want_gpu_slices": True} if want_gpu else {}
     if node_ranks is not None:
         kw["node_ranks"] = node_ranks
     probes = probe_ids(flat, headroom)
-    out = engine.run(flat.problem, scen, orders, **kw, **_usage_kw(engine, probes, node_table, len(scen)))
-    hr, hx, tab = _usage_fill(engine, out, pool, flat.problem, np.arange(len(pool))[None, :] < scen[:, :1], probes, node_table,
-                              UsageFallbackWarning, "sweep")
+    out = engine.run(flat.problem, scen, orders, **kw, **_usage_kw(engine, probes, node_table, len(scen), devices))
+    hr, hx, tab, gtab = _usage_fill(engine, out, pool, flat.problem, np.arange(len(pool))[None, :] < scen[:, :1], probes, node_table,
+                                    UsageFallbackWarning, "sweep", devices)
     pc, pm = np.cumsum(flat.problem.alloc_cpu), np.cumsum(flat.problem.alloc_mem)
     cpu_pct = [occupancy_pct(int(out.used_cpu[s]), int(pc[scen[s, 0] - 1])) for s in range(len(counts))]
     mem_pct = [occupancy_pct(int(out.used_mem[s]) * 1000, int(pm[scen[s, 0] - 1]) * 1000) for s in range(len(counts))]
@@ -776,14 +868,14 @@ def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node:
                 return _unscheduled_list(flat, out.placement[s], {})
         why = _sweep_reasons(engine, batch, out, replay, lambda s: _same_stream(cluster, apps, batch, out, s))
     return SweepResult(counts, out.unscheduled.tolist(), cpu_pct, mem_pct, None if best is None else counts[best], result, vg_pct,
-                       [_risk(out, s) for s in range(len(counts))], why, hr, hx, tab)
+                       [_risk(out, s) for s in range(len(counts))], why, hr, hx, tab, gtab)
 
 
 def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg, reasons: bool = False, headroom=None,
-                    node_table: bool = False) -> SweepResult:
+                    node_table: bool = False, devices: bool = False) -> SweepResult:
     base = list(cluster.get("Node", []))
-    hrs, hxs, tabs = [], [], []
-    if headroom is not None or node_table:
+    hrs, hxs, tabs, gtabs = [], [], [], []
+    if headroom is not None or node_table or devices:
         import warnings
         warnings.warn("sweep runs the sizes one by one and computes headroom / the node table on the host from each placement row",
                       UsageFallbackWarning, stacklevel=3)
@@ -803,7 +895,7 @@ def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, m
                          **({"want_gpu_slices": True} if want_gpu else {}))
         uns.append(int(out.unscheduled[0]))
         risks.append(_risk(out, 0))
-        for acc, v in zip((hrs, hxs, tabs), _usage_each(flat, nodes, out, headroom, node_table, arrival)):
+        for acc, v in zip((hrs, hxs, tabs, gtabs), _usage_each(flat, nodes, out, headroom, node_table, arrival, devices)):
             acc.append(v)
         if reasons:
             texts = {}
@@ -828,7 +920,7 @@ def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, m
         res.node_status = [{"node": _gpu_node_status(n, per_dev[j]) if j in per_dev else _node_out(n), "pods": per_node[j]} for j, n in enumerate(nodes)]
         result = res
     return SweepResult(list(counts), uns, cpu_pct, mem_pct, None if best is None else counts[best], result, vg_pct, risks, why,
-                       hrs if headroom is not None else None, _and_exact(hxs), tabs if node_table else None)
+                       hrs if headroom is not None else None, _and_exact(hxs), tabs if node_table else None, gtabs if devices else None)
 
 
 @dataclass
@@ -849,6 +941,7 @@ class MixSweepResult:
     headroom: Optional[List[List[int]]] = None      # headroom=[...]: per mix and probe, how many more such pods fit
     headroom_exact: Optional[List[bool]] = None     # per probe: the scheduler's own count (else an upper bound)
     node_table: Optional[List[List[dict]]] = None   # node_table=True: per mix, reportClusterInfo's table over its own nodes, pool order
+    gpu_table: Optional[List[List[dict]]] = None     # devices=True: per scenario the "GPU Node Resource" table (pkg/apply/apply.go:456-500): one row per GPU node it holds -- node, model, devices [{id, used, total, pods}]
 
 
 class MixFallbackWarning(UserWarning):
@@ -916,7 +1009,7 @@ def _caps(max_cpu, max_mem, max_vg):
 @_gc_paused
 def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_nodes: Sequence[dict], counts: Sequence[Sequence[int]],
               costs: Optional[Sequence[float]] = None, engine=None, max_cpu: int = 100, max_mem: int = 100, max_vg: int = 100,
-              reasons: bool = False, headroom=None, node_table: bool = False) -> MixSweepResult:
+              reasons: bool = False, headroom=None, node_table: bool = False, devices: bool = False) -> MixSweepResult:
     """The add-nodes search over mixes of several new-node types (Applier.Run clones ONE template, pkg/apply/apply.go:155-166): mix
     (c_1 .. c_T) = Simulate(cluster + NewFakeNodes(type_1, c_1) + ... + NewFakeNodes(type_T, c_T)), the grid = the Cartesian product of
     counts (one iterable per type).  The answer is the mix of least total cost sum_t costs[t] * c_t (default 1 per node) with no
@@ -926,7 +1019,8 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
     the segmented kernel does not take run every mix as its own problem.  reasons=True: MixSweepResult.unscheduled_pods lists, per mix,
     the pods that stay unscheduled with their FitError text, as sweep() does per count -- every failing mix of the batch explained in
     one engine.explain_own_batch call (engines without it, and mixes whose pod stream is not the pool's: simulate() of the mix).
-    headroom=[...] / node_table=True: as sweep() takes them, per mix (MixSweepResult.headroom / headroom_exact / node_table)."""
+    headroom=[...] / node_table=True / devices=True: as sweep() takes them, per mix (MixSweepResult.headroom / headroom_exact / node_table /
+    gpu_table)."""
     import itertools
     engine = engine or HipEngine()
     new_nodes = list(new_nodes)
@@ -945,7 +1039,7 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
     mixes = [tuple(int(k) for k in m) for m in itertools.product(*counts)]
     caps = _caps(max_cpu, max_mem, max_vg)
     if not getattr(engine, "supports_scenario_segments", False):
-        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, "the engine has no pool segments", reasons, headroom, node_table)
+        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, "the engine has no pool segments", reasons, headroom, node_table, devices)
     base = list(cluster.get("Node", []))
     if not base and any(sum(m) == 0 for m in mixes):   # (a scenario holds one node at least: simon_set_scenario_segments, and flatten)
         raise ValueError("sweep_mix: a cluster without nodes needs at least one new node in every mix")
@@ -966,7 +1060,7 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
         if "ImageLocality" not in str(e):
             raise
         return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps,
-                                  "nodes list the pods' images: ImageLocality depends on the node set", reasons, headroom, node_table)
+                                  "nodes list the pods' images: ImageLocality depends on the node set", reasons, headroom, node_table, devices)
     scen = np.stack([len(base) + cnt.sum(1), np.zeros(len(mixes), np.int64)], 1).astype(np.int32)
     orders = np.arange(len(pods), dtype=np.int32)[None, :]
     want_gpu = flat.problem.gpu_mem is not None
@@ -975,12 +1069,12 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
         kw["node_ranks"] = node_ranks
     probes = probe_ids(flat, headroom)
     try:
-        out = engine.run(flat.problem, scen, orders, segments=(seg_start, cnt), **kw, **_usage_kw(engine, probes, node_table, len(scen)))
+        out = engine.run(flat.problem, scen, orders, segments=(seg_start, cnt), **kw, **_usage_kw(engine, probes, node_table, len(scen), devices))
     except capi.SimonError as e:
         if getattr(e, "code", None) != capi.ESTATE:
             raise
         # a problem on the all-feature kernel (prefix scenarios only): every mix as its own problem
-        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, f"the engine refused the segmented batch: {e}", reasons, headroom, node_table)
+        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, f"the engine refused the segmented batch: {e}", reasons, headroom, node_table, devices)
     # satisfyResourceSetting over each mix's own nodes: the fixed nodes + a prefix of every segment
     pr = flat.problem
     vg_cap = None
@@ -1010,8 +1104,8 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
         why = _mix_reasons(engine, cluster, apps, flat, pool, len(base), present, scen, orders, node_ranks, (seg_start, cnt), out)
     return MixSweepResult(mixes, out.unscheduled.tolist(), cpu_pct, mem_pct, vg_pct, [_risk(out, s) for s in range(len(mixes))],
                           None if best is None else mixes[best], None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result,
-                          unscheduled_pods=why, **dict(zip(("headroom", "headroom_exact", "node_table"), _usage_fill(
-                              engine, out, pool, flat.problem, present, probes, node_table, MixFallbackWarning, "sweep_mix"))))
+                          unscheduled_pods=why, **dict(zip(("headroom", "headroom_exact", "node_table", "gpu_table"), _usage_fill(
+                              engine, out, pool, flat.problem, present, probes, node_table, MixFallbackWarning, "sweep_mix", devices))))
 
 
 def _mix_reasons(engine, cluster, apps, flat, pool, n_base, present, scen, orders, node_ranks, segments, out) -> List[List[dict]]:
@@ -1055,14 +1149,14 @@ def _mix_reasons(engine, cluster, apps, flat, pool, n_base, present, scen, order
 
 
 def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why: str, reasons: bool = False, headroom=None,
-                       node_table: bool = False) -> MixSweepResult:
+                       node_table: bool = False, devices: bool = False) -> MixSweepResult:
     """Every mix as its own Simulate(): cluster + each type's clones in type order, canonical nodeTree order."""
     import warnings
     warnings.warn(f"sweep_mix runs {len(mixes)} mixes one by one ({why})", MixFallbackWarning, stacklevel=3)
     base = list(cluster.get("Node", []))
     uns, cpu_pct, mem_pct, vg_pct, risks, kept = [], [], [], [], [], {}
     lists: List[List[dict]] = []
-    hrs, hxs, tabs = [], [], []
+    hrs, hxs, tabs, gtabs = [], [], [], []
     for s, mix in enumerate(mixes):
         nodes = base + [n for nodes in mix_fake_nodes(new_nodes, mix) for n in nodes]
         pods, _ = build_stream(cluster, apps, nodes, len(nodes))
@@ -1075,7 +1169,7 @@ def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why
                          **({"want_gpu_slices": True} if want_gpu else {}))
         uns.append(int(out.unscheduled[0]))
         risks.append(_risk(out, 0))
-        for acc, v in zip((hrs, hxs, tabs), _usage_each(flat, nodes, out, headroom, node_table, arrival)):
+        for acc, v in zip((hrs, hxs, tabs, gtabs), _usage_each(flat, nodes, out, headroom, node_table, arrival, devices)):
             acc.append(v)
         if reasons:
             texts = {}
@@ -1102,7 +1196,7 @@ def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why
     return MixSweepResult(mixes, uns, cpu_pct, mem_pct, vg_pct, risks, None if best is None else mixes[best],
                           None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result, batched=False, fallback=why,
                           unscheduled_pods=lists, headroom=hrs if headroom is not None else None, headroom_exact=_and_exact(hxs),
-                          node_table=tabs if node_table else None)
+                          node_table=tabs if node_table else None, gpu_table=gtabs if devices else None)
 
 
 @dataclass
@@ -1129,6 +1223,7 @@ class FailureSweepResult:
     headroom: Optional[List[List[int]]] = None
     headroom_exact: Optional[List[bool]] = None
     node_table: Optional[List[List[dict]]] = None
+    gpu_table: Optional[List[List[dict]]] = None     # devices=True: per scenario the "GPU Node Resource" table (pkg/apply/apply.go:456-500): one row per GPU node it holds -- node, model, devices [{id, used, total, pods}]
 
     @property
     def removable(self) -> List[int]:
@@ -1288,7 +1383,7 @@ def _failure_replay(cluster, apps, names, engine, reschedule=False) -> List[dict
 @_gc_paused
 def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], domains="node", engine=None, max_cpu: int = 100,
                    max_mem: int = 100, max_vg: int = 100, reasons: bool = False, batch_scenarios: int = 4096,
-                   reschedule=False, headroom=None, node_table: bool = False) -> FailureSweepResult:
+                   reschedule=False, headroom=None, node_table: bool = False, devices: bool = False) -> FailureSweepResult:
     """The node-failure what-if sweep: does the cluster still hold its workloads when a node, a rack or a zone is lost?  Scenario 0 is
     the whole cluster; scenario d + 1 is simulate() of the cluster without failure domain d (failure_domains: "node", a label key, or
     lists of node names), without the pods bound to its nodes and without their DaemonSet pods (cluster_without) -- lost pods are
@@ -1305,7 +1400,7 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     where it is not.  `evicted` / `evicted_unscheduled` count them per domain, `removable` lists the domains the cluster survives.
     Pods that a workload TEMPLATE binds to a node stay Unsupported (their controller would bind the new pod to the same node); an
     engine without supports_pod_eviction and evicted pods that carry a gpu-index annotation run scenario by scenario.
-    headroom=[...] / node_table=True: as sweep() takes them, per SCENARIO ([0] the whole cluster, [d + 1] without domain d)."""
+    headroom=[...] / node_table=True / devices=True: as sweep() takes them, per SCENARIO ([0] the whole cluster, [d + 1] without domain d)."""
     engine = engine or HipEngine()
     reschedule = reschedule or False
     evictable({}, reschedule or "all")
@@ -1318,7 +1413,7 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     if not present.any(axis=1).all():
         raise ValueError("sweep_failures: a failure domain holds every node of the cluster")
     caps = _caps(max_cpu, max_mem, max_vg)
-    each = lambda why: _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why, reschedule, headroom, node_table)   # noqa: E731
+    each = lambda why: _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why, reschedule, headroom, node_table, devices)   # noqa: E731
     if not getattr(engine, "supports_scenario_subsets", False):
         return each("the engine has no node subsets")
     if reschedule and not getattr(engine, "supports_pod_eviction", False):
@@ -1358,7 +1453,7 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     want_gpu = pr.gpu_mem is not None
     rows, where = [], []
     probes = probe_ids(flat, headroom)
-    hr, hx, tab = ([] if headroom is not None else None), None, ([] if node_table else None)
+    hr, hx, tab, gtab = ([] if headroom is not None else None), None, ([] if node_table else None), ([] if devices else None)
     told: Dict[int, List[dict]] = {}             # reasons: scenario -> its unscheduled_pods, from the batch's own explain
     for lo in range(0, len(present), max(1, int(batch_scenarios))):
         part = present[lo:lo + max(1, int(batch_scenarios))]
@@ -1370,12 +1465,14 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
             if evict.any():
                 kw["evict"] = evict
             out = engine.run(pr, scen, orders, present=(part, zone if 1 < len(zid) <= capi.MAX_ZONES else None), **kw,
-                             **_usage_kw(engine, probes, node_table, len(scen)))
+                             **_usage_kw(engine, probes, node_table, len(scen), devices))
         except capi.SimonError as e:
             if getattr(e, "code", None) != capi.ESTATE:
                 raise
             return each(f"the engine refused the node-subset batch: {e}")
-        h1, x1, t1 = _usage_fill(engine, out, pool, pr, part, probes, node_table, FailureFallbackWarning, "sweep_failures")
+        h1, x1, t1, g1 = _usage_fill(engine, out, pool, pr, part, probes, node_table, FailureFallbackWarning, "sweep_failures", devices)
+        if g1 is not None:
+            gtab += g1
         if h1 is not None:
             hr += h1
             hx = x1
@@ -1413,17 +1510,17 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
         preset = np.asarray(pr.preset_node)
         moved = [np.flatnonzero(evict & ~present[d + 1][np.maximum(preset, 0)]) for d in range(len(doms))]
     res = _failure_result(doms, rows, caps, where, why, True, None, moved)
-    res.headroom, res.headroom_exact, res.node_table = hr, hx, tab
+    res.headroom, res.headroom_exact, res.node_table, res.gpu_table = hr, hx, tab, gtab
     return res
 
 
 def _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why: str, reschedule=False, headroom=None,
-                         node_table: bool = False) -> FailureSweepResult:
+                         node_table: bool = False, devices: bool = False) -> FailureSweepResult:
     """Every scenario as its own Simulate(): the cluster without the domain, canonical nodeTree order."""
     import warnings
     warnings.warn(f"sweep_failures runs {len(doms) + 1} scenarios one by one ({why})", FailureFallbackWarning, stacklevel=3)
     rows, where, lists, moved = [], [], [], []
-    hrs, hxs, tabs = [], [], []
+    hrs, hxs, tabs, gtabs = [], [], [], []
     for names in [[]] + doms:
         cl, ap = _reduced(cluster, apps, names, reschedule)
         nodes = list(cl.get("Node", []))
@@ -1440,7 +1537,7 @@ def _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why: str, r
                      occupancy_pct(int(out.used_mem[0]) * 1000, int(pr.alloc_mem.sum()) * 1000),
                      occupancy_pct(int(out.used_vg[0]), int(vg_cap.sum())) if vg_cap is not None else 0, _risk(out, 0)))
         where.append((flat, out.placement[0]))
-        for acc, v in zip((hrs, hxs, tabs), _usage_each(flat, nodes, out, headroom, node_table, arrival)):
+        for acc, v in zip((hrs, hxs, tabs, gtabs), _usage_each(flat, nodes, out, headroom, node_table, arrival, devices)):
             acc.append(v)
         if reschedule and names:
             refs = _evicted_refs(cluster, apps, names, reschedule)
@@ -1449,6 +1546,7 @@ def _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why: str, r
             lists.append(_failure_replay(cluster, apps, names, engine, reschedule) if rows[-1][0] > 0 else [])
     res = _failure_result(doms, rows, caps, where, lists, False, why, moved)
     res.headroom, res.headroom_exact, res.node_table = hrs if headroom is not None else None, _and_exact(hxs), tabs if node_table else None
+    res.gpu_table = gtabs if devices else None
     return res
 
 
@@ -1474,6 +1572,7 @@ class AppSweepResult:
     headroom: Optional[List[List[List[int]]]] = None    # headroom=[...]: [U][K][probe] how many more pods like the probe fit
     headroom_exact: Optional[List[bool]] = None         # per probe: the scheduler's own count (else an upper bound)
     node_table: Optional[List[List[List[dict]]]] = None # node_table=True: [U][K] reportClusterInfo's table over the scenario's nodes
+    gpu_table: Optional[List[List[List[dict]]]] = None  # devices=True: [U][K] the "GPU Node Resource" table over the scenario's GPU nodes
 
 
 class AppFallbackWarning(UserWarning):
@@ -1519,17 +1618,18 @@ def _app_summary(apps, subs, counts, rows, by_app, caps, weights, why_lists, bat
 
 
 def _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, weights, reasons, why: str, headroom=None,
-                     node_table: bool = False) -> AppSweepResult:
+                     node_table: bool = False, devices: bool = False) -> AppSweepResult:
     """Every scenario as its own Simulate(): the cluster, the subset's apps and its new nodes, canonical nodeTree order."""
     import warnings
     warnings.warn(f"sweep_apps runs {len(subs) * len(counts)} scenarios one by one ({why})", AppFallbackWarning, stacklevel=3)
     base = list(cluster.get("Node", []))
     rows, by_app, lists = [], [], []
-    hrs, hxs, tabs = [], [], []
+    hrs, hxs, tabs, gtabs = [], [], [], []
     for sub in subs:
         mine = [apps[a] for a in sub]
         hrs.append([])
         tabs.append([])
+        gtabs.append([])
         rows.append([])
         by_app.append([])
         lists.append([])
@@ -1551,17 +1651,19 @@ def _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, weight
             pr = flat.problem
             per = [0] * len(apps)
             if not pods:
-                if headroom is not None or node_table:
+                if headroom is not None or node_table or devices:
                     raise ValueError("sweep_apps: headroom / node_table of a scenario without any pod, run on its own")
                 rows[-1].append((0, 0, 0, 0, False))
                 by_app[-1].append(per)
                 lists[-1].append([])
                 continue
-            out = engine.run(pr, np.array([[len(nodes), 0]], np.int32), np.arange(len(pods), dtype=np.int32)[None, :])
-            h1, x1, t1 = _usage_each(flat, nodes, out, headroom, node_table, arrival)
+            out = engine.run(pr, np.array([[len(nodes), 0]], np.int32), np.arange(len(pods), dtype=np.int32)[None, :],
+                             **({"want_gpu_slices": True} if devices and pr.gpu_mem is not None else {}))
+            h1, x1, t1, g1 = _usage_each(flat, nodes, out, headroom, node_table, arrival, devices)
             hrs[-1].append(h1)
             hxs.append(x1)
             tabs[-1].append(t1)
+            gtabs[-1].append(g1)
             vg_cap = _vg_caps(pr, out)
             rows[-1].append((int(out.unscheduled[0]), occupancy_pct(int(out.used_cpu[0]), int(pr.alloc_cpu.sum())),
                              occupancy_pct(int(out.used_mem[0]) * 1000, int(pr.alloc_mem.sum()) * 1000),
@@ -1576,13 +1678,15 @@ def _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, weight
             lists[-1].append(_unscheduled_list(flat, out.placement[0], texts) if reasons else [])
     res = _app_summary(apps, subs, counts, rows, by_app, caps, weights, lists if reasons else [], False, why)
     res.headroom, res.headroom_exact, res.node_table = hrs if headroom is not None else None, _and_exact(hxs), tabs if node_table else None
+    res.gpu_table = gtabs if devices else None
     return res
 
 
 @_gc_paused
 def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subsets=None, new_node: Optional[dict] = None,
                counts: Sequence[int] = (0,), weights: Optional[Sequence[float]] = None, engine=None, max_cpu: int = 100, max_mem: int = 100,
-               max_vg: int = 100, reasons: bool = False, batch_scenarios: int = 4096, headroom=None, node_table: bool = False) -> AppSweepResult:
+               max_vg: int = 100, reasons: bool = False, batch_scenarios: int = 4096, headroom=None, node_table: bool = False,
+               devices: bool = False) -> AppSweepResult:
     """Which of these apps fit on the cluster together, what has to be left out, and how many new nodes each combination costs: scenario
     (u, k) is simulate(cluster, [apps[a] for a in subsets[u]], new_nodes = counts[k] clones of new_node); the cluster's own pods are part
     of every scenario.  subsets: bool rows [U][len(apps)] or lists of app names; None = every subset of at most 12 apps (4 096 scenarios per
@@ -1599,7 +1703,7 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
     them all up front); an engine that refuses the batch (SIMON_ESTATE).  Not covered: subsets of the replicas WITHIN one app --
     ScheduleApp's unstable sorts order an app's pods by the length of the list, so a shorter replica list is not a restriction of the
     longer one's stream.
-    headroom=[...] / node_table=True: as sweep() takes them, per scenario (u, k) (AppSweepResult.headroom[u][k] etc.); a probe may be a
+    headroom=[...] / node_table=True / devices=True: as sweep() takes them, per scenario (u, k) (AppSweepResult.headroom[u][k] etc.); a probe may be a
     pod of an app the scenario lacks -- its request and class stand for "one more such pod"."""
     engine = engine or HipEngine()
     apps, counts = list(apps), list(counts)
@@ -1615,7 +1719,7 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
     w = [float(x) for x in weights] if weights is not None else [float(n) for n in lens]
     if len(w) != len(apps):
         raise ValueError(f"{len(w)} weights for {len(apps)} apps")
-    each = lambda why: _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, w, reasons, why, headroom, node_table)   # noqa: E731
+    each = lambda why: _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, w, reasons, why, headroom, node_table, devices)   # noqa: E731
     if not getattr(engine, "supports_pod_subsets", False):
         return each("the engine has no pod subsets")
     # a StorageClass that one app defines and another app's pods use: in a subset without the first app the class is unknown
@@ -1666,7 +1770,8 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
     hr = [[None] * K for _ in subs] if headroom is not None else None
     hx = None
     tab = [[None] * K for _ in subs] if node_table else None
-    on_host = (headroom is not None or node_table) and not getattr(engine, "supports_node_usage", False)     # (the host figures need the rows)
+    gtab = [[None] * K for _ in subs] if devices else None
+    on_host = (headroom is not None or node_table or devices) and not _on_device(engine, devices)     # (the host figures need the rows)
     per_launch = max(1, int(batch_scenarios) // K)                  # whole subsets per launch: K scenarios each
     for lo in range(0, len(subs), per_launch):
         us = np.arange(lo, min(lo + per_launch, len(subs)))
@@ -1675,15 +1780,17 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
         kw = {}
         if batch.node_ranks is not None:
             kw["node_ranks"] = np.tile(batch.node_ranks, (len(us), 1))
+        if devices and on_host and pr.gpu_mem is not None:
+            kw["want_gpu_slices"] = True
         try:
             out = engine.run(pr, scen, batch.orders, want_placement=reasons or on_host, pod_present=present, pod_groups=group, **kw,
-                             **_usage_kw(engine, probes, node_table, len(scen)))
+                             **_usage_kw(engine, probes, node_table, len(scen), devices))
         except capi.SimonError as e:
             if getattr(e, "code", None) != capi.ESTATE:
                 raise
             return each(f"the engine refused the pod-subset batch: {e}")
-        h1, x1, t1 = _usage_fill(engine, out, batch.pool, pr, np.arange(len(batch.pool))[None, :] < scen[:, :1], probes, node_table,
-                                 AppFallbackWarning, "sweep_apps")
+        h1, x1, t1, g1 = _usage_fill(engine, out, batch.pool, pr, np.arange(len(batch.pool))[None, :] < scen[:, :1], probes, node_table,
+                                     AppFallbackWarning, "sweep_apps", devices)
         hx = x1 if x1 is not None else hx
         vg_cap = _vg_caps(pr, out)
         cv = np.cumsum(vg_cap) if vg_cap is not None else None
@@ -1718,10 +1825,12 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
                     hr[u][k] = h1[s]
                 if t1 is not None:
                     tab[u][k] = t1[s]
+                if g1 is not None:
+                    gtab[u][k] = g1[s]
                 if reasons and s not in replayed:
                     lists[u][k] = _unscheduled_list(flat, out.placement[s], told.get(s, {}))
     res = _app_summary(apps, subs, counts, rows, by_app, caps, w, lists if reasons else [], True, None)
-    res.headroom, res.headroom_exact, res.node_table = hr, hx, tab
+    res.headroom, res.headroom_exact, res.node_table, res.gpu_table = hr, hx, tab, gtab
     return res
 
 
