@@ -2979,8 +2979,9 @@ static int run_table_batch(simon_ctx* c, const BatchRoute& r, bool want_placemen
             if (c->no_size_dispatch) snprintf(own, sizeof own, "off");
             else snprintf(own, sizeof own, "%d of %d scenarios at %d", fits, S, lo);
         }
-        fprintf(stderr, "[route] unit %s nzeq %d team %d prologue %s entries/lane %d (own size: %s)\n", table_unit_name(f), (int)f.nzeq, f.team,
-                shared_pro ? "shared-image" : "per-scenario", table_entries_per_lane(f), own);
+        fprintf(stderr, "[route] unit %s nzeq %d team %d prologue %s entries/lane %d (own size: %s) re-base %s twins %d\n", table_unit_name(f), (int)f.nzeq, f.team,
+                shared_pro ? "shared-image" : "per-scenario", table_entries_per_lane(f), own, table_rebase_at_event(f) ? "at-event" : "at-use",
+                (int)((f.sc.static_tables & kStTwins) != 0));
     }
     trace_segmented(c, "score-table kernel, ranked instantiation");
     if (int rc = timed_launch(c, [&] {

@@ -184,6 +184,9 @@ int table_entries_per_lane(const TableLaunch& a);    // summary entries per lane
 // The smaller entries-per-lane the same kernel also serves, each scenario by its own padded size (table_kernel: LO); 0: none.  A scenario takes it iff
 // its padded size is at most 64 x 16 x that many positions, unless TableScalars::static_tables holds kStOneSize.
 int table_entries_own_size(const TableLaunch& a);
+// Does the kernel re-base a summary row's class terms at the event -- in the cycle that empties a node class for the row's signature -- (true) or at the
+// row's next use (false: the two-level layout -- so the REST, SPREAD and team units and more than 128 signatures --, more than 128 node classes)?
+bool table_rebase_at_event(const TableLaunch& a);
 // Can the launch take its initial table from the shared image (a.cold's pro_image)?  The one-level instantiations of simon_table.hip on prefix scenarios in
 // canonical order: neither ranked nor segmented.  launch_table_image fills the image (the batch's largest scenario, `nb` blocks) on `st`, ahead of launch_table.
 bool table_shared_prologue(const TableLaunch& a);

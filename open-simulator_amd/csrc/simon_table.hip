@@ -470,6 +470,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     constexpr bool kStraight = !REST && !SPREAD && !MANY;
     static_assert(!(kStraight && TIE_FIRST), "the straight-line cycle defines the winner's class and record index behind the assume's loads: nothing ahead of them may read dstar / res");
     static_assert(!kStraight || NW == 1, "team mode is SPREAD: a straight-line instantiation has no helper waves");
+    // Round 12: where the cycle is straight-line code, summary row k is re-based AT THE EVENT -- in the assume, when a (signature, class) counter reaches 0
+    // (simon_table_assume.inc) -- and once for every signature behind the prologue; the plain pod asks nothing before it scans its row.  The others re-base
+    // at the row's next use (my_dirty); kCls4's conditional re-base depends on the extremes stored at the last lazy one.  The two-level layout stays lazy
+    // as well: it serves the problems with many node classes, where a row loses several classes between two of its uses and the lazy scheme re-bases once for all of
+    // them (config 3 on 80 shapes, 4 096 scenarios: 35.09 / 34.82 ms lazy, 36.72 / 35.76 ms at the event), and five of its kernels held one VGPR more.
+    constexpr bool kEager = kStraight && !kCls4 && !COARSE;
     // the initial table by copy from the shared image (prologue 2): this unit's one-level instantiations on prefix scenarios in canonical order
     constexpr bool kSharedPro = kSharedPrologueTU && !COARSE && !REST && !SPREAD && !MANY && !kCls4 && !RANKED && !LDSWS && NW == 1;
     static_assert(!MANY || (KQ == 2 && COARSE && !CN2 && !LDSX), "MANY = groups of 128 signatures on the two-level layout (since round 6 also under the REST select: its rows and counters are indexed by signature already)");
@@ -771,7 +777,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
                 b = ((w >> (j & 63)) & 1ull) ? b : 0u;
             }
             if (p < ni) tp[(unsigned)k * KS] = (unsigned char)b;
-            // class term still 0: every signature starts dirty and is re-based at its first use
+            // class term still 0: every row is re-based behind the prologue (kEager) or starts dirty and is re-based at its first use
             const unsigned m16 = row16_max_t(b ? ((b << 4) | (unsigned)(15 - (p & 15))) : 0u);
             if constexpr (COARSE) {                                   // the 64 lanes are ONE summary entry of ONE class
                 if ((lane & 15) == 0) g_fine[((size_t)(p0 >> 6) * K + k) * 4 + (lane >> 4)] = (unsigned short)m16;
@@ -889,6 +895,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         my_addz_c[q] = (unsigned)r.nz_c; my_addz_m[q] = (unsigned)r.nz_m;
         koff[q] = (unsigned)kk[q] * KS;
     }
+    if constexpr (!kEager)
     for (int j = 0; j * 64 + lane < K; ++j) my_dirty |= 1u << j;      // bit j: signature lane + 64 j starts dirty (first use re-bases it)
     // this lane's summary entries (lane, lane + 64, ...): constant of the arg-max key (low field = PMASK - position), node class,
     // and offset of the entry's class segment into the static per-class node lists (index of position p = boff + p; packed with
@@ -979,6 +986,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
             t0 += in0 ? (int)gp(cc->img)[ib + c * Cn + d0] : 0; t1 += in1 ? (int)gp(cc->img)[ib + c * Cn + d1] : 0;
         }
     };
+    // The table class of signature k (uniform k) as a scalar.  Named as global memory and consumed at once: through the generic `sigs` the load was a FLAT
+    // one into a VGPR, and with that in the loop the compiler put an s_waitcnt vmcnt(0) into the plain pod's path, in front of the state's own wait.
+    auto sig_class = [&](int k) -> int { return __builtin_amdgcn_readfirstlane(gp(&sigs[k].cls)[0]); };
     // Re-base summary row k after the set of node classes with a feasible node changed.
     auto renormalise = [&](int k, int c) {
         if (kCls4 && Cn > 128) {
@@ -1114,6 +1124,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
         }
         lead_sync();
     };
+    // every signature starts re-based (the prologues leave class term 0 in every row; summaries and counters are complete here)
+    if constexpr (kEager) {
+        for (int k = 0; k < K; ++k) renormalise(k, sig_class(k));
+    }
 
     TPROF_DECL
     // ---- REST path -------------------------------------------------------------------------------------------------------
@@ -2132,14 +2146,18 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
             }
         } else {
             const int k = r_sig;
-            const unsigned dq = (unsigned)__builtin_amdgcn_readlane((int)my_dirty, k & 63);
-            if (__builtin_expect((dq >> (k >> 6)) & 1u, 0)) {          // a node class lost its last feasible node for k (or first use)
-                renormalise(k, r_cls);
-                if (lane == (k & 63)) my_dirty &= ~(1u << (k >> 6));
+            if constexpr (!kEager) {
+                const unsigned dq = (unsigned)__builtin_amdgcn_readlane((int)my_dirty, k & 63);
+                if (__builtin_expect((dq >> (k >> 6)) & 1u, 0)) {      // a node class lost its last feasible node for k (or first use)
+                    renormalise(k, r_cls);
+                    if (lane == (k & 63)) my_dirty &= ~(1u << (k >> 6));
+                }
             }
             // -------- summary scan: one u16 per 16 (COARSE: 64) positions ------------------------------
             // (the row's offset is computed behind the re-base, from a copy of k the compiler cannot follow: shared with the re-base's own
-            // it arrives through a merge of the two paths, and the copies on the plain pod's edge cost it two branches and a flag)
+            // it arrives through a merge of the two paths, and the copies on the plain pod's edge cost it two branches and a flag.  kEager has no
+            // re-base here and no merge; the copy stays all the same: without it the plain pod's path of config 3's kernel is the same 161 / 178
+            // issued instructions with the same registers, and 36 of the unit's 98 kernels compile to other code elsewhere, which nobody measured)
             int ks = k;
             asm volatile("" : "+s"(ks));
             const unsigned short* srow = s_sum + ks * nbp;
@@ -2598,6 +2616,11 @@ int table_entries_per_lane(const TableLaunch& a) {
     if (u == TableUnit::Cls4) return 4;
     if ((u == TableUnit::Team || u == TableUnit::Rs || u == TableUnit::Spread) && table_many(a)) return 2;
     return a.coarse ? table_nbq64(a).v : table_nbq16(a).v;
+}
+// (SIMON_DEBUG_ROUTE; table_kernel: kEager -- the one-level instantiations of this unit and of simon_table_lds.hip)
+bool table_rebase_at_event(const TableLaunch& a) {
+    const TableUnit u = table_route(a);
+    return u == TableUnit::Lds || (u == TableUnit::Base && !a.coarse);
 }
 int table_entries_own_size(const TableLaunch& a) {
     return table_base_unit(a) ? table_lo_entries(a.coarse, table_ranked(a), table_entries_per_lane(a)) : 0;

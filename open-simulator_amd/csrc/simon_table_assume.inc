@@ -239,6 +239,7 @@
                     } else {
                         s_sum[k * nbp + blk] = (unsigned short)e16;
                     }
+                    if constexpr (!kEager)                                // (kEager: counted down and re-based behind the refresh, see there)
                     if (!nb) {                                            // the node stopped being feasible for this signature
                         const int cidx = k * Cn + dstar;
                         int left;
@@ -318,6 +319,45 @@
             for (int q = 0; q < KQ; ++q)
                 refresh_sig(kk[q], kvalid[q], nbq[q], bytep[q], T[q], COARSE ? F[q] : make_uint2(0u, 0u),
                             oldq[q], snq[q], q);
+            if constexpr (kEager) {
+                // The node stopped being feasible for some signature (one uniform test where the lanes' own regions stood): the lanes count their
+                // (signature, class) down, lane-local as ever, and every row whose counter reached 0 -- the class left the signature's feasible set, its
+                // class terms change -- is re-based here, at the event, by the whole wave: renormalise is a function of the counters alone and they only
+                // fall, so the row's next use finds what a re-base at that use would have written, and the plain pod asks nothing before its scan.
+                // The test: bytes, so old > new << 8 iff new == 0 < old -- ONE compare per signature, and a byte that was 0 stays 0 whatever the evaluation
+                // says.  A lane beyond K works on signature 0's row and is not masked out here (the and with kvalid made the compiler materialise the flag: a
+                // v_cndmask and a second compare per cycle): at worst it sends the wave into the rare block for nothing -- the counters below ask kvalid.
+                bool gone = false;
+#pragma unroll
+                for (int q = 0; q < KQ; ++q) gone |= oldq[q] > (nbq[q] << 8);
+                if (__builtin_expect(__ballot(gone) != 0ull, 0)) {
+                    unsigned long long emptied[KQ];
+#pragma unroll
+                    for (int q = 0; q < KQ; ++q) {
+                        bool last = false;
+                        if (kvalid[q] && oldq[q] > (nbq[q] << 8)) {
+                            // plain read-modify-write (a (signature, class) counter belongs to the lane that owns the signature): an atomic is
+                            // performed in L2 and would leave the wave's later plain loads of the counter to a stale L1 line
+                            const int cidx = kk[q] * Cn + dstar;
+                            int left;
+                            if constexpr (!CNT_LDS) { left = g_cnt[cidx] - 1; g_cnt[cidx] = left; }
+                            else { left = s_cnt[cidx] - 1; s_cnt[cidx] = left; }
+                            last = left == 0;
+#ifdef SIMON_TABLE_DEBUG
+                            printf("DBG s=%d step=%d CNT k=%d class=%d left=%d\n", s, i0 + il, kk[q], dstar, left);
+#endif
+                        }
+                        emptied[q] = __ballot(last);
+                    }
+#pragma unroll
+                    for (int q = 0; q < KQ; ++q) {
+                        for (unsigned long long m = emptied[q]; m; m &= m - 1) {
+                            const int k = 64 * q + __builtin_ctzll(m);
+                            renormalise(k, sig_class(k));
+                        }
+                    }
+                }
+            }
             // MANY: the further groups (their table rows arrived with group 0's; the signature rows of TableCold::sigs are L2-hot)
             if constexpr (MANY) {
 #pragma unroll
