@@ -504,9 +504,10 @@ int simon_fetch_group_counts(simon_ctx* ctx, const int32_t* pod_group /* [P] */,
  * SIMON_EINVAL: n < 1, a scenario id outside [0, S), a missing required output array (req_cpu, req_mem, npods, fit), a wrong
  * struct_size, K outside [1, SIMON_MAX_PROBES], a pod id outside [0, P).  A failed call leaves results and batch alone.
  * The node range is tiled to the LDS budget (env SIMON_USAGE_TILE=<nodes> overrides the tile, read once in simon_ctx_create).
- * Not covered: Open-Local VG / device usage per node (exact is 0 for such probes); probes that are not pods of the loaded stream; no
- * simon_group_* forward and no Go shim.  GPU-share devices: simon_fetch_gpu_usage / simon_fetch_headroom_gpu below (simon_fetch_headroom
- * itself keeps exact = 0 for a probe with a GPU request).  (additive: the ABI stays 7) */
+ * Not covered: probes that are not pods of the loaded stream; no simon_group_* forward and no Go shim.  Open-Local VG / device usage per
+ * node: simon_fetch_local_usage / simon_fetch_headroom_local below (exact stays 0 here for a probe with an Open-Local spec).  GPU-share
+ * devices: simon_fetch_gpu_usage / simon_fetch_headroom_gpu below (simon_fetch_headroom itself keeps exact = 0 for a probe with a GPU
+ * request).  (additive: the ABI stays 7) */
 typedef struct simon_node_usage {
     uint32_t struct_size;
     int64_t* req_cpu;      /* [n][N] Requested.MilliCPU of pool node j at the end of listed scenario i */
@@ -545,7 +546,8 @@ int simon_fetch_headroom(simon_ctx* ctx, const int32_t* probe_pod /* [K] pod ids
  * exact[k] is 1 under simon_fetch_headroom's conditions, except that such a GPU request no longer disqualifies.  A probe without
  * gpu_mem gives simon_fetch_headroom's result bit for bit.  A probe that arrives WITH a gpu-index annotation short-cuts AllocateGpuId:
  * no device bound is applied and exact is 0.  SIMON_EINVAL as for the two calls above (dev_used is the one required array).
- * Not covered: Open-Local VG / device usage; probes that are not pods of the loaded stream; no simon_group_* forward and no Go shim.
+ * Not covered: probes that are not pods of the loaded stream; no simon_group_* forward and no Go shim.  Open-Local VG / device usage:
+ * simon_fetch_local_usage / simon_fetch_headroom_local below (exact stays 0 here for a probe with an Open-Local spec).
  * (additive: the ABI stays 7) */
 typedef struct simon_gpu_usage {
     uint32_t struct_size;
@@ -556,6 +558,51 @@ int simon_fetch_gpu_usage(simon_ctx* ctx, const int32_t* scen_ids /* [n], NULL =
 
 int simon_fetch_headroom_gpu(simon_ctx* ctx, const int32_t* probe_pod /* [K] pod ids */, int32_t K,
                              int64_t* fit /* [S][K] */, int32_t* fit_nodes /* [S][K], may be NULL */, uint8_t* exact /* [K], may be NULL */);
+
+/* Open-Local storage of the last run's scenarios, replayed on the device from the placement matrix (which stays there).  Requirements and
+ * refusals are those of simon_fetch_node_usage / simon_fetch_headroom.  The storage state is not a sum: the volume group a volume lands
+ * in and the devices a pod takes depend on the node's state at that moment, so the scheduled pods whose class has a non-empty
+ * simon_local_spec are applied in the order of the scenario's stream (its order_id), each to the node its placement names.  A node's
+ * state depends only on the pods placed on it, in order, so nodes are replayed independently.  A pod bound by Spec.NodeName
+ * (preset_node >= 0) never reaches LocalPlugin.Bind (pkg/simulator/plugin/open-local.go:180-253) and commits nothing; pods that read
+ * SIMON_UNSCHEDULED or SIMON_GATED contribute nothing.
+ *
+ * Applying a pod to a node is the allocation the filter made and Bind commits: LVM volumes in spec order -- a volume whose StorageClass
+ * names a VG goes to the group of that interned name, any other to the group with the smallest free size >= the volume's size (ties:
+ * annotation order; this pod's earlier volumes count as requested); then SSD and HDD volumes by CheckExclusiveResourceMeetsPVCSize
+ * (algo/common.go:290-350): the free devices of the media type ascending by capacity (ties: annotation order), the sizes ascending as
+ * the spec carries them, two pointers -- the match fails only when the LAST device is too small, so a shortfall without that event
+ * commits fewer devices than volumes.  A placed pod passed the filter, so its allocation succeeds; should it fail (a placement row
+ * from another problem) the pod commits nothing.
+ *
+ * simon_fetch_local_usage: the "Node Local Storage" table `simon apply` ends with (pkg/apply/apply.go:401-455), for the n listed scenarios
+ * (any order, repeats allowed, NULL = scenarios 0 .. n-1).  For a node j the scenario holds and that carries the storage annotation:
+ *   vg_req[i][j][v] = init_vg_req[j][v] + the sizes committed to volume group v < local_vg_cnt[j] (0 for v >= local_vg_cnt[j]),
+ *   dev_alloc[i][j] = init_dev_alloc[j] | the devices committed (bit d = device d).
+ * A held node without the annotation reads 0 / 0; a node the scenario lacks reads vg_req 0 and dev_alloc -1.  Summed over a scenario's
+ * annotated nodes and groups, vg_req gives simon_batch_out.used_vg.  A problem without Open-Local (local_flags NULL) is answered: vg_req
+ * is 0 everywhere and dev_alloc 0 (-1 for a node the scenario lacks).
+ *
+ * simon_fetch_headroom_local: simon_fetch_headroom_gpu with the storage bound, so all three bounds at once.  For a probe pod whose class
+ * has a non-empty simon_local_spec, cap(s, j, k) = min(cap of simon_fetch_headroom_gpu, cap_local), where cap_local is the number of
+ * consecutive copies of the probe's spec that can be applied, as above, to node j's end state (each copy on top of the last); it is 0 on
+ * a node without the annotation (SIMON_FAIL_LOCAL).  The node's state after m copies depends only on m, a copy that fails changes
+ * nothing and so fails for ever, nodes are independent and Open-Local's score cannot change a count: fit is what the scheduler places.
+ * exact[k] is 1 under simon_fetch_headroom_gpu's conditions, except that an Open-Local spec no longer disqualifies.  A probe without a
+ * spec gives simon_fetch_headroom_gpu's result bit for bit, and so does every probe of a problem without Open-Local.  For a problem
+ * with GPU requests or GPU nodes the device bound applies under simon_fetch_headroom_gpu's rule (SIMON_ESTATE without
+ * SIMON_WANT_GPU_SLICES); simon_fetch_headroom and simon_fetch_headroom_gpu keep exact = 0 for a probe with a spec.
+ * SIMON_EINVAL as for the calls above (vg_req is the one required array).  The node range is tiled as theirs (SIMON_USAGE_TILE).
+ * Not covered: no simon_group_* forward and no Go shim; probes that are not pods of the loaded stream.  (additive: the ABI stays 7) */
+typedef struct simon_local_usage {
+    uint32_t struct_size;
+    int64_t* vg_req;       /* [n][N][SIMON_MAX_VG] SharedResource.Requested of volume group v of pool node j at the end of listed scenario i */
+    int32_t* dev_alloc;    /* [n][N] optional: bit d = ExclusiveResource.IsAllocated of device d; -1 = the scenario lacks node j */
+} simon_local_usage;
+int simon_fetch_local_usage(simon_ctx* ctx, const int32_t* scen_ids /* [n], NULL = 0..n-1 */, int32_t n, simon_local_usage* out);
+
+int simon_fetch_headroom_local(simon_ctx* ctx, const int32_t* probe_pod /* [K] pod ids */, int32_t K,
+                               int64_t* fit /* [S][K] */, int32_t* fit_nodes /* [S][K], may be NULL */, uint8_t* exact /* [K], may be NULL */);
 
 /* The rank rows in effect, rank[s][j] = position of pool node j in scenario s's canonical order: the caller's (simon_set_node_ranks) or
  * those of a segmented / node-subset batch, where nodes a scenario lacks read N.  SIMON_ESTATE for a batch without rank rows. */

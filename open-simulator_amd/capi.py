@@ -482,6 +482,7 @@ class BatchResult:
     headroom_exact: Optional[np.ndarray] = None    # [K] bool: headroom[:, k] is what the scheduler would place, not an upper bound
     node_usage: Optional["NodeUsage"] = None       # per-node end state of the listed scenarios (Context.fetch_node_usage; on request)
     gpu_usage: Optional["GpuUsage"] = None         # per-device end state of the listed scenarios (Context.fetch_gpu_usage; on request)
+    local_usage: Optional["LocalUsage"] = None     # Open-Local end state of the listed scenarios (Context.fetch_local_usage; on request)
 
     def c_out(self) -> BatchOut:
         o = BatchOut()
@@ -527,6 +528,18 @@ class GpuUsage:
 
 class GpuUsageC(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("dev_used", _p64), ("dev_pods", _p32)]
+
+
+@dataclass
+class LocalUsage:
+    """simon_fetch_local_usage: the Open-Local storage at the end of the listed scenarios (row i = scenarios[i], pool node j)."""
+    scenarios: np.ndarray               # [n] the indices as listed
+    vg_req: np.ndarray                  # [n][N][MAX_VG] int64 SharedResource.Requested of the node's volume groups (state before the stream included)
+    dev_alloc: Optional[np.ndarray] = None    # [n][N] int32 bit d = device d is allocated; -1 = the scenario lacks node j
+
+
+class LocalUsageC(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("vg_req", _p64), ("dev_alloc", _p32)]
 
 
 WANT_PLACEMENT, WANT_GPU_SLICES = 1, 2
@@ -576,7 +589,7 @@ EXPORTS = [
     "simon_set_image_locality", "simon_group_set_image_locality",
     "simon_set_scenario_segments", "simon_set_scenario_nodes", "simon_fetch_node_ranks", "simon_set_pod_eviction",
     "simon_set_scenario_pods", "simon_fetch_group_counts", "simon_fetch_node_usage", "simon_fetch_headroom",
-    "simon_fetch_gpu_usage", "simon_fetch_headroom_gpu",
+    "simon_fetch_gpu_usage", "simon_fetch_headroom_gpu", "simon_fetch_local_usage", "simon_fetch_headroom_local",
     "simon_group_create", "simon_group_destroy", "simon_group_last_error", "simon_group_size", "simon_group_member",
     "simon_group_load_nodes", "simon_group_load_pods", "simon_group_load_class_tables", "simon_group_load_scenarios",
     "simon_group_run_loaded", "simon_group_fetch_results", "simon_group_run_batch", "simon_group_fetch_placement", "simon_group_fetch_gpu_slices",
@@ -632,6 +645,10 @@ def load_library(path: Optional[str] = None):
     lib.simon_fetch_gpu_usage.restype = C.c_int
     lib.simon_fetch_headroom_gpu.argtypes = [vp, _p32, C.c_int32, _p64, _p32, C.POINTER(C.c_uint8)]
     lib.simon_fetch_headroom_gpu.restype = C.c_int
+    lib.simon_fetch_local_usage.argtypes = [vp, _p32, C.c_int32, C.POINTER(LocalUsageC)]
+    lib.simon_fetch_local_usage.restype = C.c_int
+    lib.simon_fetch_headroom_local.argtypes = [vp, _p32, C.c_int32, _p64, _p32, C.POINTER(C.c_uint8)]
+    lib.simon_fetch_headroom_local.restype = C.c_int
     lib.simon_min_plan.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(Plan)]
     lib.simon_min_plan_vg.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Plan), C.POINTER(C.c_int32)]
     lib.simon_explain.argtypes = [vp, Scenario, _p32, _p32, _pu16, C.c_int32]
@@ -942,17 +959,35 @@ class Context:
                     "simon_fetch_gpu_usage")
         return res
 
-    def fetch_headroom(self, probe_pods, nodes: bool = False, devices: bool = False):
+    def fetch_local_usage(self, scen_ids=None) -> LocalUsage:
+        """simon_fetch_local_usage: what every volume group of every pool node has requested and which exclusive devices are allocated at
+        the end of the listed scenarios of the last run (None: all of them), replayed on the device from the placement matrix in the
+        order of every scenario's stream."""
+        ids = np.arange(self.S, dtype=np.int32) if scen_ids is None else np.ascontiguousarray(scen_ids, dtype=np.int32).reshape(-1)
+        n, N = len(ids), self.problem.n_nodes
+        res = LocalUsage(ids, np.zeros((n, N, MAX_VG), np.int64), np.zeros((n, N), np.int32))
+        o = LocalUsageC()
+        o.struct_size = C.sizeof(LocalUsageC)
+        o.vg_req, o.dev_alloc = _ptr(res.vg_req, C.c_int64), _ptr(res.dev_alloc, C.c_int32)
+        self._check(self.lib.simon_fetch_local_usage(self.h, None if scen_ids is None else _ptr(ids, C.c_int32), n, C.byref(o)),
+                    "simon_fetch_local_usage")
+        return res
+
+    def fetch_headroom(self, probe_pods, nodes: bool = False, devices: bool = False, storage: bool = False):
         """simon_fetch_headroom: (fit [S][K] int64, fit_nodes [S][K] int32 or None, exact [K] bool) -- how many more pods like pod
         probe_pods[k] fit in every scenario of the last run, on how many nodes, and whether that count is what the scheduler would place
         (exact) or the resource-and-static-filter upper bound.  devices=True: simon_fetch_headroom_gpu -- a probe with a GPU request is
-        also bounded by the slices the nodes' devices still hold, and is exact (run with want_gpu_slices)."""
+        also bounded by the slices the nodes' devices still hold, and is exact (run with want_gpu_slices).  storage=True:
+        simon_fetch_headroom_local -- the device bound as above where the problem has GPUs, and a probe whose class has Open-Local
+        volumes is bounded by what the nodes' volume groups and exclusive devices still hold, and is exact."""
         pp = np.ascontiguousarray(probe_pods, dtype=np.int32).reshape(-1)
         K = len(pp)
         fit = np.zeros((self.S, K), np.int64)
         fn = np.zeros((self.S, K), np.int32) if nodes else None
         ex = np.zeros(K, np.uint8)
         call, name = (self.lib.simon_fetch_headroom_gpu, "simon_fetch_headroom_gpu") if devices else (self.lib.simon_fetch_headroom, "simon_fetch_headroom")
+        if storage:
+            call, name = self.lib.simon_fetch_headroom_local, "simon_fetch_headroom_local"
         self._check(call(self.h, _ptr(pp, C.c_int32), K, _ptr(fit, C.c_int64), _ptr(fn, C.c_int32), _ptr(ex, C.c_uint8)), name)
         return fit, fn, ex.astype(bool)
 

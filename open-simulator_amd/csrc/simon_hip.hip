@@ -226,6 +226,15 @@ struct simon_ctx : simon::HostInputs {
     bool usage_gpu_pods_staged = false, usage_gpu_nodes_staged = false;
     DevBuf<int64_t> d_g_pod_mem, d_g_per_dev, d_g_init_used, d_g_out_used, d_g_probe_mem;
     DevBuf<int32_t> d_g_node_cnt, d_g_out_pods, d_g_probe_cnt;
+    // simon_fetch_local_usage / simon_fetch_headroom_local: the Open-Local arrays the storage kernels read, staged likewise -- the node
+    // arrays after simon_load_nodes; the specs, every pod's spec (-1: none, or bound by Spec.NodeName) and, per loaded order, the pods with
+    // a spec in that order's sequence (local_list / local_list_off, from h_orders) after simon_load_pods, simon_load_class_tables or
+    // simon_load_scenarios; the probes' specs per call
+    bool local_nodes_staged = false, local_pods_staged = false;
+    std::vector<int32_t> h_orders;                // [n_orders][P] the loaded orders
+    DevBuf<LocalSpec> d_l_specs;
+    DevBuf<int32_t> d_l_pod_spec, d_l_list, d_l_list_off, d_l_flags, d_l_vg_cnt, d_l_vg_name, d_l_dev_cnt, d_l_dev_media, d_l_dev_init, d_l_probe_spec, d_l_out_dev;
+    DevBuf<int64_t> d_l_vg_cap, d_l_vg_init, d_l_dev_cap, d_l_out_vg;
     bool orders_perm = false;                     // every loaded order is a permutation of [0, P) (the score-table kernel's placement gather)
     std::vector<int64_t> prefix_cpu, prefix_mem;   // [N+1] allocatable of the first n nodes
     std::vector<int64_t> prefix_vg;   // [N+1] Open-Local VG capacity of the first n nodes (0 without local storage)
@@ -1755,7 +1764,7 @@ int simon_load_nodes(simon_ctx* c, const simon_nodes_soa* nd) {
             if (d < -1 || d >= c->topo_n_dom[k]) return fail(c, SIMON_EINVAL, "topo_dom[%d][%d] out of range", k, j);
         }
     c->have_nodes = true; c->staged = false; c->have_results = false;
-    c->usage_nodes_staged = false; c->usage_gpu_nodes_staged = false;
+    c->usage_nodes_staged = false; c->usage_gpu_nodes_staged = false; c->local_nodes_staged = false;
     return SIMON_OK;
 }
 
@@ -1798,7 +1807,7 @@ int simon_load_pods(simon_ctx* c, const simon_pods_soa* pd) {
     c->p_evict.clear(); c->evict_short = -1;
     c->pods_on = false;
     c->have_pods = true; c->staged = false; c->have_results = false;
-    c->usage_pods_staged = false; c->usage_gpu_pods_staged = false;
+    c->usage_pods_staged = false; c->usage_gpu_pods_staged = false; c->local_pods_staged = false;
     return SIMON_OK;
 }
 
@@ -2003,6 +2012,7 @@ int simon_load_class_tables(simon_ctx* c, const simon_class_tables* tb) {
         c->anti_off.assign(c->Cp + 1, 0); c->match_off.assign(c->Cp + 1, 0);
     }
     c->have_tables = true; c->staged = false; c->have_results = false;
+    c->local_pods_staged = false;
     return SIMON_OK;
 }
 
@@ -2172,6 +2182,9 @@ int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, co
     (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
     c->stats.h2d_ms = ms;
     c->S = S; c->n_orders = n_orders; c->max_n = max_n;
+    if (c->has_local) c->h_orders.assign(orders, orders + (size_t)n_orders * P);    // (only the storage calls read them: local_stage)
+    else c->h_orders.clear();
+    c->local_pods_staged = false;
     c->has_ranks = false;
     c->have_results = false;
     return SIMON_OK;
@@ -2670,9 +2683,64 @@ int simon_fetch_gpu_usage(simon_ctx* c, const int32_t* scen_ids, int32_t n, simo
     return SIMON_OK;
 }
 
-// simon_fetch_headroom and simon_fetch_headroom_gpu (`devices`: the device bound on top, `what` names the call in messages)
+static_assert(sizeof(LocalSpec) == sizeof(simon_local_spec) && offsetof(LocalSpec, hdd_size) == offsetof(simon_local_spec, hdd_size) &&
+              offsetof(LocalSpec, lvm_vg) == offsetof(simon_local_spec, lvm_vg), "the storage kernels read simon_local_spec as LocalSpec");
+static_assert(SIMON_MAX_VG == kLocalVG && SIMON_MAX_LDEV == kLocalDev && SIMON_MAX_LVOL == kLocalVol, "the storage kernels' array sizes");
+
+// the Open-Local spec of pod class cls: its index in l_specs, or -1 (none, or no volume at all: local_spec_of of the oracle)
+static int local_spec_index(const simon_ctx* c, int cls) {
+    if ((size_t)cls >= c->l_spec_of.size() || c->l_spec_of[cls] < 0) return -1;
+    const simon_local_spec& sp = c->l_specs[c->l_spec_of[cls]];
+    return sp.n_lvm + sp.n_ssd + sp.n_hdd > 0 ? c->l_spec_of[cls] : -1;
+}
+
+// The Open-Local arrays of both storage calls, uploaded on the first call after a reload.  A problem without Open-Local leaves l.flags
+// null: the kernels replay nothing and bound nothing.
+static int local_stage(simon_ctx* c, LocalUsage& l) {
+    if (!c->has_local) return SIMON_OK;
+    const size_t P = c->P;
+    if (!c->local_nodes_staged) {
+        HIP_TRY(c, c->d_l_flags.upload(c->l_flags, c->stream));
+        HIP_TRY(c, c->d_l_vg_cnt.upload(c->l_vg_cnt, c->stream));
+        HIP_TRY(c, c->d_l_vg_cap.upload(c->l_vg_cap, c->stream));
+        HIP_TRY(c, c->d_l_vg_init.upload(c->l_vg_req, c->stream));
+        HIP_TRY(c, c->d_l_vg_name.upload(c->l_vg_name, c->stream));
+        HIP_TRY(c, c->d_l_dev_cnt.upload(c->l_dev_cnt, c->stream));
+        HIP_TRY(c, c->d_l_dev_cap.upload(c->l_dev_cap, c->stream));
+        HIP_TRY(c, c->d_l_dev_media.upload(c->l_dev_media, c->stream));
+        HIP_TRY(c, c->d_l_dev_init.upload(c->l_dev_alloc, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->local_nodes_staged = true;
+    }
+    if (!c->local_pods_staged) {
+        std::vector<LocalSpec> specs(c->l_specs.size());
+        if (!specs.empty()) memcpy(specs.data(), c->l_specs.data(), specs.size() * sizeof(LocalSpec));
+        std::vector<int32_t> pod_spec(P, -1), list, off((size_t)c->n_orders + 1, 0);
+        for (size_t p = 0; p < P; ++p)
+            if (c->p_preset[p] < 0) pod_spec[p] = local_spec_index(c, c->p_cls[p]);
+        for (int o = 0; o < c->n_orders; ++o) {
+            for (size_t i = 0; i < P; ++i) {
+                const int32_t p = c->h_orders[(size_t)o * P + i];
+                if (pod_spec[p] >= 0) list.push_back(p);
+            }
+            off[o + 1] = (int32_t)list.size();
+        }
+        HIP_TRY(c, c->d_l_specs.upload(specs, c->stream));
+        HIP_TRY(c, c->d_l_pod_spec.upload(pod_spec, c->stream));
+        HIP_TRY(c, c->d_l_list.upload(list, c->stream));
+        HIP_TRY(c, c->d_l_list_off.upload(off, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));             // (the vectors leave scope)
+        c->local_pods_staged = true;
+    }
+    l.specs = c->d_l_specs.p; l.pod_spec = c->d_l_pod_spec.p; l.list = c->d_l_list.p; l.list_off = c->d_l_list_off.p;
+    l.flags = c->d_l_flags.p; l.vg_cnt = c->d_l_vg_cnt.p; l.vg_cap = c->d_l_vg_cap.p; l.vg_init = c->d_l_vg_init.p; l.vg_name = c->d_l_vg_name.p;
+    l.dev_cnt = c->d_l_dev_cnt.p; l.dev_cap = c->d_l_dev_cap.p; l.dev_media = c->d_l_dev_media.p; l.dev_init = c->d_l_dev_init.p;
+    return SIMON_OK;
+}
+
+// simon_fetch_headroom, simon_fetch_headroom_gpu and simon_fetch_headroom_local (`devices`: the device bound on top, `what` names the call in messages)
 static int fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int64_t* fit, int32_t* fit_nodes, uint8_t* exact, bool devices,
-                          const char* what) {
+                          const char* what, bool storage = false) {
     if (!c) return SIMON_EINVAL;
     if (!probe_pod || !fit) return fail(c, SIMON_EINVAL, "%s: missing required arrays (probe_pod, fit)", what);
     if (K < 1 || K > SIMON_MAX_PROBES) return fail(c, SIMON_EINVAL, "%s: %d probes outside [1, %d]", what, K, SIMON_MAX_PROBES);
@@ -2680,19 +2748,27 @@ static int fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int
     for (int k = 0; k < K; ++k)
         if (probe_pod[k] < 0 || probe_pod[k] >= c->P) return fail(c, SIMON_EINVAL, "%s: probe %d: pod %d outside [0,%d)", what, k, probe_pod[k], c->P);
     if (devices && c->has_gpu && !c->have_slices) return fail(c, SIMON_ESTATE, "%s: the last run did not record GPU devices (SIMON_WANT_GPU_SLICES)", what);
+    // simon_fetch_headroom_local: the device bound under simon_fetch_headroom_gpu's rule (refused above), its LDS only where GPUs exist
+    if (storage) devices = c->has_gpu || c->has_gpu_nodes;
     HIP_TRY(c, hipSetDevice(c->device));
     UsageCommon a{};
     if (const int rc = usage_stage(c, a)) return rc;
     DevUsage g{};
     if (devices)
         if (const int rc = usage_stage_gpu(c, g)) return rc;
-    usage_rows_of(c, c->usage_rows, a, c->S, devices ? kDevBytes : 0);
+    LocalUsage l{};
+    if (storage) {
+        if (const int rc = local_stage(c, l)) return rc;
+        usage_rows_of(c, c->usage_rows, a, c->S);
+        a.tile = local_tile(c->N, usage_node_bytes(a.nrows, kLocalBytes + (devices ? kDevBytes : 0)), c->usage_tile ? c->usage_tile : c->S <= c->n_cus ? 1 << 30 : 0);
+    } else
+        usage_rows_of(c, c->usage_rows, a, c->S, devices ? kDevBytes : 0);
     // the probe rows: request, the resources fitsRequest compares (fit.go:244-299), the class's static mask
     const size_t S = c->S, N = c->N, W = (N + 63) / 64, P = c->P;
     std::vector<ProbeRow> rows((size_t)K);
     std::vector<uint64_t> mask((size_t)K * W, ~0ull);
     std::vector<int64_t> gmem((size_t)K, 0);
-    std::vector<int32_t> gcnt((size_t)K, 0);
+    std::vector<int32_t> gcnt((size_t)K, 0), lspec((size_t)K, -1);
     auto none = [](const std::vector<int32_t>& off, int cls) { return (size_t)cls + 1 >= off.size() || off[cls + 1] == off[cls]; };
     for (int k = 0; k < K; ++k) {
         const int p = probe_pod[k], cls = c->p_cls[p];
@@ -2713,7 +2789,8 @@ static int fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int
         if (exact)
             exact[k] = (bound || (c->p_gpu_mem[p] == 0 && c->p_gpu_cnt[p] == 0 && c->p_gpu_index[p] == 0)) && c->p_pin[p] < 0 && c->p_preset[p] < 0 &&
                        none(c->match_off, cls) && none(c->anti_off, cls) && none(c->port_off, cls) && none(c->aff_off, cls) && none(c->sh_off, cls) &&
-                       ((size_t)cls >= c->l_spec_of.size() || c->l_spec_of[cls] < 0);
+                       (storage || (size_t)cls >= c->l_spec_of.size() || c->l_spec_of[cls] < 0);
+        if (storage && c->has_local) lspec[k] = local_spec_index(c, cls);
     }
     HeadroomArgs h{};
     const size_t cells = S * (size_t)K;
@@ -2727,8 +2804,14 @@ static int fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int
         HIP_TRY(c, c->d_g_probe_mem.upload(gmem, c->stream));
         HIP_TRY(c, c->d_g_probe_cnt.upload(gcnt, c->stream));
         g.probe_mem = c->d_g_probe_mem.p; g.probe_cnt = c->d_g_probe_cnt.p;
+    }
+    if (storage) {
+        HIP_TRY(c, c->d_l_probe_spec.upload(lspec, c->stream));
+        l.probe_spec = c->d_l_probe_spec.p;
+        HIP_TRY(c, launch_headroom_local(a, h, g, l, devices, (int)S, c->stream));
+    } else if (devices)
         HIP_TRY(c, launch_headroom_gpu(a, h, g, (int)S, c->stream));
-    } else
+    else
         HIP_TRY(c, launch_headroom(a, h, (int)S, c->stream));
     HIP_TRY(c, hipMemcpyAsync(fit, c->d_u_fit.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
     if (fit_nodes) HIP_TRY(c, hipMemcpyAsync(fit_nodes, c->d_u_fit_nodes.p, cells * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2742,6 +2825,45 @@ int simon_fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int6
 
 int simon_fetch_headroom_gpu(simon_ctx* c, const int32_t* probe_pod, int32_t K, int64_t* fit, int32_t* fit_nodes, uint8_t* exact) {
     return fetch_headroom(c, probe_pod, K, fit, fit_nodes, exact, true, "fetch_headroom_gpu");
+}
+
+int simon_fetch_headroom_local(simon_ctx* c, const int32_t* probe_pod, int32_t K, int64_t* fit, int32_t* fit_nodes, uint8_t* exact) {
+    return fetch_headroom(c, probe_pod, K, fit, fit_nodes, exact, true, "fetch_headroom_local", true);
+}
+
+int simon_fetch_local_usage(simon_ctx* c, const int32_t* scen_ids, int32_t n, simon_local_usage* out) {
+    if (!c) return SIMON_EINVAL;
+    if (!out) return fail(c, SIMON_EINVAL, "fetch_local_usage: bad arguments");
+    if (out->struct_size != sizeof(simon_local_usage)) return fail(c, SIMON_EINVAL, "fetch_local_usage: simon_local_usage size mismatch");
+    if (!out->vg_req) return fail(c, SIMON_EINVAL, "fetch_local_usage: missing required arrays (vg_req)");
+    if (n < 1) return fail(c, SIMON_EINVAL, "fetch_local_usage: %d scenarios listed", n);
+    if (!c->have_results || !c->have_placement) return fail(c, SIMON_ESTATE, "fetch_local_usage: no placements on device (run with SIMON_WANT_PLACEMENT)");
+    if (!scen_ids && n > c->S) return fail(c, SIMON_EINVAL, "fetch_local_usage: scenario %d outside [0,%d)", c->S, c->S);
+    for (int i = 0; scen_ids && i < n; ++i)
+        if (scen_ids[i] < 0 || scen_ids[i] >= c->S) return fail(c, SIMON_EINVAL, "fetch_local_usage: scenario %d outside [0,%d)", scen_ids[i], c->S);
+    HIP_TRY(c, hipSetDevice(c->device));
+    UsageCommon a{};
+    a.placement = c->d_place.p; a.scen = reinterpret_cast<const int32_t*>(c->d_scen.p);
+    a.rank = own_nodes(c) && c->has_ranks ? c->d_node_rank.p : nullptr;
+    a.P = c->P; a.N = c->N;
+    LocalUsage l{};
+    if (const int rc = local_stage(c, l)) return rc;
+    a.tile = local_tile(c->N, kLocalBytes, c->usage_tile ? c->usage_tile : n <= c->n_cus ? 1 << 30 : 0);
+    const size_t cells = (size_t)n * c->N;
+    LocalUsageOut o{};
+    HIP_TRY(c, c->d_l_out_vg.ensure(cells * SIMON_MAX_VG));
+    o.vg_req = c->d_l_out_vg.p;
+    if (out->dev_alloc) { HIP_TRY(c, c->d_l_out_dev.ensure(cells)); o.dev_alloc = c->d_l_out_dev.p; }
+    if (scen_ids) {
+        HIP_TRY(c, c->d_u_ids.ensure((size_t)n));
+        HIP_TRY(c, hipMemcpyAsync(c->d_u_ids.p, scen_ids, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        o.scen_ids = c->d_u_ids.p;
+    }
+    HIP_TRY(c, launch_local_usage(a, l, o, n, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out->vg_req, o.vg_req, cells * SIMON_MAX_VG * 8, hipMemcpyDeviceToHost, c->stream));
+    if (out->dev_alloc) HIP_TRY(c, hipMemcpyAsync(out->dev_alloc, o.dev_alloc, cells * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));                 // (simon_stats is left alone, as in simon_fetch_node_usage)
+    return SIMON_OK;
 }
 
 // The all-feature kernel gives every problem its failure codes and runs the batches no other kernel takes: staged on first use where

@@ -121,4 +121,58 @@ hipError_t launch_gpu_usage(const UsageCommon& a, const DevUsage& g, const GpuUs
 // headroom with the device bound: a.tile from usage_tile(N, nrows, forced, kDevBytes)
 hipError_t launch_headroom_gpu(const UsageCommon& a, const HeadroomArgs& h, const DevUsage& g, int S, hipStream_t st);
 
+// Open-Local storage (simon_fetch_local_usage, simon_fetch_headroom_local).  The state of a node is not a sum: which volume group a
+// volume lands in and which devices a pod takes depend on the node's state at that moment, so the scheduled storage pods are REPLAYED
+// in stream order -- per node, which is all the order that matters (a node's state depends only on the pods placed on it).  Per tile
+// node LDS holds vg_req[4] int64 and the allocated-device mask, 36 bytes; the storage pods of the scenario's order (compact list, built
+// on the host per order) are staged in chunks of kLocalChunk, and thread t applies the pods that sit on its tile nodes t, t + 256, ...
+// front to back (broadcast LDS reads, no atomics).  docs/KERNELS.md has the layout.
+constexpr int kLocalVG = 4, kLocalDev = 8, kLocalVol = 4;   // SIMON_MAX_VG, SIMON_MAX_LDEV, SIMON_MAX_LVOL
+constexpr int kLocalBytes = kLocalVG * 8 + 4;
+constexpr int kLocalChunk = 512;             // storage pods staged per pass (node and spec of each: 8 bytes)
+
+struct LocalSpec {                           // simon_local_spec, field for field
+    int32_t n_lvm, n_ssd, n_hdd, pad;
+    int64_t lvm_size[kLocalVol];
+    int32_t lvm_vg[kLocalVol];
+    int64_t ssd_size[kLocalVol], hdd_size[kLocalVol];
+};
+
+struct LocalUsage {
+    const LocalSpec* specs;                  // [n_local_specs]
+    const int32_t* pod_spec;                 // [P] spec of the pod's class; -1 = no volumes or bound by Spec.NodeName (never reaches LocalPlugin.Bind)
+    const int32_t* list;                     // the pods with pod_spec >= 0 in the sequence of every order, one order after the other
+    const int32_t* list_off;                 // [n_orders + 1] order o's pods are list[list_off[o] .. list_off[o + 1])
+    const int32_t* flags;                    // [N] bit0: the node carries the storage annotation; nullptr = a problem without Open-Local
+    const int32_t* vg_cnt;                   // [N]
+    const int64_t* vg_cap;                   // [N][kLocalVG]
+    const int64_t* vg_init;                  // [N][kLocalVG] requested before the stream
+    const int32_t* vg_name;                  // [N][kLocalVG]
+    const int32_t* dev_cnt;                  // [N]
+    const int64_t* dev_cap;                  // [N][kLocalDev]
+    const int32_t* dev_media;                // [N] 2 bits per device
+    const int32_t* dev_init;                 // [N] allocated before the stream
+    const int32_t* probe_spec;               // headroom only: [K] spec of the probe's class or -1 = no storage bound
+};
+
+struct LocalUsageOut {
+    const int32_t* scen_ids;                 // [n] listed scenarios, or nullptr = 0 .. n-1
+    int64_t* vg_req;                         // [n][N][kLocalVG]
+    int32_t* dev_alloc;                      // [n][N] or nullptr
+};
+
+// the tile of both storage kernels: as usage_tile, less the staged chunk (`per`: bytes per node, kLocalBytes included)
+inline int local_tile(int N, size_t per, int forced) {
+    int t = forced > 0 ? forced : (int)(kUsageLdsBudget / per) / 64 * 64;
+    const int cap = (int)((64 * 1024 - 2 * kMaxProbes * 8 - kLocalChunk * 8) / per);
+    t = t > cap ? cap : t;
+    return t < 1 ? 1 : (t > N ? N : t);
+}
+// a.tile from local_tile(N, kLocalBytes, forced); a.pod_req / node_init / init_npods are not read
+hipError_t launch_local_usage(const UsageCommon& a, const LocalUsage& l, const LocalUsageOut& o, int n, hipStream_t st);
+// headroom with the storage bound and, `devices`, the device bound: a.tile from local_tile(N, usage_node_bytes(nrows, kLocalBytes
+// (+ kDevBytes)), forced)
+hipError_t launch_headroom_local(const UsageCommon& a, const HeadroomArgs& h, const DevUsage& g, const LocalUsage& l, bool devices, int S,
+                                 hipStream_t st);
+
 }  // namespace simon

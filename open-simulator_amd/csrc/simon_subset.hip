@@ -248,6 +248,36 @@ __global__ __launch_bounds__(256) void gpu_usage_kernel(UsageCommon a, DevUsage 
     }
 }
 
+// The cap of one probe on node j of the tile that starts at t0, as headroom_kernel below computes it in place (that kernel keeps its
+// own copy: its code object stays what it was): pod slots, the resources fitsRequest compares and, DEV, the slices the node's devices
+// still hold.
+template <bool DEV>
+__device__ __forceinline__ long long node_cap(const UsageCommon& a, const HeadroomArgs& h, const DevUsage& g, const ProbeRow& pr, long long gm, int gc,
+                                              const unsigned long long* s_req, const int32_t* s_cnt, const unsigned long long* s_dev, int j, int t0) {
+    const int N = a.N;
+    long long cap = (long long)h.alloc_pods[j] - a.init_npods[j] - s_cnt[j - t0];      // pod slots
+    int ai = 0;                                                         // (the accumulated rows are an ascending subset of the resource rows)
+    for (int r = 0; r < kUsageRows && cap > 0; ++r) {
+        long long used = a.node_init[(size_t)r * N + j];
+        if (ai < a.nrows && a.row_src[ai] == r) used += (long long)s_req[ai++ * a.tile + (j - t0)];
+        if (!((pr.checked >> r) & 1u)) continue;
+        const long long room = h.node_alloc[(size_t)r * N + j] - used, q = pr.q[r];
+        if (room < 0) cap = 0;                                          // over-committed: Allocatable < request + Requested whatever the request
+        else if (q > 0) cap = min(cap, room / q);
+    }
+    if (DEV && gm > 0 && cap > 0) {
+        long long T = 0;
+        const int cnt = gc > 0 ? g.node_cnt[j] : 0;
+        const long long per = g.per_dev[j];
+        for (int d = 0; d < cnt; ++d) {
+            const long long idle = per - g.init_used[(size_t)j * kGpuDev + d] - (long long)s_dev[dev_slot(j - t0, d)];
+            if (idle > 0) T += idle / gm;                               // (an over-booked device holds nothing)
+        }
+        cap = gc > 0 ? min(cap, T / gc) : 0;
+    }
+    return cap;
+}
+
 // headroom_kernel: workgroup s = scenario s of the batch.  Per tile the same accumulation; then, per probe, every thread takes the cap
 // of its nodes of the tile and the workgroup adds them up in LDS.  Only [S][K] counters leave.  DEV (simon_fetch_headroom_gpu): the
 // tile also carries the device sums, and a probe with a GPU request is bounded by the slices the node's devices still hold:
@@ -277,6 +307,7 @@ __global__ __launch_bounds__(256) void headroom_kernel(UsageCommon a, HeadroomAr
             int nodes = 0;
             for (int j = t0 + tid; j < t1; j += 256) {
                 if (!((mask[j >> 6] >> (j & 63)) & 1ull) || !usage_holds(a, s, j)) continue;
+                // (node_cap<DEV> above is this computation as a function, for headroom_local_kernel: a change here belongs there too)
                 long long cap = (long long)h.alloc_pods[j] - a.init_npods[j] - s_cnt[j - t0];      // pod slots
                 int ai = 0;                                             // (the accumulated rows are an ascending subset of the resource rows)
                 for (int r = 0; r < kUsageRows && cap > 0; ++r) {
@@ -296,6 +327,229 @@ __global__ __launch_bounds__(256) void headroom_kernel(UsageCommon a, HeadroomAr
                         if (idle > 0) T += idle / gm;                   // (an over-booked device holds nothing)
                     }
                     cap = gc > 0 ? min(cap, T / gc) : 0;
+                }
+                if (cap > 0) { fit += cap; ++nodes; }
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                fit += __shfl_xor(fit, off, 64);
+                nodes += __shfl_xor(nodes, off, 64);
+            }
+            if ((tid & 63) == 0 && nodes) {
+                atomicAdd(&s_fit[k], (unsigned long long)fit);
+                atomicAdd(&s_nodes[k], nodes);
+            }
+        }
+        __syncthreads();
+    }
+    for (int k = tid; k < K; k += 256) {
+        h.fit[(size_t)s * K + k] = (long long)s_fit[k];
+        if (h.fit_nodes) h.fit_nodes[(size_t)s * K + k] = s_nodes[k];
+    }
+}
+
+// ---- Open-Local: simon_fetch_local_usage / simon_fetch_headroom_local ----------------------------------------------------------------
+struct LocalState {
+    long long req[kLocalVG];                 // SharedResource.Requested of the node's volume groups
+    int alloc;                               // bit d: ExclusiveResource.IsAllocated
+};
+
+__device__ __forceinline__ bool same_state(const LocalState& x, const LocalState& y) {
+    bool eq = x.alloc == y.alloc;
+#pragma unroll
+    for (int q = 0; q < kLocalVG; ++q) eq = eq && x.req[q] == y.req[q];
+    return eq;
+}
+
+// One pod's volumes onto node j: local_allocate + the commit of LocalPlugin.Bind as oracle/simon_oracle.c restates them, which is what
+// local_eval<COMMIT> of simon_wide.hip does for the pod it places.  LVM volumes in spec order (a named group by interned name, otherwise
+// the smallest free size that fits, ties in annotation order, this pod's earlier volumes counted); then SSD and HDD volumes by
+// CheckExclusiveResourceMeetsPVCSize: free devices ascending by (capacity, index), sizes ascending as the spec carries them, two
+// pointers, failing only when the LAST device is too small.  True = allocated, st holds the new state; false = st is untouched.
+__device__ bool local_apply(const LocalUsage& L, const LocalSpec& sp, int j, LocalState& st) {
+    if (!(L.flags[j] & 1)) return false;                                // SIMON_FAIL_LOCAL
+    long long req[kLocalVG];
+#pragma unroll
+    for (int q = 0; q < kLocalVG; ++q) req[q] = st.req[q];
+    if (sp.n_lvm > 0) {
+        const int nvg = L.vg_cnt[j];
+        if (nvg <= 0) return false;
+        long long cap[kLocalVG];
+        int name[kLocalVG];
+#pragma unroll
+        for (int q = 0; q < kLocalVG; ++q) {
+            cap[q] = L.vg_cap[(size_t)j * kLocalVG + q];
+            name[q] = L.vg_name[(size_t)j * kLocalVG + q];
+        }
+        for (int k = 0; k < sp.n_lvm; ++k) {
+            const long long size = sp.lvm_size[k];
+            const int want = sp.lvm_vg[k];
+            int pick = -1;
+            long long pick_free = 0;
+#pragma unroll
+            for (int q = 0; q < kLocalVG; ++q) {
+                if (q >= nvg) continue;
+                const long long fr = cap[q] - req[q];
+                if (want >= 0) {
+                    if (pick < 0 && name[q] == want) { pick = q; pick_free = fr; }
+                } else if (fr >= size && (pick < 0 || fr < pick_free)) {
+                    pick = q; pick_free = fr;
+                }
+            }
+            if (pick < 0 || pick_free < size) return false;
+#pragma unroll
+            for (int q = 0; q < kLocalVG; ++q)
+                if (q == pick) req[q] += size;
+        }
+    }
+    int newly = 0;
+    if (sp.n_ssd + sp.n_hdd > 0) {
+        const int cnt = L.dev_cnt[j], media = L.dev_media[j];
+        const int64_t* __restrict__ const dcap = L.dev_cap + (size_t)j * kLocalDev;
+        for (int m = 1; m <= 2; ++m) {                                  // SSD first, then HDD
+            const int n_pvc = m == 1 ? sp.n_ssd : sp.n_hdd;
+            const int64_t* const sizes = m == 1 ? sp.ssd_size : sp.hdd_size;
+            unsigned free_mask = 0;
+            for (int d = 0; d < cnt; ++d)
+                if (((media >> (2 * d)) & 3) == m && !((st.alloc >> d) & 1)) free_mask |= 1u << d;
+            const int nfree = __popc(free_mask);
+            if (nfree < n_pvc) return false;
+            int i = 0;
+            for (int step = 0; step < nfree && n_pvc > 0; ++step) {
+                int d = -1;
+                long long c = 0;
+                for (int e = 0; e < cnt; ++e)
+                    if (((free_mask >> e) & 1u) && (d < 0 || dcap[e] < c)) { d = e; c = dcap[e]; }
+                free_mask &= ~(1u << d);
+                if (c < sizes[i]) {
+                    if (step == nfree - 1) return false;
+                    continue;
+                }
+                newly |= 1 << d;
+                if (++i == n_pvc) break;
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < kLocalVG; ++q) st.req[q] = req[q];
+    st.alloc |= newly;
+    return true;
+}
+
+__device__ __forceinline__ LocalState local_load(const long long* s_vg, const int32_t* s_ldev, int tile, int jj) {
+    LocalState st;
+#pragma unroll
+    for (int q = 0; q < kLocalVG; ++q) st.req[q] = s_vg[q * tile + jj];
+    st.alloc = s_ldev[jj];
+    return st;
+}
+
+// One tile of the node range [t0, t1): s_vg[q][j - t0] / s_ldev[j - t0] = the storage state of node j after the scheduled storage pods
+// of the scenario's order (L.list[lo, hi)).  Thread t owns the tile nodes t, t + 256, ...: it sets their state before the stream and
+// applies, chunk by chunk and front to back, the staged pods whose placement names one of them -- stream order per node, nothing shared.
+// s_stage: [2][kLocalChunk] node and spec of the staged pods.  Ends behind a barrier: every thread may read the tile.
+__device__ __forceinline__ void local_replay(const UsageCommon& a, const LocalUsage& L, const int32_t* __restrict__ row, int lo, int hi, int t0,
+                                             int t1, long long* s_vg, int32_t* s_ldev, int32_t* s_stage) {
+    const int tid = threadIdx.x, tile = a.tile, tw = t1 - t0;
+    for (int jj = tid; jj < tw; jj += 256) {
+#pragma unroll
+        for (int q = 0; q < kLocalVG; ++q) s_vg[q * tile + jj] = L.flags ? L.vg_init[(size_t)(t0 + jj) * kLocalVG + q] : 0;
+        s_ldev[jj] = L.flags ? L.dev_init[t0 + jj] : 0;
+    }
+    for (int c0 = lo; L.flags && c0 < hi; c0 += kLocalChunk) {
+        const int cn = min(kLocalChunk, hi - c0);
+        __syncthreads();                                                // (the last chunk has been read)
+        for (int i = tid; i < cn; i += 256) {
+            const int p = L.list[c0 + i];
+            s_stage[i] = row[p];
+            s_stage[kLocalChunk + i] = L.pod_spec[p];
+        }
+        __syncthreads();
+        for (int i = 0; i < cn; ++i) {
+            const int jj = s_stage[i] - t0;                             // (SIMON_UNSCHEDULED / SIMON_GATED: below 0)
+            if ((unsigned)jj >= (unsigned)tw || (jj & 255) != tid) continue;
+            LocalState st = local_load(s_vg, s_ldev, tile, jj);
+            if (!local_apply(L, L.specs[s_stage[kLocalChunk + i]], t0 + jj, st)) continue;   // (a row from another problem: commits nothing)
+#pragma unroll
+            for (int q = 0; q < kLocalVG; ++q) s_vg[q * tile + jj] = st.req[q];
+            s_ldev[jj] = st.alloc;
+        }
+    }
+    __syncthreads();
+}
+
+// local_usage_kernel: workgroup b = listed scenario b.  [n][N][4] / [n][N] leave coalesced; a node the scenario lacks reads 0 / -1, a node
+// without the storage annotation 0 / 0, a volume group the node lacks 0.
+__global__ __launch_bounds__(256) void local_usage_kernel(UsageCommon a, LocalUsage L, LocalUsageOut o) {
+    extern __shared__ unsigned long long usage_smem[];
+    long long* const s_vg = (long long*)usage_smem;                     // [4][tile]
+    int32_t* const s_ldev = (int32_t*)(s_vg + (size_t)kLocalVG * a.tile);   // [tile]
+    int32_t* const s_stage = s_ldev + a.tile;                           // [2][kLocalChunk]
+    const int b = blockIdx.x, tid = threadIdx.x, N = a.N;
+    const int s = o.scen_ids ? o.scen_ids[b] : b;
+    const int32_t* __restrict__ const row = a.placement + (size_t)s * a.P;
+    const int order = a.scen[2 * s + 1];
+    const int lo = L.flags ? L.list_off[order] : 0, hi = L.flags ? L.list_off[order + 1] : 0;
+    for (int t0 = 0; t0 < N; t0 += a.tile) {
+        const int t1 = min(t0 + a.tile, N);
+        local_replay(a, L, row, lo, hi, t0, t1, s_vg, s_ldev, s_stage);
+        for (int i = tid; i < (t1 - t0) * kLocalVG; i += 256) {
+            const int jj = i >> 2, q = i & 3, j = t0 + jj;
+            const bool live = L.flags && (L.flags[j] & 1) && q < L.vg_cnt[j] && usage_holds(a, s, j);
+            o.vg_req[((size_t)b * N + j) * kLocalVG + q] = live ? s_vg[q * a.tile + jj] : 0;
+        }
+        for (int j = t0 + tid; o.dev_alloc && j < t1; j += 256)
+            o.dev_alloc[(size_t)b * N + j] = !usage_holds(a, s, j) ? -1 : L.flags && (L.flags[j] & 1) ? s_ldev[j - t0] : 0;
+        __syncthreads();                                                // (the next tile overwrites what this one read)
+    }
+}
+
+// headroom_local_kernel: headroom_kernel with the storage bound (simon_fetch_headroom_local).  After the tile's accumulation and replay a
+// probe whose class has an Open-Local spec is bounded, per node, by the number of consecutive local_apply steps of that spec that
+// succeed on a private copy of the node's end state, at most the cap so far; a step that leaves the state unchanged (no volume, no
+// device) ends the count at the cap so far.  The state after m copies depends only on m and a failed copy changes nothing, so the
+// bound is what the scheduler places.  DEV as in headroom_kernel.
+template <bool DEV>
+__global__ __launch_bounds__(256) void headroom_local_kernel(UsageCommon a, HeadroomArgs h, DevUsage g, LocalUsage L) {
+    extern __shared__ unsigned long long usage_smem[];
+    unsigned long long* const s_req = usage_smem;                       // [nrows][tile]
+    unsigned long long* const s_dev = s_req + (size_t)a.nrows * a.tile; // DEV: [tile][8]
+    long long* const s_vg = (long long*)(s_dev + (DEV ? (size_t)a.tile * kGpuDev : 0));   // [4][tile]
+    unsigned long long* const s_fit = (unsigned long long*)(s_vg + (size_t)kLocalVG * a.tile);   // [K]
+    int32_t* const s_cnt = (int32_t*)(s_fit + h.K);                     // [tile]
+    int32_t* const s_nodes = s_cnt + a.tile;                            // [K]
+    int32_t* const s_ldev = s_nodes + h.K;                              // [tile]
+    int32_t* const s_stage = s_ldev + a.tile;                           // [2][kLocalChunk]
+    const int s = blockIdx.x, tid = threadIdx.x, N = a.N, K = h.K, W = (N + 63) >> 6;
+    const int32_t* __restrict__ const row = a.placement + (size_t)s * a.P;
+    const uint64_t* __restrict__ const srow = DEV && g.slices ? g.slices + (size_t)s * a.P : nullptr;
+    const int order = a.scen[2 * s + 1];
+    const int lo = L.flags ? L.list_off[order] : 0, hi = L.flags ? L.list_off[order + 1] : 0;
+    for (int k = tid; k < K; k += 256) { s_fit[k] = 0; s_nodes[k] = 0; }
+    for (int t0 = 0; t0 < N; t0 += a.tile) {
+        const int t1 = min(t0 + a.tile, N);
+        usage_accumulate<DEV>(a, row, t0, t1, s_req, s_cnt, &g, srow, s_dev);   // (its first barrier also covers s_fit / s_nodes)
+        local_replay(a, L, row, lo, hi, t0, t1, s_vg, s_ldev, s_stage);
+        for (int k = 0; k < K; ++k) {
+            const ProbeRow& pr = h.probes[k];
+            const uint64_t* __restrict__ const mask = h.probe_mask + (size_t)k * W;
+            const long long gm = DEV ? g.probe_mem[k] : 0;
+            const int gc = DEV ? g.probe_cnt[k] : 0;
+            const int spec = L.flags ? L.probe_spec[k] : -1;
+            long long fit = 0;
+            int nodes = 0;
+            for (int j = t0 + tid; j < t1; j += 256) {
+                if (!((mask[j >> 6] >> (j & 63)) & 1ull) || !usage_holds(a, s, j)) continue;
+                long long cap = node_cap<DEV>(a, h, g, pr, gm, gc, s_req, s_cnt, s_dev, j, t0);
+                if (spec >= 0 && cap > 0) {
+                    LocalState st = local_load(s_vg, s_ldev, a.tile, j - t0);
+                    long long m = 0;
+                    while (m < cap) {
+                        const LocalState was = st;
+                        if (!local_apply(L, L.specs[spec], j, st)) break;
+                        if (same_state(was, st)) { m = cap; break; }
+                        ++m;
+                    }
+                    cap = m;
                 }
                 if (cap > 0) { fit += cap; ++nodes; }
             }
@@ -348,6 +602,31 @@ hipError_t launch_headroom_gpu(const UsageCommon& a, const HeadroomArgs& h, cons
     const size_t lds = (size_t)a.tile * usage_node_bytes(a.nrows, kDevBytes) + (size_t)h.K * 12;
     if (lds > 64 * 1024) return hipErrorInvalidValue;
     hipLaunchKernelGGL(headroom_kernel<true>, dim3((unsigned)S), dim3(256), lds, st, a, h, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_local_usage(const UsageCommon& a, const LocalUsage& l, const LocalUsageOut& o, int n, hipStream_t st) {
+    if (n <= 0 || a.N <= 0 || a.tile <= 0 || !o.vg_req) return hipErrorInvalidValue;
+    if (l.flags && (!l.specs || !l.pod_spec || !l.list || !l.list_off || !l.vg_cnt || !l.vg_cap || !l.vg_init || !l.vg_name || !l.dev_cnt || !l.dev_cap ||
+                    !l.dev_media || !l.dev_init))
+        return hipErrorInvalidValue;
+    const size_t lds = (size_t)a.tile * kLocalBytes + (size_t)kLocalChunk * 8;
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(local_usage_kernel, dim3((unsigned)n), dim3(256), lds, st, a, l, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_headroom_local(const UsageCommon& a, const HeadroomArgs& h, const DevUsage& g, const LocalUsage& l, bool devices, int S,
+                                 hipStream_t st) {
+    if (S <= 0 || a.N <= 0 || a.tile <= 0 || a.nrows < 2 || a.nrows > kUsageRows || h.K < 1 || h.K > kMaxProbes) return hipErrorInvalidValue;
+    if (devices && (!g.gpu_mem || !g.node_cnt || !g.per_dev || !g.init_used || !g.probe_mem || !g.probe_cnt)) return hipErrorInvalidValue;
+    if (l.flags && (!l.specs || !l.pod_spec || !l.list || !l.list_off || !l.vg_cnt || !l.vg_cap || !l.vg_init || !l.vg_name || !l.dev_cnt || !l.dev_cap ||
+                    !l.dev_media || !l.dev_init || !l.probe_spec))
+        return hipErrorInvalidValue;
+    const size_t lds = (size_t)a.tile * usage_node_bytes(a.nrows, kLocalBytes + (devices ? kDevBytes : 0)) + (size_t)h.K * 12 + (size_t)kLocalChunk * 8;
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    if (devices) hipLaunchKernelGGL(headroom_local_kernel<true>, dim3((unsigned)S), dim3(256), lds, st, a, h, g, l);
+    else hipLaunchKernelGGL(headroom_local_kernel<false>, dim3((unsigned)S), dim3(256), lds, st, a, h, DevUsage{}, l);
     return hipGetLastError();
 }
 

@@ -250,9 +250,11 @@ ANNO_POD_LOCAL_STORAGE = "simon/pod-local-storage"
 LVM_SC_NAMES = ("open-local-lvm", "yoda-lvm-default")    # pkg/utils/const.go:5,12
 
 
-def node_local_storage(node: dict):
+def node_local_storage(node: dict, names: bool = False):
     """utils.GetNodeStorage (pkg/utils/utils.go:519-531): None without the annotation, else (vgs, devices) with
-    vgs = [(name, capacity, requested)], devices = [(capacity, media, allocated)]; media 1 = ssd, 2 = hdd, 0 = other."""
+    vgs = [(name, capacity, requested)], devices = [(capacity, media, allocated)]; media 1 = ssd, 2 = hdd, 0 = other.
+    names=True: a third entry, per device (device path, the annotation's own mediaType text) -- what the "Node Local Storage" table
+    prints (pkg/apply/apply.go:433-446) and the problem does not carry."""
     anno = (node["metadata"].get("annotations") or {}).get(ANNO_NODE_LOCAL_STORAGE)
     if anno is None:
         return None
@@ -260,6 +262,8 @@ def node_local_storage(node: dict):
     vgs = [(v["name"], int(v.get("capacity", 0)), int(v.get("requested", 0) or 0)) for v in d.get("vgs") or []]
     devs = [(int(x.get("capacity", 0)), {"ssd": 1, "hdd": 2}.get(x.get("mediaType"), 0), str(x.get("isAllocated", "false")).lower() == "true")
             for x in d.get("devices") or []]
+    if names:
+        return vgs, devs, [(str(x.get("device", "")), str(x.get("mediaType", ""))) for x in d.get("devices") or []]
     return vgs, devs
 
 

@@ -30,14 +30,18 @@ class HipEngine:
     supports_pod_subsets = True               # pod subsets (simon_set_scenario_pods): sweep_apps() batches the combinations of apps
     supports_node_usage = True                # per-node usage and headroom reduced on the device (simon_fetch_node_usage / simon_fetch_headroom)
     supports_gpu_usage = True                 # ... GPU-share devices and the device bound of headroom (simon_fetch_gpu_usage / simon_fetch_headroom_gpu)
+    supports_local_usage = True               # ... Open-Local storage and the storage bound of headroom (simon_fetch_local_usage / simon_fetch_headroom_local)
 
     def __init__(self, device_id: int = 0):
         self.device_id = device_id
 
     def run(self, prob: capi.Problem, scen, orders, want_placement=True, node_ranks=None, want_gpu_slices=False,
             segments=None, present=None, evict=None, pod_present=None, pod_groups=None, headroom_pods=None, usage_of=None,
-            gpu_usage_of=None, headroom_devices=False) -> capi.BatchResult:
-        """gpu_usage_of: scenario indices -- the result carries gpu_usage, GPU memory and stream pods per device at the end of those
+            gpu_usage_of=None, headroom_devices=False, local_usage_of=None, headroom_storage=False) -> capi.BatchResult:
+        """local_usage_of: scenario indices -- the result carries local_usage, the volume groups' requests and the allocated devices per
+        node at the end of those scenarios (simon_fetch_local_usage).  headroom_storage: headroom_pods are answered with the storage bound
+        and, where the problem has GPUs, the device bound (simon_fetch_headroom_local: Open-Local probes become exact).
+        gpu_usage_of: scenario indices -- the result carries gpu_usage, GPU memory and stream pods per device at the end of those
         scenarios (simon_fetch_gpu_usage).  headroom_devices: headroom_pods are answered with the device bound (simon_fetch_headroom_gpu:
         GPU probes become exact).  Either one makes the run record the devices (want_gpu_slices) by itself.
         headroom_pods: pod ids [K] -- the result carries headroom [S][K] (how many more pods like each fit in every scenario) and
@@ -58,8 +62,8 @@ class HipEngine:
             ctx.load_problem(prob)
             if evict is not None:
                 ctx.set_pod_eviction(evict)
-            usage = headroom_pods is not None or usage_of is not None or gpu_usage_of is not None
-            record = want_gpu_slices or gpu_usage_of is not None or (headroom_devices and headroom_pods is not None)
+            usage = headroom_pods is not None or usage_of is not None or gpu_usage_of is not None or local_usage_of is not None
+            record = want_gpu_slices or gpu_usage_of is not None or ((headroom_devices or headroom_storage) and headroom_pods is not None)
             if node_ranks is None and segments is None and present is None and pod_present is None and pod_groups is None and not usage:
                 res = ctx.run_batch(scen, orders, want_placement, want_gpu_slices)
             else:
@@ -75,7 +79,9 @@ class HipEngine:
                 ctx.run_loaded(want_placement or pod_groups is not None or usage, record)
                 res = ctx.fetch(want_placement, want_gpu_slices)
                 if headroom_pods is not None:
-                    res.headroom, _, res.headroom_exact = ctx.fetch_headroom(headroom_pods, devices=bool(headroom_devices))
+                    res.headroom, _, res.headroom_exact = ctx.fetch_headroom(headroom_pods, devices=bool(headroom_devices), storage=bool(headroom_storage))
+                if local_usage_of is not None:
+                    res.local_usage = ctx.fetch_local_usage(local_usage_of)
                 if gpu_usage_of is not None:
                     res.gpu_usage = ctx.fetch_gpu_usage(gpu_usage_of, pods=True)
                 if usage_of is not None:
@@ -530,11 +536,135 @@ def host_gpu_usage(prob: capi.Problem, placement, slices, held, scen_ids=None) -
     return capi.GpuUsage(ids, np.where(live, used, 0), np.where(held[:, :, None], np.where(live, pods, 0), -1).astype(np.int32))
 
 
-def host_headroom(prob: capi.Problem, placement, held, probes, slices=None, devices: bool = False):
+def _local_spec(prob: capi.Problem, cls: int):
+    """The Open-Local volumes of pod class cls (a row of prob.local_specs), or None: no spec, or one without any volume."""
+    if prob.local_spec_of is None or int(prob.local_spec_of[cls]) < 0:
+        return None
+    sp = prob.local_specs[int(prob.local_spec_of[cls])]
+    return sp if int(sp["n_lvm"]) + int(sp["n_ssd"]) + int(sp["n_hdd"]) > 0 else None
+
+
+def _local_allocate(prob: capi.Problem, j: int, req: List[int], alloc: int, sp):
+    """Open-Local's allocation of one pod's volumes on node j whose volume groups have `req` requested and whose devices `alloc` (bit
+    mask) are taken: the (req, alloc) the commit leaves, or None where the filter fails (nothing changes).  ProcessLVMPVCPredicate: a
+    volume whose StorageClass names a VG goes to that group, any other to the group with the smallest free size that holds it (ties:
+    annotation order; the pod's earlier volumes count).  CheckExclusiveResourceMeetsPVCSize, SSD then HDD: free devices ascending by
+    capacity (stable), sizes ascending, two pointers; only a too-small LAST device fails, a shortfall without it takes fewer devices."""
+    if prob.local_flags is None or not int(prob.local_flags[j]) & 1:
+        return None
+    req = list(req)
+    n_lvm = int(sp["n_lvm"])
+    if n_lvm > 0:
+        nvg = int(prob.local_vg_cnt[j])
+        if nvg <= 0:
+            return None
+        cap, name = prob.local_vg_cap[j], prob.local_vg_name[j]
+        for k in range(n_lvm):
+            size, want, pick = int(sp["lvm_size"][k]), int(sp["lvm_vg"][k]), -1
+            if want >= 0:
+                pick = next((v for v in range(nvg) if int(name[v]) == want), -1)
+                if pick < 0 or int(cap[pick]) - req[pick] < size:
+                    return None
+            else:
+                for v in range(nvg):
+                    free = int(cap[v]) - req[v]
+                    if free >= size and (pick < 0 or free < int(cap[pick]) - req[pick]):
+                        pick = v
+                if pick < 0:
+                    return None
+            req[pick] += size
+    if int(sp["n_ssd"]) + int(sp["n_hdd"]) > 0:
+        cnt, media, cap, taken = int(prob.local_dev_cnt[j]), int(prob.local_dev_media[j]), prob.local_dev_cap[j], 0
+        for m, n_pvc, sizes in ((1, int(sp["n_ssd"]), sp["ssd_size"]), (2, int(sp["n_hdd"]), sp["hdd_size"])):
+            free = sorted((d for d in range(cnt) if (media >> (2 * d)) & 3 == m and not (alloc >> d) & 1), key=lambda d: int(cap[d]))
+            if len(free) < n_pvc:
+                return None
+            i = 0
+            for k, d in enumerate(free):
+                if n_pvc == 0:
+                    break
+                if int(cap[d]) < int(sizes[i]):
+                    if k == len(free) - 1:
+                        return None
+                    continue
+                taken |= 1 << d
+                i += 1
+                if i == n_pvc:
+                    break
+        alloc |= taken
+    return req, alloc
+
+
+def _local_states(prob: capi.Problem, row, order):
+    """Per pool node (vg_req [MAX_VG] list, dev_alloc) after the scheduled storage pods of one placement row, applied in stream order."""
+    N = prob.n_nodes
+    ivg = np.zeros((N, capi.MAX_VG), np.int64) if prob.init_vg_req is None else np.asarray(prob.init_vg_req, np.int64).reshape(N, capi.MAX_VG)
+    idev = np.zeros(N, np.int64) if prob.init_dev_alloc is None else np.asarray(prob.init_dev_alloc, np.int64)
+    state = [([int(x) for x in ivg[j]], int(idev[j])) for j in range(N)]
+    if prob.local_flags is None or prob.local_spec_of is None:
+        return state
+    for p in np.asarray(order).tolist():
+        j = int(row[p])
+        if j < 0 or (prob.preset_node is not None and int(prob.preset_node[p]) >= 0):
+            continue                                           # unscheduled, gated, or bound by Spec.NodeName: never reaches LocalPlugin.Bind
+        sp = _local_spec(prob, 0 if prob.pod_class is None else int(prob.pod_class[p]))
+        if sp is None:
+            continue
+        got = _local_allocate(prob, j, state[j][0], state[j][1], sp)
+        if got is not None:                                    # (a placed pod passed the filter; otherwise it commits nothing)
+            state[j] = got
+    return state
+
+
+def host_local_usage(prob: capi.Problem, placement, held, orders, scen, scen_ids=None) -> capi.LocalUsage:
+    """capi.Context.fetch_local_usage on the host: the stream of every listed scenario replayed node by node from placement rows [S][P],
+    the nodes every scenario holds (bool [S][N]), the orders [n_orders][P] and the scenarios' (n_nodes, order_id) pairs."""
+    held = np.asarray(held, bool)
+    ids = np.arange(len(held), dtype=np.int32) if scen_ids is None else np.asarray(scen_ids, np.int32)
+    placement, orders, scen = np.asarray(placement), np.asarray(orders).reshape(-1, prob.n_pods), capi.scenarios_array(scen)
+    N = prob.n_nodes
+    vg, dev = np.zeros((len(ids), N, capi.MAX_VG), np.int64), np.zeros((len(ids), N), np.int32)
+    for i, s in enumerate(ids.tolist()):
+        dev[i] = np.where(held[s], 0, -1)
+        if prob.local_flags is None:
+            continue
+        state = _local_states(prob, placement[s], orders[int(scen[s][1])])
+        for j in np.flatnonzero(held[s] & ((np.asarray(prob.local_flags) & 1) != 0)).tolist():
+            n = int(prob.local_vg_cnt[j])
+            vg[i, j, :n], dev[i, j] = state[j][0][:n], state[j][1]
+    return capi.LocalUsage(ids, vg, dev)
+
+
+def _local_caps(prob: capi.Problem, sp, state, cap):
+    """cap_local per node under the caps so far [N]: consecutive copies of spec sp that allocate on top of each other from the node's
+    end state; a copy that changes nothing ends the count at the cap so far."""
+    out = np.zeros(len(cap), np.int64)
+    for j in np.flatnonzero(cap > 0).tolist():
+        st, m = state[j], 0
+        while m < int(cap[j]):
+            got = _local_allocate(prob, j, st[0], st[1], sp)
+            if got is None:
+                break
+            if got == (list(st[0]), st[1]):
+                m = int(cap[j])
+                break
+            st, m = got, m + 1
+        out[j] = m
+    return out
+
+
+def host_headroom(prob: capi.Problem, placement, held, probes, slices=None, devices: bool = False, storage: bool = False, orders=None,
+                  scen=None):
     """capi.Context.fetch_headroom on the host: (fit [S][K] int64, fit_nodes [S][K] int32, exact [K] bool).  devices=True: with the
-    device bound of simon_fetch_headroom_gpu, from the recorded devices `slices` [S][P]."""
+    device bound of simon_fetch_headroom_gpu, from the recorded devices `slices` [S][P].  storage=True: simon_fetch_headroom_local --
+    the device bound where the problem has GPUs and the Open-Local bound, from the streams replayed in `orders` / `scen` order."""
     held = np.asarray(held, bool)
     S, N = held.shape
+    if storage:
+        devices = prob.gpu_cnt is not None or prob.gpu_mem is not None
+        if prob.local_flags is not None:
+            o_, s_ = np.asarray(orders).reshape(-1, prob.n_pods), capi.scenarios_array(scen)
+            states = [_local_states(prob, np.asarray(placement)[s], o_[int(s_[s][1])]) for s in range(S)]
     req, cnt = _usage_sums(prob, placement, held)
     if devices:
         dev_used = host_gpu_usage(prob, placement, slices, np.ones_like(held)).dev_used
@@ -566,27 +696,33 @@ def host_headroom(prob: capi.Problem, placement, held, probes, slices=None, devi
             idle *= np.arange(capi.MAX_GPU_DEV)[None, None, :] < g_cnt[None, :, None]
             c = min(of(prob.pod_gpu_cnt, p), 64)
             cap = np.minimum(cap, idle.sum(2) // c) if c > 0 else np.zeros_like(cap)
+        sp = _local_spec(prob, cls) if storage and prob.local_flags is not None else None
+        if sp is not None:
+            cap = np.stack([np.minimum(cap[s], _local_caps(prob, sp, states[s], cap[s])) for s in range(S)])
         fit[:, k], nodes[:, k] = cap.sum(1), (cap > 0).sum(1)
         none = lambda off: prob.term_topo_key is None or len(prob.term_topo_key) == 0 or off is None or off[cls + 1] == off[cls]   # noqa: E731
         exact[k] = ((bound or (not of(prob.gpu_mem, p) and not of(prob.pod_gpu_cnt, p) and not of(prob.gpu_index, p))) and of(prob.pin_node, p, -1) < 0
                     and of(prob.preset_node, p, -1) < 0 and all(none(o) for o in (prob.match_off, prob.anti_off, prob.port_off, prob.aff_off, prob.spread_hard_off))
-                    and (prob.local_spec_of is None or int(prob.local_spec_of[cls]) < 0))
+                    and (storage or prob.local_spec_of is None or int(prob.local_spec_of[cls]) < 0))
     return fit, nodes, exact
 
 
-def _on_device(engine, devices: bool) -> bool:
-    """The engine reduces what the sweep asked for itself (with devices=True it needs both pairs of calls)."""
-    return getattr(engine, "supports_node_usage", False) and (not devices or getattr(engine, "supports_gpu_usage", False))
+def _on_device(engine, devices: bool, storage: bool = False) -> bool:
+    """The engine reduces what the sweep asked for itself (with devices=True it needs both pairs of calls, with storage=True the
+    Open-Local pair as well)."""
+    return (getattr(engine, "supports_node_usage", False) and (not devices or getattr(engine, "supports_gpu_usage", False))
+            and (not storage or getattr(engine, "supports_local_usage", False)))
 
 
-def _usage_kw(engine, probes, node_table: bool, S: int, devices: bool = False) -> dict:
-    """engine.run's keywords for a batch whose sweep asked for headroom / the node table / the devices (nothing for an engine without
-    the calls)."""
-    if not _on_device(engine, devices):
+def _usage_kw(engine, probes, node_table: bool, S: int, devices: bool = False, storage: bool = False) -> dict:
+    """engine.run's keywords for a batch whose sweep asked for headroom / the node table / the devices / the storage (nothing for an
+    engine without the calls)."""
+    if not _on_device(engine, devices, storage):
         return {}
     ids = np.arange(S, dtype=np.int32)
     return {**({"headroom_pods": probes} if probes is not None else {}), **({"usage_of": ids} if node_table else {}),
-            **({"gpu_usage_of": ids, "headroom_devices": True} if devices else {})}
+            **({"gpu_usage_of": ids, "headroom_devices": True} if devices else {}),
+            **({"local_usage_of": ids, "headroom_storage": True} if storage else {})}
 
 
 def _node_rows(nodes: List[dict], prob: capi.Problem, usage: capi.NodeUsage, i: int, gpu: Optional[capi.GpuUsage] = None) -> List[dict]:
@@ -611,42 +747,76 @@ def _gpu_rows(nodes: List[dict], prob: capi.Problem, gpu: capi.GpuUsage, i: int)
             for j in np.flatnonzero((gpu.dev_pods[i, :, 0] >= 0) & (cnt > 0)).tolist()]
 
 
-def _usage_fill(engine, out, nodes, prob, held, probes, node_table: bool, warn, what: str, devices: bool = False):
+def _storage_rows(nodes: List[dict], prob: capi.Problem, local: capi.LocalUsage, i: int) -> List[dict]:
+    """The "Node Local Storage" table (pkg/apply/apply.go:412-448) for the annotated nodes scenario row i of `local` holds, in pool order:
+    per volume group {node, kind "VG", name, allocatable, requests, pct = int(float(requests) / float(allocatable) * 100)}, then per
+    exclusive device {node, kind "Device(<mediaType>)", name, allocatable, used}.  Group and device names and the media texts, which the
+    problem does not carry, come from flatten.node_local_storage(names=True) of the node -- the parse flatten itself builds the
+    problem from, so group v / device d there is group v / device d here and the group names are the strings flatten interned
+    (Flat.info["vg_names"]).  A problem whose pods ask for no volume carries no Open-Local arrays: its rows show the state that parse
+    gives, which no pod changes."""
+    rows = []
+    for j in np.flatnonzero(local.dev_alloc[i] >= 0).tolist():
+        st = fl.node_local_storage(nodes[j], names=True)
+        if st is None:
+            continue
+        vgs, devs, texts = st
+        name = nodes[j]["metadata"]["name"]
+        for v, (vg, cap, req) in enumerate(vgs):
+            req = req if prob.local_flags is None else int(local.vg_req[i, j, v])
+            rows.append({"node": name, "kind": "VG", "name": vg, "allocatable": cap, "requests": req, "pct": occupancy_pct(req, cap)})
+        for k, ((cap, _, taken), (dev, media)) in enumerate(zip(devs, texts)):
+            used = bool(taken) if prob.local_flags is None else bool((int(local.dev_alloc[i, j]) >> k) & 1)
+            rows.append({"node": name, "kind": f"Device({media})", "name": dev, "allocatable": cap, "used": used})
+    return rows
+
+
+def _usage_fill(engine, out, nodes, prob, held, probes, node_table: bool, warn, what: str, devices: bool = False, storage: bool = False,
+                orders=None, scen=None):
     """(headroom [S][K] lists, headroom_exact [K], node_table [S] lists of rows) of one engine batch -- None where not asked for: from the
     engine's own reduction, or, for an engine without supports_node_usage, the same figures on the host from the placement rows (warns).
     The fourth entry is gpu_table [S] lists of rows (None without devices); with devices=True headroom carries the device bound and the node rows the GPU columns (an
-    engine without supports_gpu_usage: on the host from the placement rows and gpu_slices, warns)."""
-    if probes is None and not node_table and not devices:
-        return None, None, None, None
-    hr, hx, usage, gpu = out.headroom, out.headroom_exact, out.node_usage, out.gpu_usage
-    if not _on_device(engine, devices):
+    engine without supports_gpu_usage: on the host from the placement rows and gpu_slices, warns).  The fifth entry is storage_table [S]
+    lists of rows (None without storage); with storage=True headroom carries the Open-Local bound, replayed in the batch's `orders` /
+    `scen` order (an engine without supports_local_usage: on the host, warns)."""
+    if probes is None and not node_table and not devices and not storage:
+        return None, None, None, None, None
+    hr, hx, usage, gpu, local = out.headroom, out.headroom_exact, out.node_usage, out.gpu_usage, out.local_usage
+    if not _on_device(engine, devices, storage):
         import warnings
-        lacks = "supports_node_usage" if not getattr(engine, "supports_node_usage", False) else "supports_gpu_usage"
+        lacks = ("supports_node_usage" if not getattr(engine, "supports_node_usage", False) else
+                 "supports_gpu_usage" if devices and not getattr(engine, "supports_gpu_usage", False) else "supports_local_usage")
         warnings.warn(f"{what} computes headroom / the node table on the host from the placement matrix (the engine has no {lacks})", warn, stacklevel=4)
         if probes is not None:
-            hr, _, hx = host_headroom(prob, out.placement, held, probes, out.gpu_slices, devices)
+            hr, _, hx = host_headroom(prob, out.placement, held, probes, out.gpu_slices, devices, storage, orders, scen)
         if node_table:
             usage = host_node_usage(prob, out.placement, held)
         if devices:
             gpu = host_gpu_usage(prob, out.placement, out.gpu_slices, held)
+        if storage:
+            local = host_local_usage(prob, out.placement, held, orders, scen)
     return (None if probes is None else np.asarray(hr).tolist(), None if probes is None else [bool(x) for x in hx],
             [_node_rows(nodes, prob, usage, i, gpu if devices else None) for i in range(len(held))] if node_table else None,
-            [_gpu_rows(nodes, prob, gpu, i) for i in range(len(held))] if devices else None)
+            [_gpu_rows(nodes, prob, gpu, i) for i in range(len(held))] if devices else None,
+            [_storage_rows(nodes, prob, local, i) for i in range(len(held))] if storage else None)
 
 
-def _usage_each(flat: fl.Flat, nodes: List[dict], out, headroom, node_table: bool, pool_order: Sequence[str], devices: bool = False):
+def _usage_each(flat: fl.Flat, nodes: List[dict], out, headroom, node_table: bool, pool_order: Sequence[str], devices: bool = False,
+                storage: bool = False):
     """_usage_fill for ONE scenario that ran as its own problem (the sweeps' fallback roads; `nodes` = its nodes in the problem's order,
-    pool_order = their names in pool order): on the host from its placement row (devices: and its gpu_slices row); always four entries,
-    the last the scenario's gpu_table (None without devices).  Probes are named (namespace, name) there: a pod id belongs to the batch's
+    pool_order = their names in pool order): on the host from its placement row (devices: and its gpu_slices row); always five
+    entries, the fourth the scenario's gpu_table (None without devices), the fifth its storage_table (None without storage; these
+    roads feed the pods in the problem's own order).  Probes are named (namespace, name) there: a pod id belongs to the batch's
     stream, which these roads do not build."""
-    hr = hx = tab = gtab = None
+    hr = hx = tab = gtab = stab = None
     held = np.ones((1, len(nodes)), bool)
-    sl = out.gpu_slices[:1] if devices and out.gpu_slices is not None else None
+    sl = out.gpu_slices[:1] if (devices or storage) and out.gpu_slices is not None else None
+    order, one = np.arange(flat.problem.n_pods, dtype=np.int32)[None, :], np.array([[len(nodes), 0]], np.int32)
     gpu = host_gpu_usage(flat.problem, out.placement[:1], sl, held) if devices else None
     if headroom is not None:
         if any(isinstance(h, (int, np.integer)) for h in headroom):
             raise ValueError("the scenarios run one by one, each with its own pod stream: name the headroom probes by (namespace, name)")
-        fit, _, ex = host_headroom(flat.problem, out.placement[:1], held, probe_ids(flat, headroom), sl, devices)
+        fit, _, ex = host_headroom(flat.problem, out.placement[:1], held, probe_ids(flat, headroom), sl, devices, storage, order, one)
         hr, hx = fit[0].tolist(), [bool(x) for x in ex]
     if node_table:
         rows = {r["node"]: r for r in _node_rows(nodes, flat.problem, host_node_usage(flat.problem, out.placement[:1], held), 0, gpu)}
@@ -654,7 +824,10 @@ def _usage_each(flat: fl.Flat, nodes: List[dict], out, headroom, node_table: boo
     if devices:
         rows = {r["node"]: r for r in _gpu_rows(nodes, flat.problem, gpu, 0)}
         gtab = [rows[n] for n in pool_order if n in rows]
-    return hr, hx, tab, gtab
+    if storage:
+        rows = _storage_rows(nodes, flat.problem, host_local_usage(flat.problem, out.placement[:1], held, order, one), 0)
+        stab = [r for n in pool_order for r in rows if r["node"] == n]
+    return hr, hx, tab, gtab, stab
 
 
 def _and_exact(rows):
@@ -684,6 +857,7 @@ class SweepResult:
     headroom_exact: Optional[List[bool]] = None
     node_table: Optional[List[List[dict]]] = None
     gpu_table: Optional[List[List[dict]]] = None     # devices=True: per scenario the "GPU Node Resource" table (pkg/apply/apply.go:456-500): one row per GPU node it holds -- node, model, devices [{id, used, total, pods}]
+    storage_table: Optional[List[List[dict]]] = None   # storage=True: per scenario the "Node Local Storage" table (pkg/apply/apply.go:401-455): per annotated node it holds, a row per volume group {node, kind, name, allocatable, requests, pct} and per exclusive device {node, kind, name, allocatable, used}
 
 
 def occupancy_pct(used: int, alloc: int) -> int:
@@ -802,7 +976,7 @@ def _sweep_reasons(engine, batch: "SweepBatch", out, replay, same_stream) -> Lis
 @_gc_paused
 def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node: Optional[dict], counts: Sequence[int],
           engine=None, max_cpu: int = 100, max_mem: int = 100, max_vg: int = 100, reasons: bool = False, headroom=None,
-          node_table: bool = False, devices: bool = False) -> SweepResult:
+          node_table: bool = False, devices: bool = False, storage: bool = False) -> SweepResult:
     """The add-nodes loop of Applier.Run (pkg/apply/apply.go:203-259) as ONE scenario batch: scenario k = the cluster plus
     counts[k] clones of new_node (utils.NewFakeNodes); the answer is the smallest count with no unscheduled pod whose
     occupancy satisfies MaxCPU / MaxMemory (satisfyResourceSetting, :689-775).  reasons=True: SweepResult.unscheduled_pods lists, per
@@ -816,7 +990,12 @@ def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node:
     devices still hold, and headroom_exact is true for it), the result gains gpu_table (per scenario the "GPU Node Resource" table,
     :456-500: one row per GPU node it holds, per device used / total / pods) and node_table rows gain gpu_mem_allocatable /
     gpu_mem_requests -- reduced on the device (simon_fetch_gpu_usage / simon_fetch_headroom_gpu); an engine without supports_gpu_usage
-    and the one-by-one roads compute the same figures on the host from the placement rows and gpu_slices (the same fallback warning)."""
+    and the one-by-one roads compute the same figures on the host from the placement rows and gpu_slices (the same fallback warning).
+    storage=True (Open-Local clusters): headroom carries the storage bound (a probe whose pod asks for local volumes is bounded by what
+    the nodes' volume groups and exclusive devices still hold, and headroom_exact is true for it; on a GPU-share cluster the device bound
+    applies as well) and the result gains storage_table (per scenario the "Node Local Storage" table, :401-455) -- replayed on the device
+    in stream order (simon_fetch_local_usage / simon_fetch_headroom_local); an engine without supports_local_usage and the one-by-one
+    roads replay on the host (host_local_usage; the same fallback warning).  storage=False leaves every result as it was."""
     engine = engine or HipEngine()
     counts = list(counts)
     if max_cpu > 100 or max_cpu < 0:
@@ -831,16 +1010,16 @@ def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node:
             raise
         # ImageLocality scores depend on the cluster size: an engine without the per-size image scores runs every size as its own
         # problem with its own static scores (and an engine without per-scenario node ranks runs a pool of several zones size by size)
-        return _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg, reasons, headroom, node_table, devices)
+        return _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg, reasons, headroom, node_table, devices, storage)
     flat, scen, orders, node_ranks, pool, base = batch.flat, batch.scen, batch.orders, batch.node_ranks, batch.pool, batch.base
     want_gpu = flat.problem.gpu_mem is not None
     kw = {"want_gpu_slices": True} if want_gpu else {}
     if node_ranks is not None:
         kw["node_ranks"] = node_ranks
     probes = probe_ids(flat, headroom)
-    out = engine.run(flat.problem, scen, orders, **kw, **_usage_kw(engine, probes, node_table, len(scen), devices))
-    hr, hx, tab, gtab = _usage_fill(engine, out, pool, flat.problem, np.arange(len(pool))[None, :] < scen[:, :1], probes, node_table,
-                                    UsageFallbackWarning, "sweep", devices)
+    out = engine.run(flat.problem, scen, orders, **kw, **_usage_kw(engine, probes, node_table, len(scen), devices, storage))
+    hr, hx, tab, gtab, stab = _usage_fill(engine, out, pool, flat.problem, np.arange(len(pool))[None, :] < scen[:, :1], probes, node_table,
+                                          UsageFallbackWarning, "sweep", devices, storage, orders, scen)
     pc, pm = np.cumsum(flat.problem.alloc_cpu), np.cumsum(flat.problem.alloc_mem)
     cpu_pct = [occupancy_pct(int(out.used_cpu[s]), int(pc[scen[s, 0] - 1])) for s in range(len(counts))]
     mem_pct = [occupancy_pct(int(out.used_mem[s]) * 1000, int(pm[scen[s, 0] - 1]) * 1000) for s in range(len(counts))]
@@ -868,14 +1047,14 @@ def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node:
                 return _unscheduled_list(flat, out.placement[s], {})
         why = _sweep_reasons(engine, batch, out, replay, lambda s: _same_stream(cluster, apps, batch, out, s))
     return SweepResult(counts, out.unscheduled.tolist(), cpu_pct, mem_pct, None if best is None else counts[best], result, vg_pct,
-                       [_risk(out, s) for s in range(len(counts))], why, hr, hx, tab, gtab)
+                       [_risk(out, s) for s in range(len(counts))], why, hr, hx, tab, gtab, stab)
 
 
 def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg, reasons: bool = False, headroom=None,
-                    node_table: bool = False, devices: bool = False) -> SweepResult:
+                    node_table: bool = False, devices: bool = False, storage: bool = False) -> SweepResult:
     base = list(cluster.get("Node", []))
-    hrs, hxs, tabs, gtabs = [], [], [], []
-    if headroom is not None or node_table or devices:
+    hrs, hxs, tabs, gtabs, stabs = [], [], [], [], []
+    if headroom is not None or node_table or devices or storage:
         import warnings
         warnings.warn("sweep runs the sizes one by one and computes headroom / the node table on the host from each placement row",
                       UsageFallbackWarning, stacklevel=3)
@@ -895,7 +1074,7 @@ def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, m
                          **({"want_gpu_slices": True} if want_gpu else {}))
         uns.append(int(out.unscheduled[0]))
         risks.append(_risk(out, 0))
-        for acc, v in zip((hrs, hxs, tabs, gtabs), _usage_each(flat, nodes, out, headroom, node_table, arrival, devices)):
+        for acc, v in zip((hrs, hxs, tabs, gtabs, stabs), _usage_each(flat, nodes, out, headroom, node_table, arrival, devices, storage)):
             acc.append(v)
         if reasons:
             texts = {}
@@ -920,7 +1099,8 @@ def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, m
         res.node_status = [{"node": _gpu_node_status(n, per_dev[j]) if j in per_dev else _node_out(n), "pods": per_node[j]} for j, n in enumerate(nodes)]
         result = res
     return SweepResult(list(counts), uns, cpu_pct, mem_pct, None if best is None else counts[best], result, vg_pct, risks, why,
-                       hrs if headroom is not None else None, _and_exact(hxs), tabs if node_table else None, gtabs if devices else None)
+                       hrs if headroom is not None else None, _and_exact(hxs), tabs if node_table else None, gtabs if devices else None,
+                       stabs if storage else None)
 
 
 @dataclass
@@ -942,6 +1122,7 @@ class MixSweepResult:
     headroom_exact: Optional[List[bool]] = None     # per probe: the scheduler's own count (else an upper bound)
     node_table: Optional[List[List[dict]]] = None   # node_table=True: per mix, reportClusterInfo's table over its own nodes, pool order
     gpu_table: Optional[List[List[dict]]] = None     # devices=True: per scenario the "GPU Node Resource" table (pkg/apply/apply.go:456-500): one row per GPU node it holds -- node, model, devices [{id, used, total, pods}]
+    storage_table: Optional[List[List[dict]]] = None   # storage=True: per scenario the "Node Local Storage" table (pkg/apply/apply.go:401-455): per annotated node it holds, a row per volume group {node, kind, name, allocatable, requests, pct} and per exclusive device {node, kind, name, allocatable, used}
 
 
 class MixFallbackWarning(UserWarning):
@@ -1009,7 +1190,7 @@ def _caps(max_cpu, max_mem, max_vg):
 @_gc_paused
 def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_nodes: Sequence[dict], counts: Sequence[Sequence[int]],
               costs: Optional[Sequence[float]] = None, engine=None, max_cpu: int = 100, max_mem: int = 100, max_vg: int = 100,
-              reasons: bool = False, headroom=None, node_table: bool = False, devices: bool = False) -> MixSweepResult:
+              reasons: bool = False, headroom=None, node_table: bool = False, devices: bool = False, storage: bool = False) -> MixSweepResult:
     """The add-nodes search over mixes of several new-node types (Applier.Run clones ONE template, pkg/apply/apply.go:155-166): mix
     (c_1 .. c_T) = Simulate(cluster + NewFakeNodes(type_1, c_1) + ... + NewFakeNodes(type_T, c_T)), the grid = the Cartesian product of
     counts (one iterable per type).  The answer is the mix of least total cost sum_t costs[t] * c_t (default 1 per node) with no
@@ -1019,8 +1200,8 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
     the segmented kernel does not take run every mix as its own problem.  reasons=True: MixSweepResult.unscheduled_pods lists, per mix,
     the pods that stay unscheduled with their FitError text, as sweep() does per count -- every failing mix of the batch explained in
     one engine.explain_own_batch call (engines without it, and mixes whose pod stream is not the pool's: simulate() of the mix).
-    headroom=[...] / node_table=True / devices=True: as sweep() takes them, per mix (MixSweepResult.headroom / headroom_exact / node_table /
-    gpu_table)."""
+    headroom=[...] / node_table=True / devices=True / storage=True: as sweep() takes them, per mix (MixSweepResult.headroom /
+    headroom_exact / node_table / gpu_table / storage_table)."""
     import itertools
     engine = engine or HipEngine()
     new_nodes = list(new_nodes)
@@ -1039,7 +1220,7 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
     mixes = [tuple(int(k) for k in m) for m in itertools.product(*counts)]
     caps = _caps(max_cpu, max_mem, max_vg)
     if not getattr(engine, "supports_scenario_segments", False):
-        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, "the engine has no pool segments", reasons, headroom, node_table, devices)
+        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, "the engine has no pool segments", reasons, headroom, node_table, devices, storage)
     base = list(cluster.get("Node", []))
     if not base and any(sum(m) == 0 for m in mixes):   # (a scenario holds one node at least: simon_set_scenario_segments, and flatten)
         raise ValueError("sweep_mix: a cluster without nodes needs at least one new node in every mix")
@@ -1060,7 +1241,7 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
         if "ImageLocality" not in str(e):
             raise
         return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps,
-                                  "nodes list the pods' images: ImageLocality depends on the node set", reasons, headroom, node_table, devices)
+                                  "nodes list the pods' images: ImageLocality depends on the node set", reasons, headroom, node_table, devices, storage)
     scen = np.stack([len(base) + cnt.sum(1), np.zeros(len(mixes), np.int64)], 1).astype(np.int32)
     orders = np.arange(len(pods), dtype=np.int32)[None, :]
     want_gpu = flat.problem.gpu_mem is not None
@@ -1069,12 +1250,12 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
         kw["node_ranks"] = node_ranks
     probes = probe_ids(flat, headroom)
     try:
-        out = engine.run(flat.problem, scen, orders, segments=(seg_start, cnt), **kw, **_usage_kw(engine, probes, node_table, len(scen), devices))
+        out = engine.run(flat.problem, scen, orders, segments=(seg_start, cnt), **kw, **_usage_kw(engine, probes, node_table, len(scen), devices, storage))
     except capi.SimonError as e:
         if getattr(e, "code", None) != capi.ESTATE:
             raise
         # a problem on the all-feature kernel (prefix scenarios only): every mix as its own problem
-        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, f"the engine refused the segmented batch: {e}", reasons, headroom, node_table, devices)
+        return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, f"the engine refused the segmented batch: {e}", reasons, headroom, node_table, devices, storage)
     # satisfyResourceSetting over each mix's own nodes: the fixed nodes + a prefix of every segment
     pr = flat.problem
     vg_cap = None
@@ -1104,8 +1285,8 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
         why = _mix_reasons(engine, cluster, apps, flat, pool, len(base), present, scen, orders, node_ranks, (seg_start, cnt), out)
     return MixSweepResult(mixes, out.unscheduled.tolist(), cpu_pct, mem_pct, vg_pct, [_risk(out, s) for s in range(len(mixes))],
                           None if best is None else mixes[best], None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result,
-                          unscheduled_pods=why, **dict(zip(("headroom", "headroom_exact", "node_table", "gpu_table"), _usage_fill(
-                              engine, out, pool, flat.problem, present, probes, node_table, MixFallbackWarning, "sweep_mix", devices))))
+                          unscheduled_pods=why, **dict(zip(("headroom", "headroom_exact", "node_table", "gpu_table", "storage_table"), _usage_fill(
+                              engine, out, pool, flat.problem, present, probes, node_table, MixFallbackWarning, "sweep_mix", devices, storage, orders, scen))))
 
 
 def _mix_reasons(engine, cluster, apps, flat, pool, n_base, present, scen, orders, node_ranks, segments, out) -> List[List[dict]]:
@@ -1149,14 +1330,14 @@ def _mix_reasons(engine, cluster, apps, flat, pool, n_base, present, scen, order
 
 
 def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why: str, reasons: bool = False, headroom=None,
-                       node_table: bool = False, devices: bool = False) -> MixSweepResult:
+                       node_table: bool = False, devices: bool = False, storage: bool = False) -> MixSweepResult:
     """Every mix as its own Simulate(): cluster + each type's clones in type order, canonical nodeTree order."""
     import warnings
     warnings.warn(f"sweep_mix runs {len(mixes)} mixes one by one ({why})", MixFallbackWarning, stacklevel=3)
     base = list(cluster.get("Node", []))
     uns, cpu_pct, mem_pct, vg_pct, risks, kept = [], [], [], [], [], {}
     lists: List[List[dict]] = []
-    hrs, hxs, tabs, gtabs = [], [], [], []
+    hrs, hxs, tabs, gtabs, stabs = [], [], [], [], []
     for s, mix in enumerate(mixes):
         nodes = base + [n for nodes in mix_fake_nodes(new_nodes, mix) for n in nodes]
         pods, _ = build_stream(cluster, apps, nodes, len(nodes))
@@ -1169,7 +1350,7 @@ def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why
                          **({"want_gpu_slices": True} if want_gpu else {}))
         uns.append(int(out.unscheduled[0]))
         risks.append(_risk(out, 0))
-        for acc, v in zip((hrs, hxs, tabs, gtabs), _usage_each(flat, nodes, out, headroom, node_table, arrival, devices)):
+        for acc, v in zip((hrs, hxs, tabs, gtabs, stabs), _usage_each(flat, nodes, out, headroom, node_table, arrival, devices, storage)):
             acc.append(v)
         if reasons:
             texts = {}
@@ -1196,7 +1377,8 @@ def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why
     return MixSweepResult(mixes, uns, cpu_pct, mem_pct, vg_pct, risks, None if best is None else mixes[best],
                           None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result, batched=False, fallback=why,
                           unscheduled_pods=lists, headroom=hrs if headroom is not None else None, headroom_exact=_and_exact(hxs),
-                          node_table=tabs if node_table else None, gpu_table=gtabs if devices else None)
+                          node_table=tabs if node_table else None, gpu_table=gtabs if devices else None,
+                          storage_table=stabs if storage else None)
 
 
 @dataclass
@@ -1224,6 +1406,7 @@ class FailureSweepResult:
     headroom_exact: Optional[List[bool]] = None
     node_table: Optional[List[List[dict]]] = None
     gpu_table: Optional[List[List[dict]]] = None     # devices=True: per scenario the "GPU Node Resource" table (pkg/apply/apply.go:456-500): one row per GPU node it holds -- node, model, devices [{id, used, total, pods}]
+    storage_table: Optional[List[List[dict]]] = None   # storage=True: per scenario the "Node Local Storage" table (pkg/apply/apply.go:401-455): per annotated node it holds, a row per volume group {node, kind, name, allocatable, requests, pct} and per exclusive device {node, kind, name, allocatable, used}
 
     @property
     def removable(self) -> List[int]:
@@ -1383,7 +1566,7 @@ def _failure_replay(cluster, apps, names, engine, reschedule=False) -> List[dict
 @_gc_paused
 def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], domains="node", engine=None, max_cpu: int = 100,
                    max_mem: int = 100, max_vg: int = 100, reasons: bool = False, batch_scenarios: int = 4096,
-                   reschedule=False, headroom=None, node_table: bool = False, devices: bool = False) -> FailureSweepResult:
+                   reschedule=False, headroom=None, node_table: bool = False, devices: bool = False, storage: bool = False) -> FailureSweepResult:
     """The node-failure what-if sweep: does the cluster still hold its workloads when a node, a rack or a zone is lost?  Scenario 0 is
     the whole cluster; scenario d + 1 is simulate() of the cluster without failure domain d (failure_domains: "node", a label key, or
     lists of node names), without the pods bound to its nodes and without their DaemonSet pods (cluster_without) -- lost pods are
@@ -1400,7 +1583,7 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     where it is not.  `evicted` / `evicted_unscheduled` count them per domain, `removable` lists the domains the cluster survives.
     Pods that a workload TEMPLATE binds to a node stay Unsupported (their controller would bind the new pod to the same node); an
     engine without supports_pod_eviction and evicted pods that carry a gpu-index annotation run scenario by scenario.
-    headroom=[...] / node_table=True / devices=True: as sweep() takes them, per SCENARIO ([0] the whole cluster, [d + 1] without domain d)."""
+    headroom=[...] / node_table=True / devices=True / storage=True: as sweep() takes them, per SCENARIO ([0] the whole cluster, [d + 1] without domain d)."""
     engine = engine or HipEngine()
     reschedule = reschedule or False
     evictable({}, reschedule or "all")
@@ -1413,7 +1596,7 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     if not present.any(axis=1).all():
         raise ValueError("sweep_failures: a failure domain holds every node of the cluster")
     caps = _caps(max_cpu, max_mem, max_vg)
-    each = lambda why: _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why, reschedule, headroom, node_table, devices)   # noqa: E731
+    each = lambda why: _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why, reschedule, headroom, node_table, devices, storage)   # noqa: E731
     if not getattr(engine, "supports_scenario_subsets", False):
         return each("the engine has no node subsets")
     if reschedule and not getattr(engine, "supports_pod_eviction", False):
@@ -1454,6 +1637,7 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     rows, where = [], []
     probes = probe_ids(flat, headroom)
     hr, hx, tab, gtab = ([] if headroom is not None else None), None, ([] if node_table else None), ([] if devices else None)
+    stab = [] if storage else None
     told: Dict[int, List[dict]] = {}             # reasons: scenario -> its unscheduled_pods, from the batch's own explain
     for lo in range(0, len(present), max(1, int(batch_scenarios))):
         part = present[lo:lo + max(1, int(batch_scenarios))]
@@ -1465,12 +1649,15 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
             if evict.any():
                 kw["evict"] = evict
             out = engine.run(pr, scen, orders, present=(part, zone if 1 < len(zid) <= capi.MAX_ZONES else None), **kw,
-                             **_usage_kw(engine, probes, node_table, len(scen), devices))
+                             **_usage_kw(engine, probes, node_table, len(scen), devices, storage))
         except capi.SimonError as e:
             if getattr(e, "code", None) != capi.ESTATE:
                 raise
             return each(f"the engine refused the node-subset batch: {e}")
-        h1, x1, t1, g1 = _usage_fill(engine, out, pool, pr, part, probes, node_table, FailureFallbackWarning, "sweep_failures", devices)
+        h1, x1, t1, g1, s1 = _usage_fill(engine, out, pool, pr, part, probes, node_table, FailureFallbackWarning, "sweep_failures", devices, storage,
+                                         orders, scen)
+        if s1 is not None:
+            stab += s1
         if g1 is not None:
             gtab += g1
         if h1 is not None:
@@ -1510,17 +1697,17 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
         preset = np.asarray(pr.preset_node)
         moved = [np.flatnonzero(evict & ~present[d + 1][np.maximum(preset, 0)]) for d in range(len(doms))]
     res = _failure_result(doms, rows, caps, where, why, True, None, moved)
-    res.headroom, res.headroom_exact, res.node_table, res.gpu_table = hr, hx, tab, gtab
+    res.headroom, res.headroom_exact, res.node_table, res.gpu_table, res.storage_table = hr, hx, tab, gtab, stab
     return res
 
 
 def _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why: str, reschedule=False, headroom=None,
-                         node_table: bool = False, devices: bool = False) -> FailureSweepResult:
+                         node_table: bool = False, devices: bool = False, storage: bool = False) -> FailureSweepResult:
     """Every scenario as its own Simulate(): the cluster without the domain, canonical nodeTree order."""
     import warnings
     warnings.warn(f"sweep_failures runs {len(doms) + 1} scenarios one by one ({why})", FailureFallbackWarning, stacklevel=3)
     rows, where, lists, moved = [], [], [], []
-    hrs, hxs, tabs, gtabs = [], [], [], []
+    hrs, hxs, tabs, gtabs, stabs = [], [], [], [], []
     for names in [[]] + doms:
         cl, ap = _reduced(cluster, apps, names, reschedule)
         nodes = list(cl.get("Node", []))
@@ -1537,7 +1724,7 @@ def _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why: str, r
                      occupancy_pct(int(out.used_mem[0]) * 1000, int(pr.alloc_mem.sum()) * 1000),
                      occupancy_pct(int(out.used_vg[0]), int(vg_cap.sum())) if vg_cap is not None else 0, _risk(out, 0)))
         where.append((flat, out.placement[0]))
-        for acc, v in zip((hrs, hxs, tabs, gtabs), _usage_each(flat, nodes, out, headroom, node_table, arrival, devices)):
+        for acc, v in zip((hrs, hxs, tabs, gtabs, stabs), _usage_each(flat, nodes, out, headroom, node_table, arrival, devices, storage)):
             acc.append(v)
         if reschedule and names:
             refs = _evicted_refs(cluster, apps, names, reschedule)
@@ -1546,7 +1733,7 @@ def _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why: str, r
             lists.append(_failure_replay(cluster, apps, names, engine, reschedule) if rows[-1][0] > 0 else [])
     res = _failure_result(doms, rows, caps, where, lists, False, why, moved)
     res.headroom, res.headroom_exact, res.node_table = hrs if headroom is not None else None, _and_exact(hxs), tabs if node_table else None
-    res.gpu_table = gtabs if devices else None
+    res.gpu_table, res.storage_table = gtabs if devices else None, stabs if storage else None
     return res
 
 
@@ -1573,6 +1760,7 @@ class AppSweepResult:
     headroom_exact: Optional[List[bool]] = None         # per probe: the scheduler's own count (else an upper bound)
     node_table: Optional[List[List[List[dict]]]] = None # node_table=True: [U][K] reportClusterInfo's table over the scenario's nodes
     gpu_table: Optional[List[List[List[dict]]]] = None  # devices=True: [U][K] the "GPU Node Resource" table over the scenario's GPU nodes
+    storage_table: Optional[List[List[List[dict]]]] = None  # storage=True: [U][K] the "Node Local Storage" table over the scenario's annotated nodes
 
 
 class AppFallbackWarning(UserWarning):
@@ -1618,18 +1806,19 @@ def _app_summary(apps, subs, counts, rows, by_app, caps, weights, why_lists, bat
 
 
 def _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, weights, reasons, why: str, headroom=None,
-                     node_table: bool = False, devices: bool = False) -> AppSweepResult:
+                     node_table: bool = False, devices: bool = False, storage: bool = False) -> AppSweepResult:
     """Every scenario as its own Simulate(): the cluster, the subset's apps and its new nodes, canonical nodeTree order."""
     import warnings
     warnings.warn(f"sweep_apps runs {len(subs) * len(counts)} scenarios one by one ({why})", AppFallbackWarning, stacklevel=3)
     base = list(cluster.get("Node", []))
     rows, by_app, lists = [], [], []
-    hrs, hxs, tabs, gtabs = [], [], [], []
+    hrs, hxs, tabs, gtabs, stabs = [], [], [], [], []
     for sub in subs:
         mine = [apps[a] for a in sub]
         hrs.append([])
         tabs.append([])
         gtabs.append([])
+        stabs.append([])
         rows.append([])
         by_app.append([])
         lists.append([])
@@ -1651,19 +1840,20 @@ def _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, weight
             pr = flat.problem
             per = [0] * len(apps)
             if not pods:
-                if headroom is not None or node_table or devices:
+                if headroom is not None or node_table or devices or storage:
                     raise ValueError("sweep_apps: headroom / node_table of a scenario without any pod, run on its own")
                 rows[-1].append((0, 0, 0, 0, False))
                 by_app[-1].append(per)
                 lists[-1].append([])
                 continue
             out = engine.run(pr, np.array([[len(nodes), 0]], np.int32), np.arange(len(pods), dtype=np.int32)[None, :],
-                             **({"want_gpu_slices": True} if devices and pr.gpu_mem is not None else {}))
-            h1, x1, t1, g1 = _usage_each(flat, nodes, out, headroom, node_table, arrival, devices)
+                             **({"want_gpu_slices": True} if (devices or storage) and pr.gpu_mem is not None else {}))
+            h1, x1, t1, g1, s1 = _usage_each(flat, nodes, out, headroom, node_table, arrival, devices, storage)
             hrs[-1].append(h1)
             hxs.append(x1)
             tabs[-1].append(t1)
             gtabs[-1].append(g1)
+            stabs[-1].append(s1)
             vg_cap = _vg_caps(pr, out)
             rows[-1].append((int(out.unscheduled[0]), occupancy_pct(int(out.used_cpu[0]), int(pr.alloc_cpu.sum())),
                              occupancy_pct(int(out.used_mem[0]) * 1000, int(pr.alloc_mem.sum()) * 1000),
@@ -1678,7 +1868,7 @@ def _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, weight
             lists[-1].append(_unscheduled_list(flat, out.placement[0], texts) if reasons else [])
     res = _app_summary(apps, subs, counts, rows, by_app, caps, weights, lists if reasons else [], False, why)
     res.headroom, res.headroom_exact, res.node_table = hrs if headroom is not None else None, _and_exact(hxs), tabs if node_table else None
-    res.gpu_table = gtabs if devices else None
+    res.gpu_table, res.storage_table = gtabs if devices else None, stabs if storage else None
     return res
 
 
@@ -1686,7 +1876,7 @@ def _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, weight
 def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subsets=None, new_node: Optional[dict] = None,
                counts: Sequence[int] = (0,), weights: Optional[Sequence[float]] = None, engine=None, max_cpu: int = 100, max_mem: int = 100,
                max_vg: int = 100, reasons: bool = False, batch_scenarios: int = 4096, headroom=None, node_table: bool = False,
-               devices: bool = False) -> AppSweepResult:
+               devices: bool = False, storage: bool = False) -> AppSweepResult:
     """Which of these apps fit on the cluster together, what has to be left out, and how many new nodes each combination costs: scenario
     (u, k) is simulate(cluster, [apps[a] for a in subsets[u]], new_nodes = counts[k] clones of new_node); the cluster's own pods are part
     of every scenario.  subsets: bool rows [U][len(apps)] or lists of app names; None = every subset of at most 12 apps (4 096 scenarios per
@@ -1703,7 +1893,7 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
     them all up front); an engine that refuses the batch (SIMON_ESTATE).  Not covered: subsets of the replicas WITHIN one app --
     ScheduleApp's unstable sorts order an app's pods by the length of the list, so a shorter replica list is not a restriction of the
     longer one's stream.
-    headroom=[...] / node_table=True / devices=True: as sweep() takes them, per scenario (u, k) (AppSweepResult.headroom[u][k] etc.); a probe may be a
+    headroom=[...] / node_table=True / devices=True / storage=True: as sweep() takes them, per scenario (u, k) (AppSweepResult.headroom[u][k] etc.); a probe may be a
     pod of an app the scenario lacks -- its request and class stand for "one more such pod"."""
     engine = engine or HipEngine()
     apps, counts = list(apps), list(counts)
@@ -1719,7 +1909,7 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
     w = [float(x) for x in weights] if weights is not None else [float(n) for n in lens]
     if len(w) != len(apps):
         raise ValueError(f"{len(w)} weights for {len(apps)} apps")
-    each = lambda why: _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, w, reasons, why, headroom, node_table, devices)   # noqa: E731
+    each = lambda why: _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, w, reasons, why, headroom, node_table, devices, storage)   # noqa: E731
     if not getattr(engine, "supports_pod_subsets", False):
         return each("the engine has no pod subsets")
     # a StorageClass that one app defines and another app's pods use: in a subset without the first app the class is unknown
@@ -1771,7 +1961,8 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
     hx = None
     tab = [[None] * K for _ in subs] if node_table else None
     gtab = [[None] * K for _ in subs] if devices else None
-    on_host = (headroom is not None or node_table or devices) and not _on_device(engine, devices)     # (the host figures need the rows)
+    stab = [[None] * K for _ in subs] if storage else None
+    on_host = (headroom is not None or node_table or devices or storage) and not _on_device(engine, devices, storage)     # (the host figures need the rows)
     per_launch = max(1, int(batch_scenarios) // K)                  # whole subsets per launch: K scenarios each
     for lo in range(0, len(subs), per_launch):
         us = np.arange(lo, min(lo + per_launch, len(subs)))
@@ -1780,17 +1971,17 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
         kw = {}
         if batch.node_ranks is not None:
             kw["node_ranks"] = np.tile(batch.node_ranks, (len(us), 1))
-        if devices and on_host and pr.gpu_mem is not None:
+        if (devices or storage) and on_host and pr.gpu_mem is not None:
             kw["want_gpu_slices"] = True
         try:
             out = engine.run(pr, scen, batch.orders, want_placement=reasons or on_host, pod_present=present, pod_groups=group, **kw,
-                             **_usage_kw(engine, probes, node_table, len(scen), devices))
+                             **_usage_kw(engine, probes, node_table, len(scen), devices, storage))
         except capi.SimonError as e:
             if getattr(e, "code", None) != capi.ESTATE:
                 raise
             return each(f"the engine refused the pod-subset batch: {e}")
-        h1, x1, t1, g1 = _usage_fill(engine, out, batch.pool, pr, np.arange(len(batch.pool))[None, :] < scen[:, :1], probes, node_table,
-                                     AppFallbackWarning, "sweep_apps", devices)
+        h1, x1, t1, g1, s1 = _usage_fill(engine, out, batch.pool, pr, np.arange(len(batch.pool))[None, :] < scen[:, :1], probes, node_table,
+                                         AppFallbackWarning, "sweep_apps", devices, storage, batch.orders, scen)
         hx = x1 if x1 is not None else hx
         vg_cap = _vg_caps(pr, out)
         cv = np.cumsum(vg_cap) if vg_cap is not None else None
@@ -1827,10 +2018,12 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
                     tab[u][k] = t1[s]
                 if g1 is not None:
                     gtab[u][k] = g1[s]
+                if s1 is not None:
+                    stab[u][k] = s1[s]
                 if reasons and s not in replayed:
                     lists[u][k] = _unscheduled_list(flat, out.placement[s], told.get(s, {}))
     res = _app_summary(apps, subs, counts, rows, by_app, caps, w, lists if reasons else [], True, None)
-    res.headroom, res.headroom_exact, res.node_table, res.gpu_table = hr, hx, tab, gtab
+    res.headroom, res.headroom_exact, res.node_table, res.gpu_table, res.storage_table = hr, hx, tab, gtab, stab
     return res
 
 
