@@ -476,6 +476,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     // as well: it serves the problems with many node classes, where a row loses several classes between two of its uses and the lazy scheme re-bases once for all of
     // them (config 3 on 80 shapes, 4 096 scenarios: 35.09 / 34.82 ms lazy, 36.72 / 35.76 ms at the event), and five of its kernels held one VGPR more.
     constexpr bool kEager = kStraight && !kCls4 && !COARSE;
+    // Round 13: where the cycle is straight-line code and the workspace is in HBM, the touched node's state is stored by every lane (one address, one
+    // value) instead of by lane 0 inside an EXEC region of its own.  Not for the three instructions of the region: behind a store that MAY have been
+    // issued the compiler's wait for the table byte, in front of the refresh, was vmcnt(0) -- the store's acknowledgement from memory sat on every
+    // cycle's chain.  Behind an unconditional store it is vmcnt(1): row and byte arrived, the store still in flight (simon_table_assume.inc).
+    // Config 3 9.65 -> 8.92 ms, 80 shapes 35.0 -> 34.5, 160 shapes 52.7 -> 51.1 (docs/KERNELS.md, round 13).  With the workspace in LDS nothing
+    // leaves the chip, and config 3 at 64 scenarios measured 4.82 -> 4.85 ms with it: lane 0 keeps the store there.  Left out as well, because their
+    // kernels held one to four VGPRs more with it: NonZeroRequested apart from Requested (a second such store in front of this one), and the ranked
+    // instantiations of kCls4 and of the two-level layout with two signatures per lane.
+    constexpr bool kLanesStore = kStraight && !LDSWS && NZEQ && !(RANKED && (kCls4 || (COARSE && KQ > 1)));
     // the initial table by copy from the shared image (prologue 2): this unit's one-level instantiations on prefix scenarios in canonical order
     constexpr bool kSharedPro = kSharedPrologueTU && !COARSE && !REST && !SPREAD && !MANY && !kCls4 && !RANKED && !LDSWS && NW == 1;
     static_assert(!MANY || (KQ == 2 && COARSE && !CN2 && !LDSX), "MANY = groups of 128 signatures on the two-level layout (since round 6 also under the REST select: its rows and counters are indexed by signature already)");

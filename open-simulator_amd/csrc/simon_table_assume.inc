@@ -210,7 +210,12 @@
                 if (lane == 0) g_nz[pstar] = z;
                 nzc = (double)z.x; nzm = (double)z.y;
             }
-            if (lane == 0) *stp = st;
+            // (kLanesStore: every lane holds the same state and stores it to the same address -- no EXEC region around the store, and the wait for
+            // the table byte below no longer waits for this store to be acknowledged, see simon_table.hip)
+            if (kLanesStore || lane == 0) *stp = st;
+            // (the region's end was a boundary for the instruction scheduler as well: without one here it interleaves the state update with the
+            // evaluation, and the kernels hold up to seven VGPRs more)
+            if constexpr (kLanesStore) __builtin_amdgcn_sched_barrier(0);
             const double rq_c = (double)st.rq_c, rq_m = (double)st.rq_m;
             TPROF(8);                                                  // state update (readlanes of the signature's request), state store
             // Signature k's byte of the touched node, its block key, summary entries and feasible-node counter (lane-local k).
@@ -272,6 +277,12 @@
             // signatures the host puts a signature's twin -- same request, another table class (static mask / Simon row) -- 64 slots up
             // whenever every upper signature has one (TableScalars::static_tables & kStTwins): the upper byte is the lower lane's, unmasked.
             unsigned nbq[KQ];
+            // (kLanesStore: without the store's region between them and the refresh, the compiler sinks the selectors' scalar load and the class terms'
+            // LDS read into the refresh's region, where the wave waits for each in turn; read here, they stay issued ahead of the state's wait)
+            if constexpr (kLanesStore) {
+#pragma unroll
+                for (int q = 0; q < KQ; ++q) asm volatile("" : : "v"(snq[q]), "s"(selA.x), "s"(selB.x));
+            }
             nbq[0] = eval_node(my_req_c[0], my_req_m[0], my_nz_c[0], my_nz_m[0], my_zero[0], rq_c, rq_m, nzc, nzm, (int)st.freep, sh);
             if constexpr (KQ > 1) {
                 if (sc.static_tables & kStTwins) nbq[KQ - 1] = nbq[0];
