@@ -134,7 +134,8 @@ __device__ __forceinline__ int ba_term(uint32_t cap_c, uint32_t req_c, uint32_t 
 // q0 = RN(req*rc) is within 1.5 ulp; one residual step makes it faithful, the second one
 // (with rc strictly within half an ulp of 1/cap, true for every integer cap) rounds correctly
 // (Markstein 1990; Muller et al., Handbook of FP Arithmetic, thm. 4.7).  All operands are
-// integers < 2^31, far from under/overflow.  Verified against '/' on-device in tests.
+// integers < 2^31, far from under/overflow.  Verified against '/' on-device by tests/test_gpu_duels.py
+// (equal-fraction and near-integer duels on coprime capacities up to 2^31, tests/duel_util.py).
 __device__ __forceinline__ double div_by_rcp(double num, double den, double rc) {
     double q = num * rc;
     double e = __builtin_fma(-q, den, num);
