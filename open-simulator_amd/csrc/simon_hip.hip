@@ -2518,9 +2518,53 @@ int simon_fetch_group_counts(simon_ctx* c, const int32_t* pod_group, int32_t G, 
     return SIMON_OK;
 }
 
-// ---- simon_fetch_node_usage / simon_fetch_headroom ----
-// The compact int64 copies both kernels read (the per-family pod rows are normalised: not usable here), uploaded on the first call after
-// a reload, and the launch arguments the two calls share.
+// ---- simon_fetch_node_usage / _gpu_usage / _local_usage and simon_fetch_headroom / _gpu / _local ----
+static_assert(sizeof(ScenarioDesc) == 8, "the usage kernels read ScenarioDesc as int32 pairs");
+
+// the launch arguments every usage and headroom call shares
+static void usage_base(const simon_ctx* c, UsageCommon& a) {
+    a.placement = c->d_place.p; a.scen = reinterpret_cast<const int32_t*>(c->d_scen.p);
+    a.rank = own_nodes(c) && c->has_ranks ? c->d_node_rank.p : nullptr;
+    a.P = c->P; a.N = c->N;
+}
+
+// the tile a launch of `blocks` workgroups forces (usage_tile's `forced`): SIMON_USAGE_TILE; or, where the launch puts at most one
+// workgroup on a CU anyway, the largest that fits a workgroup (fewer passes over the placement row: config 5's 256 scenarios,
+// profiles/usage/README.md); or 0 = the LDS budget's (four workgroups per CU)
+static int usage_forced_tile(const simon_ctx* c, int blocks) { return c->usage_tile ? c->usage_tile : blocks <= c->n_cus ? 1 << 30 : 0; }
+
+// The opening of the three listed-scenario calls, in two steps with the call's own test of its required arrays between them (no field
+// behind struct_size is read before the ABI guard has passed).  First the context and the output struct: `size` = its struct_size
+// (null without a struct) against the `want` of `type`.
+static int usage_out_check(simon_ctx* c, const char* what, const char* type, const uint32_t* size, size_t want) {
+    if (!c) return SIMON_EINVAL;
+    if (!size) return fail(c, SIMON_EINVAL, "%s: bad arguments", what);
+    if (*size != want) return fail(c, SIMON_EINVAL, "%s: %s size mismatch", what, type);
+    return SIMON_OK;
+}
+
+// Then the scenario list and the state of the context (`devices`: the recorded devices too), the launch arguments every usage kernel
+// takes and the listed ids on the device (*d_ids: null for scen_ids = null).
+static int usage_open(simon_ctx* c, const char* what, const int32_t* scen_ids, int32_t n, bool devices, UsageCommon& a, const int32_t** d_ids) {
+    if (n < 1) return fail(c, SIMON_EINVAL, "%s: %d scenarios listed", what, n);
+    if (!c->have_results || !c->have_placement) return fail(c, SIMON_ESTATE, "%s: no placements on device (run with SIMON_WANT_PLACEMENT)", what);
+    if (!scen_ids && n > c->S) return fail(c, SIMON_EINVAL, "%s: scenario %d outside [0,%d)", what, c->S, c->S);
+    for (int i = 0; scen_ids && i < n; ++i)
+        if (scen_ids[i] < 0 || scen_ids[i] >= c->S) return fail(c, SIMON_EINVAL, "%s: scenario %d outside [0,%d)", what, scen_ids[i], c->S);
+    if (devices && c->has_gpu && !c->have_slices) return fail(c, SIMON_ESTATE, "%s: the last run did not record GPU devices (SIMON_WANT_GPU_SLICES)", what);
+    HIP_TRY(c, hipSetDevice(c->device));
+    usage_base(c, a);
+    *d_ids = nullptr;
+    if (scen_ids) {
+        HIP_TRY(c, c->d_u_ids.ensure((size_t)n));
+        HIP_TRY(c, hipMemcpyAsync(c->d_u_ids.p, scen_ids, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        *d_ids = c->d_u_ids.p;
+    }
+    return SIMON_OK;
+}
+
+// The compact int64 copies node_usage_kernel and headroom_kernel read (the per-family pod rows are normalised: not usable here),
+// uploaded on the first call after a reload, and their launch arguments (on top of usage_base's).
 static int usage_stage(simon_ctx* c, UsageCommon& a) {
     const size_t P = c->P, N = c->N;
     const int K = c->K;
@@ -2554,56 +2598,37 @@ static int usage_stage(simon_ctx* c, UsageCommon& a) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->usage_nodes_staged = true;
     }
-    a.placement = c->d_place.p; a.scen = reinterpret_cast<const int32_t*>(c->d_scen.p);
-    a.rank = own_nodes(c) && c->has_ranks ? c->d_node_rank.p : nullptr;
     a.pod_req = c->d_u_pod_req.p; a.node_init = c->d_u_node_init.p; a.init_npods = c->d_u_init_npods.p;
-    a.P = c->P; a.N = c->N;
     return SIMON_OK;
 }
 
-// the rows a launch of `blocks` workgroups accumulates: `rows` (bits over the resource rows) in ascending order, and the node tile for
-// them -- the LDS budget's (four workgroups per CU), or, where the launch puts at most one workgroup on a CU anyway, the largest that
-// fits a workgroup (fewer passes over the placement row: config 5's 256 scenarios, profiles/usage/README.md)
-static void usage_rows_of(const simon_ctx* c, uint32_t rows, UsageCommon& a, int blocks, int dev = 0) {
+// the rows a launch accumulates: `rows` (bits over the resource rows) in ascending order
+static void usage_rows_of(uint32_t rows, UsageCommon& a) {
     a.nrows = 0;
     for (int r = 0; r < kUsageRows; ++r)
         if ((rows >> r) & 1u) a.row_src[a.nrows++] = r;
     for (int i = a.nrows; i < kUsageRows; ++i) a.row_src[i] = -1;
-    a.tile = usage_tile(c->N, a.nrows, c->usage_tile ? c->usage_tile : blocks <= c->n_cus ? 1 << 30 : 0, dev);
 }
 
-static_assert(sizeof(ScenarioDesc) == 8, "the usage kernels read ScenarioDesc as int32 pairs");
-
 int simon_fetch_node_usage(simon_ctx* c, const int32_t* scen_ids, int32_t n, simon_node_usage* out) {
-    if (!c) return SIMON_EINVAL;
-    if (!out) return fail(c, SIMON_EINVAL, "fetch_node_usage: bad arguments");
-    if (out->struct_size != sizeof(simon_node_usage)) return fail(c, SIMON_EINVAL, "fetch_node_usage: simon_node_usage size mismatch");
-    if (!out->req_cpu || !out->req_mem || !out->npods) return fail(c, SIMON_EINVAL, "fetch_node_usage: missing required arrays (req_cpu, req_mem, npods)");
-    if (n < 1) return fail(c, SIMON_EINVAL, "fetch_node_usage: %d scenarios listed", n);
-    if (!c->have_results || !c->have_placement) return fail(c, SIMON_ESTATE, "fetch_node_usage: no placements on device (run with SIMON_WANT_PLACEMENT)");
-    if (!scen_ids && n > c->S) return fail(c, SIMON_EINVAL, "fetch_node_usage: scenario %d outside [0,%d)", c->S, c->S);
-    for (int i = 0; scen_ids && i < n; ++i)
-        if (scen_ids[i] < 0 || scen_ids[i] >= c->S) return fail(c, SIMON_EINVAL, "fetch_node_usage: scenario %d outside [0,%d)", scen_ids[i], c->S);
-    HIP_TRY(c, hipSetDevice(c->device));
     UsageCommon a{};
+    UsageOut o{};
+    if (const int rc = usage_out_check(c, "fetch_node_usage", "simon_node_usage", out ? &out->struct_size : nullptr, sizeof *out)) return rc;
+    if (!out->req_cpu || !out->req_mem || !out->npods) return fail(c, SIMON_EINVAL, "fetch_node_usage: missing required arrays (req_cpu, req_mem, npods)");
+    if (const int rc = usage_open(c, "fetch_node_usage", scen_ids, n, false, a, &o.scen_ids)) return rc;
     if (const int rc = usage_stage(c, a)) return rc;
     const size_t N = c->N, K = c->K, cells = (size_t)n * N;
     const bool eph = out->req_eph != nullptr, sc = out->scalar_req != nullptr && K > 0;
-    usage_rows_of(c, 3u | (eph ? 4u : 0u) | (sc ? ((1u << K) - 1u) << 3 : 0u), a, n);
+    usage_rows_of(3u | (eph ? 4u : 0u) | (sc ? ((1u << K) - 1u) << 3 : 0u), a);
+    a.tile = usage_tile(c->N, usage_node_bytes(a.nrows), kTileReserve, usage_forced_tile(c, n));
     HIP_TRY(c, c->d_u_out64.ensure(cells * (size_t)a.nrows));
     HIP_TRY(c, c->d_u_npods.ensure(cells));
-    UsageOut o{};
     o.npods = c->d_u_npods.p;
     int64_t* const d_sc = c->d_u_out64.p + cells * (2 + (eph ? 1 : 0));          // [n][K][N]
     for (int i = 0; i < a.nrows; ++i) {
         const int r = a.row_src[i];
         if (r < 3) { o.rows[i] = c->d_u_out64.p + cells * i; o.row_stride[i] = N; }
         else { o.rows[i] = d_sc + (size_t)(r - 3) * N; o.row_stride[i] = K * N; }
-    }
-    if (scen_ids) {
-        HIP_TRY(c, c->d_u_ids.ensure((size_t)n));
-        HIP_TRY(c, hipMemcpyAsync(c->d_u_ids.p, scen_ids, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        o.scen_ids = c->d_u_ids.p;
     }
     HIP_TRY(c, launch_node_usage(a, o, n, c->stream));
     HIP_TRY(c, hipMemcpyAsync(out->req_cpu, o.rows[0], cells * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2647,35 +2672,18 @@ static int usage_stage_gpu(simon_ctx* c, DevUsage& g) {
 static_assert(SIMON_MAX_GPU_DEV == kGpuDev, "the device kernels unpack one slices byte per device");
 
 int simon_fetch_gpu_usage(simon_ctx* c, const int32_t* scen_ids, int32_t n, simon_gpu_usage* out) {
-    if (!c) return SIMON_EINVAL;
-    if (!out) return fail(c, SIMON_EINVAL, "fetch_gpu_usage: bad arguments");
-    if (out->struct_size != sizeof(simon_gpu_usage)) return fail(c, SIMON_EINVAL, "fetch_gpu_usage: simon_gpu_usage size mismatch");
-    if (!out->dev_used) return fail(c, SIMON_EINVAL, "fetch_gpu_usage: missing required arrays (dev_used)");
-    if (n < 1) return fail(c, SIMON_EINVAL, "fetch_gpu_usage: %d scenarios listed", n);
-    if (!c->have_results || !c->have_placement) return fail(c, SIMON_ESTATE, "fetch_gpu_usage: no placements on device (run with SIMON_WANT_PLACEMENT)");
-    if (!scen_ids && n > c->S) return fail(c, SIMON_EINVAL, "fetch_gpu_usage: scenario %d outside [0,%d)", c->S, c->S);
-    for (int i = 0; scen_ids && i < n; ++i)
-        if (scen_ids[i] < 0 || scen_ids[i] >= c->S) return fail(c, SIMON_EINVAL, "fetch_gpu_usage: scenario %d outside [0,%d)", scen_ids[i], c->S);
-    if (c->has_gpu && !c->have_slices) return fail(c, SIMON_ESTATE, "fetch_gpu_usage: the last run did not record GPU devices (SIMON_WANT_GPU_SLICES)");
-    HIP_TRY(c, hipSetDevice(c->device));
     UsageCommon a{};
-    a.placement = c->d_place.p; a.scen = reinterpret_cast<const int32_t*>(c->d_scen.p);
-    a.rank = own_nodes(c) && c->has_ranks ? c->d_node_rank.p : nullptr;
-    a.P = c->P; a.N = c->N;
+    GpuUsageOut o{};
+    if (const int rc = usage_out_check(c, "fetch_gpu_usage", "simon_gpu_usage", out ? &out->struct_size : nullptr, sizeof *out)) return rc;
+    if (!out->dev_used) return fail(c, SIMON_EINVAL, "fetch_gpu_usage: missing required arrays (dev_used)");
+    if (const int rc = usage_open(c, "fetch_gpu_usage", scen_ids, n, true, a, &o.scen_ids)) return rc;
     DevUsage g{};
     if (const int rc = usage_stage_gpu(c, g)) return rc;
-    const int dev = kDevBytes + (out->dev_pods ? kDevPodsBytes : 0);
-    a.tile = usage_tile(c->N, 0, c->usage_tile ? c->usage_tile : n <= c->n_cus ? 1 << 30 : 0, dev);
+    a.tile = usage_tile(c->N, usage_node_bytes(0, kDevBytes + (out->dev_pods ? kDevPodsBytes : 0)), kTileReserve, usage_forced_tile(c, n));
     const size_t cells = (size_t)n * c->N * SIMON_MAX_GPU_DEV;
-    GpuUsageOut o{};
     HIP_TRY(c, c->d_g_out_used.ensure(cells));
     o.dev_used = c->d_g_out_used.p;
     if (out->dev_pods) { HIP_TRY(c, c->d_g_out_pods.ensure(cells)); o.dev_pods = c->d_g_out_pods.p; }
-    if (scen_ids) {
-        HIP_TRY(c, c->d_u_ids.ensure((size_t)n));
-        HIP_TRY(c, hipMemcpyAsync(c->d_u_ids.p, scen_ids, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        o.scen_ids = c->d_u_ids.p;
-    }
     HIP_TRY(c, launch_gpu_usage(a, g, o, n, c->stream));
     HIP_TRY(c, hipMemcpyAsync(out->dev_used, o.dev_used, cells * 8, hipMemcpyDeviceToHost, c->stream));
     if (out->dev_pods) HIP_TRY(c, hipMemcpyAsync(out->dev_pods, o.dev_pods, cells * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2738,31 +2746,38 @@ static int local_stage(simon_ctx* c, LocalUsage& l) {
     return SIMON_OK;
 }
 
-// simon_fetch_headroom, simon_fetch_headroom_gpu and simon_fetch_headroom_local (`devices`: the device bound on top, `what` names the call in messages)
-static int fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int64_t* fit, int32_t* fit_nodes, uint8_t* exact, bool devices,
-                          const char* what, bool storage = false) {
+// The bounds of a headroom call: resources = simon_fetch_headroom, devices = simon_fetch_headroom_gpu (the device bound on top), storage =
+// simon_fetch_headroom_local: the storage bound on top, and the device bound under simon_fetch_headroom_gpu's rule where the problem has
+// GPU requests or GPU nodes (a problem without GPUs pays no device LDS).
+enum class Headroom { resources, devices, storage };
+static bool headroom_devices(const simon_ctx* c, Headroom bounds) {
+    return bounds == Headroom::devices || (bounds == Headroom::storage && (c->has_gpu || c->has_gpu_nodes));
+}
+
+// the three headroom calls (`what` names the call in messages)
+static int fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int64_t* fit, int32_t* fit_nodes, uint8_t* exact, Headroom bounds,
+                          const char* what) {
     if (!c) return SIMON_EINVAL;
+    const bool devices = headroom_devices(c, bounds), storage = bounds == Headroom::storage;
     if (!probe_pod || !fit) return fail(c, SIMON_EINVAL, "%s: missing required arrays (probe_pod, fit)", what);
     if (K < 1 || K > SIMON_MAX_PROBES) return fail(c, SIMON_EINVAL, "%s: %d probes outside [1, %d]", what, K, SIMON_MAX_PROBES);
     if (!c->have_results || !c->have_placement) return fail(c, SIMON_ESTATE, "%s: no placements on device (run with SIMON_WANT_PLACEMENT)", what);
     for (int k = 0; k < K; ++k)
         if (probe_pod[k] < 0 || probe_pod[k] >= c->P) return fail(c, SIMON_EINVAL, "%s: probe %d: pod %d outside [0,%d)", what, k, probe_pod[k], c->P);
     if (devices && c->has_gpu && !c->have_slices) return fail(c, SIMON_ESTATE, "%s: the last run did not record GPU devices (SIMON_WANT_GPU_SLICES)", what);
-    // simon_fetch_headroom_local: the device bound under simon_fetch_headroom_gpu's rule (refused above), its LDS only where GPUs exist
-    if (storage) devices = c->has_gpu || c->has_gpu_nodes;
     HIP_TRY(c, hipSetDevice(c->device));
     UsageCommon a{};
+    usage_base(c, a);
     if (const int rc = usage_stage(c, a)) return rc;
     DevUsage g{};
     if (devices)
         if (const int rc = usage_stage_gpu(c, g)) return rc;
     LocalUsage l{};
-    if (storage) {
+    if (storage)
         if (const int rc = local_stage(c, l)) return rc;
-        usage_rows_of(c, c->usage_rows, a, c->S);
-        a.tile = local_tile(c->N, usage_node_bytes(a.nrows, kLocalBytes + (devices ? kDevBytes : 0)), c->usage_tile ? c->usage_tile : c->S <= c->n_cus ? 1 << 30 : 0);
-    } else
-        usage_rows_of(c, c->usage_rows, a, c->S, devices ? kDevBytes : 0);
+    usage_rows_of(c->usage_rows, a);
+    const HeadroomLds lds{a.nrows, K, devices, storage};
+    a.tile = usage_tile(c->N, lds.node_bytes(), lds.reserve_bytes(), usage_forced_tile(c, c->S));
     // the probe rows: request, the resources fitsRequest compares (fit.go:244-299), the class's static mask
     const size_t S = c->S, N = c->N, W = (N + 63) / 64, P = c->P;
     std::vector<ProbeRow> rows((size_t)K);
@@ -2808,11 +2823,8 @@ static int fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int
     if (storage) {
         HIP_TRY(c, c->d_l_probe_spec.upload(lspec, c->stream));
         l.probe_spec = c->d_l_probe_spec.p;
-        HIP_TRY(c, launch_headroom_local(a, h, g, l, devices, (int)S, c->stream));
-    } else if (devices)
-        HIP_TRY(c, launch_headroom_gpu(a, h, g, (int)S, c->stream));
-    else
-        HIP_TRY(c, launch_headroom(a, h, (int)S, c->stream));
+    }
+    HIP_TRY(c, launch_headroom(a, h, g, l, devices, storage, (int)S, c->stream));
     HIP_TRY(c, hipMemcpyAsync(fit, c->d_u_fit.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
     if (fit_nodes) HIP_TRY(c, hipMemcpyAsync(fit_nodes, c->d_u_fit_nodes.p, cells * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));                 // (also: rows and mask outlive their uploads)
@@ -2820,45 +2832,30 @@ static int fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int
 }
 
 int simon_fetch_headroom(simon_ctx* c, const int32_t* probe_pod, int32_t K, int64_t* fit, int32_t* fit_nodes, uint8_t* exact) {
-    return fetch_headroom(c, probe_pod, K, fit, fit_nodes, exact, false, "fetch_headroom");
+    return fetch_headroom(c, probe_pod, K, fit, fit_nodes, exact, Headroom::resources, "fetch_headroom");
 }
 
 int simon_fetch_headroom_gpu(simon_ctx* c, const int32_t* probe_pod, int32_t K, int64_t* fit, int32_t* fit_nodes, uint8_t* exact) {
-    return fetch_headroom(c, probe_pod, K, fit, fit_nodes, exact, true, "fetch_headroom_gpu");
+    return fetch_headroom(c, probe_pod, K, fit, fit_nodes, exact, Headroom::devices, "fetch_headroom_gpu");
 }
 
 int simon_fetch_headroom_local(simon_ctx* c, const int32_t* probe_pod, int32_t K, int64_t* fit, int32_t* fit_nodes, uint8_t* exact) {
-    return fetch_headroom(c, probe_pod, K, fit, fit_nodes, exact, true, "fetch_headroom_local", true);
+    return fetch_headroom(c, probe_pod, K, fit, fit_nodes, exact, Headroom::storage, "fetch_headroom_local");
 }
 
 int simon_fetch_local_usage(simon_ctx* c, const int32_t* scen_ids, int32_t n, simon_local_usage* out) {
-    if (!c) return SIMON_EINVAL;
-    if (!out) return fail(c, SIMON_EINVAL, "fetch_local_usage: bad arguments");
-    if (out->struct_size != sizeof(simon_local_usage)) return fail(c, SIMON_EINVAL, "fetch_local_usage: simon_local_usage size mismatch");
-    if (!out->vg_req) return fail(c, SIMON_EINVAL, "fetch_local_usage: missing required arrays (vg_req)");
-    if (n < 1) return fail(c, SIMON_EINVAL, "fetch_local_usage: %d scenarios listed", n);
-    if (!c->have_results || !c->have_placement) return fail(c, SIMON_ESTATE, "fetch_local_usage: no placements on device (run with SIMON_WANT_PLACEMENT)");
-    if (!scen_ids && n > c->S) return fail(c, SIMON_EINVAL, "fetch_local_usage: scenario %d outside [0,%d)", c->S, c->S);
-    for (int i = 0; scen_ids && i < n; ++i)
-        if (scen_ids[i] < 0 || scen_ids[i] >= c->S) return fail(c, SIMON_EINVAL, "fetch_local_usage: scenario %d outside [0,%d)", scen_ids[i], c->S);
-    HIP_TRY(c, hipSetDevice(c->device));
     UsageCommon a{};
-    a.placement = c->d_place.p; a.scen = reinterpret_cast<const int32_t*>(c->d_scen.p);
-    a.rank = own_nodes(c) && c->has_ranks ? c->d_node_rank.p : nullptr;
-    a.P = c->P; a.N = c->N;
+    LocalUsageOut o{};
+    if (const int rc = usage_out_check(c, "fetch_local_usage", "simon_local_usage", out ? &out->struct_size : nullptr, sizeof *out)) return rc;
+    if (!out->vg_req) return fail(c, SIMON_EINVAL, "fetch_local_usage: missing required arrays (vg_req)");
+    if (const int rc = usage_open(c, "fetch_local_usage", scen_ids, n, false, a, &o.scen_ids)) return rc;
     LocalUsage l{};
     if (const int rc = local_stage(c, l)) return rc;
-    a.tile = local_tile(c->N, kLocalBytes, c->usage_tile ? c->usage_tile : n <= c->n_cus ? 1 << 30 : 0);
+    a.tile = usage_tile(c->N, kLocalBytes, kTileReserve + kLocalStageBytes, usage_forced_tile(c, n));
     const size_t cells = (size_t)n * c->N;
-    LocalUsageOut o{};
     HIP_TRY(c, c->d_l_out_vg.ensure(cells * SIMON_MAX_VG));
     o.vg_req = c->d_l_out_vg.p;
     if (out->dev_alloc) { HIP_TRY(c, c->d_l_out_dev.ensure(cells)); o.dev_alloc = c->d_l_out_dev.p; }
-    if (scen_ids) {
-        HIP_TRY(c, c->d_u_ids.ensure((size_t)n));
-        HIP_TRY(c, hipMemcpyAsync(c->d_u_ids.p, scen_ids, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        o.scen_ids = c->d_u_ids.p;
-    }
     HIP_TRY(c, launch_local_usage(a, l, o, n, c->stream));
     HIP_TRY(c, hipMemcpyAsync(out->vg_req, o.vg_req, cells * SIMON_MAX_VG * 8, hipMemcpyDeviceToHost, c->stream));
     if (out->dev_alloc) HIP_TRY(c, hipMemcpyAsync(out->dev_alloc, o.dev_alloc, cells * 4, hipMemcpyDeviceToHost, c->stream));

@@ -105,21 +105,25 @@ struct GpuUsageOut {
 
 __host__ __device__ inline int dev_slot(int jj, int d) { return jj * kGpuDev + ((d + (jj >> 1)) & (kGpuDev - 1)); }
 
-// bytes of LDS one node of a tile costs (`dev`: 0, kDevBytes or kDevBytes + kDevPodsBytes on top of the resource rows; nrows = 0: devices
-// only), and the tile the launchers use for N nodes (`forced` > 0: SIMON_USAGE_TILE)
+// bytes of LDS one node of a tile costs in the two listed-scenario kernels (`dev`: 0, kDevBytes or kDevBytes + kDevPodsBytes on top of the
+// resource rows; nrows = 0: devices only)
 inline size_t usage_node_bytes(int nrows, int dev = 0) { return (nrows > 0 ? (size_t)nrows * 8 + 4 : 0) + (size_t)dev; }
-inline int usage_tile(int N, int nrows, int forced, int dev = 0) {
-    int t = forced > 0 ? forced : (int)(kUsageLdsBudget / usage_node_bytes(nrows, dev)) / 64 * 64;
-    const int cap = (int)((64 * 1024 - 2 * kMaxProbes * 8) / usage_node_bytes(nrows, dev));   // (one workgroup's 64 KB, less the headroom counters)
+// what the tile rule leaves free of a workgroup's 64 KB whatever the call: the headroom counters of kMaxProbes probes (16 B each kept)
+constexpr size_t kTileReserve = 2 * kMaxProbes * 8;
+// The node tile of every usage / headroom launch: N nodes of `per` bytes each next to `fixed` bytes of LDS that do not grow with the
+// tile.  forced = 0: the largest multiple of 64 nodes inside the LDS budget; forced > 0 (SIMON_USAGE_TILE; 1 << 30 = a workgroup has a
+// CU to itself): that, capped at what one workgroup's 64 KB hold.
+inline int usage_tile(int N, size_t per, size_t fixed, int forced) {
+    int t = forced > 0 ? forced : (int)(kUsageLdsBudget / per) / 64 * 64;
+    const int cap = (int)((64 * 1024 - fixed) / per);
     t = t > cap ? cap : t;
     return t < 1 ? 1 : (t > N ? N : t);
 }
+// a.tile from usage_tile(N, usage_node_bytes(nrows), kTileReserve, forced)
 hipError_t launch_node_usage(const UsageCommon& a, const UsageOut& o, int n, hipStream_t st);
-hipError_t launch_headroom(const UsageCommon& a, const HeadroomArgs& h, int S, hipStream_t st);
-// a.tile from usage_tile(N, 0, forced, kDevBytes (+ kDevPodsBytes with dev_pods)); a.pod_req / node_init / init_npods are not read
+// a.tile from usage_tile(N, usage_node_bytes(0, kDevBytes (+ kDevPodsBytes with dev_pods)), kTileReserve, forced); a.pod_req / node_init /
+// init_npods are not read
 hipError_t launch_gpu_usage(const UsageCommon& a, const DevUsage& g, const GpuUsageOut& o, int n, hipStream_t st);
-// headroom with the device bound: a.tile from usage_tile(N, nrows, forced, kDevBytes)
-hipError_t launch_headroom_gpu(const UsageCommon& a, const HeadroomArgs& h, const DevUsage& g, int S, hipStream_t st);
 
 // Open-Local storage (simon_fetch_local_usage, simon_fetch_headroom_local).  The state of a node is not a sum: which volume group a
 // volume lands in and which devices a pod takes depend on the node's state at that moment, so the scheduled storage pods are REPLAYED
@@ -130,6 +134,7 @@ hipError_t launch_headroom_gpu(const UsageCommon& a, const HeadroomArgs& h, cons
 constexpr int kLocalVG = 4, kLocalDev = 8, kLocalVol = 4;   // SIMON_MAX_VG, SIMON_MAX_LDEV, SIMON_MAX_LVOL
 constexpr int kLocalBytes = kLocalVG * 8 + 4;
 constexpr int kLocalChunk = 512;             // storage pods staged per pass (node and spec of each: 8 bytes)
+constexpr size_t kLocalStageBytes = (size_t)kLocalChunk * 8;
 
 struct LocalSpec {                           // simon_local_spec, field for field
     int32_t n_lvm, n_ssd, n_hdd, pad;
@@ -161,18 +166,36 @@ struct LocalUsageOut {
     int32_t* dev_alloc;                      // [n][N] or nullptr
 };
 
-// the tile of both storage kernels: as usage_tile, less the staged chunk (`per`: bytes per node, kLocalBytes included)
-inline int local_tile(int N, size_t per, int forced) {
-    int t = forced > 0 ? forced : (int)(kUsageLdsBudget / per) / 64 * 64;
-    const int cap = (int)((64 * 1024 - 2 * kMaxProbes * 8 - kLocalChunk * 8) / per);
-    t = t > cap ? cap : t;
-    return t < 1 ? 1 : (t > N ? N : t);
-}
-// a.tile from local_tile(N, kLocalBytes, forced); a.pod_req / node_init / init_npods are not read
+// a.tile from usage_tile(N, kLocalBytes, kTileReserve + kLocalStageBytes, forced); a.pod_req / node_init / init_npods are not read
 hipError_t launch_local_usage(const UsageCommon& a, const LocalUsage& l, const LocalUsageOut& o, int n, hipStream_t st);
-// headroom with the storage bound and, `devices`, the device bound: a.tile from local_tile(N, usage_node_bytes(nrows, kLocalBytes
-// (+ kDevBytes)), forced)
-hipError_t launch_headroom_local(const UsageCommon& a, const HeadroomArgs& h, const DevUsage& g, const LocalUsage& l, bool devices, int S,
-                                 hipStream_t st);
+
+// The LDS of one headroom workgroup (simon_fetch_headroom / _gpu / _local), stated once: headroom_kernel carves its arrays from these
+// element counts in this order -- all 8-byte arrays ahead of all 4-byte ones, an absent part has size 0 --, the launcher sizes the
+// launch with bytes(tile) and the host picks the tile from node_bytes() / reserve_bytes().
+struct HeadroomLds {
+    int nrows, K;                            // accumulated resource rows (>= 2), probes
+    bool devices, storage;                   // the device bound's sums; the storage bound's node state and staged chunk
+    __host__ __device__ size_t req(int tile) const { return (size_t)nrows * tile; }                  // u64 s_req[nrows][tile]
+    __host__ __device__ size_t dev(int tile) const { return devices ? (size_t)tile * kGpuDev : 0; }  // u64 s_dev[tile][8]
+    __host__ __device__ size_t vg(int tile) const { return storage ? (size_t)kLocalVG * tile : 0; }  // i64 s_vg[4][tile]
+    __host__ __device__ size_t fit() const { return (size_t)K; }                                     // u64 s_fit[K]
+    __host__ __device__ size_t cnt(int tile) const { return (size_t)tile; }                          // i32 s_cnt[tile]
+    __host__ __device__ size_t nodes() const { return (size_t)K; }                                   // i32 s_nodes[K]
+    __host__ __device__ size_t ldev(int tile) const { return storage ? (size_t)tile : 0; }           // i32 s_ldev[tile]
+    __host__ __device__ size_t stage() const { return storage ? (size_t)2 * kLocalChunk : 0; }       // i32 s_stage[2][kLocalChunk]
+    __host__ __device__ size_t bytes(int tile) const {
+        return 8 * (req(tile) + dev(tile) + vg(tile) + fit()) + 4 * (cnt(tile) + nodes() + ldev(tile) + stage());
+    }
+    __host__ __device__ size_t node_bytes() const { return bytes(1) - bytes(0); }    // rows x 8 + 4 (+ 64) (+ 36)
+    __host__ __device__ size_t fixed_bytes() const { return bytes(0); }              // 12 K (+ 4 096)
+    // the fixed bytes the tile is chosen for: a tile does not depend on K (fixed_bytes() <= reserve_bytes() for every K <= kMaxProbes)
+    __host__ __device__ size_t reserve_bytes() const { return kTileReserve + 4 * stage(); }
+};
+
+// simon_fetch_headroom (neither flag), simon_fetch_headroom_gpu (`devices`: the device bound, g complete) and simon_fetch_headroom_local
+// (`storage`: the storage bound, l complete or l.flags null; with `devices` all three bounds).  a.tile from usage_tile(N, lds.node_bytes(),
+// lds.reserve_bytes(), forced) of HeadroomLds lds{a.nrows, h.K, devices, storage}.
+hipError_t launch_headroom(const UsageCommon& a, const HeadroomArgs& h, const DevUsage& g, const LocalUsage& l, bool devices, bool storage, int S,
+                           hipStream_t st);
 
 }  // namespace simon

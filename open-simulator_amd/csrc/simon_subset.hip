@@ -248,9 +248,8 @@ __global__ __launch_bounds__(256) void gpu_usage_kernel(UsageCommon a, DevUsage 
     }
 }
 
-// The cap of one probe on node j of the tile that starts at t0, as headroom_kernel below computes it in place (that kernel keeps its
-// own copy: its code object stays what it was): pod slots, the resources fitsRequest compares and, DEV, the slices the node's devices
-// still hold.
+// The cap of one probe on node j of the tile that starts at t0 (headroom_kernel below): pod slots, the resources fitsRequest compares
+// and, DEV, the slices the node's devices still hold.
 template <bool DEV>
 __device__ __forceinline__ long long node_cap(const UsageCommon& a, const HeadroomArgs& h, const DevUsage& g, const ProbeRow& pr, long long gm, int gc,
                                               const unsigned long long* s_req, const int32_t* s_cnt, const unsigned long long* s_dev, int j, int t0) {
@@ -276,75 +275,6 @@ __device__ __forceinline__ long long node_cap(const UsageCommon& a, const Headro
         cap = gc > 0 ? min(cap, T / gc) : 0;
     }
     return cap;
-}
-
-// headroom_kernel: workgroup s = scenario s of the batch.  Per tile the same accumulation; then, per probe, every thread takes the cap
-// of its nodes of the tile and the workgroup adds them up in LDS.  Only [S][K] counters leave.  DEV (simon_fetch_headroom_gpu): the
-// tile also carries the device sums, and a probe with a GPU request is bounded by the slices the node's devices still hold:
-// T = sum over the node's devices of max(per_dev - used, 0) / mem, cap_gpu = T / count (GpuNodeInfo.AllocateGpuId accepts such a pod iff
-// T >= count, and every accepted pod lowers T by count).
-template <bool DEV>
-__global__ __launch_bounds__(256) void headroom_kernel(UsageCommon a, HeadroomArgs h, DevUsage g) {
-    extern __shared__ unsigned long long usage_smem[];
-    unsigned long long* const s_req = usage_smem;                       // [nrows][tile]
-    unsigned long long* const s_dev = s_req + (size_t)a.nrows * a.tile; // DEV: [tile][8]
-    unsigned long long* const s_fit = s_dev + (DEV ? (size_t)a.tile * kGpuDev : 0);   // [K]
-    int32_t* const s_cnt = (int32_t*)(s_fit + h.K);                     // [tile]
-    int32_t* const s_nodes = s_cnt + a.tile;                            // [K]
-    const int s = blockIdx.x, tid = threadIdx.x, N = a.N, K = h.K, W = (N + 63) >> 6;
-    const int32_t* __restrict__ const row = a.placement + (size_t)s * a.P;
-    const uint64_t* __restrict__ const srow = DEV && g.slices ? g.slices + (size_t)s * a.P : nullptr;
-    for (int k = tid; k < K; k += 256) { s_fit[k] = 0; s_nodes[k] = 0; }
-    for (int t0 = 0; t0 < N; t0 += a.tile) {
-        const int t1 = min(t0 + a.tile, N);
-        usage_accumulate<DEV>(a, row, t0, t1, s_req, s_cnt, &g, srow, s_dev);   // (its first barrier also covers s_fit / s_nodes)
-        for (int k = 0; k < K; ++k) {
-            const ProbeRow& pr = h.probes[k];
-            const uint64_t* __restrict__ const mask = h.probe_mask + (size_t)k * W;
-            const long long gm = DEV ? g.probe_mem[k] : 0;
-            const int gc = DEV ? g.probe_cnt[k] : 0;
-            long long fit = 0;
-            int nodes = 0;
-            for (int j = t0 + tid; j < t1; j += 256) {
-                if (!((mask[j >> 6] >> (j & 63)) & 1ull) || !usage_holds(a, s, j)) continue;
-                // (node_cap<DEV> above is this computation as a function, for headroom_local_kernel: a change here belongs there too)
-                long long cap = (long long)h.alloc_pods[j] - a.init_npods[j] - s_cnt[j - t0];      // pod slots
-                int ai = 0;                                             // (the accumulated rows are an ascending subset of the resource rows)
-                for (int r = 0; r < kUsageRows && cap > 0; ++r) {
-                    long long used = a.node_init[(size_t)r * N + j];
-                    if (ai < a.nrows && a.row_src[ai] == r) used += (long long)s_req[ai++ * a.tile + (j - t0)];
-                    if (!((pr.checked >> r) & 1u)) continue;
-                    const long long room = h.node_alloc[(size_t)r * N + j] - used, q = pr.q[r];
-                    if (room < 0) cap = 0;                              // over-committed: Allocatable < request + Requested whatever the request
-                    else if (q > 0) cap = min(cap, room / q);
-                }
-                if (DEV && gm > 0 && cap > 0) {
-                    long long T = 0;
-                    const int cnt = gc > 0 ? g.node_cnt[j] : 0;
-                    const long long per = g.per_dev[j];
-                    for (int d = 0; d < cnt; ++d) {
-                        const long long idle = per - g.init_used[(size_t)j * kGpuDev + d] - (long long)s_dev[dev_slot(j - t0, d)];
-                        if (idle > 0) T += idle / gm;                   // (an over-booked device holds nothing)
-                    }
-                    cap = gc > 0 ? min(cap, T / gc) : 0;
-                }
-                if (cap > 0) { fit += cap; ++nodes; }
-            }
-            for (int off = 32; off > 0; off >>= 1) {
-                fit += __shfl_xor(fit, off, 64);
-                nodes += __shfl_xor(nodes, off, 64);
-            }
-            if ((tid & 63) == 0 && nodes) {
-                atomicAdd(&s_fit[k], (unsigned long long)fit);
-                atomicAdd(&s_nodes[k], nodes);
-            }
-        }
-        __syncthreads();
-    }
-    for (int k = tid; k < K; k += 256) {
-        h.fit[(size_t)s * K + k] = (long long)s_fit[k];
-        if (h.fit_nodes) h.fit_nodes[(size_t)s * K + k] = s_nodes[k];
-    }
 }
 
 // ---- Open-Local: simon_fetch_local_usage / simon_fetch_headroom_local ----------------------------------------------------------------
@@ -503,44 +433,76 @@ __global__ __launch_bounds__(256) void local_usage_kernel(UsageCommon a, LocalUs
     }
 }
 
-// headroom_local_kernel: headroom_kernel with the storage bound (simon_fetch_headroom_local).  After the tile's accumulation and replay a
-// probe whose class has an Open-Local spec is bounded, per node, by the number of consecutive local_apply steps of that spec that
-// succeed on a private copy of the node's end state, at most the cap so far; a step that leaves the state unchanged (no volume, no
-// device) ends the count at the cap so far.  The state after m copies depends only on m and a failed copy changes nothing, so the
-// bound is what the scheduler places.  DEV as in headroom_kernel.
-template <bool DEV>
-__global__ __launch_bounds__(256) void headroom_local_kernel(UsageCommon a, HeadroomArgs h, DevUsage g, LocalUsage L) {
+// headroom_kernel: workgroup s = scenario s of the batch.  Per tile the same accumulation; then, per probe, every thread takes the cap
+// of its nodes of the tile (node_cap) and the workgroup adds them up in LDS.  Only [S][K] counters leave.  DEV
+// (simon_fetch_headroom_gpu): the tile also carries the device sums, and a probe with a GPU request is bounded by the slices the
+// node's devices still hold: T = sum over the node's devices of max(per_dev - used, 0) / mem, cap_gpu = T / count
+// (GpuNodeInfo.AllocateGpuId accepts such a pod iff T >= count, and every accepted pod lowers T by count).  LOCAL
+// (simon_fetch_headroom_local): the storage pods are replayed after the tile's accumulation, and a probe whose class has an Open-Local
+// spec is bounded, per node, by the number of consecutive local_apply steps of that spec that succeed on a private copy of the node's
+// end state, at most the cap so far; a step that leaves the state unchanged (no volume, no device) ends the count at the cap so far.
+// The state after m copies depends only on m and a failed copy changes nothing, so the bound is what the scheduler places.
+template <bool DEV, bool LOCAL>
+__global__ __launch_bounds__(256) void headroom_kernel(UsageCommon a, HeadroomArgs h, DevUsage g, LocalUsage L) {
     extern __shared__ unsigned long long usage_smem[];
+    const HeadroomLds lds{a.nrows, h.K, DEV, LOCAL};
     unsigned long long* const s_req = usage_smem;                       // [nrows][tile]
-    unsigned long long* const s_dev = s_req + (size_t)a.nrows * a.tile; // DEV: [tile][8]
-    long long* const s_vg = (long long*)(s_dev + (DEV ? (size_t)a.tile * kGpuDev : 0));   // [4][tile]
-    unsigned long long* const s_fit = (unsigned long long*)(s_vg + (size_t)kLocalVG * a.tile);   // [K]
-    int32_t* const s_cnt = (int32_t*)(s_fit + h.K);                     // [tile]
-    int32_t* const s_nodes = s_cnt + a.tile;                            // [K]
-    int32_t* const s_ldev = s_nodes + h.K;                              // [tile]
-    int32_t* const s_stage = s_ldev + a.tile;                           // [2][kLocalChunk]
+    unsigned long long* const s_dev = s_req + lds.req(a.tile);          // DEV: [tile][8]
+    long long* const s_vg = (long long*)(s_dev + lds.dev(a.tile));      // LOCAL: [4][tile]
+    unsigned long long* const s_fit = (unsigned long long*)(s_vg + lds.vg(a.tile));   // [K]
+    int32_t* const s_cnt = (int32_t*)(s_fit + lds.fit());               // [tile]
+    int32_t* const s_nodes = s_cnt + lds.cnt(a.tile);                   // [K]
+    int32_t* const s_ldev = s_nodes + lds.nodes();                      // LOCAL: [tile]
+    int32_t* const s_stage = s_ldev + lds.ldev(a.tile);                 // LOCAL: [2][kLocalChunk]
     const int s = blockIdx.x, tid = threadIdx.x, N = a.N, K = h.K, W = (N + 63) >> 6;
     const int32_t* __restrict__ const row = a.placement + (size_t)s * a.P;
     const uint64_t* __restrict__ const srow = DEV && g.slices ? g.slices + (size_t)s * a.P : nullptr;
-    const int order = a.scen[2 * s + 1];
-    const int lo = L.flags ? L.list_off[order] : 0, hi = L.flags ? L.list_off[order + 1] : 0;
+    const int order = LOCAL ? a.scen[2 * s + 1] : 0;
+    const int lo = LOCAL && L.flags ? L.list_off[order] : 0, hi = LOCAL && L.flags ? L.list_off[order + 1] : 0;
     for (int k = tid; k < K; k += 256) { s_fit[k] = 0; s_nodes[k] = 0; }
     for (int t0 = 0; t0 < N; t0 += a.tile) {
         const int t1 = min(t0 + a.tile, N);
         usage_accumulate<DEV>(a, row, t0, t1, s_req, s_cnt, &g, srow, s_dev);   // (its first barrier also covers s_fit / s_nodes)
-        local_replay(a, L, row, lo, hi, t0, t1, s_vg, s_ldev, s_stage);
+        if (LOCAL) local_replay(a, L, row, lo, hi, t0, t1, s_vg, s_ldev, s_stage);
         for (int k = 0; k < K; ++k) {
             const ProbeRow& pr = h.probes[k];
             const uint64_t* __restrict__ const mask = h.probe_mask + (size_t)k * W;
             const long long gm = DEV ? g.probe_mem[k] : 0;
             const int gc = DEV ? g.probe_cnt[k] : 0;
-            const int spec = L.flags ? L.probe_spec[k] : -1;
+            const int spec = LOCAL && L.flags ? L.probe_spec[k] : -1;
             long long fit = 0;
             int nodes = 0;
             for (int j = t0 + tid; j < t1; j += 256) {
                 if (!((mask[j >> 6] >> (j & 63)) & 1ull) || !usage_holds(a, s, j)) continue;
-                long long cap = node_cap<DEV>(a, h, g, pr, gm, gc, s_req, s_cnt, s_dev, j, t0);
-                if (spec >= 0 && cap > 0) {
+                long long cap;
+                if (DEV && !LOCAL) {
+                    // node_cap<true> in place, for this instantiation only, kept because in place the kernel compiles to the instruction
+                    // stream it had (so its time needs no argument), not because the call was shown to be too slow: with the call it
+                    // came out in another order and measured 2.790 against 2.778 ms (8 GPU probes, config 5's shape, five rounds: one
+                    // round 0.6 us past the parent's spread, profiles/usage_refactor/README.md).  A change there belongs here too.
+                    cap = (long long)h.alloc_pods[j] - a.init_npods[j] - s_cnt[j - t0];
+                    int ai = 0;
+                    for (int r = 0; r < kUsageRows && cap > 0; ++r) {
+                        long long used = a.node_init[(size_t)r * N + j];
+                        if (ai < a.nrows && a.row_src[ai] == r) used += (long long)s_req[ai++ * a.tile + (j - t0)];
+                        if (!((pr.checked >> r) & 1u)) continue;
+                        const long long room = h.node_alloc[(size_t)r * N + j] - used, q = pr.q[r];
+                        if (room < 0) cap = 0;
+                        else if (q > 0) cap = min(cap, room / q);
+                    }
+                    if (gm > 0 && cap > 0) {
+                        long long T = 0;
+                        const int cnt = gc > 0 ? g.node_cnt[j] : 0;
+                        const long long per = g.per_dev[j];
+                        for (int d = 0; d < cnt; ++d) {
+                            const long long idle = per - g.init_used[(size_t)j * kGpuDev + d] - (long long)s_dev[dev_slot(j - t0, d)];
+                            if (idle > 0) T += idle / gm;
+                        }
+                        cap = gc > 0 ? min(cap, T / gc) : 0;
+                    }
+                } else
+                    cap = node_cap<DEV>(a, h, g, pr, gm, gc, s_req, s_cnt, s_dev, j, t0);
+                if (LOCAL && spec >= 0 && cap > 0) {
                     LocalState st = local_load(s_vg, s_ldev, a.tile, j - t0);
                     long long m = 0;
                     while (m < cap) {
@@ -572,6 +534,15 @@ __global__ __launch_bounds__(256) void headroom_local_kernel(UsageCommon a, Head
 
 }  // namespace
 
+// every array a launch reads is there (`headroom`: the per-probe ones too); a LocalUsage without flags is a problem without Open-Local
+static bool complete(const DevUsage& g, bool headroom) {
+    return g.gpu_mem && g.node_cnt && g.init_used && (!headroom || (g.per_dev && g.probe_mem && g.probe_cnt));
+}
+static bool complete(const LocalUsage& l, bool headroom) {
+    return !l.flags || (l.specs && l.pod_spec && l.list && l.list_off && l.vg_cnt && l.vg_cap && l.vg_init && l.vg_name && l.dev_cnt && l.dev_cap &&
+                        l.dev_media && l.dev_init && (!headroom || l.probe_spec));
+}
+
 hipError_t launch_node_usage(const UsageCommon& a, const UsageOut& o, int n, hipStream_t st) {
     if (n <= 0 || a.N <= 0 || a.tile <= 0 || a.nrows < 2 || a.nrows > kUsageRows) return hipErrorInvalidValue;
     const size_t lds = (size_t)a.tile * usage_node_bytes(a.nrows);
@@ -580,53 +551,31 @@ hipError_t launch_node_usage(const UsageCommon& a, const UsageOut& o, int n, hip
     return hipGetLastError();
 }
 
-hipError_t launch_headroom(const UsageCommon& a, const HeadroomArgs& h, int S, hipStream_t st) {
-    if (S <= 0 || a.N <= 0 || a.tile <= 0 || a.nrows < 2 || a.nrows > kUsageRows || h.K < 1 || h.K > kMaxProbes) return hipErrorInvalidValue;
-    const size_t lds = (size_t)a.tile * usage_node_bytes(a.nrows) + (size_t)h.K * 12;
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(headroom_kernel<false>, dim3((unsigned)S), dim3(256), lds, st, a, h, DevUsage{});
-    return hipGetLastError();
-}
-
 hipError_t launch_gpu_usage(const UsageCommon& a, const DevUsage& g, const GpuUsageOut& o, int n, hipStream_t st) {
-    if (n <= 0 || a.N <= 0 || a.tile <= 0 || !o.dev_used || !g.gpu_mem || !g.node_cnt || !g.init_used) return hipErrorInvalidValue;
+    if (n <= 0 || a.N <= 0 || a.tile <= 0 || !o.dev_used || !complete(g, false)) return hipErrorInvalidValue;
     const size_t lds = (size_t)a.tile * usage_node_bytes(0, kDevBytes + (o.dev_pods ? kDevPodsBytes : 0));
     if (lds > 64 * 1024) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gpu_usage_kernel, dim3((unsigned)n), dim3(256), lds, st, a, g, o);
     return hipGetLastError();
 }
 
-hipError_t launch_headroom_gpu(const UsageCommon& a, const HeadroomArgs& h, const DevUsage& g, int S, hipStream_t st) {
-    if (S <= 0 || a.N <= 0 || a.tile <= 0 || a.nrows < 2 || a.nrows > kUsageRows || h.K < 1 || h.K > kMaxProbes) return hipErrorInvalidValue;
-    if (!g.gpu_mem || !g.node_cnt || !g.per_dev || !g.init_used || !g.probe_mem || !g.probe_cnt) return hipErrorInvalidValue;
-    const size_t lds = (size_t)a.tile * usage_node_bytes(a.nrows, kDevBytes) + (size_t)h.K * 12;
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(headroom_kernel<true>, dim3((unsigned)S), dim3(256), lds, st, a, h, g);
-    return hipGetLastError();
-}
-
 hipError_t launch_local_usage(const UsageCommon& a, const LocalUsage& l, const LocalUsageOut& o, int n, hipStream_t st) {
-    if (n <= 0 || a.N <= 0 || a.tile <= 0 || !o.vg_req) return hipErrorInvalidValue;
-    if (l.flags && (!l.specs || !l.pod_spec || !l.list || !l.list_off || !l.vg_cnt || !l.vg_cap || !l.vg_init || !l.vg_name || !l.dev_cnt || !l.dev_cap ||
-                    !l.dev_media || !l.dev_init))
-        return hipErrorInvalidValue;
-    const size_t lds = (size_t)a.tile * kLocalBytes + (size_t)kLocalChunk * 8;
+    if (n <= 0 || a.N <= 0 || a.tile <= 0 || !o.vg_req || !complete(l, false)) return hipErrorInvalidValue;
+    const size_t lds = (size_t)a.tile * kLocalBytes + kLocalStageBytes;
     if (lds > 64 * 1024) return hipErrorInvalidValue;
     hipLaunchKernelGGL(local_usage_kernel, dim3((unsigned)n), dim3(256), lds, st, a, l, o);
     return hipGetLastError();
 }
 
-hipError_t launch_headroom_local(const UsageCommon& a, const HeadroomArgs& h, const DevUsage& g, const LocalUsage& l, bool devices, int S,
-                                 hipStream_t st) {
+hipError_t launch_headroom(const UsageCommon& a, const HeadroomArgs& h, const DevUsage& g, const LocalUsage& l, bool devices, bool storage, int S,
+                           hipStream_t st) {
     if (S <= 0 || a.N <= 0 || a.tile <= 0 || a.nrows < 2 || a.nrows > kUsageRows || h.K < 1 || h.K > kMaxProbes) return hipErrorInvalidValue;
-    if (devices && (!g.gpu_mem || !g.node_cnt || !g.per_dev || !g.init_used || !g.probe_mem || !g.probe_cnt)) return hipErrorInvalidValue;
-    if (l.flags && (!l.specs || !l.pod_spec || !l.list || !l.list_off || !l.vg_cnt || !l.vg_cap || !l.vg_init || !l.vg_name || !l.dev_cnt || !l.dev_cap ||
-                    !l.dev_media || !l.dev_init || !l.probe_spec))
-        return hipErrorInvalidValue;
-    const size_t lds = (size_t)a.tile * usage_node_bytes(a.nrows, kLocalBytes + (devices ? kDevBytes : 0)) + (size_t)h.K * 12 + (size_t)kLocalChunk * 8;
+    if ((devices && !complete(g, true)) || (storage && !complete(l, true))) return hipErrorInvalidValue;
+    const size_t lds = HeadroomLds{a.nrows, h.K, devices, storage}.bytes(a.tile);
     if (lds > 64 * 1024) return hipErrorInvalidValue;
-    if (devices) hipLaunchKernelGGL(headroom_local_kernel<true>, dim3((unsigned)S), dim3(256), lds, st, a, h, g, l);
-    else hipLaunchKernelGGL(headroom_local_kernel<false>, dim3((unsigned)S), dim3(256), lds, st, a, h, DevUsage{}, l);
+    const auto kernel = storage ? (devices ? headroom_kernel<true, true> : headroom_kernel<false, true>)
+                                : (devices ? headroom_kernel<true, false> : headroom_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)S), dim3(256), lds, st, a, h, devices ? g : DevUsage{}, storage ? l : LocalUsage{});
     return hipGetLastError();
 }
 

@@ -4,7 +4,7 @@ fetching the placement matrix and gpu_slices and reducing them with numpy on the
 devices=True) -- at config 5's shape (synth.config5: S = 256, P = 50 000, N = 5 000, devices recorded).  Wall time of each call, best of
 five after one run; the device figures are compared with the host's (they must be equal).  The numpy reduction runs over the first
 --host-scenarios scenarios (its cost is linear in the scenarios; the line says how many).  Under `rocprofv3 --kernel-trace --stats --
-python ... --no-host --only usage|headroom|fetch` the trace gives the kernel time of gpu_usage_kernel / headroom_kernel<true> / the
+python ... --no-host --only usage|headroom|fetch` the trace gives the kernel time of gpu_usage_kernel / headroom_kernel<true, false> / the
 copies of the parent's road, each in a run of its own.
 usage: python profiles/gpu_usage/gpu_usage_probe.py [--no-host] [--only usage|headroom|fetch] [--host-scenarios 32] [--tiles 256,512]"""
 import argparse

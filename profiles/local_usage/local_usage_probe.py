@@ -6,7 +6,7 @@ config 5's pod shapes (synth.gen_pods, P = 50 000) of which 10 % ask for local v
 S = 64 and 256 prefix scenarios over four orders.  Wall time of each call, best of five after one run; the device figures are compared
 with the host's over the first --host-scenarios scenarios (they must be equal; the host replay is a Python loop, linear in the
 scenarios).  Under `rocprofv3 --kernel-trace --stats -- python ... --no-host --only usage|headroom|fetch --scenarios 256` the trace
-gives the kernel time of local_usage_kernel / headroom_local_kernel<false> / the copy of the parent's road, each in a run of its own.
+gives the kernel time of local_usage_kernel / headroom_kernel<false, true> / the copy of the parent's road, each in a run of its own.
 usage: python profiles/local_usage/local_usage_probe.py [--no-host] [--only usage|headroom|fetch] [--host-scenarios 4] [--scenarios 64,256] [--tiles 512]"""
 import argparse
 import os

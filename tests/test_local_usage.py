@@ -2,8 +2,8 @@
 bit for bit against the host replay (simulate.host_local_usage / host_headroom(storage=True), which test_local_usage_host.py checks
 against the unmodified oracle) of the placements the device itself fetched, and those placements against the oracle -- the random
 cases with the tile unset and forced to 7 and 64 nodes, a pile-up longer than one staged chunk, two orders in one batch, listed
-scenarios with repeats and in reverse, GPU share next to Open-Local, a problem without Open-Local, every refusal.  Run with -m gpu on
-an MI355X."""
+scenarios with repeats and in reverse, GPU share next to Open-Local, 1 / 5 / 64 probes on all three headroom calls, a problem without
+Open-Local, every refusal.  Run with -m gpu on an MI355X."""
 import ctypes as C
 import functools
 
@@ -189,6 +189,39 @@ def test_gpu_share_next_to_open_local_all_three_bounds(monkeypatch):
         assert (fit[:, :k] < dev[:, :k]).any() and (dev[:, :k] < plain[:, :k]).any(), "storage below devices below resources somewhere"
     for j, p in enumerate(both[:2]):
         UU.check_probe_against_oracle(prob, N, orders[1], ref.placement[0], p, fit[0, j])
+
+
+@functools.lru_cache(maxsize=None)
+def _probe_count_case():
+    """The problem of the test above with the first 64 pod ids as probes (P = 80: none repeats), and, from the oracle's placements and
+    devices, the host restatement of all three calls for the 64 -- a probe's column does not depend on its neighbours, so the first K
+    columns are the answer for the first K probes."""
+    N, P = 23, 80
+    prob = randprob.rand_problem(70, N=N, P=P, local=True, gpu=True, static_mask=True, init_state=True, gates=True)
+    orders = np.stack([np.arange(P), np.random.default_rng(3).permutation(P)]).astype(np.int32)
+    scen = np.array([[N, 1], [N - 6, 0], [N, 0]], np.int32)
+    ref = O.run(prob, scen, orders, want_gpu_slices=True)
+    held, probes = UU.held_rows(prob, scen), np.arange(64, dtype=np.int32)
+    want = {mode: sim.host_headroom(prob, ref.placement, held, probes, ref.gpu_slices, devices=mode == "devices", storage=mode == "storage",
+                                    orders=orders, scen=scen) for mode in ("resources", "devices", "storage")}
+    return prob, scen, orders, ref, want
+
+
+@pytest.mark.parametrize("tile", [None, 7])
+@pytest.mark.parametrize("K", [1, 5, 64])
+def test_probe_count_edges_on_all_three_headroom_calls(K, tile, monkeypatch):
+    """s_fit[K] and s_nodes[K] sit between the per-tile arrays of the headroom workgroup's LDS: one probe, a few, and SIMON_MAX_PROBES."""
+    prob, scen, orders, ref, want = _probe_count_case()
+    probes = np.arange(K, dtype=np.int32)
+    _tile(monkeypatch, tile)
+    with capi.Context(0) as ctx:
+        res = _run(ctx, prob, scen, orders, slices=True)
+        assert res.placement.tolist() == ref.placement.tolist() and res.gpu_slices.tolist() == ref.gpu_slices.tolist()
+        for mode, flags in (("resources", {}), ("devices", dict(devices=True)), ("storage", dict(storage=True))):
+            fit, nodes, exact = ctx.fetch_headroom(probes, nodes=True, **flags)
+            rf, rn, rx = want[mode]
+            assert fit.shape == (len(scen), K) and nodes.shape == (len(scen), K), mode
+            assert fit.tolist() == rf[:, :K].tolist() and nodes.tolist() == rn[:, :K].tolist() and exact.tolist() == rx[:K].tolist(), mode
 
 
 @pytest.mark.parametrize("gpu", [False, True])
