@@ -110,6 +110,31 @@ __device__ __forceinline__ int la_term_t(double r, double rc100) {   // == la_te
     const double C = 100.0 + 0x1.0p-33;
     return (int)__builtin_fma(-r, rc100, C);
 }
+// `r >= cap ? 0 : la_term_t(r, rc100)` as ONE conversion (round 14): v_cvt_u32_f64 truncates towards zero and gives 0 for every negative value, -inf
+// and NaN, so the select behind the term goes (a C++ cast of those is undefined, hence the instruction by name; its result is read several
+// instructions on and costs no hazard s_nop).  With v = fma(-r, rc100, 100 + 2^-33), within 3e-14 of 100 (cap - r) / cap + 2^-33:
+//   r <  cap: v lies in (0, 100 + 2^-33 + 3e-14) and truncates as the signed conversion does;
+//   r == cap: v = 2^-33 +- 3e-14, inside (0, 1): 0;
+//   r >  cap: v < 2^-33 + 3e-14 (the error is relative to r rc100, so v falls with r): inside (-1, 1) it truncates to 0, below it is clamped to 0;
+//   cap == 0: rc100 = +inf, v = -inf (r > 0) or NaN (r == 0): 0 -- where `r >= 0` makes the select give 0.
+// (tests/test_la_term_sat.py compares the two forms on the host, under the sanitizers)
+__device__ __forceinline__ int la_term_sat_t(double r, double rc100) {
+    const double C = 100.0 + 0x1.0p-33;
+    const double v = __builtin_fma(-r, rc100, C);
+    unsigned t;
+    asm("v_cvt_u32_f64 %0, %1" : "=v"(t) : "v"(v));
+    return (int)t;
+}
+// The sum of the two terms the evaluation halves: the second conversion and the add stand in ONE statement behind the first, so a single register
+// lives across the BalancedAllocation sequence between them and the add -- left to the scheduler both terms did, and the kernels held two to five VGPRs
+// more, some across a waves-per-SIMD step.  (A conversion's result read by the next VALU instruction is an ordinary, interlocked dependency.)
+__device__ __forceinline__ int la_sum_sat_t(double r_c, double rc100_c, double r_m, double rc100_m) {
+    const double C = 100.0 + 0x1.0p-33;
+    unsigned s = (unsigned)la_term_sat_t(r_c, rc100_c), t;
+    const double v = __builtin_fma(-r_m, rc100_m, C);
+    asm("v_cvt_u32_f64 %1, %2\n\tv_add_u32_e32 %0, %0, %1" : "+v"(s), "=&v"(t) : "v"(v));
+    return (int)s;
+}
 
 // max over the 16 bytes of one table row of (byte << 4 | 15 - position)
 __device__ __forceinline__ unsigned block_key16_t(const uint4 R) {
@@ -327,23 +352,54 @@ __device__ __forceinline__ unsigned long long gpu_commit_t(unsigned (&u)[8], int
 
 // (feasible, LeastAllocated + BalancedAllocation) of one signature on one node: 0 when NodeResourcesFit fails
 // (fit.go:230-302), else 1 + score.  Same fp64 sequences as simon_fast.hip::eval_slot.  Shared by table_kernel (prologue, refresh) and table_image_kernel.
+// Round 14, eval_node_fit_t: the same evaluation with the value and the fit apart, the fit also as its three compares -- the one-level straight-line
+// cycle (kFitMask) joins their masks with its own as scalar logic (fit_mask_t; simon_table_assume.inc) and selects once -- and with the
+// LeastAllocated terms as saturating converts (la_term_sat_t).  eval_node_t<NZEQ, true> is its byte: the prologue of those kernels and the image
+// kernel that feeds it.  Every other instantiation takes eval_node_t<NZEQ, false>, the sequence it always had, and compiles to the code it had.
+struct NodeEval { unsigned val; bool ok, free, fit_c, fit_m; };       // 1 + score whatever the fit says; NodeResourcesFit; a free pod slot, cpu and memory fit
 template <bool NZEQ>
-__device__ __forceinline__ unsigned eval_node_t(double q_req_c, double q_req_m, double q_nz_c, double q_nz_m, bool q_zero, double rq_c, double rq_m,
-                                                double nzs_c, double nzs_m, int freep, const ShapeRow& sh) {
+__device__ __forceinline__ NodeEval eval_node_fit_t(double q_req_c, double q_req_m, double q_nz_c, double q_nz_m, bool q_zero, double rq_c, double rq_m,
+                                                    double nzs_c, double nzs_m, int freep, const ShapeRow& sh) {
     const double t_c = rq_c + q_req_c, t_m = rq_m + q_req_m;
-    const bool res_ok = (sh.cap_c >= t_c) && (sh.cap_m >= t_m);
-    const bool ok = (freep >= 1) && (q_zero || res_ok);
-    // resource_allocation.go:91-98: requested = NonZeroRequested + pod non-zero request
+    const bool fit_c = sh.cap_c >= t_c, fit_m = sh.cap_m >= t_m, free = freep >= 1;
+    const bool res_ok = fit_c && fit_m;
+    const bool ok = free && (q_zero || res_ok);
     const double r_c = NZEQ ? t_c : nzs_c + q_nz_c;
     const double r_m = NZEQ ? t_m : nzs_m + q_nz_m;
-    const bool ge_c = r_c >= sh.cap_c, ge_m = r_m >= sh.cap_m;
-    const int la_c = ge_c ? 0 : la_term_t(r_c, sh.rc100_c);           // least_allocated.go:108-117
-    const int la_m = ge_m ? 0 : la_term_t(r_m, sh.rc100_m);
-    const double cf = div_by_rcp1(r_c, sh.cap_c, sh.rc_c);            // balanced_allocation.go:82-119; operands < 2^31 (simon_device.h)
+    const bool ge_c = r_c >= sh.cap_c, ge_m = r_m >= sh.cap_m;        // (stay for the BalancedAllocation mask)
+    const int la_sum = la_sum_sat_t(r_c, sh.rc100_c, r_m, sh.rc100_m);   // least_allocated.go:108-117, each term 0 at and beyond the capacity
+    const double cf = div_by_rcp1(r_c, sh.cap_c, sh.rc_c);
     const double mf = div_by_rcp1(r_m, sh.cap_m, sh.rc_m);
     const int bs = (int)((1.0 - __builtin_fabs(cf - mf)) * 100.0);
-    const int base = ((la_c + la_m) >> 1) + ((ge_c || ge_m) ? 0 : bs);
-    return ok ? (unsigned)(base + 1) : 0u;
+    const int base = (la_sum >> 1) + ((ge_c || ge_m) ? 0 : bs);
+    return NodeEval{(unsigned)(base + 1), ok, free, fit_c, fit_m};
+}
+template <bool NZEQ, bool SAT>
+__device__ __forceinline__ unsigned eval_node_t(double q_req_c, double q_req_m, double q_nz_c, double q_nz_m, bool q_zero, double rq_c, double rq_m,
+                                                double nzs_c, double nzs_m, int freep, const ShapeRow& sh) {
+    if constexpr (SAT) {
+        const NodeEval e = eval_node_fit_t<NZEQ>(q_req_c, q_req_m, q_nz_c, q_nz_m, q_zero, rq_c, rq_m, nzs_c, nzs_m, freep, sh);
+        return e.ok ? e.val : 0u;
+    } else {
+        const double t_c = rq_c + q_req_c, t_m = rq_m + q_req_m;
+        const bool res_ok = (sh.cap_c >= t_c) && (sh.cap_m >= t_m);
+        const bool ok = (freep >= 1) && (q_zero || res_ok);
+        // resource_allocation.go:91-98: requested = NonZeroRequested + pod non-zero request
+        const double r_c = NZEQ ? t_c : nzs_c + q_nz_c;
+        const double r_m = NZEQ ? t_m : nzs_m + q_nz_m;
+        const bool ge_c = r_c >= sh.cap_c, ge_m = r_m >= sh.cap_m;
+        const int la_c = ge_c ? 0 : la_term_t(r_c, sh.rc100_c);           // least_allocated.go:108-117
+        const int la_m = ge_m ? 0 : la_term_t(r_m, sh.rc100_m);
+        const double cf = div_by_rcp1(r_c, sh.cap_c, sh.rc_c);            // balanced_allocation.go:82-119; operands < 2^31 (simon_device.h)
+        const double mf = div_by_rcp1(r_m, sh.cap_m, sh.rc_m);
+        const int bs = (int)((1.0 - __builtin_fabs(cf - mf)) * 100.0);
+        const int base = ((la_c + la_m) >> 1) + ((ge_c || ge_m) ? 0 : bs);
+        return ok ? (unsigned)(base + 1) : 0u;
+    }
+}
+// The fit as a mask of the wave (every lane active): ballots of plain compares are the compares' own SGPR pairs, the rest is scalar logic.
+__device__ __forceinline__ unsigned long long fit_mask_t(const NodeEval& e, unsigned long long free_m, unsigned long long zero_m) {
+    return free_m & (zero_m | (__ballot(e.fit_c) & __ballot(e.fit_m)));
 }
 
 // KQ: signatures per lane (1: K <= 64, 2: K <= 128).  HAS_PIN: the stream holds pinned pods (own instantiation: the extra
@@ -476,6 +532,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     // as well: it serves the problems with many node classes, where a row loses several classes between two of its uses and the lazy scheme re-bases once for all of
     // them (config 3 on 80 shapes, 4 096 scenarios: 35.09 / 34.82 ms lazy, 36.72 / 35.76 ms at the event), and five of its kernels held one VGPR more.
     constexpr bool kEager = kStraight && !kCls4 && !COARSE;
+    // Round 14: the same instantiations with the workspace in HBM take the evaluation's fit as a mask of the wave, apart from the value (eval_node_fit_t):
+    // the new byte, the lanes that refresh and the "a byte dropped to 0" test are scalar logic on it (simon_table_assume.inc; every lane is active in
+    // that cycle), and their LeastAllocated terms are saturating converts (la_term_sat_t).  Every other instantiation keeps the code it had -- those
+    // with the workspace in LDS too: config 3 at 64 scenarios measured 4.83 -> 4.90 ms with the two.
+    constexpr bool kFitMask = kEager && !LDSWS;
     // Round 13: where the cycle is straight-line code and the workspace is in HBM, the touched node's state is stored by every lane (one address, one
     // value) instead of by lane 0 inside an EXEC region of its own.  Not for the three instructions of the region: behind a store that MAY have been
     // issued the compiler's wait for the table byte, in front of the refresh, was vmcnt(0) -- the store's acknowledgement from memory sat on every
@@ -671,7 +732,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
 
     auto eval_node = [&](double q_req_c, double q_req_m, double q_nz_c, double q_nz_m, bool q_zero, double rq_c, double rq_m,
                          double nzs_c, double nzs_m, int freep, const ShapeRow& sh) -> unsigned {
-        return eval_node_t<NZEQ>(q_req_c, q_req_m, q_nz_c, q_nz_m, q_zero, rq_c, rq_m, nzs_c, nzs_m, freep, sh);
+        return eval_node_t<NZEQ, kFitMask>(q_req_c, q_req_m, q_nz_c, q_nz_m, q_zero, rq_c, rq_m, nzs_c, nzs_m, freep, sh);
+    };
+    auto eval_node_fit = [&](double q_req_c, double q_req_m, double q_nz_c, double q_nz_m, bool q_zero, double rq_c, double rq_m,
+                             double nzs_c, double nzs_m, int freep, const ShapeRow& sh) -> NodeEval {
+        return eval_node_fit_t<NZEQ>(q_req_c, q_req_m, q_nz_c, q_nz_m, q_zero, rq_c, rq_m, nzs_c, nzs_m, freep, sh);
     };
 
     // ---- prologue 2: node rows, table and summary; lanes = 64 consecutive positions (4 blocks) ----
@@ -891,13 +956,19 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPREAD 
     unsigned my_greq[KQ];                                             // GPU fold: this lane's signatures' GPU requests (SigRow::pad)
     int my_gnum[KQ];
     unsigned my_dirty = 0;
+    // (round 14, kFitMask) kvalid and my_zero are masks of the wave first, taken where they are compared, and flags by the masks' lane bits: the
+    // straight-line cycle joins the masks with the evaluation's as scalar logic (a ballot of a flag that arrives from another block is
+    // materialised per lane and compared again), and one SGPR pair serves both readings
+    unsigned long long kvalid_m[KQ], zero_m[KQ];                      // (kFitMask only)
 #pragma unroll
     for (int q = 0; q < KQ; ++q) {
-        kvalid[q] = lane + 64 * q < K;
+        if constexpr (kFitMask) { kvalid_m[q] = __ballot(lane + 64 * q < K); kvalid[q] = __builtin_amdgcn_inverse_ballot_w64(kvalid_m[q]); }
+        else kvalid[q] = lane + 64 * q < K;
         kk[q] = kvalid[q] ? lane + 64 * q : 0;
         const SigRow r = sigs[kk[q]];
         my_req_c[q] = r.req_c; my_req_m[q] = r.req_m; my_nz_c[q] = r.nz_c; my_nz_m[q] = r.nz_m;
-        my_zero[q] = r.flags & 1u;
+        if constexpr (kFitMask) { zero_m[q] = __ballot((r.flags & 1u) != 0u); my_zero[q] = __builtin_amdgcn_inverse_ballot_w64(zero_m[q]); }
+        else my_zero[q] = r.flags & 1u;
         if constexpr (kCls4) my_tc[q] = r.cls;
         my_greq[q] = (unsigned)r.pad[0]; my_gnum[q] = kvalid[q] ? r.pad[1] : 0;
         my_add_c[q] = (unsigned)r.req_c; my_add_m[q] = (unsigned)r.req_m;
@@ -2512,7 +2583,7 @@ __global__ __launch_bounds__(64) void table_image_kernel(const TableCold* __rest
     const ShapeRow sh = cold->shapes[d];
     for (int k = blockIdx.y; k < K; k += gridDim.y) {
         const SigRow q = cold->sigs[k];
-        unsigned b = eval_node_t<NZEQ>(q.req_c, q.req_m, q.nz_c, q.nz_m, q.flags & 1u, (double)st.rq_c, (double)st.rq_m, (double)z.x, (double)z.y, (int)st.freep, sh);
+        unsigned b = eval_node_t<NZEQ, true>(q.req_c, q.req_m, q.nz_c, q.nz_m, q.flags & 1u, (double)st.rq_c, (double)st.rq_m, (double)z.x, (double)z.y, (int)st.freep, sh);
         b = real ? b : 0u;
         if (static_mask != nullptr) {                                 // NodeUnschedulable/NodeName/TaintToleration/NodeAffinity: static per (class, node)
             const uint64_t w = static_mask[(size_t)q.cls * sc.mask_words + (j >> 6)];

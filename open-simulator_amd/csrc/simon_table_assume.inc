@@ -212,6 +212,10 @@
             }
             // (kLanesStore: every lane holds the same state and stores it to the same address -- no EXEC region around the store, and the wait for
             // the table byte below no longer waits for this store to be acknowledged, see simon_table.hip)
+            // (kFitMask: the free-slot compare of the evaluation's fit, taken here, ahead of the barrier below: left to the scheduler it came last and the
+            // slot count lived through the evaluation, one VGPR -- for config 3's fused kernel the one across a waves-per-SIMD step)
+            unsigned long long free_m;                                 // (kFitMask only)
+            if constexpr (kFitMask) free_m = __ballot((int)st.freep >= 1);
             if (kLanesStore || lane == 0) *stp = st;
             // (the region's end was a boundary for the instruction scheduler as well: without one here it interleaves the state update with the
             // evaluation, and the kernels hold up to seven VGPRs more)
@@ -283,15 +287,51 @@
 #pragma unroll
                 for (int q = 0; q < KQ; ++q) asm volatile("" : : "v"(snq[q]), "s"(selA.x), "s"(selB.x));
             }
-            nbq[0] = eval_node(my_req_c[0], my_req_m[0], my_nz_c[0], my_nz_m[0], my_zero[0], rq_c, rq_m, nzc, nzm, (int)st.freep, sh);
-            if constexpr (KQ > 1) {
-                if (sc.static_tables & kStTwins) nbq[KQ - 1] = nbq[0];
-                else nbq[KQ - 1] = eval_node(my_req_c[KQ - 1], my_req_m[KQ - 1], my_nz_c[KQ - 1], my_nz_m[KQ - 1], my_zero[KQ - 1], rq_c, rq_m, nzc, nzm, (int)st.freep, sh);
-            }
-            if constexpr (kFoldable) {
-                if (__builtin_expect(fold, 0)) {                      // folded exclusions: the signatures this landing rules out get byte 0
+            // Round 14 (kFitMask: one-level layout, re-base at the event, no folds): the evaluation hands out its value and its fit apart, the fit as a mask
+            // of the wave (every lane is active here), and what the refresh and the re-base ask is scalar logic on SGPR pairs -- the new byte is ONE select on
+            // fit & (old != 0), the lanes that refresh are valid & (old != 0) (a byte that comes out as it was is stored again: same byte, same entry;
+            // the `nb != old` of the others is a compare per cycle), and "a byte dropped to 0" is (old != 0) & ~fit, formed HERE, in the block of the
+            // compares: asked for behind the refresh's region, a flag is materialised per lane and compared again.  The compare of the old byte is the
+            // only vector instruction the three cost.  A byte that is 0 stays 0 (static mask, monotone infeasibility) and is not counted as gone.
+            unsigned long long goneq[KQ];                              // (kFitMask only)
+            if constexpr (kFitMask) {
+                NodeEval ev[KQ];
+                unsigned long long fitq[KQ];
+                ev[0] = eval_node_fit(my_req_c[0], my_req_m[0], my_nz_c[0], my_nz_m[0], my_zero[0], rq_c, rq_m, nzc, nzm, (int)st.freep, sh);
+                fitq[0] = fit_mask_t(ev[0], free_m, zero_m[0]);
+                if constexpr (KQ > 1) {
+                    if (sc.static_tables & kStTwins) { ev[KQ - 1] = ev[0]; fitq[KQ - 1] = fitq[0]; }   // the twin takes the one evaluation's value and mask
+                    else {
+                        ev[KQ - 1] = eval_node_fit(my_req_c[KQ - 1], my_req_m[KQ - 1], my_nz_c[KQ - 1], my_nz_m[KQ - 1], my_zero[KQ - 1], rq_c, rq_m, nzc, nzm, (int)st.freep, sh);
+                        fitq[KQ - 1] = fit_mask_t(ev[KQ - 1], free_m, zero_m[KQ - 1]);
+                    }
+                }
+                unsigned long long oldm[KQ];
 #pragma unroll
-                    for (int q = 0; q < KQ; ++q) nbq[q] = ((xfold[q] >> (kk[q] & 31)) & 1u) ? 0u : nbq[q];
+                for (int q = 0; q < KQ; ++q) {
+                    oldm[q] = __ballot(oldq[q] != 0u);
+                    goneq[q] = oldm[q] & ~fitq[q];
+                }
+#pragma unroll
+                for (int q = 0; q < KQ; ++q) {
+                    nbq[q] = __builtin_amdgcn_inverse_ballot_w64(fitq[q] & oldm[q]) ? ev[q].val : 0u;
+                    if (__builtin_amdgcn_inverse_ballot_w64(kvalid_m[q] & oldm[q])) {
+                        byte_at(bytep[q], pos) = (unsigned char)nbq[q];
+                        const unsigned m = block_key16_patched<kStraight>(T[q], nbq[q], pos, selA, selB, pos_c, c15);
+                        s_sum[kk[q] * nbp + blk] = (unsigned short)((m >> 4) ? m + (snq[q] << 4) : 0u);
+                    }
+                }
+            } else {
+                nbq[0] = eval_node(my_req_c[0], my_req_m[0], my_nz_c[0], my_nz_m[0], my_zero[0], rq_c, rq_m, nzc, nzm, (int)st.freep, sh);
+                if constexpr (KQ > 1) {
+                    if (sc.static_tables & kStTwins) nbq[KQ - 1] = nbq[0];
+                    else nbq[KQ - 1] = eval_node(my_req_c[KQ - 1], my_req_m[KQ - 1], my_nz_c[KQ - 1], my_nz_m[KQ - 1], my_zero[KQ - 1], rq_c, rq_m, nzc, nzm, (int)st.freep, sh);
+                }
+                if constexpr (kFoldable) {
+                    if (__builtin_expect(fold, 0)) {                      // folded exclusions: the signatures this landing rules out get byte 0
+#pragma unroll
+                        for (int q = 0; q < KQ; ++q) nbq[q] = ((xfold[q] >> (kk[q] & 31)) & 1u) ? 0u : nbq[q];
+                    }
                 }
             }
             unsigned gu[8] = {0, 0, 0, 0, 0, 0, 0, 0};                   // GPU fold: the landing node's devices after Reserve (MANY: the further groups read them)
@@ -326,10 +366,12 @@
                     }
                 }
             }
+            if constexpr (!kFitMask) {                                 // (kFitMask: refreshed above)
 #pragma unroll
-            for (int q = 0; q < KQ; ++q)
-                refresh_sig(kk[q], kvalid[q], nbq[q], bytep[q], T[q], COARSE ? F[q] : make_uint2(0u, 0u),
-                            oldq[q], snq[q], q);
+                for (int q = 0; q < KQ; ++q)
+                    refresh_sig(kk[q], kvalid[q], nbq[q], bytep[q], T[q], COARSE ? F[q] : make_uint2(0u, 0u),
+                                oldq[q], snq[q], q);
+            }
             if constexpr (kEager) {
                 // The node stopped being feasible for some signature (one uniform test where the lanes' own regions stood): the lanes count their
                 // (signature, class) down, lane-local as ever, and every row whose counter reached 0 -- the class left the signature's feasible set, its
@@ -341,7 +383,16 @@
                 bool gone = false;
 #pragma unroll
                 for (int q = 0; q < KQ; ++q) gone |= oldq[q] > (nbq[q] << 8);
-                if (__builtin_expect(__ballot(gone) != 0ull, 0)) {
+                // (kFitMask: the uniform test is the masks' own, (old != 0) & ~fit from above, and costs no vector instruction -- the compares of `gone` are
+                // dead there; the rare block's per-lane test reads the bytes as ever: the new byte is 0 exactly where the fit failed)
+                bool any_gone;
+                if constexpr (kFitMask) {
+                    unsigned long long gone_m = 0ull;
+#pragma unroll
+                    for (int q = 0; q < KQ; ++q) gone_m |= goneq[q];
+                    any_gone = gone_m != 0ull;
+                } else any_gone = __ballot(gone) != 0ull;
+                if (__builtin_expect(any_gone, 0)) {
                     unsigned long long emptied[KQ];
 #pragma unroll
                     for (int q = 0; q < KQ; ++q) {
