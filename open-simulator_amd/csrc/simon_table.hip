@@ -300,6 +300,7 @@ __host__ __device__ inline size_t table_ws_of(int K, int ni, bool nzeq, bool coa
 // Open-Gpu-Share on gcd-normalised 32-bit quantities (all < 2^31): GpuNodeInfo.AllocateGpuId, pkg/type/open-gpu-share/cache/
 // gpunodeinfo.go:232-290 -- the feasibility question Filter asks (open-gpu-share.go:74-78) and the commit Reserve performs
 // (:147-188), the same walk as simon_wide.hip::gpu_feasible / gpu_commit_regs.
+// The 31-bit edges, over-booked devices, slices and the tightest-fit rule are verified by tests/test_gpu_fit_duels.py (tests/fit_duel_util.py).
 __device__ __forceinline__ bool gpu_fits_t(const unsigned (&u)[8], int cnt, unsigned tot, unsigned req, int num) {
     if (req == 0u || num <= 0 || cnt <= 0) return false;
     if (num == 1) {                                       // tightest fit exists iff some device has room (:255-267)
@@ -410,6 +411,7 @@ __device__ __forceinline__ unsigned long long fit_mask_t(const NodeEval& e, unsi
 // and a wave takes the one its own scenario fits (table_kernel with LO, behind this one) -- a choice per wave ahead of the prologue.
 // fitsRequest's ephemeral-storage and extended-resource checks (fit.go:264-299) of one request on one node: component 0 is checked
 // whatever the request, an extended resource only when the pod names it (non-zero)
+// (unsigned on purpose: req + used reaches 2^32 - 2; verified by tests/test_gpu_fit_duels.py on the fit duels of tests/fit_duel_util.py)
 __device__ __forceinline__ bool xres_fits_t(const unsigned (&req)[5], const unsigned (&used)[5], const unsigned (&alloc)[5]) {
     bool ok = !(alloc[0] < req[0] + used[0]);
 #pragma unroll
