@@ -449,6 +449,16 @@ int simon_set_scenario_nodes(simon_ctx* ctx, const uint32_t* present /* [S][(N+3
  * node-subset batch is in effect. */
 int simon_set_pod_eviction(simon_ctx* ctx, const uint8_t* evict /* [P] */);
 
+/* Segmented and node-subset batches on the all-feature kernel (opt-in; additive, ABI stays 7).  A context option: on != 0 lets the next
+ * simon_run_loaded RUN such a batch when its problem routes to SIMON_KERNEL_WIDE (Open-Local storage, hard hostname spread constraints,
+ * preset pods with ephemeral or extended requests, more than 128 node classes, counters beyond a byte, SIMON_FORCE_WIDE=1) instead of
+ * refusing it: one workgroup per scenario over the pool, presence from the batch's rank rows, every rule of the batch kinds above
+ * (gates, pins, eviction flags, pod subsets, simon_min_plan* over each scenario's own totals, used_vg over its own nodes).
+ * simon_get_stats reports SIMON_KERNEL_WIDE, generation 0.  simon_explain_own_batch then accepts a wide-routed batch too, unless the
+ * problem has Open-Local storage (refused as before: replay such a scenario's own problem).  Off by default -- both refusals keep their
+ * text and code -- and sticky: it survives every load until it is set again.  SIMON_EINVAL: ctx == NULL. */
+int simon_set_own_nodes_all_feature(simon_ctx* ctx, int32_t on);
+
 /* Pod-subset batches: the workload itself varies by scenario -- which of these apps fit on the cluster together, what has to be left
  * out, how many new nodes each release combination costs.  Scenario s holds pod p iff bit (p & 31) of present[s][p >> 5] is set (by
  * POD ID, not by stream position) AND its gate admits it (the prefix rule gate_node < n_nodes, or "the scenario holds gate_node" in a

@@ -588,6 +588,7 @@ EXPORTS = [
     "simon_group_set_scalar_entries", "simon_group_set_pod_priorities", "simon_group_fetch_preempt_risk",
     "simon_set_image_locality", "simon_group_set_image_locality",
     "simon_set_scenario_segments", "simon_set_scenario_nodes", "simon_fetch_node_ranks", "simon_set_pod_eviction",
+    "simon_set_own_nodes_all_feature",
     "simon_set_scenario_pods", "simon_fetch_group_counts", "simon_fetch_node_usage", "simon_fetch_headroom",
     "simon_fetch_gpu_usage", "simon_fetch_headroom_gpu", "simon_fetch_local_usage", "simon_fetch_headroom_local",
     "simon_group_create", "simon_group_destroy", "simon_group_last_error", "simon_group_size", "simon_group_member",
@@ -633,6 +634,8 @@ def load_library(path: Optional[str] = None):
     lib.simon_fetch_node_ranks.argtypes = [vp, _p32]
     lib.simon_set_pod_eviction.argtypes = [vp, C.POINTER(C.c_uint8)]
     lib.simon_set_pod_eviction.restype = C.c_int
+    lib.simon_set_own_nodes_all_feature.argtypes = [vp, C.c_int32]
+    lib.simon_set_own_nodes_all_feature.restype = C.c_int
     lib.simon_set_scenario_pods.argtypes = [vp, C.POINTER(C.c_uint32)]
     lib.simon_set_scenario_pods.restype = C.c_int
     lib.simon_fetch_group_counts.argtypes = [vp, _p32, C.c_int32, _p32, _p32]
@@ -892,6 +895,11 @@ class Context:
         if e.shape != (self.problem.n_pods,):
             raise ValueError(f"evict has shape {e.shape}, the problem {self.problem.n_pods} pods")
         self._check(self.lib.simon_set_pod_eviction(self.h, _ptr(e, C.c_uint8)), "simon_set_pod_eviction")
+
+    def set_own_nodes_all_feature(self, on: bool = True) -> None:
+        """Context option (include/simon_hip.h: simon_set_own_nodes_all_feature): a segmented / node-subset batch whose problem routes to
+        the all-feature kernel runs there instead of being refused.  Off by default; survives every load."""
+        self._check(self.lib.simon_set_own_nodes_all_feature(self.h, 1 if on else 0), "simon_set_own_nodes_all_feature")
 
     def set_scenario_pods(self, present) -> None:
         """Pod subsets: scenario s holds pod p iff present[s][p] (bool [S][P], or the packed uint32 words [S][ceil(P / 32)]) and its gate

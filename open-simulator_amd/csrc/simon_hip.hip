@@ -195,6 +195,9 @@ struct simon_ctx : simon::HostInputs {
     // bit j & 31 of word j >> 5).  Rides on the segmented batch's kernel path (ranks, h_scls, seg_tot); a context holds one kind at a time.
     // sub_zone [N]: nodeTree zone ids (empty: one zone).  subset_host: env SIMON_SUBSET_STAGE=host -- the arrays from host loops (A/B + tests)
     bool sub_on = false, subset_host = false;
+    // simon_set_own_nodes_all_feature: a segmented / node-subset batch that routes to the all-feature kernel runs there (its own-nodes run
+    // forms, simon_wide_own.hip) instead of being refused.  A context option: off by default, survives every load.
+    bool own_wide = false;
     int sub_W = 0;
     std::vector<uint32_t> sub_words;
     std::vector<int32_t> sub_zone;
@@ -1842,6 +1845,12 @@ int simon_set_pod_eviction(simon_ctx* c, const uint8_t* evict) {
     return SIMON_OK;
 }
 
+int simon_set_own_nodes_all_feature(simon_ctx* c, int32_t on) {
+    if (!c) return SIMON_EINVAL;
+    c->own_wide = on != 0;           // (read by the next simon_run_loaded / simon_explain_own_batch: nothing staged depends on it)
+    return SIMON_OK;
+}
+
 int simon_set_pod_priorities(simon_ctx* c, const int32_t* priority, int32_t init_min_priority) {
     if (!c) return SIMON_EINVAL;
     if (!c->have_pods) return fail(c, SIMON_ESTATE, "set_pod_priorities: load pods first");
@@ -2899,7 +2908,9 @@ static size_t lds_with_home(const simon_ctx* c, size_t table_lds, size_t home) {
 // (SIMON_DEBUG_ROUTE: the `[route] variant` line on stderr).
 static BatchRoute route_batch(const simon_ctx* c) {
     const int S = c->S;
-    auto wide = [&](int slots) { return BatchRoute{SIMON_KERNEL_WIDE, 0, wide_workgroup(c, S, c->max_n), slots, 1, false, false, 0}; };
+    // (an own-nodes batch that the context's opt-in lets run on the all-feature kernel walks the pool: its workgroup is sized by N.  With the
+    // option off such a batch is refused, and its route is what it was)
+    auto wide = [&](int slots) { return BatchRoute{SIMON_KERNEL_WIDE, 0, wide_workgroup(c, S, own_nodes(c) && c->own_wide ? c->N : c->max_n), slots, 1, false, false, 0}; };
     // per-scenario node ranks: the score-table kernel (own per-class lists) or the all-feature kernel
     if (c->variant != SIMON_KERNEL_NARROW || (c->has_ranks && !c->table_ranks_ok)) return wide(0);
     // workgroup shape: T = 256 (4 waves) with up to 8 node slots per lane covers 2048 nodes;
@@ -2971,11 +2982,12 @@ static void trace_segmented(const simon_ctx* c, const char* outcome) {
 // The launchers of simon_run_loaded, one per kernel: the loaded batch on route `r`, its launches between the context's event pair.
 static int run_wide_batch(simon_ctx* c, const BatchRoute& r, bool want_placement, bool want_slices) {
     if (int rc = ensure_wide_staged(c)) return rc;   // (a NARROW problem whose batch cannot use the cache kernel but has pinned pods)
+    const bool own = own_nodes(c);                   // (simon_run_loaded let it through: the option is on and the rank rows are staged)
     return timed_launch(c, [&] {
-        return wide_run(c->wide, *c, reinterpret_cast<const WideScenario*>(c->d_scen.p), c->S, c->d_orders.p, c->max_n, r.T, c->d_unsched.p,
+        return wide_run(c->wide, *c, reinterpret_cast<const WideScenario*>(c->d_scen.p), c->S, c->d_orders.p, own ? c->N : c->max_n, r.T, c->d_unsched.p,
                         c->d_used_cpu.p, c->d_used_mem.p, c->d_used_vg.p, want_placement ? c->d_place.p : nullptr,
                         c->has_ranks ? c->d_node_rank.p : nullptr, c->has_ranks ? c->d_node_inv.p : nullptr,
-                        want_slices ? c->d_gpu_slices.p : nullptr, c->stream, c->err, pod_rows(c), c->pod_W);
+                        want_slices ? c->d_gpu_slices.p : nullptr, c->stream, c->err, pod_rows(c), c->pod_W, own);
     });
 }
 
@@ -3149,10 +3161,13 @@ int simon_run_loaded(simon_ctx* c, int32_t want_placement) {
     }
     if (want_place) HIP_TRY(c, c->d_place.ensure((size_t)S * P));
     const BatchRoute r = route_batch(c);
-    if (r.kernel == SIMON_KERNEL_WIDE && own_nodes(c)) {     // the all-feature kernel takes prefix scenarios only
+    // the all-feature kernel takes prefix scenarios, and -- the context's opt-in, simon_set_own_nodes_all_feature -- own-nodes batches
+    // whose rank rows are staged
+    if (r.kernel == SIMON_KERNEL_WIDE && own_nodes(c) && !(c->own_wide && c->has_ranks)) {
         trace_segmented(c, "all-feature kernel -- refused");
         return fail(c, SIMON_ESTATE, "run_loaded: %s batch on a problem the score-table kernel does not take; run each scenario's own problem", own_kind(c));
     }
+    if (r.kernel == SIMON_KERNEL_WIDE && own_nodes(c)) trace_segmented(c, "all-feature kernel, own-nodes run form");
     int rc;
     switch (r.kernel) {
         case SIMON_KERNEL_WIDE: rc = run_wide_batch(c, r, want_place, want_slices); break;
@@ -3434,7 +3449,9 @@ int simon_explain_own_batch(simon_ctx* c, const int32_t* scenarios, int32_t n_sc
         return fail(c, SIMON_EINVAL, "explain_own_batch: bad arguments");
     if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "explain_own_batch: no scenarios loaded");
     if (!own_nodes(c)) return fail(c, SIMON_ESTATE, "explain_own_batch: prefix batch; use simon_explain_batch");
-    if (!c->has_ranks || route_batch(c).kernel == SIMON_KERNEL_WIDE)     // (the batch simon_run_loaded refuses: its pods' gates and presets were never checked against a run)
+    // (the batch simon_run_loaded refuses: its pods' gates and presets were never checked against a run.  With the opt-in a wide-routed batch
+    // runs, and replays, unless the problem has Open-Local storage: the replay's own-nodes form is the full variant's)
+    if (!c->has_ranks || (route_batch(c).kernel == SIMON_KERNEL_WIDE && !(c->own_wide && !c->has_local)))
         return fail(c, SIMON_ESTATE, "explain_own_batch: %s batch on a problem the score-table kernel does not take; explain each scenario's own problem", own_kind(c));
     const int N = c->N;
     std::vector<WideScenario> hs((size_t)n_scen);

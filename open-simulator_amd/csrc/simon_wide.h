@@ -227,7 +227,8 @@ constexpr uint32_t kArgGpu = 1u, kArgMask = 2u, kArgEph = 4u, kArgNzeq = 8u, kAr
                    // ABI v7: ImageLocality scores per (size slot of the scenario, pod class, node class), added to the class term
                    kArgImage = 131072u,
                    // simon_explain_own_batch: a scenario holds pool node j iff its rank row says node_rank[j] < N (segmented / node-subset
-                   // batches), not the prefix j < n_nodes.  Honoured by the EXPLAIN form of the full variant alone (wide_kernel: kCanOwn)
+                   // batches), not the prefix j < n_nodes.  Honoured by the EXPLAIN form of the full variant, and what the own-nodes run
+                   // forms are launched with (wide_kernel: kCanOwn; wide_run's `own`)
                    kArgOwn = 262144u,
                    // simon_set_scenario_pods: WideCold::pod_present decides, next to the gate, which pods a scenario holds
                    kArgPodSets = 524288u;
@@ -287,20 +288,25 @@ struct WideDevice {
             *st_scalar = nullptr, *st_gpu = nullptr, *st_gmax = nullptr;
     uint32_t* mask_lanes = nullptr;      // lane-major static mask of the last launch's workgroup size
     int mask_lanes_T = 0;
+    uint8_t* own_reg = nullptr;          // own-nodes run (wide_run): the batch's registered flags [S][E][R], grown on demand
+    size_t own_reg_cap = 0;
     int32_t *st_npods = nullptr, *st_cnt = nullptr, *st_seen = nullptr;
     void release();
 };
 
 // staging / launching (simon_wide.hip)
 // launches of the instantiations that live outside simon_wide.hip (simon_wide_local.hip: the Open-Local variant; simon_wide_explain.hip:
-// the EXPLAIN form of the full variant); T in {64, 256, 512, 1024}
+// the EXPLAIN form of the full variant; simon_wide_own.hip: the run forms of an own-nodes batch, with or without Open-Local);
+// T in {64, 256, 512, 1024}
 hipError_t wide_launch_local(const WideArgs& a, int T, bool explain, size_t lds, hipStream_t st);
 hipError_t wide_launch_explain(const WideArgs& a, int T, size_t lds, hipStream_t st);
+hipError_t wide_launch_own(const WideArgs& a, int T, bool local, size_t lds, hipStream_t st);
 int wide_stage(WideDevice& w, const HostInputs& in, hipStream_t st, std::string& err);
 int wide_run(WideDevice& w, const HostInputs& in, const WideScenario* d_scen, int S, const int32_t* d_orders, int max_n, int T,
              int32_t* d_unsched, int64_t* d_used_cpu, int64_t* d_used_mem, int64_t* d_used_vg, int32_t* d_place,
              const int32_t* d_node_rank, const int32_t* d_node_inv, uint64_t* d_gpu_slices, hipStream_t st, std::string& err,
-             const uint32_t* d_pod_present = nullptr /*[S][pp_words] or null*/, int pp_words = 0);
+             const uint32_t* d_pod_present = nullptr /*[S][pp_words] or null*/, int pp_words = 0,
+             bool own = false /*own-nodes batch (kArgOwn): rank rows required, max_n = the pool size*/);
 
 // One EXPLAIN launch (simon_explain, simon_explain_loaded, simon_explain_batch): the listed scenarios replayed by one workgroup each.
 // Host pointers unless named d_; everything per listed scenario is in launch order.

@@ -657,7 +657,8 @@ __device__ __forceinline__ void pts_raw8(const WideArgs& A, const NodeView& v, c
 }
 
 // VAR: 0 = lean (pod flags beyond kPodZero | kPodTerms cannot occur: their code folds away and with it ~40 VGPRs of
-// spills), 1 = every plugin except Open-Local, 2 = every plugin
+// spills), 1 = every plugin except Open-Local, 2 = every plugin; 3 / 4 = 1 / 2 as the RUN form of an own-nodes batch (kArgOwn: segmented and
+// node-subset scenarios; simon_wide_own.hip) -- new values, so that the instantiations of 0 / 1 / 2 keep their names and their code
 template <int T, bool EXPLAIN, int VAR>
 __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArgs A) {
     constexpr int NW = T / 64;
@@ -684,9 +685,11 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
     const int s = blockIdx.x;
     const int N = A.N, P = A.P, K = A.K, Cn = A.Cn;
     // Own-nodes replay (kArgOwn, simon_explain_own_batch): the scenario holds pool node j iff its rank row says so, and every node loop
-    // runs over the pool.  Only the EXPLAIN form of the full variant honours the flag; everywhere else `own` is a constant.
-    constexpr bool kCanOwn = EXPLAIN && VAR == 1;
-    const bool own = kCanOwn && (A.flags & kArgOwn) != 0u;
+    // runs over the pool.  The EXPLAIN form of the full variant honours the flag, and the own-nodes run forms (VAR 3 / 4) are launched with
+    // nothing else; everywhere else `own` is a constant.
+    constexpr bool kOwnRun = VAR >= 3;
+    constexpr bool kCanOwn = (EXPLAIN && VAR == 1) || kOwnRun;
+    const bool own = kOwnRun || (kCanOwn && (A.flags & kArgOwn) != 0u);
     const int n = own ? N : A.scen[s].n_nodes;
     if (((A.flags & kArgClassMode) != 0u) && Cn <= 8)
         for (int c = 0; c < Cn; ++c) s_kc[c * T + tid] = 0u;
@@ -728,7 +731,7 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
             v.gmax()[j] = gpu_max_idle(COLD(A)->i_gpu_used + (size_t)j * SIMON_MAX_GPU_DEV, COLD(A)->gpu_cnt[j], COLD(A)->gpu_mem_total[j]);
         }
     }
-    constexpr bool LOCAL = VAR == 2;
+    constexpr bool LOCAL = VAR == 2 || VAR == 4;
     if (LOCAL && (A.flags & kArgLocal)) {
         for (int j = tid; j < n; j += T) {
 #pragma unroll
@@ -1083,8 +1086,15 @@ __global__ __launch_bounds__(T, T == 256 ? 2 : 1) void wide_kernel(const WideArg
                                 const int32_t* rrow = COLD(A)->sh_first_reg + (size_t)e * N;
                                 const long long slack = (long long)COLD(A)->sh_skew[e] - (COLD(A)->sh_self[e] ? 1 : 0) + sel4(hard_min, e - lo);
                                 int d[kUT], rg[kUT], cv[kUT];
+                                if (kCanOwn && own) {      // registered = the scenario's own flag of (constraint, domain), as head_code reads it
 #pragma unroll
-                                for (int u = 0; u < kUT; ++u) { d[u] = act[u] ? drow[jn[u]] : -1; rg[u] = act[u] ? rrow[jn[u]] : INT_MAX; }
+                                    for (int u = 0; u < kUT; ++u) d[u] = act[u] ? drow[jn[u]] : -1;
+#pragma unroll
+                                    for (int u = 0; u < kUT; ++u) rg[u] = (d[u] >= 0 && own_reg[(size_t)e * COLD(A)->own_reg_R + d[u]] != 0) ? 0 : INT_MAX;
+                                } else {
+#pragma unroll
+                                    for (int u = 0; u < kUT; ++u) { d[u] = act[u] ? drow[jn[u]] : -1; rg[u] = act[u] ? rrow[jn[u]] : INT_MAX; }
+                                }
 #pragma unroll
                                 for (int u = 0; u < kUT; ++u) cv[u] = (d[u] >= 0 && rg[u] < n) ? v.cnt_match()[off + d[u]] : 0;
 #pragma unroll
@@ -1687,10 +1697,11 @@ static size_t wide_lds_bytes(const WideArgs& a, int T) {
     return lds;
 }
 
-// Launch of one instantiation.  The 20 instantiations (workgroup size x EXPLAIN x variant) live in three translation units since round 5
-// -- this one (lean / full, the scenario kernels), simon_wide_local.hip (the Open-Local variant, both EXPLAIN forms) and
-// simon_wide_explain.hip (the full variant's EXPLAIN form) -- because build() runs one hipcc process per unit and this file alone took
-// 4.6 minutes.  A workgroup of 128 threads runs as 256 (wide_workgroup: the shape is a tuning knob, never visible in a result).
+// Launch of one instantiation.  The 28 instantiations (workgroup size x EXPLAIN x variant) live in four translation units
+// -- this one (lean / full, the scenario kernels), simon_wide_local.hip (the Open-Local variant, both EXPLAIN forms),
+// simon_wide_explain.hip (the full variant's EXPLAIN form) and simon_wide_own.hip (the own-nodes run forms, VAR 3 / 4) -- because build()
+// runs one hipcc process per unit and this file alone took 4.6 minutes.  A workgroup of 128 threads runs as 256 (wide_workgroup: the
+// shape is a tuning knob, never visible in a result).
 template <int TT, bool EXPLAIN, int VAR>
 static hipError_t launch_one(const WideArgs& a, size_t lds, hipStream_t st) {
     if (lds > 48 * 1024) {                                                 // beyond the default dynamic-LDS limit: raise it for the instantiation that runs
@@ -1715,6 +1726,10 @@ static hipError_t launch_sized(const WideArgs& a, int T, size_t lds, hipStream_t
 hipError_t wide_launch_local(const WideArgs& a, int T, bool explain, size_t lds, hipStream_t st) {
     return explain ? launch_sized<true, 2>(a, T, lds, st) : launch_sized<false, 2>(a, T, lds, st);
 }
+#elif defined(SIMON_WIDE_OWN_TU)
+hipError_t wide_launch_own(const WideArgs& a, int T, bool local, size_t lds, hipStream_t st) {
+    return local ? launch_sized<false, 4>(a, T, lds, st) : launch_sized<false, 3>(a, T, lds, st);
+}
 #elif defined(SIMON_WIDE_EXPLAIN_TU)
 hipError_t wide_launch_explain(const WideArgs& a, int T, size_t lds, hipStream_t st) { return launch_sized<true, 1>(a, T, lds, st); }
 #else
@@ -1722,6 +1737,7 @@ namespace {
 template <bool EXPLAIN>
 hipError_t launch(const WideArgs& a, int T, hipStream_t st) {
     const size_t lds = wide_lds_bytes(a, T);
+    if (!EXPLAIN && (a.flags & kArgOwn)) return wide_launch_own(a, T, (a.flags & kArgLocal) != 0u, lds, st);   // (a lean problem too: its own-nodes batch is ranked)
     if (a.flags & kArgLocal) return wide_launch_local(a, T, EXPLAIN, lds, st);
     if (!EXPLAIN && (a.flags & kArgLean) && !(a.flags & kArgRanked)) return launch_sized<false, 0>(a, T, lds, st);
     if (EXPLAIN) return wide_launch_explain(a, T, lds, st);
@@ -1835,6 +1851,8 @@ void WideDevice::release() {
     if (d_cold) { (void)hipFree(d_cold); d_cold = nullptr; }
     if (mask_lanes) { (void)hipFree(mask_lanes); mask_lanes = nullptr; }
     mask_lanes_T = 0;
+    if (own_reg) { (void)hipFree(own_reg); own_reg = nullptr; }
+    own_reg_cap = 0;
 }
 
 int wide_stage(WideDevice& w, const HostInputs& in, hipStream_t st, std::string& err) {
@@ -2097,12 +2115,27 @@ int launch_chunks(WideDevice& w, const HostInputs& in, const WideLaunch& L, int 
 int wide_run(WideDevice& w, const HostInputs& in, const WideScenario* d_scen, int S, const int32_t* d_orders, int max_n, int T,
              int32_t* d_unsched, int64_t* d_used_cpu, int64_t* d_used_mem, int64_t* d_used_vg, int32_t* d_place,
              const int32_t* d_node_rank, const int32_t* d_node_inv, uint64_t* d_gpu_slices, hipStream_t st, std::string& err,
-             const uint32_t* d_pod_present, int pp_words) {
+             const uint32_t* d_pod_present, int pp_words, bool own) {
     WideLaunch L;
+    if (own && (!d_node_rank || !d_node_inv || max_n != in.N)) { err = "wide run: an own-nodes batch needs rank rows and the pool size"; return SIMON_EINVAL; }
     if (int rc = prepare(w, in, S, max_n, T, st, err, L)) return rc;
     WideArgs& a = L.a;
     WideCold& c = L.c;
     L.ranks(d_node_rank, d_node_inv);
+    if (own) {
+        // the registered flags of the hard spread constraints, [S][E][R] bytes of the WHOLE batch (R: the most domains a topology key has):
+        // zeros here, set by each scenario's prologue; a chunked launch indexes them by scen_base + s, like the rank and pod rows
+        const size_t reg_E = in.sh_idx.size(), reg_R = (size_t)std::max(1, in.topo_n_dom.empty() ? 1 : *std::max_element(in.topo_n_dom.begin(), in.topo_n_dom.end()));
+        const size_t bytes = std::max<size_t>((size_t)S * reg_E * reg_R, 256);
+        if (bytes > w.own_reg_cap) {
+            if (w.own_reg) { (void)hipFree(w.own_reg); w.own_reg = nullptr; }
+            w.own_reg_cap = 0;
+            if (hipError_t e = hipMalloc((void**)&w.own_reg, bytes); e != hipSuccess) { err = std::string("hipMalloc(own_reg): ") + hipGetErrorString(e); return SIMON_ENOMEM; }
+            w.own_reg_cap = bytes;
+        }
+        TRY(hipMemsetAsync(w.own_reg, 0, bytes, st));
+        a.flags |= kArgOwn; c.own_reg = w.own_reg; c.own_reg_R = (int32_t)reg_R; c.own_reg_E = (int32_t)reg_E;
+    }
     c.gpu_slices = d_gpu_slices;
     if (d_pod_present) { c.pod_present = d_pod_present; c.pp_words = pp_words; a.flags |= kArgPodSets; }
     if (a.flags & kArgImage) {
@@ -2274,5 +2307,5 @@ int wide_replay(WideDevice& w, const HostInputs& in, const WideReplay& job, int 
 }
 #undef TRY
 
-#endif  // SIMON_WIDE_LOCAL_TU / SIMON_WIDE_EXPLAIN_TU
+#endif  // SIMON_WIDE_LOCAL_TU / SIMON_WIDE_OWN_TU / SIMON_WIDE_EXPLAIN_TU
 }  // namespace simon

@@ -31,9 +31,21 @@ class HipEngine:
     supports_node_usage = True                # per-node usage and headroom reduced on the device (simon_fetch_node_usage / simon_fetch_headroom)
     supports_gpu_usage = True                 # ... GPU-share devices and the device bound of headroom (simon_fetch_gpu_usage / simon_fetch_headroom_gpu)
     supports_local_usage = True               # ... Open-Local storage and the storage bound of headroom (simon_fetch_local_usage / simon_fetch_headroom_local)
+    supports_own_nodes_all_feature = False    # own-nodes batches on the all-feature kernel: per engine, HipEngine(own_nodes_all_feature=True)
 
-    def __init__(self, device_id: int = 0):
+    def __init__(self, device_id: int = 0, own_nodes_all_feature: bool = False):
+        """own_nodes_all_feature: segmented and node-subset batches of a problem that routes to the all-feature kernel (Open-Local storage,
+        hard hostname spread constraints, ...) RUN there (simon_set_own_nodes_all_feature) instead of being refused: sweep_mix,
+        sweep_failures and sweep_apps then batch such clusters instead of falling back to one run per scenario."""
         self.device_id = device_id
+        self.supports_own_nodes_all_feature = bool(own_nodes_all_feature)
+
+    def _context(self) -> capi.Context:
+        """A context of this engine's device with the engine's options set."""
+        ctx = capi.Context(self.device_id)
+        if self.supports_own_nodes_all_feature:
+            ctx.set_own_nodes_all_feature(True)
+        return ctx
 
     def run(self, prob: capi.Problem, scen, orders, want_placement=True, node_ranks=None, want_gpu_slices=False,
             segments=None, present=None, evict=None, pod_present=None, pod_groups=None, headroom_pods=None, usage_of=None,
@@ -58,7 +70,7 @@ class HipEngine:
             raise ValueError("a batch has pool segments or node subsets, not both")
         if evict is not None and present is None:
             raise ValueError("evicted pods belong to a node-subset batch: pass present")
-        with capi.Context(self.device_id) as ctx:
+        with self._context() as ctx:
             ctx.load_problem(prob)
             if evict is not None:
                 ctx.set_pod_eviction(evict)
@@ -96,7 +108,7 @@ class HipEngine:
 
     def explain(self, prob: capi.Problem, n_nodes: int, order, max_failed: int):
         """(n_failed, failed pod ids, [k][n_nodes] failure codes, [k][n_nodes][4] Open-Local error sizes or None)."""
-        with capi.Context(self.device_id) as ctx:
+        with self._context() as ctx:
             ctx.load_problem(prob)
             nf, failed, codes = ctx.explain(n_nodes, order, max_failed)
             return nf, failed, codes, ctx.explain_local_detail(len(failed), n_nodes)
@@ -111,7 +123,7 @@ class HipEngine:
         buffers stay within `buffer_bytes` (a group is one scenario at least: that one's buffers are explain_loaded's)."""
         ids = [int(s) for s in ids]
         per_bins = max_failed * (8 + 8 * max_bins)                           # failed_pods + n_bins + bins, per listed scenario
-        with capi.Context(self.device_id) as ctx:
+        with self._context() as ctx:
             ctx.load_problem(prob)
             ctx.load_scenarios(scen, orders)
             if pod_present is not None:              # (every listed scenario is replayed with its own pod row)
@@ -150,7 +162,7 @@ class HipEngine:
             raise ValueError("evicted pods belong to a node-subset batch: pass present")
         ids = [int(s) for s in ids]
         per_bins = max_failed * (8 + 8 * max_bins)                           # failed_pods + n_bins + bins, per listed scenario
-        with capi.Context(self.device_id) as ctx:
+        with self._context() as ctx:
             ctx.load_problem(prob)
             if evict is not None:
                 ctx.set_pod_eviction(evict)
