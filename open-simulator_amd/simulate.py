@@ -429,34 +429,10 @@ def _gc_paused(fn):
 def simulate(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], engine=None, new_nodes: Sequence[dict] = ()) -> SimulateResult:
     """simulator.Simulate for ONE cluster size: cluster["Node"] + new_nodes, canonical nodeTree order."""
     engine = engine or HipEngine()
-    nodes = list(cluster.get("Node", [])) + list(new_nodes)
-    # the pod stream follows the INPUT node order (DaemonSet pods are made node by node from cluster.Nodes + new nodes,
-    # pkg/simulator/core.go:85-95); only the engine's node arrays are in nodeTree order
-    pods, _ = build_stream(cluster, apps, nodes, len(nodes))
-    arrival = [n["metadata"]["name"] for n in nodes]               # order in which the scheduler cache meets the nodes
-    order = k8s.canonical_node_order(nodes)
-    nodes = [nodes[j] for j in order]
-    flat = fl.flatten(nodes, pods, cluster.get("Service", []), cluster.get("ReplicaSet", []), cluster.get("StatefulSet", []),
-                      storage_classes=_storage_classes(cluster, apps), image_total=len(nodes), node_arrival_order=arrival)
-    P = len(pods)
-    scen = np.array([[len(nodes), 0]], np.int32)
-    orders = np.arange(P, dtype=np.int32)[None, :]
-    want_gpu = flat.problem.gpu_mem is not None
-    out = engine.run(flat.problem, scen, orders, want_gpu_slices=True) if want_gpu else engine.run(flat.problem, scen, orders)
-    if _risk(out, 0):
-        raise NeedsReference(f"{int(out.unscheduled[0])} pod(s) failed while pods of lower priority were placed: DefaultPreemption may evict there")
-    reasons = {}
-    if out.unscheduled[0] > 0:
-        nf, failed, codes, detail = engine.explain(flat.problem, len(nodes), orders[0], int(out.unscheduled[0]))
-        for i, (pid, row) in enumerate(zip(failed.tolist(), codes)):
-            ns, name = flat.pod_refs[pid]
-            reasons[pid] = fiterror.unscheduled_reason(ns, name, row, node_names=flat.node_names,
-                                                       static_reasons=flat.static_reasons, scalar_names=flat.scalar_names,
-                                                       local_detail=None if detail is None else detail[i],
-                                                       vg_names=flat.info.get("vg_names", ()))
-    res, per_node, per_dev = _unflatten(flat, out.placement[0], len(nodes), reasons, out.gpu_slices[0] if want_gpu and out.gpu_slices is not None else None)
-    res.node_status = [{"node": _gpu_node_status(n, per_dev[j]) if j in per_dev else _node_out(n), "pods": per_node[j]} for j, n in enumerate(nodes)]
-    return res
+    a = _run_alone(cluster, apps, list(cluster.get("Node", [])) + list(new_nodes), engine)
+    if a.row[4]:                                                   # (before the engine is asked for the reasons)
+        raise NeedsReference(f"{a.row[0]} pod(s) failed while pods of lower priority were placed: DefaultPreemption may evict there")
+    return a.result(_alone_reasons(engine, a))
 
 
 class UsageFallbackWarning(UserWarning):
@@ -798,7 +774,8 @@ def _usage_fill(engine, out, nodes, prob, held, probes, node_table: bool, warn, 
         import warnings
         lacks = ("supports_node_usage" if not getattr(engine, "supports_node_usage", False) else
                  "supports_gpu_usage" if devices and not getattr(engine, "supports_gpu_usage", False) else "supports_local_usage")
-        warnings.warn(f"{what} computes headroom / the node table on the host from the placement matrix (the engine has no {lacks})", warn, stacklevel=4)
+        # (_usage_fill <- _Usage.add_launch <- the sweep <- _gc_paused's wrapper <- the sweep's caller)
+        warnings.warn(f"{what} computes headroom / the node table on the host from the placement matrix (the engine has no {lacks})", warn, stacklevel=5)
         if probes is not None:
             hr, _, hx = host_headroom(prob, out.placement, held, probes, out.gpu_slices, devices, storage, orders, scen)
         if node_table:
@@ -842,10 +819,47 @@ def _usage_each(flat: fl.Flat, nodes: List[dict], out, headroom, node_table: boo
     return hr, hx, tab, gtab, stab
 
 
-def _and_exact(rows):
-    """headroom_exact over scenarios that ran as their own problems: exact where every one of them says so."""
-    rows = [r for r in rows if r is not None]
-    return [all(r[k] for r in rows) for k in range(len(rows[0]))] if rows else None
+class _Usage:
+    """What a sweep was asked for beyond its rows -- headroom probes, node_table, devices, storage -- and the five results that answer
+    it: headroom, headroom_exact, node_table, gpu_table, storage_table (None where not asked for), one entry per scenario in the order
+    the scenarios are added, launch by launch (add_launch: _usage_fill) or one by one (add_alone: _usage_each)."""
+
+    def __init__(self, headroom, node_table=False, devices=False, storage=False):
+        self.headroom, self.node_table, self.devices, self.storage = headroom, node_table, devices, storage
+        self.asked = headroom is not None or node_table or devices or storage
+        self.lists = [[] if on else None for on in (headroom is not None, node_table, devices, storage)]   # all but headroom_exact
+        self.exact = None
+        self.probes = None
+
+    def bind(self, flat: fl.Flat):
+        """The probes' pod ids in the stream of a batch (ValueError for a probe that stream does not hold)."""
+        self.probes = probe_ids(flat, self.headroom)
+
+    def kw(self, engine, S: int) -> dict:
+        return _usage_kw(engine, self.probes, self.node_table, S, self.devices, self.storage)
+
+    def take(self, five, launch: bool):
+        """Take in _usage_fill's five entries for the scenarios of one launch (lists over them), or _usage_each's for one scenario that
+        ran as its own problem.  headroom_exact: the launches of a batch share the problem, so the last launch's flags stand; scenarios
+        that ran alone each bring their own classes and terms, and a probe is exact where every one of them says so."""
+        hr, hx, *tables = five
+        for acc, v in zip(self.lists, (hr, *tables)):
+            if acc is not None:
+                acc.extend(v) if launch else acc.append(v)
+        if hx is not None:
+            self.exact = hx if launch or self.exact is None else [x and y for x, y in zip(self.exact, hx)]
+
+    def add_launch(self, engine, out, nodes, prob, held, warn, what: str, orders, scen):
+        self.take(_usage_fill(engine, out, nodes, prob, held, self.probes, self.node_table, warn, what, self.devices, self.storage, orders, scen), True)
+
+    def add_alone(self, a: "_Alone"):
+        self.take(_usage_each(a.flat, a.nodes, a.out, self.headroom, self.node_table, a.arrival, self.devices, self.storage), False)
+
+    def onto(self, res, K: Optional[int] = None):
+        """Write the five fields onto a sweep's result (K: sweep_apps nests its scenarios [U][K]); returns the result."""
+        res.headroom, res.node_table, res.gpu_table, res.storage_table = (v if v is None or K is None else _nested(v, K) for v in self.lists)
+        res.headroom_exact = self.exact
+        return res
 
 
 @dataclass
@@ -950,6 +964,126 @@ def _own_reason_texts(flat: fl.Flat, e: "ExplainedScenario", present_row) -> Dic
     return _reason_texts(flat, e.failed, rows, None, [(e.n_nodes, b) for b in e.bins], [flat.node_names[j] for j in own.tolist()])
 
 
+def _explain_own(engine, flat: fl.Flat, scen, orders, node_ranks, failing, out, held, **shape) -> Dict[int, Dict[int, str]]:
+    """{scenario: {pod id: reason text}} of the scenarios `failing` of an own-nodes batch, from one engine.explain_own_batch call on the
+    context shape the batch ran with (`shape`: segments=, or present= and evict=); held: bool [S][N], the nodes every scenario holds.
+    Empty for an engine without the call and for a batch the library refuses to explain (ESTATE): the caller replays those."""
+    texts: Dict[int, Dict[int, str]] = {}
+    if failing and getattr(engine, "supports_explain_own", False):
+        try:
+            for e in engine.explain_own_batch(flat.problem, scen, orders, node_ranks, failing, int(max(out.unscheduled[s] for s in failing)), **shape):
+                texts[e.scenario] = _own_reason_texts(flat, e, held[e.scenario])
+        except capi.SimonError as err:
+            if getattr(err, "code", None) != capi.ESTATE:
+                raise
+    return texts
+
+
+def _ns_name(pod: dict) -> tuple:
+    """(namespace, name) exactly as the pod carries them, to compare two streams; _pod_ref reads a missing namespace as "default", this does not."""
+    return (pod["metadata"].get("namespace"), pod["metadata"]["name"])
+
+
+def _vg_caps(pr: capi.Problem, out) -> Optional[np.ndarray]:
+    """Volume-group capacity per node (the MaxVG cap's denominator, pkg/apply/apply.go:753-771), or None: no Open-Local arrays or sums."""
+    if pr.local_flags is None or out.used_vg is None:
+        return None
+    return (pr.local_vg_cap * (np.arange(capi.MAX_VG)[None, :] < pr.local_vg_cnt[:, None])).sum(1)
+
+
+def _alloc_of_prefixes(pr: capi.Problem, out, sizes, segments=None):
+    """Allocatable (cpu, memory, volume-group capacity or None) of the scenarios that hold the first sizes[s] nodes, int64 [S] each:
+    a cumulative sum indexed per scenario (sweep and sweep_apps, whose scenarios are prefixes of the pool by construction).
+    segments = (seg_start [G], counts [S][G]): and the first counts[s][g] nodes from seg_start[g] on, a prefix difference per segment
+    (sweep_mix: over a 64 x 64 grid this costs 0.05 ms per quantity where held @ v costs 30)."""
+    sizes = np.asarray(sizes, np.int64)
+
+    def total(v):
+        c = np.concatenate([[0], np.cumsum(np.asarray(v, np.int64))])
+        t = c[sizes]
+        for g, st in enumerate([] if segments is None else np.asarray(segments[0]).tolist()):
+            t = t + c[st + np.asarray(segments[1])[:, g]] - c[st]
+        return t
+    return tuple(None if v is None else total(v) for v in (pr.alloc_cpu, pr.alloc_mem, _vg_caps(pr, out)))
+
+
+def _alloc_of_subsets(pr: capi.Problem, out, held):
+    """_alloc_of_prefixes for scenarios that hold the nodes of their row of held (bool [S][N]): held @ v in int64 (sweep_failures and
+    the scenarios that run alone)."""
+    held = np.asarray(held, bool)
+    return tuple(None if v is None else held @ np.asarray(v, np.int64) for v in (pr.alloc_cpu, pr.alloc_mem, _vg_caps(pr, out)))
+
+
+def _scenario_rows(out, alloc_cpu, alloc_mem, alloc_vg=None) -> List[tuple]:
+    """(unscheduled, cpu_pct, mem_pct, vg_pct, needs_reference) per scenario of an engine result: satisfyResourceSetting's occupancies
+    (pkg/apply/apply.go:737-771) of the used sums over each scenario's own allocatable, exact integers up to occupancy_pct (memory in
+    both terms * 1000, as the reference's MilliValue); vg_pct 0 without Open-Local sums."""
+    return [(int(out.unscheduled[s]), occupancy_pct(int(out.used_cpu[s]), int(alloc_cpu[s])),
+             occupancy_pct(int(out.used_mem[s]) * 1000, int(alloc_mem[s]) * 1000),
+             occupancy_pct(int(out.used_vg[s]), int(alloc_vg[s])) if alloc_vg is not None else 0, _risk(out, s))
+            for s in range(len(out.unscheduled))]
+
+
+def _within(row: tuple, caps) -> bool:
+    """A row of _scenario_rows schedules every pod within the (MaxCPU, MaxMemory, MaxVG) caps."""
+    return row[0] == 0 and row[1] <= caps[0] and row[2] <= caps[1] and row[3] <= caps[2]
+
+
+def _scenario_result(flat: fl.Flat, out, s: int, nodes: List[dict], held, reasons: Optional[Dict[int, str]] = None) -> SimulateResult:
+    """SimulateResult of scenario s of `out`: node_status over the nodes `held` (indices into `nodes`, the problem's nodes in its order)."""
+    res, per_node, per_dev = _unflatten(flat, out.placement[s], len(nodes), reasons or {}, None if out.gpu_slices is None else out.gpu_slices[s])
+    res.node_status = [{"node": _gpu_node_status(nodes[j], per_dev[j]) if j in per_dev else _node_out(nodes[j]), "pods": per_node[j]} for j in held]
+    return res
+
+
+@dataclass
+class _Alone:
+    """One scenario that ran as its own problem (_run_alone)."""
+    flat: fl.Flat
+    out: Optional[capi.BatchResult]      # the engine's one-scenario result (None: a stream without pods that was not run)
+    nodes: List[dict]                    # the scenario's nodes in canonical nodeTree order, the problem's
+    arrival: List[str]                   # their names in the order given
+    row: Optional[tuple]                 # _scenario_rows' row
+    unscheduled_pods: Optional[List[dict]] = None    # explain=True: as simulate() lists them
+
+    def result(self, reasons: Optional[Dict[int, str]] = None) -> SimulateResult:
+        return _scenario_result(self.flat, self.out, 0, self.nodes, range(len(self.nodes)), reasons)
+
+
+def _alone_reasons(engine, a: _Alone) -> Dict[int, str]:
+    """UnscheduledPod.Reason by pod id of a scenario that ran alone, from engine.explain on its own problem (none failed: no call)."""
+    if a.row[0] == 0:
+        return {}
+    nf, failed, codes, detail = engine.explain(a.flat.problem, len(a.nodes), np.arange(len(a.flat.pods), dtype=np.int32), a.row[0])
+    return _reason_texts(a.flat, failed, codes, detail)
+
+
+def _run_alone(cluster, apps, nodes, engine, *, want_slices: bool = True, usage: Optional[_Usage] = None, explain: bool = False,
+               explain_at_risk: bool = True, skip_empty: bool = False) -> _Alone:
+    """simulator.Simulate's host side for ONE scenario, `nodes` with the cluster's and the apps' pods: the road of simulate() and of every
+    sweep that cannot batch.  want_slices: record the GPU devices where the problem has GPU memory.  usage: the sweep's carrier gains the
+    scenario's figures, on the host (ValueError for integer probes, _usage_each).  explain: unscheduled_pods as simulate() lists them
+    (explain_at_risk=False: without texts where DefaultPreemption could have acted).  skip_empty: a stream without pods is not run."""
+    # the pod stream follows the INPUT node order (DaemonSet pods are made node by node from cluster.Nodes + new nodes,
+    # pkg/simulator/core.go:85-95); only the engine's node arrays are in nodeTree order
+    pods, _ = build_stream(cluster, apps, nodes, len(nodes))
+    arrival = [n["metadata"]["name"] for n in nodes]               # order in which the scheduler cache meets the nodes
+    nodes = [nodes[j] for j in k8s.canonical_node_order(nodes)]
+    flat = fl.flatten(nodes, pods, cluster.get("Service", []), cluster.get("ReplicaSet", []), cluster.get("StatefulSet", []),
+                      storage_classes=_storage_classes(cluster, apps), image_total=len(nodes), node_arrival_order=arrival)
+    if skip_empty and not pods:
+        return _Alone(flat, None, nodes, arrival, None)
+    pr = flat.problem
+    out = engine.run(pr, np.array([[len(nodes), 0]], np.int32), np.arange(len(pods), dtype=np.int32)[None, :],
+                     **({"want_gpu_slices": True} if want_slices and pr.gpu_mem is not None else {}))
+    a = _Alone(flat, out, nodes, arrival, _scenario_rows(out, *_alloc_of_subsets(pr, out, np.ones((1, len(nodes)), bool)))[0])
+    if usage is not None:
+        usage.add_alone(a)
+    if explain:
+        a.unscheduled_pods = _unscheduled_list(flat, out.placement[0], _alone_reasons(engine, a) if explain_at_risk or not a.row[4] else {})
+    return a
+
+
 def _same_stream(cluster, apps, batch: "SweepBatch", out, s: int) -> bool:
     """Whether simulate() of size s feeds the pods in the order the batch fed them (the pool's stream without the pods gated at that size).
     An app's DaemonSet makes one pod per pool node, and the two unstable queue sorts of ScheduleApp (workloads.app_pods) then order the
@@ -957,9 +1091,8 @@ def _same_stream(cluster, apps, batch: "SweepBatch", out, s: int) -> bool:
     The comparison builds the size's stream on the host: one build_stream per FAILING size, and only for apps with a DaemonSet."""
     if not any(app.resource.get("DaemonSet") for app in apps):
         return True
-    ref = lambda p: (p["metadata"].get("namespace"), p["metadata"]["name"])
-    mine = [ref(batch.flat.pods[pid]) for pid, j in enumerate(out.placement[s].tolist()) if j != capi.GATED]
-    return mine == [ref(p) for p in build_stream(cluster, apps, batch.pool[:int(batch.scen[s, 0])], len(batch.base))[0]]
+    mine = [_ns_name(batch.flat.pods[pid]) for pid, j in enumerate(out.placement[s].tolist()) if j != capi.GATED]
+    return mine == [_ns_name(p) for p in build_stream(cluster, apps, batch.pool[:int(batch.scen[s, 0])], len(batch.base))[0]]
 
 
 def _sweep_reasons(engine, batch: "SweepBatch", out, replay, same_stream) -> List[List[dict]]:
@@ -1010,10 +1143,7 @@ def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node:
     roads replay on the host (host_local_usage; the same fallback warning).  storage=False leaves every result as it was."""
     engine = engine or HipEngine()
     counts = list(counts)
-    if max_cpu > 100 or max_cpu < 0:
-        max_cpu = 100
-    if max_mem > 100 or max_mem < 0:
-        max_mem = 100
+    caps = _caps(max_cpu, max_mem, max_vg)
     try:
         batch = sweep_batch(cluster, apps, new_node, counts, ranks_ok=getattr(engine, "supports_node_ranks", True),
                             image_batch=getattr(engine, "supports_image_locality", False))
@@ -1022,34 +1152,17 @@ def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node:
             raise
         # ImageLocality scores depend on the cluster size: an engine without the per-size image scores runs every size as its own
         # problem with its own static scores (and an engine without per-scenario node ranks runs a pool of several zones size by size)
-        return _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg, reasons, headroom, node_table, devices, storage)
-    flat, scen, orders, node_ranks, pool, base = batch.flat, batch.scen, batch.orders, batch.node_ranks, batch.pool, batch.base
-    want_gpu = flat.problem.gpu_mem is not None
-    kw = {"want_gpu_slices": True} if want_gpu else {}
+        return _sweep_per_size(cluster, apps, new_node, counts, engine, *caps, reasons, headroom, node_table, devices, storage)
+    flat, scen, orders, node_ranks, pool = batch.flat, batch.scen, batch.orders, batch.node_ranks, batch.pool
+    kw = {"want_gpu_slices": True} if flat.problem.gpu_mem is not None else {}
     if node_ranks is not None:
         kw["node_ranks"] = node_ranks
-    probes = probe_ids(flat, headroom)
-    out = engine.run(flat.problem, scen, orders, **kw, **_usage_kw(engine, probes, node_table, len(scen), devices, storage))
-    hr, hx, tab, gtab, stab = _usage_fill(engine, out, pool, flat.problem, np.arange(len(pool))[None, :] < scen[:, :1], probes, node_table,
-                                          UsageFallbackWarning, "sweep", devices, storage, orders, scen)
-    pc, pm = np.cumsum(flat.problem.alloc_cpu), np.cumsum(flat.problem.alloc_mem)
-    cpu_pct = [occupancy_pct(int(out.used_cpu[s]), int(pc[scen[s, 0] - 1])) for s in range(len(counts))]
-    mem_pct = [occupancy_pct(int(out.used_mem[s]) * 1000, int(pm[scen[s, 0] - 1]) * 1000) for s in range(len(counts))]
-    if max_vg > 100 or max_vg < 0:
-        max_vg = 100
-    vg_pct = [0] * len(counts)
-    if flat.problem.local_flags is not None and out.used_vg is not None:     # MaxVG cap, pkg/apply/apply.go:753-771
-        cap = np.cumsum((flat.problem.local_vg_cap * (np.arange(capi.MAX_VG)[None, :] < flat.problem.local_vg_cnt[:, None])).sum(1))
-        vg_pct = [occupancy_pct(int(out.used_vg[s]), int(cap[scen[s, 0] - 1])) for s in range(len(counts))]
-    ok = [s for s in range(len(counts)) if out.unscheduled[s] == 0 and cpu_pct[s] <= max_cpu and mem_pct[s] <= max_mem
-          and vg_pct[s] <= max_vg]
-    best = min(ok, key=lambda s: (counts[s], s)) if ok else None
-    result = None
-    if best is not None:
-        n = int(scen[best, 0])
-        res, per_node, per_dev = _unflatten(flat, out.placement[best], n, {}, out.gpu_slices[best] if want_gpu and out.gpu_slices is not None else None)
-        res.node_status = [{"node": _gpu_node_status(pool[j], per_dev[j]) if j in per_dev else _node_out(pool[j]), "pods": per_node[j]} for j in range(n)]
-        result = res
+    usage = _Usage(headroom, node_table, devices, storage)
+    usage.bind(flat)
+    out = engine.run(flat.problem, scen, orders, **kw, **usage.kw(engine, len(scen)))
+    usage.add_launch(engine, out, pool, flat.problem, np.arange(len(pool))[None, :] < scen[:, :1], UsageFallbackWarning, "sweep", orders, scen)
+    rows = _scenario_rows(out, *_alloc_of_prefixes(flat.problem, out, scen[:, 0]))
+    best = min((s for s, r in enumerate(rows) if _within(r, caps)), key=lambda s: (counts[s], s), default=None)
     why = []
     if reasons:
         def replay(s):                       # (NeedsReference: the size is flagged in needs_reference; its pods stay without a text)
@@ -1058,61 +1171,33 @@ def sweep(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_node:
             except NeedsReference:
                 return _unscheduled_list(flat, out.placement[s], {})
         why = _sweep_reasons(engine, batch, out, replay, lambda s: _same_stream(cluster, apps, batch, out, s))
-    return SweepResult(counts, out.unscheduled.tolist(), cpu_pct, mem_pct, None if best is None else counts[best], result, vg_pct,
-                       [_risk(out, s) for s in range(len(counts))], why, hr, hx, tab, gtab, stab)
+    return usage.onto(_sweep_result(counts, rows, best, None if best is None else _scenario_result(flat, out, best, pool, range(int(scen[best, 0]))), why))
+
+
+def _sweep_result(counts, rows, best: Optional[int], result: Optional[SimulateResult], why) -> SweepResult:
+    return SweepResult(list(counts), [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows], None if best is None else counts[best],
+                       result, [r[3] for r in rows], [r[4] for r in rows], why)
 
 
 def _sweep_per_size(cluster, apps, new_node, counts, engine, max_cpu, max_mem, max_vg, reasons: bool = False, headroom=None,
                     node_table: bool = False, devices: bool = False, storage: bool = False) -> SweepResult:
+    """Every size as its own Simulate(): the cluster plus counts[s] clones of new_node, canonical nodeTree order."""
     base = list(cluster.get("Node", []))
-    hrs, hxs, tabs, gtabs, stabs = [], [], [], [], []
-    if headroom is not None or node_table or devices or storage:
+    usage = _Usage(headroom, node_table, devices, storage)
+    if usage.asked:                      # sweep alone warns only when the host figures were asked for: without them the result is the batch's
         import warnings
         warnings.warn("sweep runs the sizes one by one and computes headroom / the node table on the host from each placement row",
                       UsageFallbackWarning, stacklevel=3)
-    if max_vg > 100 or max_vg < 0:
-        max_vg = 100
-    uns, cpu_pct, mem_pct, vg_pct, kept, risks = [], [], [], [], {}, []
-    why: List[List[dict]] = []
+    caps = _caps(max_cpu, max_mem, max_vg)
+    rows, why, kept = [], [], {}
     for s, k in enumerate(counts):
-        nodes = base + (wl.new_fake_nodes(new_node, k) if k > 0 else [])
-        pods, _ = build_stream(cluster, apps, nodes, len(nodes))
-        arrival = [n["metadata"]["name"] for n in nodes]
-        nodes = [nodes[j] for j in k8s.canonical_node_order(nodes)]
-        flat = fl.flatten(nodes, pods, cluster.get("Service", []), cluster.get("ReplicaSet", []), cluster.get("StatefulSet", []),
-                          storage_classes=_storage_classes(cluster, apps), image_total=len(nodes), node_arrival_order=arrival)
-        want_gpu = flat.problem.gpu_mem is not None
-        out = engine.run(flat.problem, np.array([[len(nodes), 0]], np.int32), np.arange(len(pods), dtype=np.int32)[None, :],
-                         **({"want_gpu_slices": True} if want_gpu else {}))
-        uns.append(int(out.unscheduled[0]))
-        risks.append(_risk(out, 0))
-        for acc, v in zip((hrs, hxs, tabs, gtabs, stabs), _usage_each(flat, nodes, out, headroom, node_table, arrival, devices, storage)):
-            acc.append(v)
-        if reasons:
-            texts = {}
-            if uns[-1] > 0:
-                nf, failed, codes, detail = engine.explain(flat.problem, len(nodes), np.arange(len(pods), dtype=np.int32), uns[-1])
-                texts = _reason_texts(flat, failed, codes, detail)
-            why.append(_unscheduled_list(flat, out.placement[0], texts))
-        cpu_pct.append(occupancy_pct(int(out.used_cpu[0]), int(flat.problem.alloc_cpu.sum())))
-        mem_pct.append(occupancy_pct(int(out.used_mem[0]) * 1000, int(flat.problem.alloc_mem.sum()) * 1000))
-        vg = 0
-        if flat.problem.local_flags is not None and out.used_vg is not None:
-            cap = int((flat.problem.local_vg_cap * (np.arange(capi.MAX_VG)[None, :] < flat.problem.local_vg_cnt[:, None])).sum())
-            vg = occupancy_pct(int(out.used_vg[0]), cap)
-        vg_pct.append(vg)
-        if uns[-1] == 0 and cpu_pct[-1] <= max_cpu and mem_pct[-1] <= max_mem and vg <= max_vg:
-            kept[s] = (flat, out, nodes)
-    best = min(kept, key=lambda s: (counts[s], s)) if kept else None
-    result = None
-    if best is not None:
-        flat, out, nodes = kept[best]
-        res, per_node, per_dev = _unflatten(flat, out.placement[0], len(nodes), {}, out.gpu_slices[0] if out.gpu_slices is not None else None)
-        res.node_status = [{"node": _gpu_node_status(n, per_dev[j]) if j in per_dev else _node_out(n), "pods": per_node[j]} for j, n in enumerate(nodes)]
-        result = res
-    return SweepResult(list(counts), uns, cpu_pct, mem_pct, None if best is None else counts[best], result, vg_pct, risks, why,
-                       hrs if headroom is not None else None, _and_exact(hxs), tabs if node_table else None, gtabs if devices else None,
-                       stabs if storage else None)
+        a = _run_alone(cluster, apps, base + (wl.new_fake_nodes(new_node, k) if k > 0 else []), engine, usage=usage, explain=reasons)
+        rows.append(a.row)
+        why.append(a.unscheduled_pods)
+        if _within(a.row, caps):
+            kept[s] = a
+    best = min(kept, key=lambda s: (counts[s], s), default=None)
+    return usage.onto(_sweep_result(counts, rows, best, None if best is None else kept[best].result(), why if reasons else []))
 
 
 @dataclass
@@ -1256,56 +1341,39 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
                                   "nodes list the pods' images: ImageLocality depends on the node set", reasons, headroom, node_table, devices, storage)
     scen = np.stack([len(base) + cnt.sum(1), np.zeros(len(mixes), np.int64)], 1).astype(np.int32)
     orders = np.arange(len(pods), dtype=np.int32)[None, :]
-    want_gpu = flat.problem.gpu_mem is not None
-    kw = {"want_gpu_slices": True} if want_gpu else {}
+    kw = {"want_gpu_slices": True} if flat.problem.gpu_mem is not None else {}
     if node_ranks is not None:
         kw["node_ranks"] = node_ranks
-    probes = probe_ids(flat, headroom)
+    usage = _Usage(headroom, node_table, devices, storage)
+    usage.bind(flat)
     try:
-        out = engine.run(flat.problem, scen, orders, segments=(seg_start, cnt), **kw, **_usage_kw(engine, probes, node_table, len(scen), devices, storage))
+        out = engine.run(flat.problem, scen, orders, segments=(seg_start, cnt), **kw, **usage.kw(engine, len(scen)))
     except capi.SimonError as e:
         if getattr(e, "code", None) != capi.ESTATE:
             raise
         # a problem on the all-feature kernel (prefix scenarios only): every mix as its own problem
         return _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, f"the engine refused the segmented batch: {e}", reasons, headroom, node_table, devices, storage)
     # satisfyResourceSetting over each mix's own nodes: the fixed nodes + a prefix of every segment
-    pr = flat.problem
-    vg_cap = None
-    if pr.local_flags is not None and out.used_vg is not None:
-        vg_cap = (pr.local_vg_cap * (np.arange(capi.MAX_VG)[None, :] < pr.local_vg_cnt[:, None])).sum(1)
-    def totals(v):
-        c = np.concatenate([[0], np.cumsum(np.asarray(v, np.int64))])
-        t = np.full(len(mixes), c[len(base)], np.int64)
-        for g, st in enumerate(seg_start.tolist()):
-            t += c[st + cnt[:, g]] - c[st]
-        return t
-    ac, am = totals(pr.alloc_cpu), totals(pr.alloc_mem)
-    av = totals(vg_cap) if vg_cap is not None else None
-    cpu_pct = [occupancy_pct(int(out.used_cpu[s]), int(ac[s])) for s in range(len(mixes))]
-    mem_pct = [occupancy_pct(int(out.used_mem[s]) * 1000, int(am[s]) * 1000) for s in range(len(mixes))]
-    vg_pct = [occupancy_pct(int(out.used_vg[s]), int(av[s])) for s in range(len(mixes))] if av is not None else [0] * len(mixes)
-    ok = [s for s in range(len(mixes)) if out.unscheduled[s] == 0 and cpu_pct[s] <= caps[0] and mem_pct[s] <= caps[1] and vg_pct[s] <= caps[2]]
-    best = _best_mix(mixes, ok, costs)
-    result = None
-    if best is not None:
-        res, per_node, per_dev = _unflatten(flat, out.placement[best], len(pool), {}, out.gpu_slices[best] if want_gpu and out.gpu_slices is not None else None)
-        res.node_status = [{"node": _gpu_node_status(pool[j], per_dev[j]) if j in per_dev else _node_out(pool[j]), "pods": per_node[j]}
-                           for j in np.flatnonzero(present[best]).tolist()]
-        result = res
+    rows = _scenario_rows(out, *_alloc_of_prefixes(flat.problem, out, np.full(len(mixes), len(base)), (seg_start, cnt)))
+    best = _best_mix(mixes, [s for s, r in enumerate(rows) if _within(r, caps)], costs)
+    result = None if best is None else _scenario_result(flat, out, best, pool, np.flatnonzero(present[best]).tolist())
     why = []
     if reasons:
         why = _mix_reasons(engine, cluster, apps, flat, pool, len(base), present, scen, orders, node_ranks, (seg_start, cnt), out)
-    return MixSweepResult(mixes, out.unscheduled.tolist(), cpu_pct, mem_pct, vg_pct, [_risk(out, s) for s in range(len(mixes))],
+    usage.add_launch(engine, out, pool, flat.problem, present, MixFallbackWarning, "sweep_mix", orders, scen)
+    return usage.onto(_mix_result(mixes, costs, rows, best, result, why))
+
+
+def _mix_result(mixes, costs, rows, best: Optional[int], result: Optional[SimulateResult], why, fallback: Optional[str] = None) -> MixSweepResult:
+    return MixSweepResult(mixes, [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows], [r[3] for r in rows], [r[4] for r in rows],
                           None if best is None else mixes[best], None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result,
-                          unscheduled_pods=why, **dict(zip(("headroom", "headroom_exact", "node_table", "gpu_table", "storage_table"), _usage_fill(
-                              engine, out, pool, flat.problem, present, probes, node_table, MixFallbackWarning, "sweep_mix", devices, storage, orders, scen))))
+                          batched=fallback is None, fallback=fallback, unscheduled_pods=why)
 
 
 def _mix_reasons(engine, cluster, apps, flat, pool, n_base, present, scen, orders, node_ranks, segments, out) -> List[List[dict]]:
     """MixSweepResult.unscheduled_pods of a batched sweep_mix, as _sweep_reasons fills SweepResult's: every failing mix explained in one
     engine.explain_own_batch call; a failing mix whose pod stream is not the pool's (an app with a DaemonSet, _same_stream), an engine
     without the call and a batch the library refuses to explain take simulate() of the mix's own cluster."""
-    ref = lambda p: (p["metadata"].get("namespace"), p["metadata"]["name"])                    # noqa: E731
     with_ds = any(app.resource.get("DaemonSet") for app in apps)
 
     def nodes_of(s):
@@ -1314,8 +1382,8 @@ def _mix_reasons(engine, cluster, apps, flat, pool, n_base, present, scen, order
     def same_stream(s):
         if not with_ds:
             return True
-        mine = [ref(flat.pods[pid]) for pid, j in enumerate(out.placement[s].tolist()) if j != capi.GATED]
-        return mine == [ref(p) for p in build_stream(cluster, apps, nodes_of(s), n_base)[0]]
+        mine = [_ns_name(flat.pods[pid]) for pid, j in enumerate(out.placement[s].tolist()) if j != capi.GATED]
+        return mine == [_ns_name(p) for p in build_stream(cluster, apps, nodes_of(s), n_base)[0]]
 
     def replay(s):                           # (NeedsReference: the mix is flagged in needs_reference; its pods stay without a text)
         try:
@@ -1323,18 +1391,10 @@ def _mix_reasons(engine, cluster, apps, flat, pool, n_base, present, scen, order
         except NeedsReference:
             return _unscheduled_list(flat, out.placement[s], {})
 
-    failing = [s for s in range(len(scen)) if out.unscheduled[s] > 0]
+    failing = [s for s in range(len(scen)) if out.unscheduled[s] > 0]          # (sweep_mix explains the mixes at preemption risk too)
     lists: Dict[int, List[dict]] = {s: replay(s) for s in failing if not same_stream(s)}
     failing = [s for s in failing if s not in lists]
-    texts: Dict[int, Dict[int, str]] = {}
-    if failing and getattr(engine, "supports_explain_own", False):
-        try:
-            for e in engine.explain_own_batch(flat.problem, scen, orders, node_ranks, failing, int(max(out.unscheduled[s] for s in failing)),
-                                              segments=segments):
-                texts[e.scenario] = _own_reason_texts(flat, e, present[e.scenario])
-        except capi.SimonError as err:
-            if getattr(err, "code", None) != capi.ESTATE:
-                raise
+    texts = _explain_own(engine, flat, scen, orders, node_ranks, failing, out, present, segments=segments)
     for s in failing:
         if s not in texts:
             lists[s] = replay(s)
@@ -1345,52 +1405,18 @@ def _sweep_mix_per_mix(cluster, apps, new_nodes, mixes, costs, engine, caps, why
                        node_table: bool = False, devices: bool = False, storage: bool = False) -> MixSweepResult:
     """Every mix as its own Simulate(): cluster + each type's clones in type order, canonical nodeTree order."""
     import warnings
-    warnings.warn(f"sweep_mix runs {len(mixes)} mixes one by one ({why})", MixFallbackWarning, stacklevel=3)
+    warnings.warn(f"sweep_mix runs {len(mixes)} mixes one by one ({why})", MixFallbackWarning, stacklevel=3)       # (sweep_mix: always)
     base = list(cluster.get("Node", []))
-    uns, cpu_pct, mem_pct, vg_pct, risks, kept = [], [], [], [], [], {}
-    lists: List[List[dict]] = []
-    hrs, hxs, tabs, gtabs, stabs = [], [], [], [], []
+    usage = _Usage(headroom, node_table, devices, storage)
+    rows, lists, kept = [], [], {}
     for s, mix in enumerate(mixes):
-        nodes = base + [n for nodes in mix_fake_nodes(new_nodes, mix) for n in nodes]
-        pods, _ = build_stream(cluster, apps, nodes, len(nodes))
-        arrival = [n["metadata"]["name"] for n in nodes]
-        nodes = [nodes[j] for j in k8s.canonical_node_order(nodes)]
-        flat = fl.flatten(nodes, pods, cluster.get("Service", []), cluster.get("ReplicaSet", []), cluster.get("StatefulSet", []),
-                          storage_classes=_storage_classes(cluster, apps), image_total=len(nodes), node_arrival_order=arrival)
-        want_gpu = flat.problem.gpu_mem is not None
-        out = engine.run(flat.problem, np.array([[len(nodes), 0]], np.int32), np.arange(len(pods), dtype=np.int32)[None, :],
-                         **({"want_gpu_slices": True} if want_gpu else {}))
-        uns.append(int(out.unscheduled[0]))
-        risks.append(_risk(out, 0))
-        for acc, v in zip((hrs, hxs, tabs, gtabs, stabs), _usage_each(flat, nodes, out, headroom, node_table, arrival, devices, storage)):
-            acc.append(v)
-        if reasons:
-            texts = {}
-            if uns[-1] > 0:
-                nf, failed, codes, detail = engine.explain(flat.problem, len(nodes), np.arange(len(pods), dtype=np.int32), uns[-1])
-                texts = _reason_texts(flat, failed, codes, detail)
-            lists.append(_unscheduled_list(flat, out.placement[0], texts))
-        cpu_pct.append(occupancy_pct(int(out.used_cpu[0]), int(flat.problem.alloc_cpu.sum())))
-        mem_pct.append(occupancy_pct(int(out.used_mem[0]) * 1000, int(flat.problem.alloc_mem.sum()) * 1000))
-        vg = 0
-        if flat.problem.local_flags is not None and out.used_vg is not None:
-            cap = int((flat.problem.local_vg_cap * (np.arange(capi.MAX_VG)[None, :] < flat.problem.local_vg_cnt[:, None])).sum())
-            vg = occupancy_pct(int(out.used_vg[0]), cap)
-        vg_pct.append(vg)
-        if uns[-1] == 0 and cpu_pct[-1] <= caps[0] and mem_pct[-1] <= caps[1] and vg <= caps[2]:
-            kept[s] = (flat, out, nodes)
+        a = _run_alone(cluster, apps, base + [n for nodes in mix_fake_nodes(new_nodes, mix) for n in nodes], engine, usage=usage, explain=reasons)
+        rows.append(a.row)
+        lists.append(a.unscheduled_pods)
+        if _within(a.row, caps):
+            kept[s] = a
     best = _best_mix(mixes, list(kept), costs)
-    result = None
-    if best is not None:
-        flat, out, nodes = kept[best]
-        res, per_node, per_dev = _unflatten(flat, out.placement[0], len(nodes), {}, out.gpu_slices[0] if out.gpu_slices is not None else None)
-        res.node_status = [{"node": _gpu_node_status(n, per_dev[j]) if j in per_dev else _node_out(n), "pods": per_node[j]} for j, n in enumerate(nodes)]
-        result = res
-    return MixSweepResult(mixes, uns, cpu_pct, mem_pct, vg_pct, risks, None if best is None else mixes[best],
-                          None if best is None else sum(c * k for c, k in zip(costs, mixes[best])), result, batched=False, fallback=why,
-                          unscheduled_pods=lists, headroom=hrs if headroom is not None else None, headroom_exact=_and_exact(hxs),
-                          node_table=tabs if node_table else None, gpu_table=gtabs if devices else None,
-                          storage_table=stabs if storage else None)
+    return usage.onto(_mix_result(mixes, costs, rows, best, None if best is None else kept[best].result(), lists if reasons else [], why))
 
 
 @dataclass
@@ -1546,12 +1572,6 @@ def _evicted_refs(cluster, apps, names, reschedule) -> set:
     return {_pod_ref(p) for pods in lists for p in pods if _bound_to(p) in gone and evictable(p, reschedule)} if reschedule else set()
 
 
-def _vg_caps(pr: capi.Problem, out) -> Optional[np.ndarray]:
-    if pr.local_flags is None or out.used_vg is None:
-        return None
-    return (pr.local_vg_cap * (np.arange(capi.MAX_VG)[None, :] < pr.local_vg_cnt[:, None])).sum(1)
-
-
 def _failure_result(doms, rows, caps, where, why, batched, fallback, moved=None) -> FailureSweepResult:
     """rows[s] = (unscheduled, cpu_pct, mem_pct, vg_pct, needs_reference) of scenario s (0 = the whole cluster).  moved[d]: ids (in
     scenario d + 1's own problem) of the pods rescheduled for domain d, counted on the placement rows already fetched."""
@@ -1559,7 +1579,7 @@ def _failure_result(doms, rows, caps, where, why, batched, fallback, moved=None)
     for d, mine in enumerate(moved or []):
         evicted[d] = len(mine)
         evicted_uns[d] = int((np.asarray(where[d + 1][1])[mine] == capi.UNSCHEDULED).sum()) if len(mine) else 0
-    ok = [u == 0 and c <= caps[0] and m <= caps[1] and v <= caps[2] for u, c, m, v, _ in rows]
+    ok = [_within(r, caps) for r in rows]
     base = dict(zip(("unscheduled", "cpu_pct", "mem_pct", "vg_pct", "needs_reference"), rows[0]), survives=ok[0])
     per = rows[1:]
     critical = sorted((d for d in range(len(doms)) if not ok[d + 1]), key=lambda d: (-per[d][0], d))
@@ -1624,12 +1644,11 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     if any(a.resource.get("DaemonSet") or any((p.get("spec") or {}).get("nodeName") for p in a.resource.get("Pod", [])) for a in apps):
         # such an app's pod list depends on the node set, and ScheduleApp's unstable sorts order it by its length (_same_stream): the
         # batch stands only if every scenario's own stream is the pool's without the pods that die with the domain
-        ref = lambda p: (p["metadata"].get("namespace"), p["metadata"]["name"])                # noqa: E731
         for names in doms:
             lost = {index[n] for n in names}
-            mine = [ref(p) for p, g in zip(pods, gates) if g not in lost]          # (flagged pods have no gate: they stay)
+            mine = [_ns_name(p) for p, g in zip(pods, gates) if g not in lost]     # (flagged pods have no gate: they stay)
             cl, ap = _reduced(cluster, apps, names, reschedule)
-            if mine != [ref(p) for p in build_stream(cl, ap, cl["Node"], len(cl["Node"]))[0]]:
+            if mine != [_ns_name(p) for p in build_stream(cl, ap, cl["Node"], len(cl["Node"]))[0]]:
                 return each("an app holds a DaemonSet or a pod bound to a node, and a scenario's pod order is not the cluster's")
     for p in pods:
         if p["spec"].get("nodeName") and p["metadata"].get("ownerReferences") and not (reschedule and listed(p)):
@@ -1645,61 +1664,36 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     zone = np.array([zid.setdefault(k8s.zone_key(n), len(zid)) for n in pool], np.int32)
     pr = flat.problem
     orders = np.arange(len(pods), dtype=np.int32)[None, :]
-    want_gpu = pr.gpu_mem is not None
     rows, where = [], []
-    probes = probe_ids(flat, headroom)
-    hr, hx, tab, gtab = ([] if headroom is not None else None), None, ([] if node_table else None), ([] if devices else None)
-    stab = [] if storage else None
+    usage = _Usage(headroom, node_table, devices, storage)
+    usage.bind(flat)
     told: Dict[int, List[dict]] = {}             # reasons: scenario -> its unscheduled_pods, from the batch's own explain
     for lo in range(0, len(present), max(1, int(batch_scenarios))):
         part = present[lo:lo + max(1, int(batch_scenarios))]
         scen = np.stack([part.sum(1), np.zeros(len(part), np.int64)], 1).astype(np.int32)
-        kw = {"want_gpu_slices": True} if want_gpu else {}
+        kw = {"want_gpu_slices": True} if pr.gpu_mem is not None else {}
         if len(zid) > capi.MAX_ZONES:            # more zones than the device staging takes: the rank rows travel instead
             kw["node_ranks"] = mix_node_ranks(pool, part)
+        shape = (part, zone if 1 < len(zid) <= capi.MAX_ZONES else None)
         try:
             if evict.any():
                 kw["evict"] = evict
-            out = engine.run(pr, scen, orders, present=(part, zone if 1 < len(zid) <= capi.MAX_ZONES else None), **kw,
-                             **_usage_kw(engine, probes, node_table, len(scen), devices, storage))
+            out = engine.run(pr, scen, orders, present=shape, **kw, **usage.kw(engine, len(scen)))
         except capi.SimonError as e:
             if getattr(e, "code", None) != capi.ESTATE:
                 raise
             return each(f"the engine refused the node-subset batch: {e}")
-        h1, x1, t1, g1, s1 = _usage_fill(engine, out, pool, pr, part, probes, node_table, FailureFallbackWarning, "sweep_failures", devices, storage,
-                                         orders, scen)
-        if s1 is not None:
-            stab += s1
-        if g1 is not None:
-            gtab += g1
-        if h1 is not None:
-            hr += h1
-            hx = x1
-        if t1 is not None:
-            tab += t1
+        usage.add_launch(engine, out, pool, pr, part, FailureFallbackWarning, "sweep_failures", orders, scen)
+        # sweep_failures explains the failing scenarios that are not at preemption risk (_failure_replay lists nothing for those): this
+        # launch's, on the context shape it ran with; a pod evicted in a scenario is listed as its controller recreates it
+        # (cluster_evicted; status as make_valid_pod leaves it), like simulate() of that scenario's own cluster
         failing = [s for s in range(len(part)) if lo + s > 0 and out.unscheduled[s] > 0 and not _risk(out, s)] if reasons else []
-        if failing and getattr(engine, "supports_explain_own", False):
-            # the failing scenarios of this launch on the context shape it ran with; a pod evicted in a scenario is listed as its
-            # controller recreates it (cluster_evicted; status as make_valid_pod leaves it), like simulate() of that scenario's own cluster
-            try:
-                for e in engine.explain_own_batch(pr, scen, orders, kw.get("node_ranks"), failing, int(max(out.unscheduled[s] for s in failing)),
-                                                  present=(part, zone if 1 < len(zid) <= capi.MAX_ZONES else None), evict=kw.get("evict")):
-                    s = e.scenario
-                    texts = _own_reason_texts(flat, e, part[s])
-                    gone = evict & ~part[s][np.maximum(np.asarray(pr.preset_node), 0)] if evict.any() else evict
-                    told[lo + s] = [{"pod": _public(dict(_recreated(flat.pods[pid]), status={}) if gone[pid] else flat.pods[pid]), "reason": texts.get(pid, "")}
-                                    for pid, j in enumerate(out.placement[s].tolist()) if j == capi.UNSCHEDULED]
-            except capi.SimonError as e:
-                if getattr(e, "code", None) != capi.ESTATE:
-                    raise
-        vg_cap = _vg_caps(pr, out)
-        ac, am = part @ np.asarray(pr.alloc_cpu, np.int64), part @ np.asarray(pr.alloc_mem, np.int64)
-        av = part @ np.asarray(vg_cap, np.int64) if vg_cap is not None else None
-        for s in range(len(part)):
-            rows.append((int(out.unscheduled[s]), occupancy_pct(int(out.used_cpu[s]), int(ac[s])),
-                         occupancy_pct(int(out.used_mem[s]) * 1000, int(am[s]) * 1000),
-                         occupancy_pct(int(out.used_vg[s]), int(av[s])) if av is not None else 0, _risk(out, s)))
-            where.append((flat, out.placement[s]))
+        for s, texts in _explain_own(engine, flat, scen, orders, kw.get("node_ranks"), failing, out, part, present=shape, evict=kw.get("evict")).items():
+            gone = evict & ~part[s][np.maximum(np.asarray(pr.preset_node), 0)] if evict.any() else evict
+            told[lo + s] = [{"pod": _public(dict(_recreated(flat.pods[pid]), status={}) if gone[pid] else flat.pods[pid]), "reason": texts.get(pid, "")}
+                            for pid, j in enumerate(out.placement[s].tolist()) if j == capi.UNSCHEDULED]
+        rows += _scenario_rows(out, *_alloc_of_subsets(pr, out, part))
+        where += [(flat, out.placement[s]) for s in range(len(part))]
     why = []
     if reasons:
         why = [told[d + 1] if d + 1 in told else _failure_replay(cluster, apps, names, engine, reschedule) if rows[d + 1][0] > 0 else []
@@ -1708,45 +1702,27 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     if evict.any():
         preset = np.asarray(pr.preset_node)
         moved = [np.flatnonzero(evict & ~present[d + 1][np.maximum(preset, 0)]) for d in range(len(doms))]
-    res = _failure_result(doms, rows, caps, where, why, True, None, moved)
-    res.headroom, res.headroom_exact, res.node_table, res.gpu_table, res.storage_table = hr, hx, tab, gtab, stab
-    return res
+    return usage.onto(_failure_result(doms, rows, caps, where, why, True, None, moved))
 
 
 def _sweep_failures_each(cluster, apps, doms, engine, caps, reasons, why: str, reschedule=False, headroom=None,
                          node_table: bool = False, devices: bool = False, storage: bool = False) -> FailureSweepResult:
     """Every scenario as its own Simulate(): the cluster without the domain, canonical nodeTree order."""
     import warnings
-    warnings.warn(f"sweep_failures runs {len(doms) + 1} scenarios one by one ({why})", FailureFallbackWarning, stacklevel=3)
+    warnings.warn(f"sweep_failures runs {len(doms) + 1} scenarios one by one ({why})", FailureFallbackWarning, stacklevel=3)   # (sweep_failures: always)
+    usage = _Usage(headroom, node_table, devices, storage)
     rows, where, lists, moved = [], [], [], []
-    hrs, hxs, tabs, gtabs, stabs = [], [], [], [], []
     for names in [[]] + doms:
         cl, ap = _reduced(cluster, apps, names, reschedule)
-        nodes = list(cl.get("Node", []))
-        pods, _ = build_stream(cl, ap, nodes, len(nodes))
-        arrival = [n["metadata"]["name"] for n in nodes]
-        nodes = [nodes[j] for j in k8s.canonical_node_order(nodes)]
-        flat = fl.flatten(nodes, pods, cl.get("Service", []), cl.get("ReplicaSet", []), cl.get("StatefulSet", []),
-                          storage_classes=_storage_classes(cl, ap), image_total=len(nodes), node_arrival_order=arrival)
-        pr = flat.problem
-        out = engine.run(pr, np.array([[len(nodes), 0]], np.int32), np.arange(len(pods), dtype=np.int32)[None, :],
-                         **({"want_gpu_slices": True} if pr.gpu_mem is not None else {}))
-        vg_cap = _vg_caps(pr, out)
-        rows.append((int(out.unscheduled[0]), occupancy_pct(int(out.used_cpu[0]), int(pr.alloc_cpu.sum())),
-                     occupancy_pct(int(out.used_mem[0]) * 1000, int(pr.alloc_mem.sum()) * 1000),
-                     occupancy_pct(int(out.used_vg[0]), int(vg_cap.sum())) if vg_cap is not None else 0, _risk(out, 0)))
-        where.append((flat, out.placement[0]))
-        for acc, v in zip((hrs, hxs, tabs, gtabs, stabs), _usage_each(flat, nodes, out, headroom, node_table, arrival, devices, storage)):
-            acc.append(v)
+        a = _run_alone(cl, ap, list(cl.get("Node", [])), engine, usage=usage)
+        rows.append(a.row)
+        where.append((a.flat, a.out.placement[0]))
         if reschedule and names:
             refs = _evicted_refs(cluster, apps, names, reschedule)
-            moved.append(np.array([pid for pid, r in enumerate(flat.pod_refs) if r in refs], np.int64))
-        if reasons and names:
-            lists.append(_failure_replay(cluster, apps, names, engine, reschedule) if rows[-1][0] > 0 else [])
-    res = _failure_result(doms, rows, caps, where, lists, False, why, moved)
-    res.headroom, res.headroom_exact, res.node_table = hrs if headroom is not None else None, _and_exact(hxs), tabs if node_table else None
-    res.gpu_table, res.storage_table = gtabs if devices else None, stabs if storage else None
-    return res
+            moved.append(np.array([pid for pid, r in enumerate(a.flat.pod_refs) if r in refs], np.int64))
+        if reasons and names:                    # sweep_failures takes the reasons from the reduced cluster's own simulate(), not from engine.explain
+            lists.append(_failure_replay(cluster, apps, names, engine, reschedule) if a.row[0] > 0 else [])
+    return usage.onto(_failure_result(doms, rows, caps, where, lists, False, why, moved))
 
 
 @dataclass
@@ -1802,10 +1778,14 @@ def _app_subsets(apps, subsets) -> List[tuple]:
     return out
 
 
+def _nested(v: list, K: int) -> list:
+    """[U * K] over the scenarios (u, k), k fastest -> [U][K]."""
+    return [v[i:i + K] for i in range(0, len(v), K)]
+
+
 def _app_summary(apps, subs, counts, rows, by_app, caps, weights, why_lists, batched, fallback) -> AppSweepResult:
     """rows[u][k] = (unscheduled, cpu_pct, mem_pct, vg_pct, needs_reference)."""
-    max_cpu, max_mem, max_vg = caps
-    fits = [[r[0] == 0 and r[1] <= max_cpu and r[2] <= max_mem and r[3] <= max_vg for r in row] for row in rows]
+    fits = [[_within(r, caps) for r in row] for row in rows]
     min_count = [min((counts[k] for k in range(len(counts)) if f[k]), default=None) for f in fits]
     weight = [sum(weights[a] for a in sub) for sub in subs]
     ok = [u for u in range(len(subs)) if fits[u][0]]
@@ -1821,67 +1801,40 @@ def _sweep_apps_each(cluster, apps, subs, new_node, counts, engine, caps, weight
                      node_table: bool = False, devices: bool = False, storage: bool = False) -> AppSweepResult:
     """Every scenario as its own Simulate(): the cluster, the subset's apps and its new nodes, canonical nodeTree order."""
     import warnings
-    warnings.warn(f"sweep_apps runs {len(subs) * len(counts)} scenarios one by one ({why})", AppFallbackWarning, stacklevel=3)
+    warnings.warn(f"sweep_apps runs {len(subs) * len(counts)} scenarios one by one ({why})", AppFallbackWarning, stacklevel=3)   # (sweep_apps: always)
     base = list(cluster.get("Node", []))
-    rows, by_app, lists = [], [], []
-    hrs, hxs, tabs, gtabs, stabs = [], [], [], [], []
+    usage = _Usage(headroom, node_table, devices, storage)
+    rows, by_app, lists = [], [], []             # over the scenarios (u, k), k fastest
     for sub in subs:
-        mine = [apps[a] for a in sub]
-        hrs.append([])
-        tabs.append([])
-        gtabs.append([])
-        stabs.append([])
-        rows.append([])
-        by_app.append([])
-        lists.append([])
+        mine = [apps[i] for i in sub]
         for k in counts:
             if k > 0 and new_node is None:
                 raise ValueError("new node is nil when adding node to cluster")
             nodes = base + (wl.new_fake_nodes(new_node, k) if k > 0 else [])
-            pods, _ = build_stream(cluster, mine, nodes, len(nodes))
-            own = [len(wl.app_pods(apps[a].name, apps[a].resource, nodes)) for a in sub]      # (the stream: cluster pods, then app by app)
-            group = np.full(len(pods), -1, np.int64)
-            at = len(pods) - sum(own)
-            for a, n_a in zip(sub, own):
-                group[at:at + n_a] = a
-                at += n_a
-            arrival = [n["metadata"]["name"] for n in nodes]
-            nodes = [nodes[j] for j in k8s.canonical_node_order(nodes)]
-            flat = fl.flatten(nodes, pods, cluster.get("Service", []), cluster.get("ReplicaSet", []), cluster.get("StatefulSet", []),
-                              storage_classes=_storage_classes(cluster, mine), image_total=len(nodes), node_arrival_order=arrival)
-            pr = flat.problem
+            # sweep_apps alone records the GPU devices only where devices / storage need them, leaves a scenario at preemption risk
+            # without reason texts, and does not run a scenario without pods
+            a = _run_alone(cluster, mine, nodes, engine, want_slices=devices or storage, usage=usage, explain=reasons, explain_at_risk=False,
+                           skip_empty=True)
             per = [0] * len(apps)
-            if not pods:
-                if headroom is not None or node_table or devices or storage:
+            if a.out is None:
+                if usage.asked:
                     raise ValueError("sweep_apps: headroom / node_table of a scenario without any pod, run on its own")
-                rows[-1].append((0, 0, 0, 0, False))
-                by_app[-1].append(per)
-                lists[-1].append([])
-                continue
-            out = engine.run(pr, np.array([[len(nodes), 0]], np.int32), np.arange(len(pods), dtype=np.int32)[None, :],
-                             **({"want_gpu_slices": True} if (devices or storage) and pr.gpu_mem is not None else {}))
-            h1, x1, t1, g1, s1 = _usage_each(flat, nodes, out, headroom, node_table, arrival, devices, storage)
-            hrs[-1].append(h1)
-            hxs.append(x1)
-            tabs[-1].append(t1)
-            gtabs[-1].append(g1)
-            stabs[-1].append(s1)
-            vg_cap = _vg_caps(pr, out)
-            rows[-1].append((int(out.unscheduled[0]), occupancy_pct(int(out.used_cpu[0]), int(pr.alloc_cpu.sum())),
-                             occupancy_pct(int(out.used_mem[0]) * 1000, int(pr.alloc_mem.sum()) * 1000),
-                             occupancy_pct(int(out.used_vg[0]), int(vg_cap.sum())) if vg_cap is not None else 0, _risk(out, 0)))
-            for a in group[(out.placement[0] == capi.UNSCHEDULED) & (group >= 0)].tolist():
-                per[a] += 1
-            by_app[-1].append(per)
-            texts = {}
-            if reasons and out.unscheduled[0] > 0 and not _risk(out, 0):
-                nf, failed, codes, detail = engine.explain(pr, len(nodes), np.arange(len(pods), dtype=np.int32), int(out.unscheduled[0]))
-                texts = _reason_texts(flat, failed, codes, detail)
-            lists[-1].append(_unscheduled_list(flat, out.placement[0], texts) if reasons else [])
-    res = _app_summary(apps, subs, counts, rows, by_app, caps, weights, lists if reasons else [], False, why)
-    res.headroom, res.headroom_exact, res.node_table = hrs if headroom is not None else None, _and_exact(hxs), tabs if node_table else None
-    res.gpu_table, res.storage_table = gtabs if devices else None, stabs if storage else None
-    return res
+                a.row, a.unscheduled_pods = (0, 0, 0, 0, False), []
+            else:
+                own = [len(wl.app_pods(apps[i].name, apps[i].resource, nodes)) for i in sub]      # (the stream: cluster pods, then app by app)
+                group = np.full(len(a.flat.pods), -1, np.int64)
+                at = len(group) - sum(own)
+                for i, n_i in zip(sub, own):
+                    group[at:at + n_i] = i
+                    at += n_i
+                for i in group[(a.out.placement[0] == capi.UNSCHEDULED) & (group >= 0)].tolist():
+                    per[i] += 1
+            rows.append(a.row)
+            by_app.append(per)
+            lists.append(a.unscheduled_pods)
+    K = len(counts)
+    return usage.onto(_app_summary(apps, subs, counts, _nested(rows, K), _nested(by_app, K), caps, weights, _nested(lists, K) if reasons else [],
+                                   False, why), K)
 
 
 @_gc_paused
@@ -1950,31 +1903,23 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
     if any(a.resource.get("DaemonSet") for a in apps):
         # such an app makes one pod per pool node, and ScheduleApp's unstable sorts order its pods by the length of that list: the batch
         # stands only if at every size the app's own list is the pool's list without the pods gated at that size
-        ref = lambda p: (p["metadata"].get("namespace"), p["metadata"]["name"])                # noqa: E731
         gate = np.asarray(pr.gate_node) if pr.gate_node is not None else np.full(P, -1)
         for a, app in enumerate(apps):
             if not app.resource.get("DaemonSet"):
                 continue
             for k in counts:
                 n = len(base) + k
-                mine = [ref(flat.pods[pid]) for pid in np.flatnonzero((group == a) & (gate < n)).tolist()]
-                if mine != [ref(p) for p in wl.app_pods(app.name, app.resource, pool[:n])]:
+                mine = [_ns_name(flat.pods[pid]) for pid in np.flatnonzero((group == a) & (gate < n)).tolist()]
+                if mine != [_ns_name(p) for p in wl.app_pods(app.name, app.resource, pool[:n])]:
                     return each(f"app {app.name} holds a DaemonSet, and its pod order with {k} new nodes is not the pool's")
     member = np.zeros((len(subs), A), bool)
     for u, sub in enumerate(subs):
         member[u, list(sub)] = True
     rows_of = lambda us: np.where(group[None, :] >= 0, member[us][:, np.maximum(group, 0)], True)   # noqa: E731  (cluster pods: always present)
-    pc, pm = np.cumsum(pr.alloc_cpu), np.cumsum(pr.alloc_mem)
-    rows = [[None] * K for _ in subs]
-    by_app = [[None] * K for _ in subs]
-    lists = [[[] for _ in counts] for _ in subs]
-    probes = probe_ids(flat, headroom)
-    hr = [[None] * K for _ in subs] if headroom is not None else None
-    hx = None
-    tab = [[None] * K for _ in subs] if node_table else None
-    gtab = [[None] * K for _ in subs] if devices else None
-    stab = [[None] * K for _ in subs] if storage else None
-    on_host = (headroom is not None or node_table or devices or storage) and not _on_device(engine, devices, storage)     # (the host figures need the rows)
+    rows, by_app, lists = [], [], []             # over the scenarios (u, k), k fastest: the launches hold whole subsets, in order
+    usage = _Usage(headroom, node_table, devices, storage)
+    usage.bind(flat)
+    on_host = usage.asked and not _on_device(engine, devices, storage)     # (the host figures need the rows)
     per_launch = max(1, int(batch_scenarios) // K)                  # whole subsets per launch: K scenarios each
     for lo in range(0, len(subs), per_launch):
         us = np.arange(lo, min(lo + per_launch, len(subs)))
@@ -1987,56 +1932,36 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
             kw["want_gpu_slices"] = True
         try:
             out = engine.run(pr, scen, batch.orders, want_placement=reasons or on_host, pod_present=present, pod_groups=group, **kw,
-                             **_usage_kw(engine, probes, node_table, len(scen), devices, storage))
+                             **usage.kw(engine, len(scen)))
         except capi.SimonError as e:
             if getattr(e, "code", None) != capi.ESTATE:
                 raise
             return each(f"the engine refused the pod-subset batch: {e}")
-        h1, x1, t1, g1, s1 = _usage_fill(engine, out, batch.pool, pr, np.arange(len(batch.pool))[None, :] < scen[:, :1], probes, node_table,
-                                         AppFallbackWarning, "sweep_apps", devices, storage, batch.orders, scen)
-        hx = x1 if x1 is not None else hx
-        vg_cap = _vg_caps(pr, out)
-        cv = np.cumsum(vg_cap) if vg_cap is not None else None
+        usage.add_launch(engine, out, batch.pool, pr, np.arange(len(batch.pool))[None, :] < scen[:, :1], AppFallbackWarning, "sweep_apps",
+                         batch.orders, scen)
         told: Dict[int, Dict[int, str]] = {}
+        replayed: Dict[int, List[dict]] = {}
+        # sweep_apps explains the failing scenarios that are not at preemption risk
         failing = [s for s in range(len(scen)) if out.unscheduled[s] > 0 and not _risk(out, s)] if reasons else []
         if failing and not getattr(engine, "supports_explain_batch", False):
             # no batched explain: each failing scenario's own simulate() tells its pods and texts
             for s in failing:
                 u, k = int(us[s // K]), s % K
                 try:
-                    lists[u][k] = simulate(cluster, [apps[a] for a in subs[u]], engine, wl.new_fake_nodes(new_node, counts[k]) if counts[k] > 0 else ()).unscheduled_pods
+                    replayed[s] = simulate(cluster, [apps[a] for a in subs[u]], engine, wl.new_fake_nodes(new_node, counts[k]) if counts[k] > 0 else ()).unscheduled_pods
                 except NeedsReference:
-                    lists[u][k] = _unscheduled_list(flat, out.placement[s], {})
-            replayed = set(failing)
-            failing = []
-        else:
-            replayed = set()
-        if failing:
+                    replayed[s] = _unscheduled_list(flat, out.placement[s], {})
+        elif failing:
             # the failing scenarios of this launch in one explain_batch call, each replayed with its own pod row
             for e in engine.explain_batch(pr, scen, batch.orders, kw.get("node_ranks"), failing, int(max(out.unscheduled[s] for s in failing)),
                                           pod_present=present):
                 told[e.scenario] = _reason_texts(flat, e.failed, e.rows, e.detail, [(e.n_nodes, b) for b in e.bins])
-        for i, u in enumerate(us.tolist()):
-            for k in range(K):
-                s, n = i * K + k, int(scen[i * K + k, 0])
-                rows[u][k] = (int(out.unscheduled[s]), occupancy_pct(int(out.used_cpu[s]), int(pc[n - 1])),
-                              occupancy_pct(int(out.used_mem[s]) * 1000, int(pm[n - 1]) * 1000),
-                              occupancy_pct(int(out.used_vg[s]), int(cv[n - 1])) if cv is not None else 0, _risk(out, s))
-                g = out.group_unscheduled[s]
-                by_app[u][k] = [int(g[a]) if a < len(g) else 0 for a in range(A)]
-                if h1 is not None:
-                    hr[u][k] = h1[s]
-                if t1 is not None:
-                    tab[u][k] = t1[s]
-                if g1 is not None:
-                    gtab[u][k] = g1[s]
-                if s1 is not None:
-                    stab[u][k] = s1[s]
-                if reasons and s not in replayed:
-                    lists[u][k] = _unscheduled_list(flat, out.placement[s], told.get(s, {}))
-    res = _app_summary(apps, subs, counts, rows, by_app, caps, w, lists if reasons else [], True, None)
-    res.headroom, res.headroom_exact, res.node_table, res.gpu_table, res.storage_table = hr, hx, tab, gtab, stab
-    return res
+        rows += _scenario_rows(out, *_alloc_of_prefixes(pr, out, scen[:, 0]))
+        for s in range(len(scen)):
+            g = out.group_unscheduled[s]
+            by_app.append([int(g[a]) if a < len(g) else 0 for a in range(A)])
+            lists.append(replayed[s] if s in replayed else _unscheduled_list(flat, out.placement[s], told.get(s, {})) if reasons else [])
+    return usage.onto(_app_summary(apps, subs, counts, _nested(rows, K), _nested(by_app, K), caps, w, _nested(lists, K) if reasons else [], True, None), K)
 
 
 def _claimed_storage_classes(app: AppResource) -> set:
