@@ -385,6 +385,28 @@ typedef struct simon_image_locality {
  * SIMON_ERANGE for sizes and counts, with a message. */
 int simon_set_image_locality(simon_ctx* ctx, const simon_image_locality* img);
 
+/* ImageLocality in own-nodes batches (additive, ABI stays 7).  node_size[q] = the sizeBytes that node j's OWN entry lists, parallel to
+ * simon_image_locality.node_image.  With sizes attached simon_set_scenario_segments and simon_set_scenario_nodes accept an image
+ * problem and score every scenario by its own image states: schedulerCache.addNodeImageStates (cache.go:675-698) over the scenario's
+ * nodes fed in pool order -- NumNodes of node j's entry = the scenario's listers of that image at or before j, Size = the sizeBytes of
+ * its first lister, totalNumNodes = its node count.  Scenarios with equal node counts and equal presence over the listing nodes share
+ * one slot of the score table; the table [slots][image-scoring pod classes][node classes], every listing node a class of its own,
+ * is computed on the device (env SIMON_IMAGE_STAGE=host: in a host loop; read once in simon_ctx_create).  Design limit: a batch whose
+ * table exceeds 256 MB (env SIMON_IMAGE_STATE_MB, read once in simon_ctx_create) is refused with SIMON_ESTATE.
+ * Call after simon_set_image_locality, before or after simon_load_scenarios (the context keeps the loaded orders of every image problem
+ * for the re-staging); NULL detaches; cleared whenever image locality is cleared.  Attaching or detaching while an own-nodes image
+ * batch is loaded unloads it: load the scenarios again.  Cost to know: simon_load_scenarios stages the per-size slots of the prefix batch
+ * and the own-nodes call stages the tables a second time for the image states, so such a batch pays the staging twice.  SIMON_ERANGE: a size outside
+ * [0, 2^53).  SIMON_ESTATE: no image locality loaded.  Arrival orders other than pool order are not covered.  No simon_group_*
+ * forward and no Go shim. */
+int simon_set_image_node_sizes(simon_ctx* ctx, const int64_t* node_size /* [nnz] */);
+
+/* The ImageLocality score of every (pod class, pool node) in one scenario of the loaded batch -- prefix, segmented or node-subset --
+ * read back from the table the kernels read and expanded through the (refined) node class of every node: what simon_fetch_node_ranks
+ * is for the rank staging.  Nodes the scenario lacks and classes without a listed image read 0.  SIMON_ESTATE: nothing loaded, or the
+ * problem has no image that a pod runs and a node lists.  No simon_group_* forward and no Go shim. */
+int simon_fetch_image_scores(simon_ctx* ctx, int32_t scenario, uint8_t* score /* [Cp][N] */);
+
 /* Canonical (nodeTree) order per scenario.  By default the canonical order of a scenario's nodes is their pool order.  With
  * nodes in several zones the nodeTree order of a larger cluster does not extend a smaller one's (zones are visited round
  * robin, V/internal/cache/node_tree.go:119-143), so the host may supply rank[s][j] = position of pool node j in scenario
@@ -402,7 +424,9 @@ int simon_set_node_ranks(simon_ctx* ctx, const int32_t* rank /* [S][N] */);
  * Call after simon_load_scenarios (which clears it); n_seg = 0 returns to prefix scenarios.  SIMON_EINVAL: n_seg < 0, missing
  * arrays, starts not ascending, a count beyond its segment, an n_nodes mismatch, a scenario of no nodes at all
  * (no fixed nodes, every count 0), n_seg > SIMON_MAX_SEGMENTS, a segment node with pods bound before the
- * stream (init_*) or the target of a preset pod.  SIMON_ESTATE: ImageLocality in effect (simon_set_image_locality).  A segmented batch
+ * stream (init_*) or the target of a preset pod.  SIMON_ESTATE: ImageLocality in effect (simon_set_image_locality) without node
+ * sizes (simon_set_image_node_sizes); with them, image states beyond the cap, and SIMON_EINVAL ("arrival order is not pool order") when
+ * node_count / size are not the pool-order reading of the whole pool.  A segmented batch
  * runs on the score-table kernel only: simon_run_loaded refuses (SIMON_ESTATE) a problem that needs the all-feature kernel, and
  * simon_explain / simon_explain_loaded / simon_explain_batch refuse while one is loaded -- simon_explain_own_batch explains its
  * scenarios.  A call that fails leaves the batch a prefix batch. */
@@ -422,7 +446,9 @@ int simon_set_scenario_segments(simon_ctx* ctx, int32_t n_seg, const int32_t* se
  * Call after simon_load_scenarios (which clears it); present == NULL returns to prefix scenarios.  It replaces segments and is replaced
  * by them.  SIMON_EINVAL: bits set at or beyond N, an n_nodes mismatch, a scenario of no nodes, zone ids outside [0, n_zones) or
  * n_zones outside [1, SIMON_MAX_ZONES] with node_zone given, a node absent from some scenario that carries pods bound before the
- * stream (init_*) or is the preset target of a pod neither gated on it nor flagged (simon_set_pod_eviction).  SIMON_ESTATE: nothing loaded, ImageLocality in effect.  A call that
+ * stream (init_*) or is the preset target of a pod neither gated on it nor flagged (simon_set_pod_eviction).  SIMON_ESTATE: nothing loaded, ImageLocality in effect without node sizes
+ * (simon_set_image_node_sizes; with them: image states beyond the cap, and SIMON_EINVAL when node_count / size are not the pool-order
+ * reading, as for segments).  A call that
  * fails leaves the batch a prefix batch.  Like a segmented batch it runs on the score-table kernel only: simon_run_loaded refuses
  * (SIMON_ESTATE, "node-subset batch") a problem that needs the all-feature kernel, and simon_explain / simon_explain_loaded /
  * simon_explain_batch refuse while one is loaded (simon_explain_own_batch explains its scenarios).  The per-scenario arrays are built on
@@ -740,7 +766,8 @@ int simon_explain_batch(simon_ctx* ctx, const int32_t* scenarios, int32_t n_scen
  * SIMON_ESTATE also where simon_run_loaded would refuse the batch: a problem whose route is the all-feature kernel (env
  * SIMON_FORCE_WIDE=1 included).  SIMON_EINVAL: an index outside the batch, bad sizes (as simon_explain_batch), code_stride < N with
  * fail_codes given.  simon_explain / simon_explain_loaded / simon_explain_batch keep refusing such batches.
- * Not covered: no simon_group_* forward and no Go shim; no Open-Local sizes and no ImageLocality (neither occurs in such a batch).
+ * Not covered: no simon_group_* forward and no Go shim; no Open-Local sizes.  An image batch (simon_set_image_node_sizes)
+ * is replayed with its image states, each listed scenario with its own slot.
  * (additive: the ABI stays 7) */
 int simon_explain_own_batch(simon_ctx* ctx, const int32_t* scenarios, int32_t n_scen, int32_t max_failed, int32_t max_bins,
                             int32_t* n_failed, int32_t* failed_pods, int32_t* n_bins, simon_fail_bin* bins,

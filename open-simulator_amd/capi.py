@@ -133,9 +133,14 @@ class ImageLocality:
     node_count: np.ndarray    # [nnz] int32
     class_off: np.ndarray     # [Cp+1] int32
     class_image: np.ndarray   # [class_off[-1]] int32
+    # [nnz] int64: the sizeBytes node j's own entry lists (simon_set_image_node_sizes).  With it segmented and node-subset batches take the
+    # problem and score every scenario by its own image states; node_count / size must then be the pool-order reading.
+    node_size: Optional[np.ndarray] = None
 
     def normalise(self):
         self.size = np.ascontiguousarray(self.size, dtype=np.int64).reshape(-1)
+        if self.node_size is not None:
+            self.node_size = np.ascontiguousarray(self.node_size, dtype=np.int64).reshape(-1)
         for name in ("node_off", "node_image", "node_count", "class_off", "class_image"):
             setattr(self, name, np.ascontiguousarray(getattr(self, name), dtype=np.int32).reshape(-1))
         return self
@@ -586,7 +591,7 @@ EXPORTS = [
     "simon_explain_own_batch",
     "simon_set_scalar_entries", "simon_set_pod_priorities", "simon_fetch_preempt_risk",
     "simon_group_set_scalar_entries", "simon_group_set_pod_priorities", "simon_group_fetch_preempt_risk",
-    "simon_set_image_locality", "simon_group_set_image_locality",
+    "simon_set_image_locality", "simon_group_set_image_locality", "simon_set_image_node_sizes", "simon_fetch_image_scores",
     "simon_set_scenario_segments", "simon_set_scenario_nodes", "simon_fetch_node_ranks", "simon_set_pod_eviction",
     "simon_set_own_nodes_all_feature",
     "simon_set_scenario_pods", "simon_fetch_group_counts", "simon_fetch_node_usage", "simon_fetch_headroom",
@@ -632,6 +637,9 @@ def load_library(path: Optional[str] = None):
     lib.simon_set_scenario_nodes.argtypes = [vp, C.POINTER(C.c_uint32), _p32, C.c_int32]
     lib.simon_set_scenario_nodes.restype = C.c_int
     lib.simon_fetch_node_ranks.argtypes = [vp, _p32]
+    lib.simon_set_image_node_sizes.argtypes = [vp, _p64]
+    lib.simon_set_image_node_sizes.restype = C.c_int
+    lib.simon_fetch_image_scores.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint8)]
     lib.simon_set_pod_eviction.argtypes = [vp, C.POINTER(C.c_uint8)]
     lib.simon_set_pod_eviction.restype = C.c_int
     lib.simon_set_own_nodes_all_feature.argtypes = [vp, C.c_int32]
@@ -797,6 +805,8 @@ class Context:
         if prob.image_locality is not None:
             im = prob.image_locality.c_struct()
             self._check(self.lib.simon_set_image_locality(self.h, C.byref(im)), "simon_set_image_locality")
+            if prob.image_locality.node_size is not None:
+                self.set_image_node_sizes(prob.image_locality.node_size, nnz=len(prob.image_locality.node_image))
         self.problem = prob
 
     def load_scenarios(self, scen, orders: np.ndarray):
@@ -998,6 +1008,28 @@ class Context:
             call, name = self.lib.simon_fetch_headroom_local, "simon_fetch_headroom_local"
         self._check(call(self.h, _ptr(pp, C.c_int32), K, _ptr(fit, C.c_int64), _ptr(fn, C.c_int32), _ptr(ex, C.c_uint8)), name)
         return fit, fn, ex.astype(bool)
+
+    def set_image_node_sizes(self, node_size, nnz: Optional[int] = None) -> None:
+        """simon_set_image_node_sizes: int64 [nnz] sizeBytes of every node entry (parallel to ImageLocality.node_image), None detaches."""
+        if node_size is None:
+            self._check(self.lib.simon_set_image_node_sizes(self.h, None), "simon_set_image_node_sizes")
+            return
+        a = np.ascontiguousarray(node_size, dtype=np.int64).reshape(-1)
+        if nnz is None:                          # (the library reads as many entries as the loaded image input lists)
+            prob = getattr(self, "problem", None)
+            # (no image input went through load_problem: the library refuses with SIMON_ESTATE before it reads anything)
+            nnz = len(a) if prob is None or prob.image_locality is None else len(prob.image_locality.node_image)
+        if len(a) != nnz:
+            raise ValueError(f"node_size has {len(a)} entries, the image input lists {nnz}")
+        keep = a if len(a) else np.zeros(1, np.int64)
+        self._check(self.lib.simon_set_image_node_sizes(self.h, _ptr(keep, C.c_int64)), "simon_set_image_node_sizes")
+
+    def fetch_image_scores(self, scenario: int) -> np.ndarray:
+        """[Cp][N] uint8: ImageLocality of every (pod class, pool node) in one scenario of the loaded batch, read back from the staged
+        device table (0 for absent nodes and for classes that run no listed image); SIMON_ESTATE without a batch or without images."""
+        out = np.zeros((self.problem.n_pod_classes, self.problem.n_nodes), np.uint8)
+        self._check(self.lib.simon_fetch_image_scores(self.h, int(scenario), out.ctypes.data_as(C.POINTER(C.c_uint8))), "simon_fetch_image_scores")
+        return out
 
     def fetch_node_ranks(self) -> np.ndarray:
         """[S][N] the rank rows in effect (nodes a segmented / node-subset scenario lacks: N); SIMON_ESTATE for a batch without rows."""

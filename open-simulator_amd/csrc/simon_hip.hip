@@ -266,6 +266,17 @@ struct simon_ctx : simon::HostInputs {
     int img_stride_t = 0;                           // table classes x internal node classes (TableCold::img_stride)
     std::vector<int32_t> h_img_slot;                // host sources of d_img_slot / d_img_explain: they outlive the asynchronous uploads
     std::vector<unsigned char> h_img_explain;
+    // own-nodes image states (HostInputs::img_own_*): the table comes from image_states_kernel (simon_subset.hip), or, image_host (env
+    // SIMON_IMAGE_STAGE=host), from a host loop.  img_state_cap: bytes of [T][img_R][Cn] a batch may ask for (env SIMON_IMAGE_STATE_MB).
+    // img_orders: the loaded orders, kept for every image problem (the re-staging derives the inverse orders again).  h_tc_of / t_img_staged:
+    // table class of every pod class while d_t_img is current (simon_fetch_image_scores)
+    bool image_host = false, t_img_staged = false;
+    size_t img_state_cap = (size_t)256 << 20;
+    std::vector<int32_t> img_orders, h_tc_of;
+    DevBuf<uint32_t> d_is_words;
+    DevBuf<int32_t> d_is_i32, d_is_scratch;
+    DevBuf<int64_t> d_is_size;
+    DevBuf<unsigned char> d_is_out;
     simon_stats stats{};
 };
 
@@ -343,19 +354,108 @@ void img_slot_scores(const simon_ctx* c, int n, uint8_t* out) {
     }
 }
 
+// The image-state table of an own-nodes batch in a host loop (SIMON_IMAGE_STAGE=host; image_states_kernel's A/B and fallback):
+// addNodeImageStates over the slot's nodes in pool order, then img_score's arithmetic on the slot's own counts and sizes.
+void img_own_scores_host(simon_ctx* c) {
+    const int N = c->N, I = (int)c->img_size.size(), W = (N + 31) / 32;
+    const size_t slot = (size_t)c->img_R * c->Cn;
+    std::vector<int32_t> cnt(c->img_node_image.size()), run(I), first(I);
+    for (int t = 0; t < c->img_own_T; ++t) {
+        const uint32_t* row = c->img_own_words.data() + (size_t)t * W;
+        auto in = [&](int j) { return (row[j >> 5] >> (j & 31)) & 1u; };
+        std::fill(run.begin(), run.end(), 0); std::fill(first.begin(), first.end(), -1);
+        for (int j = 0; j < N; ++j)
+            for (int q = c->img_node_off[j]; in(j) && q < c->img_node_off[j + 1]; ++q) {
+                const int im = c->img_node_image[q];
+                cnt[q] = ++run[im];
+                if (first[im] < 0) first[im] = q;
+            }
+        const int n = c->img_own_n[t];
+        for (int cp = 0; cp < c->Cp; ++cp) {
+            const int r = c->img_row_of[cp], e0 = c->img_class_off[cp], e1 = c->img_class_off[cp + 1];
+            if (r < 0) continue;
+            const int64_t mb = 1024 * 1024, lo = 23 * mb, hi = 1000 * mb * (int64_t)(e1 - e0);
+            for (int k = 0; k < c->Cn; ++k) {
+                const int j = c->img_rep[k];
+                if (j < 0 || !in(j)) continue;                       // (an absent representative scores 0)
+                int64_t sum = 0;
+                for (int e = e0; e < e1; ++e) {
+                    const int im = c->img_class_image[e];
+                    if (im < 0) continue;
+                    for (int q = c->img_node_off[j]; q < c->img_node_off[j + 1]; ++q)
+                        if (c->img_node_image[q] == im) {
+                            sum += (int64_t)((double)c->img_node_size[first[im]] * ((double)cnt[q] / (double)n));
+                            break;
+                        }
+                    if (sum > hi) sum = hi + 1;
+                }
+                if (sum < lo) sum = lo; else if (sum > hi) sum = hi;
+                c->img_cls[t * slot + (size_t)r * c->Cn + k] = (uint8_t)(100 * (sum - lo) / (hi - lo));
+            }
+        }
+    }
+}
+
+// ... and on the device: the lister lists (a CSR by image, pool order) and the flat inputs go up in one int32 buffer, the table comes
+// back into img_cls (stage_narrow / wide_stage lay it out for their kernels)
+int img_own_scores_device(simon_ctx* c) {
+    const int N = c->N, I = (int)c->img_size.size(), W = (N + 31) / 32, T = c->img_own_T, Cp = c->Cp;
+    const size_t nnz = c->img_node_image.size();
+    std::vector<int32_t> lis_off(I + 1, 0), lis_node(nnz), lis_ent(nnz), row_class(c->img_R);
+    for (size_t q = 0; q < nnz; ++q) ++lis_off[c->img_node_image[q] + 1];
+    for (int i = 0; i < I; ++i) lis_off[i + 1] += lis_off[i];
+    {
+        std::vector<int32_t> at(lis_off.begin(), lis_off.end() - 1);
+        for (int j = 0; j < N; ++j)
+            for (int q = c->img_node_off[j]; q < c->img_node_off[j + 1]; ++q) {
+                const int k = at[c->img_node_image[q]]++;
+                lis_node[k] = j; lis_ent[k] = q;
+            }
+    }
+    for (int cp = 0; cp < Cp; ++cp) if (c->img_row_of[cp] >= 0) row_class[c->img_row_of[cp]] = cp;
+    std::vector<int32_t> flat;
+    size_t off[10];
+    const std::vector<int32_t>* parts[10] = {&lis_off, &lis_node, &lis_ent, &c->img_node_off, &c->img_node_image, &c->img_class_off, &c->img_class_image, &row_class, &c->img_rep, &c->img_own_n};
+    for (int k = 0; k < 10; ++k) { off[k] = flat.size(); flat.insert(flat.end(), parts[k]->begin(), parts[k]->end()); }
+    const size_t out_bytes = (size_t)T * c->img_R * c->Cn;
+    HIP_TRY(c, c->d_is_i32.upload(flat, c->stream));
+    HIP_TRY(c, c->d_is_words.upload(c->img_own_words, c->stream));
+    HIP_TRY(c, c->d_is_size.upload(c->img_node_size, c->stream));
+    HIP_TRY(c, c->d_is_out.ensure(out_bytes));
+    ImageStates a{};
+    const int32_t* const b = c->d_is_i32.p;
+    a.present = c->d_is_words.p; a.slot_n = b + off[9];
+    a.lis_off = b + off[0]; a.lis_node = b + off[1]; a.lis_ent = b + off[2];
+    a.node_size = c->d_is_size.p; a.node_off = b + off[3]; a.node_image = b + off[4];
+    a.class_off = b + off[5]; a.class_image = b + off[6]; a.row_class = b + off[7]; a.rep = b + off[8];
+    a.T = T; a.W = W; a.I = I; a.nnz = (int32_t)nnz; a.R = c->img_R; a.Cn = c->Cn;
+    if ((nnz + I) * sizeof(int32_t) > kImageLdsBudget) {              // (decided by size, here: the counts of a slot in a global row)
+        HIP_TRY(c, c->d_is_scratch.ensure((size_t)T * (nnz + I)));
+        a.scratch = c->d_is_scratch.p;
+    }
+    a.out = c->d_is_out.p;
+    HIP_TRY(c, launch_image_states(a, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->img_cls.data(), c->d_is_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SIMON_OK;
+}
+
 // Split the caller's node classes by image CONTENT -- (image, NumNodes) of every entry of the node -- so that the nodes of a class score
 // alike for EVERY cluster size (simon_explain of a size outside the batch included), and derive the per-slot tables of the batch
 // (img_sizes).  Classes of nodes without entries keep their ids: a problem whose nodes list nothing stages exactly as without images.
-void img_refine(simon_ctx* c) {
+// Own-nodes form (img_own_T > 0): a node's NumNodes depends on which listers the scenario holds, so every node with an entry is a class
+// of its own and the slots are the batch's image states; the score-table staging interns equal score columns again.
+int img_refine(simon_ctx* c) {
     img_unrefine(c);
     c->img_row_of.assign(c->Cp, -1);
     c->img_R = 0; c->img_cls.clear(); c->img_rep.clear();
-    if (!c->has_img) return;
+    if (!c->has_img) return SIMON_OK;
     for (int cp = 0; cp < c->Cp; ++cp)
         for (int e = c->img_class_off[cp]; e < c->img_class_off[cp + 1]; ++e)
             if (c->img_class_image[e] >= 0) { c->img_row_of[cp] = c->img_R++; break; }
-    if (c->img_R == 0) return;
+    if (c->img_R == 0) return SIMON_OK;
     const int N = c->N, Cn0 = c->Cn;
+    const bool own = c->img_own_T > 0;
     std::map<std::vector<int32_t>, int> ids;
     for (int k = 0; k < Cn0; ++k) ids.emplace(std::vector<int32_t>{k}, k);
     std::vector<int32_t> ncls(N), rep(Cn0, -1);
@@ -364,6 +464,7 @@ void img_refine(simon_ctx* c) {
         for (int q = c->img_node_off[j]; q < c->img_node_off[j + 1]; ++q) ent.emplace_back(c->img_node_image[q], c->img_node_count[q]);
         std::sort(ent.begin(), ent.end());
         std::vector<int32_t> key{c->node_class[j]};
+        if (own && !ent.empty()) { key = {-1, j}; ent.clear(); }      // (its own pre-class)
         for (auto& e : ent) { key.push_back(e.first); key.push_back(e.second); }
         auto it = ids.emplace(std::move(key), (int)ids.size());
         if (it.second) rep.push_back(-1);
@@ -389,8 +490,14 @@ void img_refine(simon_ctx* c) {
     }
     c->img_rep = rep;
     const size_t slot = (size_t)c->img_R * c->Cn;
-    c->img_cls.assign(c->img_sizes.size() * slot, 0);
+    c->img_cls.assign(c->img_slots() * slot, 0);
+    if (own) {
+        if (!c->image_host) return img_own_scores_device(c);
+        img_own_scores_host(c);
+        return SIMON_OK;
+    }
     for (size_t t = 0; t < c->img_sizes.size(); ++t) img_slot_scores(c, c->img_sizes[t], c->img_cls.data() + t * slot);
+    return SIMON_OK;
 }
 
 // every slot's image scores of pod class cp, appended to a content key (nothing for a class that scores 0 everywhere)
@@ -399,7 +506,7 @@ void img_row_append(const simon_ctx* c, int cp, std::vector<T>& key) {
     if (c->img_R == 0 || c->img_row_of[cp] < 0) return;
     const size_t slot = (size_t)c->img_R * c->Cn, off = (size_t)c->img_row_of[cp] * c->Cn;
     key.push_back((T)-1);                            // (a separator: rows of different lengths never alias)
-    for (size_t t = 0; t < c->img_sizes.size(); ++t)
+    for (size_t t = 0; t < c->img_slots(); ++t)
         for (int k = 0; k < c->Cn; ++k) key.push_back((T)c->img_cls[t * slot + off + k]);
 }
 
@@ -1293,7 +1400,7 @@ int stage_narrow(simon_ctx* c) {
                     for (const std::vector<int64_t>* tab : {&c->na_raw, &c->tt_raw, &c->static_add})
                         if (!tab->empty()) col.push_back((int32_t)(*tab)[(size_t)tc_rep[tc] * c->Cn + nc]);
                     const int ir = c->img_R ? c->img_row_of[tc_rep[tc]] : -1;   // ImageLocality: the class's score column for every size of the batch
-                    for (size_t t = 0; ir >= 0 && t < c->img_sizes.size(); ++t)
+                    for (size_t t = 0; ir >= 0 && t < c->img_slots(); ++t)
                         col.push_back(c->img_cls[(t * c->img_R + ir) * c->Cn + nc]);
                 }
                 content_of[nc] = col_id.emplace(std::move(col), (int)col_id.size()).first->second;
@@ -1349,9 +1456,9 @@ int stage_narrow(simon_ctx* c) {
                 HIP_TRY(c, buf->upload(t, st));
             }
             if (c->img_R > 0) {                                       // ImageLocality: [slot][table class][internal node class]
-                const size_t nslot = std::max<size_t>(c->img_sizes.size(), 1);
+                const size_t nslot = std::max<size_t>(c->img_slots(), 1);
                 std::vector<unsigned char> img_t(nslot * Ctc * Ct, 0);
-                for (size_t t = 0; t < c->img_sizes.size(); ++t)
+                for (size_t t = 0; t < c->img_slots(); ++t)
                     for (int tc = 0; tc < Ctc; ++tc) {
                         const int ir = c->img_row_of[tc_rep[tc]];
                         if (ir < 0) continue;
@@ -1360,6 +1467,7 @@ int stage_narrow(simon_ctx* c) {
                 HIP_TRY(c, c->d_t_img.upload(img_t, st));
                 HIP_TRY(c, hipStreamSynchronize(st));                  // (img_t dies at the end of this block)
                 c->img_stride_t = Ctc * Ct;
+                c->h_tc_of = tc_of; c->t_img_staged = true;
             }
             if (c->has_mask) {
                 std::vector<uint64_t> mask_t((size_t)Ctc * words);
@@ -1491,10 +1599,11 @@ int stage(simon_ctx* c) {
     c->has_gpu = c->has_gpu_nodes;
     if (!c->has_gpu)
         for (int p = 0; p < c->P; ++p) if (c->p_gpu_mem[p] > 0) { c->has_gpu = true; break; }
-    img_refine(c);                                                  // (ABI v7: node classes split by image content, the batch's size slots)
+    c->t_img_staged = false;
+    if (const int rc = img_refine(c)) return rc;                    // (ABI v7: node classes split by image content, the batch's size slots or image states)
     if (c->debug_route && c->img_R > 0)
-        fprintf(stderr, "[route] image split: %d node classes (caller %d), %d image-scoring pod classes, %zu sizes\n", c->Cn,
-                c->img_refined ? c->img_base_Cn : c->Cn, c->img_R, c->img_sizes.size());
+        fprintf(stderr, "[route] image split: %d node classes (caller %d), %d image-scoring pod classes, %zu %s\n", c->Cn,
+                c->img_refined ? c->img_base_Cn : c->Cn, c->img_R, c->img_slots(), c->img_own_T > 0 ? "image states" : "sizes");
     choose_variant(c);
     if (c->variant != SIMON_KERNEL_NARROW) c->spread = false;         // (a later precondition sent the problem to the all-feature kernel)
     // prefix sums of allocatable for the occupancy caps (satisfyResourceSetting, apply.go:737-760)
@@ -1684,6 +1793,8 @@ simon_ctx* simon_ctx_create(int device_id) {
     c->no_shared_prologue = getenv("SIMON_NO_SHARED_PROLOGUE") != nullptr;
     c->no_size_dispatch = getenv("SIMON_NO_SIZE_DISPATCH") != nullptr;
     if (const char* e = getenv("SIMON_SUBSET_STAGE")) c->subset_host = strcmp(e, "host") == 0;   // A/B + tests: node-subset staging in host loops
+    if (const char* e = getenv("SIMON_IMAGE_STAGE")) c->image_host = strcmp(e, "host") == 0;     // A/B + tests: image states of an own-nodes batch in a host loop
+    if (const char* e = getenv("SIMON_IMAGE_STATE_MB")) c->img_state_cap = (size_t)std::max(atoll(e), 0ll) << 20;
     if (const char* e = getenv("SIMON_USAGE_TILE")) c->usage_tile = std::max(atoi(e), 0);        // tests: node tiles of simon_fetch_node_usage / _headroom
     c->debug_route = getenv("SIMON_DEBUG_ROUTE") != nullptr;
     c->force_table = getenv("SIMON_FORCE_TABLE") != nullptr;         // A/B + tests: keep 257 .. 384 signatures on the score-table kernel   // A/B: node classes not split into with / without devices
@@ -1726,7 +1837,7 @@ int simon_load_nodes(simon_ctx* c, const simon_nodes_soa* nd) {
     if (nd->n_scalar > 0 && !nd->scalar_alloc) return fail(c, SIMON_EINVAL, "scalar_alloc missing");
     if (nd->n_topo_keys < 0 || (nd->n_topo_keys > 0 && (!nd->topo_dom || !nd->topo_n_dom))) return fail(c, SIMON_EINVAL, "topology arrays missing");
     img_unrefine(c);                     // (a new pool: the image input no longer describes it)
-    c->has_img = false; c->img_sizes.clear();
+    c->has_img = false; c->img_sizes.clear(); c->img_node_size.clear(); c->img_own_T = 0;
     c->N = N; c->K = nd->n_scalar; c->Kt = nd->n_topo_keys;
     copy_opt(c->alloc_cpu, nd->alloc_cpu, N); copy_opt(c->alloc_mem, nd->alloc_mem, N);
     copy_opt(c->alloc_eph, nd->alloc_eph, N); copy_opt(c->alloc_pods, nd->alloc_pods, N);
@@ -1865,7 +1976,7 @@ int simon_set_image_locality(simon_ctx* c, const simon_image_locality* im) {
     if (!c->have_nodes || !c->have_tables) return fail(c, SIMON_ESTATE, "set_image_locality: load nodes and class tables first");
     img_unrefine(c);
     c->staged = false; c->wide_staged = false; c->have_results = false;
-    c->has_img = false; c->img_sizes.clear();
+    c->has_img = false; c->img_sizes.clear(); c->img_node_size.clear(); c->img_own_T = 0;
     c->img_size.clear(); c->img_node_off.clear(); c->img_node_image.clear(); c->img_node_count.clear(); c->img_class_off.clear(); c->img_class_image.clear();
     if (!im) return SIMON_OK;
     const int N = c->N, Cp = c->Cp, I = im->n_images;
@@ -1906,13 +2017,27 @@ int simon_set_image_locality(simon_ctx* c, const simon_image_locality* im) {
     return SIMON_OK;
 }
 
+int simon_set_image_node_sizes(simon_ctx* c, const int64_t* node_size) {
+    if (!c) return SIMON_EINVAL;
+    if (!c->has_img) return fail(c, SIMON_ESTATE, "set_image_node_sizes: load image locality first");
+    if (c->img_own_T > 0) { c->img_own_T = 0; c->staged = false; c->wide_staged = false; c->have_results = false; }   // (an own-nodes image batch is loaded again)
+    c->img_node_size.clear();
+    if (!node_size) return SIMON_OK;
+    const size_t nnz = c->img_node_image.size();
+    for (size_t q = 0; q < nnz; ++q)
+        if (node_size[q] < 0 || node_size[q] >= (1ll << 53)) return fail(c, SIMON_ERANGE, "set_image_node_sizes: entry %zu: size %lld outside [0, 2^53)", q, (long long)node_size[q]);
+    c->img_node_size.assign(node_size, node_size + nnz);
+    if (nnz == 0) c->img_node_size.assign(1, 0);                  // (attached, though no node lists anything: "empty" means detached)
+    return SIMON_OK;
+}
+
 int simon_load_class_tables(simon_ctx* c, const simon_class_tables* tb) {
     if (!c || !tb) return SIMON_EINVAL;
     if (tb->struct_size != sizeof(simon_class_tables)) return fail(c, SIMON_EINVAL, "simon_class_tables size mismatch");
     if (!c->have_nodes) return fail(c, SIMON_ESTATE, "load nodes before class tables");
     if (tb->n_pod_classes <= 0 || tb->n_node_classes <= 0 || !tb->simon_raw) return fail(c, SIMON_EINVAL, "class tables: bad sizes");
     img_unrefine(c);                     // (new class tables: the image input no longer describes them)
-    c->has_img = false; c->img_sizes.clear();
+    c->has_img = false; c->img_sizes.clear(); c->img_node_size.clear(); c->img_own_T = 0;
     c->Cp = tb->n_pod_classes; c->Cn = tb->n_node_classes;
     const size_t words = (size_t)(c->N + 63) / 64;
     c->has_mask = tb->static_mask != nullptr;
@@ -2105,10 +2230,38 @@ static int table_layout(simon_ctx* c) {
     return SIMON_OK;
 }
 
+// What a loaded batch derives from the staged problem next to its scenarios (simon_load_scenarios; again after an own-nodes image batch
+// has re-staged the tables): for the score-table kernel the inverse orders -- placements are recorded by scheduling step and gathered
+// back to pod ids through them, which takes every order to be a permutation of [0, P) -- and the layout of the batch.
+static int batch_orders_stage(simon_ctx* c, const int32_t* orders, int n_orders, int S, int max_n) {
+    const int P = c->P;
+    c->scen_ni.assign(S, 0);
+    c->orders_perm = false;
+    c->table_perm_ok = false;
+    if (c->variant == SIMON_KERNEL_NARROW && c->table_ok) {
+        std::vector<int32_t> inv((size_t)n_orders * P, -1);
+        bool is_perm = true;
+        for (int o = 0; o < n_orders && is_perm; ++o)
+            for (int i = 0; i < P; ++i) {
+                int32_t& slot = inv[(size_t)o * P + orders[(size_t)o * P + i]];
+                if (slot >= 0) { is_perm = false; break; }
+                slot = i;
+            }
+        c->orders_perm = is_perm;
+        c->S = S; c->max_n = max_n;
+        if (is_perm) {
+            HIP_TRY(c, c->d_inv_orders.upload(inv, c->stream));
+            if (const int rc = table_layout(c)) return rc;           // (synchronises: inv may die)
+        }
+    }
+    return SIMON_OK;
+}
+
 int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, const int32_t* orders, int32_t n_orders) {
     if (!c || !scen || S <= 0 || !orders || n_orders <= 0) return c ? fail(c, SIMON_EINVAL, "load_scenarios: bad arguments") : SIMON_EINVAL;
     c->seg_n = 0; c->sub_on = false;                     // (segments and node subsets belong to the batch they were set for)
     c->pods_on = false;                                  // (and so do pod rows)
+    if (c->img_own_T > 0) { c->img_own_T = 0; c->staged = false; }   // (image states belong to the own-nodes batch they were built for)
     if (c->has_img) {                    // ImageLocality: one slot per distinct cluster size; another set of sizes re-stages the tables
         std::vector<int32_t> sizes(S);
         for (int s = 0; s < S; ++s) sizes[s] = scen[s].n_nodes;
@@ -2163,28 +2316,10 @@ int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, co
     }
     c->wide.img_slot_ext = c->img_R > 0 ? c->d_img_slot.p : nullptr;
     c->h_perm = perm;
-    c->scen_ni.assign(S, 0);
-    c->orders_perm = false;
-    c->table_perm_ok = false;
-    if (c->variant == SIMON_KERNEL_NARROW && c->table_ok) {
-        // placements are recorded by scheduling step and gathered back to pod ids through the inverse orders,
-        // which exist only when every order is a permutation of [0, P)
-        std::vector<int32_t> inv((size_t)n_orders * P, -1);
-        bool is_perm = true;
-        for (int o = 0; o < n_orders && is_perm; ++o)
-            for (int i = 0; i < P; ++i) {
-                int32_t& slot = inv[(size_t)o * P + orders[(size_t)o * P + i]];
-                if (slot >= 0) { is_perm = false; break; }
-                slot = i;
-            }
-        c->orders_perm = is_perm;
-        c->S = S; c->max_n = max_n;
-        if (is_perm) {
-            HIP_TRY(c, c->d_inv_orders.upload(inv, c->stream));
-            rc = table_layout(c);
-            if (rc) return rc;
-        }
-    }
+    rc = batch_orders_stage(c, orders, n_orders, S, max_n);
+    if (rc) return rc;
+    if (c->has_img) c->img_orders.assign(orders, orders + (size_t)n_orders * P);   // (an own-nodes batch re-stages, whenever the sizes arrive: img_own_restage)
+    else c->img_orders.clear();
     HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // caller buffers may die after return
     float ms = 0;
@@ -2273,9 +2408,89 @@ int simon_set_node_ranks(simon_ctx* c, const int32_t* rank) {
     return load_ranks(c, rank);
 }
 
+// the slot of every loaded scenario on the device
+static int img_slots_upload(simon_ctx* c) {
+    HIP_TRY(c, c->d_img_slot.upload(c->h_img_slot, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->wide.img_slot_ext = c->img_R > 0 ? c->d_img_slot.p : nullptr;
+    return SIMON_OK;
+}
+
+// the tables staged again for another set of slots, the loaded scenarios, orders and pod rows kept
+static int img_own_restage(simon_ctx* c) {
+    c->seg_n = 0; c->sub_on = false;                              // (the layout of a prefix batch first: the class counts of an own-nodes one are the caller's next step)
+    c->has_ranks = false; c->table_ranks_ok = false; c->have_results = false;
+    c->staged = false;
+    if (const int rc = stage(c)) return rc;
+    return batch_orders_stage(c, c->img_orders.data(), c->n_orders, c->S, c->max_n);
+}
+
+// An own-nodes batch leaves its image states: the per-size slots of the prefix batch again.
+static int img_own_leave(simon_ctx* c) {
+    if (c->img_own_T == 0) return SIMON_OK;
+    c->img_own_T = 0; c->img_own_n.clear(); c->img_own_words.clear();
+    if (const int rc = img_own_restage(c)) return rc;
+    if (c->img_R == 0) return SIMON_OK;
+    c->h_img_slot.resize(c->S);
+    for (int s = 0; s < c->S; ++s) c->h_img_slot[s] = (int32_t)(std::lower_bound(c->img_sizes.begin(), c->img_sizes.end(), c->scen[s].n_nodes) - c->img_sizes.begin());
+    return img_slots_upload(c);
+}
+
+// An image problem enters an own-nodes batch (simon_set_scenario_segments / simon_set_scenario_nodes after their validation; words [S][W]
+// = the presence rows).  The caller's NumNodes / Size must be the pool-order reading of the whole pool, which is what the slots'
+// own readings restrict.  A slot is (node count, presence of the listing nodes): scenarios that agree on both score alike.
+static int img_own_enter(simon_ctx* c, const char* who, const std::vector<uint32_t>& words) {
+    const int S = c->S, N = c->N, W = (N + 31) / 32, I = (int)c->img_size.size();
+    if (c->img_orders.size() != (size_t)c->n_orders * c->P)      // (cannot happen through the public calls: every road to a staged image batch keeps them)
+        return fail(c, SIMON_ESTATE, "%s: the loaded orders of the image batch are gone; load the scenarios again", who);
+    std::vector<int32_t> run(I, 0);
+    std::vector<uint32_t> lists(W, 0);
+    for (int j = 0; j < N; ++j)
+        for (int q = c->img_node_off[j]; q < c->img_node_off[j + 1]; ++q) {
+            const int im = c->img_node_image[q];
+            lists[j >> 5] |= 1u << (j & 31);
+            if (c->img_node_count[q] != ++run[im] || (run[im] == 1 && c->img_size[im] != c->img_node_size[q]))
+                return fail(c, SIMON_EINVAL, "%s: image %d at node %d: arrival order is not pool order (NumNodes %d, the pool-order reading is %d; Size is the first lister's)", who, im, j, c->img_node_count[q], run[im]);
+        }
+    std::map<std::vector<uint32_t>, int> ids;
+    std::vector<int32_t> slot(S), own_n;
+    std::vector<uint32_t> own_words, key(W + 1);
+    for (int s = 0; s < S; ++s) {
+        key[0] = (uint32_t)c->scen[s].n_nodes;
+        for (int w = 0; w < W; ++w) key[w + 1] = words[(size_t)s * W + w] & lists[w];
+        const auto it = ids.emplace(key, (int)ids.size());
+        if (it.second) {
+            own_n.push_back(c->scen[s].n_nodes);
+            own_words.insert(own_words.end(), words.begin() + (size_t)s * W, words.begin() + (size_t)(s + 1) * W);
+        }
+        slot[s] = it.first->second;
+    }
+    int img_R = 0, listing = 0;
+    for (int cp = 0; cp < c->Cp; ++cp)
+        for (int e = c->img_class_off[cp]; e < c->img_class_off[cp + 1]; ++e)
+            if (c->img_class_image[e] >= 0) { ++img_R; break; }
+    for (int j = 0; j < N; ++j) listing += c->img_node_off[j + 1] > c->img_node_off[j];
+    const size_t Cn1 = (size_t)(c->img_refined ? c->img_base_Cn : c->Cn) + (img_R ? listing : 0);
+    // (the cap also counts the kernel's global count rows, one per slot, where the counts do not fit its LDS)
+    const size_t per_slot = (c->img_node_image.size() + (size_t)I) * sizeof(int32_t);
+    const size_t scratch = (!c->image_host && per_slot > kImageLdsBudget) ? ids.size() * per_slot : 0;
+    if (ids.size() * (size_t)img_R * Cn1 + scratch > c->img_state_cap)
+        return fail(c, SIMON_ESTATE, "%s: %zu image states x %d image-scoring pod classes x %zu node classes (+ %zu bytes of count rows) exceed the cap of %zu MB (SIMON_IMAGE_STATE_MB)", who, ids.size(), img_R, Cn1, scratch, c->img_state_cap >> 20);
+    c->img_own_T = (int32_t)ids.size(); c->img_own_n = own_n; c->img_own_words = own_words;
+    if (const int rc = img_own_restage(c)) return rc;
+    if (c->img_R == 0) return SIMON_OK;
+    c->h_img_slot = slot;
+    return img_slots_upload(c);
+}
+
 // a failed simon_set_scenario_segments / simon_set_scenario_nodes leaves the batch as a prefix batch: its own layout again, no ranks
 static int seg_abandon(simon_ctx* c, int rc) {
     c->seg_n = 0; c->sub_on = false;
+    if (c->img_own_T > 0) {                                       // (the per-size slots restored; the refusal keeps its own code and text)
+        const std::string why = c->err;
+        (void)img_own_leave(c);
+        c->err = why;
+    }
     c->has_ranks = false; c->table_ranks_ok = false; c->have_results = false;
     if (c->variant == SIMON_KERNEL_NARROW && c->table_ok && c->orders_perm) (void)table_layout(c);
     return rc;
@@ -2295,37 +2510,51 @@ static bool node_busy(const simon_ctx* c, int j) {
 int simon_set_scenario_segments(simon_ctx* c, int32_t n_seg, const int32_t* seg_start, const int32_t* count) {
     if (!c) return SIMON_EINVAL;
     if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "set_scenario_segments: load scenarios first");
-    if (c->has_img) return fail(c, SIMON_ESTATE, "set_scenario_segments: ImageLocality is in effect (its image counts depend on the node set)");
+    if (c->has_img && c->img_node_size.empty()) return fail(c, SIMON_ESTATE, "set_scenario_segments: ImageLocality is in effect (its image counts depend on the node set)");
     const int S = c->S, N = c->N;
-    if (n_seg < 0 || n_seg > SIMON_MAX_SEGMENTS) return fail(c, SIMON_EINVAL, "set_scenario_segments: n_seg %d outside [0,%d]", n_seg, SIMON_MAX_SEGMENTS);
-    if (n_seg > 0 && (!seg_start || !count)) return fail(c, SIMON_EINVAL, "set_scenario_segments: %d segments without starts / counts", n_seg);
+    // (with an own-nodes image batch loaded a refusal also gives the per-size slots back: "a call that fails leaves a prefix batch")
+    auto bad = [&](int rc) { return c->img_own_T > 0 ? seg_abandon(c, rc) : rc; };
+    if (n_seg < 0 || n_seg > SIMON_MAX_SEGMENTS) return bad(fail(c, SIMON_EINVAL, "set_scenario_segments: n_seg %d outside [0,%d]", n_seg, SIMON_MAX_SEGMENTS));
+    if (n_seg > 0 && (!seg_start || !count)) return bad(fail(c, SIMON_EINVAL, "set_scenario_segments: %d segments without starts / counts", n_seg));
     if (n_seg == 0) {                                        // back to prefix scenarios
         if (!own_nodes(c)) return SIMON_OK;
         c->seg_n = 0; c->sub_on = false;
         c->has_ranks = false; c->table_ranks_ok = false; c->have_results = false;
+        if (c->img_own_T > 0) return img_own_leave(c);           // (re-stages for the per-size slots, the layout included)
         return (c->variant == SIMON_KERNEL_NARROW && c->table_ok && c->orders_perm) ? table_layout(c) : SIMON_OK;
     }
     for (int g = 0; g < n_seg; ++g) {
         const int end = g + 1 < n_seg ? seg_start[g + 1] : N;
-        if (seg_start[g] < 0 || seg_start[g] > end || end > N) return fail(c, SIMON_EINVAL, "set_scenario_segments: segment %d [%d,%d) is not ascending inside [0,%d]", g, seg_start[g], end, N);
+        if (seg_start[g] < 0 || seg_start[g] > end || end > N) return bad(fail(c, SIMON_EINVAL, "set_scenario_segments: segment %d [%d,%d) is not ascending inside [0,%d]", g, seg_start[g], end, N));
     }
     const int fixed = seg_start[0];
     for (int s = 0; s < S; ++s) {
         long long tot = fixed;
         for (int g = 0; g < n_seg; ++g) {
             const int cnt = count[(size_t)s * n_seg + g], len = (g + 1 < n_seg ? seg_start[g + 1] : N) - seg_start[g];
-            if (cnt < 0 || cnt > len) return fail(c, SIMON_EINVAL, "set_scenario_segments: scenario %d: count %d of segment %d outside [0,%d]", s, cnt, g, len);
+            if (cnt < 0 || cnt > len) return bad(fail(c, SIMON_EINVAL, "set_scenario_segments: scenario %d: count %d of segment %d outside [0,%d]", s, cnt, g, len));
             tot += cnt;
         }
-        if (tot != c->scen[s].n_nodes) return fail(c, SIMON_EINVAL, "set_scenario_segments: scenario %d: n_nodes %d, but its fixed nodes and counts make %lld", s, c->scen[s].n_nodes, tot);
-        if (tot == 0) return fail(c, SIMON_EINVAL, "set_scenario_segments: scenario %d holds no node at all (no fixed nodes, every count 0)", s);   // (the ranked instantiations have never run an empty scenario)
+        if (tot != c->scen[s].n_nodes) return bad(fail(c, SIMON_EINVAL, "set_scenario_segments: scenario %d: n_nodes %d, but its fixed nodes and counts make %lld", s, c->scen[s].n_nodes, tot));
+        if (tot == 0) return bad(fail(c, SIMON_EINVAL, "set_scenario_segments: scenario %d holds no node at all (no fixed nodes, every count 0)", s));   // (the ranked instantiations have never run an empty scenario)
     }
     // a segment node starts empty: pods bound before the stream or by Spec.NodeName would need it in every scenario
     for (int j = fixed; j < N; ++j) {
-        if (node_busy(c, j)) return fail(c, SIMON_EINVAL, "set_scenario_segments: segment node %d carries pods bound before the stream", j);
+        if (node_busy(c, j)) return bad(fail(c, SIMON_EINVAL, "set_scenario_segments: segment node %d carries pods bound before the stream", j));
     }
     for (int p = 0; p < c->P; ++p)
-        if (c->p_preset[p] >= fixed) return fail(c, SIMON_EINVAL, "set_scenario_segments: pod %d is preset to segment node %d", p, c->p_preset[p]);
+        if (c->p_preset[p] >= fixed) return bad(fail(c, SIMON_EINVAL, "set_scenario_segments: pod %d is preset to segment node %d", p, c->p_preset[p]));
+    if (c->has_img) {                                          // image states of the scenarios' own node sets (presence words from the counts)
+        const int W = (N + 31) / 32;
+        std::vector<uint32_t> words((size_t)S * W, 0);
+        for (int s = 0; s < S; ++s) {
+            uint32_t* row = words.data() + (size_t)s * W;
+            for (int j = 0; j < fixed; ++j) row[j >> 5] |= 1u << (j & 31);
+            for (int g = 0; g < n_seg; ++g)
+                for (int j = seg_start[g]; j < seg_start[g] + count[(size_t)s * n_seg + g]; ++j) row[j >> 5] |= 1u << (j & 31);
+        }
+        if (const int rc = img_own_enter(c, "set_scenario_segments", words)) return seg_abandon(c, rc);
+    }
     c->seg_n = n_seg; c->sub_on = false;                       // (segments replace a node-subset batch)
     c->seg_start.assign(seg_start, seg_start + n_seg);
     c->seg_count.assign(count, count + (size_t)S * n_seg);
@@ -2437,7 +2666,7 @@ int simon_set_scenario_nodes(simon_ctx* c, const uint32_t* present, const int32_
     if (!c) return SIMON_EINVAL;
     if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "set_scenario_nodes: load scenarios first");
     if (!present) return simon_set_scenario_segments(c, 0, nullptr, nullptr);        // back to prefix scenarios
-    if (c->has_img) return fail(c, SIMON_ESTATE, "set_scenario_nodes: ImageLocality is in effect (its image counts depend on the node set)");
+    if (c->has_img && c->img_node_size.empty()) return fail(c, SIMON_ESTATE, "set_scenario_nodes: ImageLocality is in effect (its image counts depend on the node set)");
     const int S = c->S, N = c->N, W = (N + 31) / 32;
     // every refusal leaves a prefix batch, whatever the batch was before
     if (node_zone) {
@@ -2465,8 +2694,13 @@ int simon_set_scenario_nodes(simon_ctx* c, const uint32_t* present, const int32_
         if (c->p_preset[p] >= 0 && !always(c->p_preset[p]) && c->p_gate[p] != c->p_preset[p] && !evicted_pod(c, p))
             return seg_abandon(c, fail(c, SIMON_EINVAL, "set_scenario_nodes: pod %d is preset to node %d, absent from some scenario, and not gated on it", p, c->p_preset[p]));
     HIP_TRY(c, hipSetDevice(c->device));
+    {
+        const std::vector<uint32_t> words(present, present + (size_t)S * W);     // (also: present may be c->sub_words' own storage no longer)
+        if (c->has_img)
+            if (const int rc = img_own_enter(c, "set_scenario_nodes", words)) return seg_abandon(c, rc);
+        c->sub_words = words;
+    }
     c->seg_n = 0; c->sub_on = true; c->sub_W = W;                    // (a node-subset batch replaces segments)
-    c->sub_words.assign(present, present + (size_t)S * W);
     if (node_zone) c->sub_zone.assign(node_zone, node_zone + N); else c->sub_zone.clear();
     int rc = SIMON_OK;
     if (!c->subset_host) {
@@ -3465,11 +3699,45 @@ int simon_explain_own_batch(simon_ctx* c, const int32_t* scenarios, int32_t n_sc
     WideReplay job;
     job.scen = hs.data(); job.S = n_scen; job.max_n = N; job.d_orders = c->d_orders.p; job.own = true;
     job.rank_row = scenarios; job.d_node_rank = c->d_node_rank.p; job.d_node_inv = c->d_node_inv.p;
+    std::vector<int32_t> slots;                                  // the batch's image states and each listed scenario's slot
+    if (c->img_R > 0 && c->img_own_T > 0) {
+        for (int k = 0; k < n_scen; ++k) slots.push_back(c->h_img_slot[scenarios[k]]);
+        job.d_img = c->wide.img; job.img_slot = slots.data();
+    }
     if (c->pods_on) { job.d_pod_present = c->d_pod_words.p; job.pod_row = scenarios; job.pp_words = c->pod_W; }
     job.max_failed = max_failed; job.n_failed = n_failed; job.failed_pods = failed_pods;
     job.max_bins = max_bins; job.n_bins = n_bins; job.bins = bins;
     job.fail_codes = fail_codes; job.code_stride = code_stride;
     return wide_replay(c->wide, *c, job, wide_workgroup(c, n_scen, N), c->stream, c->err);
+}
+
+int simon_fetch_image_scores(simon_ctx* c, int32_t scenario, uint8_t* score) {
+    if (!c || !score) return c ? fail(c, SIMON_EINVAL, "fetch_image_scores: bad arguments") : SIMON_EINVAL;
+    if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "fetch_image_scores: no scenarios loaded");
+    if (c->img_R == 0) return fail(c, SIMON_ESTATE, "fetch_image_scores: the problem has no image that a pod runs and a node lists");
+    if (scenario < 0 || scenario >= c->S) return fail(c, SIMON_EINVAL, "fetch_image_scores: scenario %d outside [0,%d)", scenario, c->S);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int N = c->N, Cp = c->Cp, slot = c->h_img_slot[scenario];
+    std::fill(score, score + (size_t)Cp * N, (uint8_t)0);
+    std::vector<unsigned char> tab;
+    if (c->variant == SIMON_KERNEL_NARROW && c->t_img_staged) {      // the score-table kernel's [slot][table class][internal node class]
+        const int Ct = c->Cn_t;
+        tab.resize((size_t)c->img_stride_t);
+        HIP_TRY(c, hipMemcpyAsync(tab.data(), c->d_t_img.p + (size_t)slot * c->img_stride_t, tab.size(), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (int cp = 0; cp < Cp; ++cp)
+            for (int j = 0; j < N; ++j)
+                if (node_in(c, scenario, j)) score[(size_t)cp * N + j] = tab[(size_t)c->h_tc_of[cp] * Ct + c->h_ncls_t[j]];
+        return SIMON_OK;
+    }
+    if (int rc = ensure_wide_staged(c)) return rc;                    // ... or the all-feature kernel's [slot][row][node class]
+    tab.resize((size_t)c->img_R * c->Cn);
+    HIP_TRY(c, hipMemcpyAsync(tab.data(), c->wide.img + (size_t)slot * tab.size(), tab.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int cp = 0; cp < Cp; ++cp)
+        for (int j = 0; c->img_row_of[cp] >= 0 && j < N; ++j)
+            if (node_in(c, scenario, j)) score[(size_t)cp * N + j] = tab[(size_t)c->img_row_of[cp] * c->Cn + c->node_class[j]];
+    return SIMON_OK;
 }
 
 int simon_get_stats(simon_ctx* c, simon_stats* st) {

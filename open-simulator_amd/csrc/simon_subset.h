@@ -27,6 +27,31 @@ struct SubsetStage {
 // one wave per scenario on `st`; nothing is read back here
 hipError_t launch_subset_stage(const SubsetStage& a, hipStream_t st);
 
+// image_states_kernel: the ImageLocality score table of an own-nodes batch, one 256-thread workgroup per slot (image state: a node count
+// and a presence row).  schedulerCache.addNodeImageStates over the slot's nodes in pool order (cache.go:675-698): NumNodes of node j's
+// entry of image i = present listers of i at or before j, Size(i) = the first present lister's own sizeBytes.  Phase A derives both from
+// the lister lists (a CSR by image, pool order) with ballots and a carry across 64-lister chunks; phase B scores every (image-scoring
+// row, node class) at the class's representative node in plain IEEE fp64, as img_score of simon_hip.hip does.
+constexpr size_t kImageLdsBudget = 48 * 1024;   // counts [nnz] + first listers [I] as int32 stay in LDS up to this, else in a global row per slot
+
+struct ImageStates {
+    // inputs
+    const uint32_t* present;                 // [T][W] presence words of every slot
+    const int32_t* slot_n;                   // [T] node count of the slot, >= 1
+    const int32_t *lis_off, *lis_node, *lis_ent;   // [I + 1]; [nnz] listers of image i in pool order: the node, its entry index q
+    const int64_t* node_size;                // [nnz] sizeBytes of entry q
+    const int32_t *node_off, *node_image;    // [N + 1]; [nnz] entries by node
+    const int32_t *class_off, *class_image;  // [Cp + 1]; containers by pod class (-1: listed nowhere)
+    const int32_t* row_class;                // [R] pod class of image-scoring row r
+    const int32_t* rep;                      // [Cn] representative node of a node class, -1 = the class is empty
+    int32_t T, W, I, nnz, R, Cn;
+    int32_t* scratch;                        // [T][nnz + I], or nullptr = LDS ((nnz + I) * 4 <= kImageLdsBudget)
+    // output
+    uint8_t* out;                            // [T][R][Cn]
+};
+
+hipError_t launch_image_states(const ImageStates& a, hipStream_t st);
+
 // simon_fetch_group_counts: per scenario and pod group, the pods left unscheduled (placement == -1) and the pods placed (>= 0) -- a pod that
 // is not part of the scenario (-2) counts in neither.  placement [S][P] by pod id, pod_group [P] in [0, G) or -1 (validated by the caller),
 // unscheduled / placed [S][G] (placed may be null).  One workgroup per scenario, two G-entry histograms in LDS.

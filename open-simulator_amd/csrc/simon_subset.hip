@@ -116,6 +116,64 @@ __global__ __launch_bounds__(64) void subset_stage_kernel(SubsetStage a) {
     for (int d = lane; d < Ct; d += 64) a.scls[(size_t)s * Ct + d] = s_fill[d];
 }
 
+// image_states_kernel (simon_subset.h): workgroup t = slot t.  s_cnt[q] = NumNodes of entry q in this slot (written for the entries of
+// present nodes only: nothing else is read), s_first[i] = entry of the first present lister of image i, -1 = none present.
+__global__ __launch_bounds__(256) void image_states_kernel(ImageStates a) {
+    extern __shared__ int32_t smem[];
+    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int32_t* const s_cnt = a.scratch ? a.scratch + (size_t)t * ((size_t)a.nnz + a.I) : smem;   // [nnz]
+    int32_t* const s_first = s_cnt + a.nnz;                                                     // [I]
+    const uint32_t* __restrict__ const row = a.present + (size_t)t * a.W;
+    const unsigned long long below = (1ull << lane) - 1;
+
+    // ---- phase A: one wave per image, 64 listers per turn; the count so far is carried from chunk to chunk ----
+    for (int i = wave; i < a.I; i += 4) {
+        const int lo = a.lis_off[i], hi = a.lis_off[i + 1];
+        int carry = 0, first = -1;
+        for (int base = lo; base < hi; base += 64) {
+            const int k = base + lane;
+            const int j = k < hi ? a.lis_node[k] : 0;
+            const bool in = k < hi && ((row[j >> 5] >> (j & 31)) & 1u) != 0;
+            const int q = in ? a.lis_ent[k] : 0;
+            const unsigned long long m = __ballot(in);
+            if (in) s_cnt[q] = carry + __popcll(m & below) + 1;           // (the node itself counts: "up to and including")
+            if (first < 0 && m) first = __shfl(q, __ffsll(m) - 1, 64);
+            carry += __popcll(m);
+        }
+        if (lane == 0) s_first[i] = first;
+    }
+    __syncthreads();                                                      // (a barrier orders the workgroup's own global writes too)
+
+    // ---- phase B: one byte per (row, node class) ----
+    const int n = a.slot_n[t];
+    const long long mb = 1024 * 1024, lo_b = 23 * mb;
+    uint8_t* const out = a.out + (size_t)t * a.R * a.Cn;
+    for (int x = tid; x < a.R * a.Cn; x += 256) {
+        const int r = x / a.Cn, k = x - r * a.Cn;
+        const int j = a.rep[k];
+        int score = 0;
+        if (j >= 0 && ((row[j >> 5] >> (j & 31)) & 1u)) {
+            const int cp = a.row_class[r], e0 = a.class_off[cp], e1 = a.class_off[cp + 1];
+            const long long hi_b = 1000 * mb * (long long)(e1 - e0);
+            const int q0 = a.node_off[j], q1 = a.node_off[j + 1];
+            long long sum = 0;
+            for (int e = e0; e < e1; ++e) {
+                const int im = a.class_image[e];
+                if (im < 0) continue;
+                for (int q = q0; q < q1; ++q)
+                    if (a.node_image[q] == im) {
+                        sum += (long long)((double)a.node_size[s_first[im]] * ((double)s_cnt[q] / (double)n));
+                        break;
+                    }
+                if (sum > hi_b) sum = hi_b + 1;                           // (saturates as img_score does)
+            }
+            sum = sum < lo_b ? lo_b : sum > hi_b ? hi_b : sum;
+            score = (int)(100 * (sum - lo_b) / (hi_b - lo_b));
+        }
+        out[x] = (uint8_t)score;
+    }
+}
+
 // group_counts_kernel: the placement row and pod_group are read coalesced (8 B per pod: the kernel is HBM-bound), the two histograms live in
 // LDS behind LDS atomics and leave as rows of [S][G].
 __global__ __launch_bounds__(256) void group_counts_kernel(const int32_t* __restrict__ placement, const int32_t* __restrict__ pod_group, int P, int G,
@@ -583,6 +641,15 @@ hipError_t launch_group_counts(const int32_t* placement, const int32_t* pod_grou
                                hipStream_t st) {
     if (S <= 0 || G <= 0 || G > kMaxPodGroups) return hipErrorInvalidValue;
     hipLaunchKernelGGL(group_counts_kernel, dim3((unsigned)S), dim3(256), (size_t)2 * G * sizeof(int32_t), st, placement, pod_group, P, G, unscheduled, placed);
+    return hipGetLastError();
+}
+
+hipError_t launch_image_states(const ImageStates& a, hipStream_t st) {
+    if (a.T <= 0 || a.R <= 0 || a.Cn <= 0) return hipSuccess;
+    if (a.W <= 0 || a.I < 0 || a.nnz < 0 || !a.out || !a.present || !a.slot_n || !a.rep) return hipErrorInvalidValue;
+    const size_t lds = ((size_t)a.nnz + a.I) * sizeof(int32_t);
+    if (!a.scratch && lds > kImageLdsBudget) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(image_states_kernel, dim3((unsigned)a.T), dim3(256), a.scratch ? 0 : lds, st, a);
     return hipGetLastError();
 }
 

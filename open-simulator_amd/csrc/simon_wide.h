@@ -47,6 +47,14 @@ struct HostInputs {
     std::vector<int32_t> img_sizes;      // distinct n_nodes of the loaded batch, ascending (one slot each)
     std::vector<uint8_t> img_cls;        // [slots][img_R][Cn]
     std::vector<int32_t> img_rep;        // [Cn] a node of every (split) node class
+    // own-nodes batches (simon_set_image_node_sizes + simon_set_scenario_segments / _nodes): a slot is an IMAGE STATE -- a node count and
+    // the presence bits of the listing nodes -- instead of a size.  img_own_T > 0: the staged tables hold these slots (img_sizes keeps the
+    // prefix batch's sizes for the way back); every listing node is then a node class of its own.
+    std::vector<int64_t> img_node_size;  // [nnz] sizeBytes of node j's own entry (empty: not attached)
+    int32_t img_own_T = 0;
+    std::vector<int32_t> img_own_n;      // [T] node count of the slot
+    std::vector<uint32_t> img_own_words; // [T][ceil(N / 32)] presence words of the slot (a scenario that has it)
+    size_t img_slots() const { return img_own_T > 0 ? (size_t)img_own_T : img_sizes.size(); }
     // topology terms (InterPodAffinity + PodTopologySpread)
     std::vector<int32_t> term_key, term_set;
     std::vector<uint64_t> node_sets;

@@ -358,15 +358,21 @@ def normalized_image_names(pod: dict) -> List[str]:
     return out
 
 
-def image_locality_inputs(nodes: List[dict], class_rep: List[dict], wanted, img_states) -> "capi.ImageLocality":
+def image_locality_inputs(nodes: List[dict], class_rep: List[dict], wanted, img_states, own: bool = False) -> "capi.ImageLocality":
     """The engine's ImageLocality inputs (ABI v7, capi.ImageLocality) for the pool `nodes` (pool order) and the pod classes: the images
     some class runs AND some node lists, per node its (image, NumNodes) entries as the arrival order leaves them (image_states), per
-    class one image per container (-1 where no node lists it)."""
+    class one image per container (-1 where no node lists it).  own: also node_size, per entry the sizeBytes of the node's first image
+    that carries the name -- what addNodeImageStates (cache.go:675-698) takes as the summary's Size when this node is the first to
+    arrive with the image, as in a scenario that lacks the earlier listers."""
     ids: Dict[str, int] = {}
     size: List[int] = []
-    node_off, node_image, node_count = [0], [], []
+    node_off, node_image, node_count, node_size = [0], [], [], []
     for n in nodes:
         st = img_states[n["metadata"]["name"]]
+        mine: Dict[str, int] = {}
+        for img in (n.get("status") or {}).get("images") or []:
+            for name in img.get("names") or []:
+                mine.setdefault(name, int(img.get("sizeBytes") or 0))
         for name in sorted(st):
             if name not in wanted:
                 continue
@@ -375,13 +381,15 @@ def image_locality_inputs(nodes: List[dict], class_rep: List[dict], wanted, img_
                 size.append(st[name][0])
             node_image.append(ids[name])
             node_count.append(st[name][1])
+            node_size.append(mine[name])
         node_off.append(len(node_image))
     class_off, class_image = [0], []
     for p in class_rep:
         class_image += [ids.get(name, -1) for name in normalized_image_names(p)]
         class_off.append(len(class_image))
     return capi.ImageLocality(np.array(size, np.int64), np.array(node_off, np.int32), np.array(node_image, np.int32),
-                              np.array(node_count, np.int32), np.array(class_off, np.int32), np.array(class_image, np.int32)).normalise()
+                              np.array(node_count, np.int32), np.array(class_off, np.int32), np.array(class_image, np.int32),
+                              np.array(node_size, np.int64) if own else None).normalise()
 
 
 def image_locality_score(pod: dict, states: Dict[str, Tuple[int, int]], total_nodes: int) -> int:
@@ -403,13 +411,17 @@ def image_locality_score(pod: dict, states: Dict[str, Tuple[int, int]], total_no
 
 def flatten(nodes: List[dict], pods: List[dict], services=(), replicasets=(), statefulsets=(),
             gates: Optional[List[int]] = None, storage_classes=(), image_total: Optional[int] = None,
-            node_arrival_order: Optional[List[str]] = None, image_batch: bool = False) -> Flat:
+            node_arrival_order: Optional[List[str]] = None, image_batch=False) -> Flat:
     """nodes: the pool in canonical order (cluster nodes, then new-node clones).  pods: the stream in scheduling order;
     a pod with spec.nodeName is bound without filtering (V/eventhandlers.go:223-236).  gates[p] = node index the pod
     depends on (DaemonSet pods of new nodes, pkg/simulator/core.go:85-95) or -1.
     image_batch: ImageLocality travels as its inputs (capi.ImageLocality, ABI v7) and the engine scores it per scenario size, for
     batches of several sizes; static_add then carries NodePreferAvoidPods only.  Without it a node that lists an image the pods run
-    needs image_total (one size) and raises Unsupported otherwise."""
+    needs image_total (one size) and raises Unsupported otherwise.  image_batch="own": the same problem plus every entry's own
+    sizeBytes (capi.ImageLocality.node_size), for segmented and node-subset batches that score each scenario by its own image states;
+    the arrival order must then be pool order (node_arrival_order None)."""
+    if image_batch == "own" and node_arrival_order is not None:
+        raise ValueError("image_batch='own' reads the image states in pool order: node_arrival_order must be None")
     N, P = len(nodes), len(pods)
     node_names = [n["metadata"]["name"] for n in nodes]
     node_index = {name: j for j, name in enumerate(node_names)}
@@ -544,7 +556,7 @@ def flatten(nodes: List[dict], pods: List[dict], services=(), replicasets=(), st
 
     image_locality = None
     if img_states is not None and image_batch:
-        image_locality = image_locality_inputs(nodes, class_rep, wanted, img_states)
+        image_locality = image_locality_inputs(nodes, class_rep, wanted, img_states, own=image_batch == "own")
 
     # ---- static filters per (pod class, node): first failing plugin in registry order --------------------------
     # A class looks at a node only through the label keys its nodeSelector / node affinity name, the node's taints,

@@ -24,6 +24,7 @@ class HipEngine:
     """The product engine: libsimon_hip.so on one device."""
 
     supports_image_locality = True            # ImageLocality per scenario size on the device (ABI v7): sweep() batches image clusters
+    supports_image_own_nodes = True           # ... and per scenario's own image states in segmented / node-subset batches (simon_set_image_node_sizes): sweep_mix() and sweep_failures() batch them too
     supports_scenario_segments = True         # pool segments (simon_set_scenario_segments): sweep_mix() batches node-type mixes
     supports_scenario_subsets = True          # node subsets (simon_set_scenario_nodes): sweep_failures() batches the loss of every failure domain
     supports_pod_eviction = True              # ... and reschedules the pods of the lost nodes (simon_set_pod_eviction): sweep_failures(reschedule=...)
@@ -1225,7 +1226,7 @@ class MixSweepResult:
 class MixFallbackWarning(UserWarning):
     """sweep_mix could not batch the grid and runs every mix as its own problem: one engine context, flatten and launch per mix
     (a 64 x 64 grid is 4 096 of them).  The reason names what refused: an engine without pool segments, nodes that list the pods'
-    images (ImageLocality over a node set), or a problem the segmented score-table kernel does not take (the all-feature kernel
+    images on an engine without supports_image_own_nodes (ImageLocality over a node set), or a problem the segmented score-table kernel does not take (the all-feature kernel
     runs prefix scenarios only: Open-Local, hard hostname spread, pools beyond the table's limits)."""
 
 
@@ -1293,8 +1294,9 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
     counts (one iterable per type).  The answer is the mix of least total cost sum_t costs[t] * c_t (default 1 per node) with no
     unscheduled pod and the MaxCPU / MaxMemory / MaxVG caps of satisfyResourceSetting over its own nodes; ties go to fewer new nodes,
     then to the smallest count vector.  One engine batch over the pool cluster + every type's clones up to its largest count, one
-    segment per type (simon_set_scenario_segments); engines without segments, clusters whose nodes list the pods' images and problems
-    the segmented kernel does not take run every mix as its own problem.  reasons=True: MixSweepResult.unscheduled_pods lists, per mix,
+    segment per type (simon_set_scenario_segments); nodes that list the pods' images are scored per mix by the mix's own image states
+    (supports_image_own_nodes).  Engines without segments, image clusters on an engine without those states (or whose states exceed
+    the engine's cap) and problems the segmented kernel does not take run every mix as its own problem.  reasons=True: MixSweepResult.unscheduled_pods lists, per mix,
     the pods that stay unscheduled with their FitError text, as sweep() does per count -- every failing mix of the batch explained in
     one engine.explain_own_batch call (engines without it, and mixes whose pod stream is not the pool's: simulate() of the mix).
     headroom=[...] / node_table=True / devices=True / storage=True: as sweep() takes them, per mix (MixSweepResult.headroom /
@@ -1333,7 +1335,8 @@ def sweep_mix(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], new_n
     pods, gates = build_stream(cluster, apps, pool, len(base))
     try:
         flat = fl.flatten(pool, pods, cluster.get("Service", []), cluster.get("ReplicaSet", []), cluster.get("StatefulSet", []), gates,
-                          storage_classes=_storage_classes(cluster, apps))
+                          storage_classes=_storage_classes(cluster, apps),
+                          image_batch="own" if getattr(engine, "supports_image_own_nodes", False) else False)
     except fl.Unsupported as e:
         if "ImageLocality" not in str(e):
             raise
@@ -1464,8 +1467,8 @@ class FailureSweepResult:
 
 class FailureFallbackWarning(UserWarning):
     """sweep_failures could not batch the scenarios and runs each as its own problem: one engine context, flatten and launch per
-    failure domain.  The reason names what refused: an engine without node subsets, nodes that list the pods' images (ImageLocality
-    over a node set), an app whose pod order depends on the node set (a DaemonSet, a pod bound to a node: _same_stream), or a problem
+    failure domain.  The reason names what refused: an engine without node subsets, nodes that list the pods' images on an engine
+    without supports_image_own_nodes (ImageLocality over a node set), an app whose pod order depends on the node set (a DaemonSet, a pod bound to a node: _same_stream), or a problem
     the score-table kernel does not take (the all-feature kernel runs prefix scenarios only)."""
 
 
@@ -1605,8 +1608,9 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
     dropped, not rescheduled.  One node-subset engine batch over the cluster's nodes (simon_set_scenario_nodes; batch_scenarios per
     launch): every node-bound pod is gated on its node, each scenario runs in the nodeTree order of its own nodes.  reasons=True
     explains the failing scenarios of every launch in one engine.explain_own_batch call for their unscheduled_pods (an engine without
-    supports_explain_own, and a batch the library refuses to explain: simulate() of every failing scenario, one by one).  Engines without node subsets, clusters
-    whose nodes list the pods' images, apps whose pod list depends on the node set and problems the score-table kernel does not take
+    supports_explain_own, and a batch the library refuses to explain: simulate() of every failing scenario, one by one).  Nodes that list the pods' images are
+    scored per scenario by its own image states (supports_image_own_nodes).  Engines without node subsets, image clusters on an engine
+    without those states (or whose states exceed the engine's cap), apps whose pod list depends on the node set and problems the score-table kernel does not take
     run every scenario as its own problem (FailureFallbackWarning, batched=False).  A domain that leaves no node: ValueError.
     reschedule="owned" / "all": the N-1 / drain / scale-down question for a cluster ingested with its Running pods -- scenario d + 1 is
     simulate(*cluster_evicted(cluster, apps, names, reschedule)): the evictable pods of the lost nodes ("owned": those a controller
@@ -1655,7 +1659,8 @@ def sweep_failures(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], 
             raise fl.Unsupported(f"workload pod {p['metadata']['name']} is bound to node {p['spec']['nodeName']} by its template")
     try:
         flat = fl.flatten(pool, pods, cluster.get("Service", []), cluster.get("ReplicaSet", []), cluster.get("StatefulSet", []), gates,
-                          storage_classes=_storage_classes(cluster, apps))
+                          storage_classes=_storage_classes(cluster, apps),
+                          image_batch="own" if getattr(engine, "supports_image_own_nodes", False) else False)
     except fl.Unsupported as e:
         if "ImageLocality" not in str(e):
             raise
