@@ -7,7 +7,10 @@ constant, a dropped correction step, a contraction or an int32 intermediate send
 
 Every case is (fixture, route): the result must equal the CPU oracle's, and the route must be the one meant -- simon_stats'
 kernel_variant and kernel_generation, and what SIMON_DEBUG_ROUTE prints of it (unit, prologue, signature count).  Each route sets its
-knobs itself, SIMON_LDS_WS included.  The all-feature kernel (int64 arithmetic) is the control.
+knobs itself, SIMON_LDS_WS included.  The all-feature kernel is the control: its class terms are int64 divisions (divq) and its
+LeastAllocated an int64 quotient seeded by the fp64 fraction and corrected in integers (la_from_frac) -- but its BalancedAllocation is
+div_by_rcp like the others', and its InterPodAffinity term, which these problems do not have, is fp64 on a stored reciprocal
+(tests/test_gpu_term_duels.py).
 
 Sizes: at most 200 nodes (the 100-duel problem: two nodes per duel; every other problem at most 120), 180 pods and 6 scenarios per case --
 the full pool under four orders and two prefix scenarios that end behind a whole duel, so the shared initial image's prefix copy runs.
