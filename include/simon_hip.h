@@ -500,8 +500,9 @@ int simon_set_own_nodes_all_feature(simon_ctx* ctx, int32_t on);
  * whatever want_placement says (as priorities do).  simon_explain_loaded, simon_explain_batch and simon_explain_own_batch replay a
  * scenario with its row; simon_explain refuses (SIMON_ESTATE) while rows are loaded: an ad-hoc scenario has no row, as with ranks.
  * simon_min_plan* and simon_fetch_preempt_risk keep their definitions.  The words travel to the device as given (S x ceil(P / 32) u32).
- * Not covered: no simon_group_* forward and no Go shim; no replica-level subsets within one app on the Python side (ScheduleApp's
- * unstable sorts order an app's pods by list length, so a shorter replica list is not a restriction of the longer one's stream).
+ * Not covered: no simon_group_* forward and no Go shim.  Replica-level subsets within one app need an order of their own per level
+ * (ScheduleApp's unstable sorts order an app's pods by list length, so a shorter replica list is not a restriction of the longer
+ * one's stream): simon_load_scenarios_composed below loads such orders together with their rows (Python: simulate.sweep_scale).
  * (additive: the ABI stays 7) */
 int simon_set_scenario_pods(simon_ctx* ctx, const uint32_t* present /* [S][(P+31)/32], pod p = bit (p & 31) of word p >> 5 */);
 
@@ -513,6 +514,44 @@ int simon_set_scenario_pods(simon_ctx* ctx, const uint32_t* present /* [S][(P+31
 #define SIMON_MAX_POD_GROUPS 1024
 int simon_fetch_group_counts(simon_ctx* ctx, const int32_t* pod_group /* [P] */, int32_t G,
                              int32_t* unscheduled /* [S][G] */, int32_t* placed /* [S][G], may be NULL */);
+
+/* Order rows composed on the device: simon_load_scenarios for batches whose orders are concatenations of a few per-segment pieces -- the
+ * replica levels of a Deployment, where every level brings its own order of the app's pods (see above) and a grid over two workloads
+ * at 64 levels each is 4 096 distinct orders that differ in two segments only.  The stream positions are cut into G segments (the
+ * cluster's pods, then one per app); segment g has n_variants[g] rows over the SAME set of len_g pod ids, and order o is the
+ * concatenation of row choice[o][g] of every segment.  The host uploads the table (sum_g n_variants[g] x len_g ids, n_orders x G
+ * choices); the orders, the inverse orders the score-table kernel gathers through and the presence rows are built on the device
+ * (SIMON_ORDER_STAGE=host, read at simon_ctx_create: in host loops, then uploaded -- A/B and tests).
+ * The call does everything simon_load_scenarios does -- every refusal, clearing and staging step is shared -- and differs in where the
+ * order rows come from.  Every variant row of segment g must be a permutation of the same set of pod ids, the sets of the segments
+ * must be disjoint and together [0, P): every composed row is then a permutation of [0, P) by construction, and validation costs
+ * sum_g n_variants[g] x len_g, not n_orders x P.  SIMON_EINVAL: struct_size; G outside [1, SIMON_MAX_ORDER_SEGMENTS]; starts that do
+ * not run from 0 to P in ascending order; n_variants[g] < 1 or more than SIMON_MAX_ORDER_VARIANTS variants in all; a variant row that is not a permutation of its segment's set; segments
+ * that overlap or do not cover [0, P); a live value outside [0, len_g]; a choice outside [0, n_variants[g]); and whatever
+ * simon_load_scenarios refuses.  A failing call leaves no batch loaded.
+ * variant_live given: the call also installs pod rows, exactly as if simon_set_scenario_pods had been called -- scenario s holds pod p
+ * iff p sits among the first live entries of its variant in order scen[s].order_id.  Everything documented for pod rows applies
+ * (SIMON_GATED, placement stored whatever want_placement says, group counts, the explain calls, usage and headroom); a later
+ * simon_set_scenario_pods replaces the rows, NULL detaches them.
+ * simon_fetch_orders: rows [first, first + n) of the loaded orders, after either load call, and -- present != NULL -- the presence words
+ * of the composed rows BY ORDER (all ones when no composed rows are installed; bits at and beyond P are 0).  SIMON_ESTATE: nothing
+ * loaded; SIMON_EINVAL: a bad range.  (simon_load_scenarios_composed: SIMON_ENOMEM where the host cannot hold the table.)
+ * No simon_group_* forward and no Go shim, as for simon_set_scenario_pods.  (additive: the ABI stays 7) */
+#define SIMON_MAX_ORDER_SEGMENTS 64
+#define SIMON_MAX_ORDER_VARIANTS (1 << 24)
+typedef struct simon_order_segments {
+    uint32_t struct_size;
+    int32_t  n_seg;               /* G in [1, SIMON_MAX_ORDER_SEGMENTS] */
+    const int32_t* seg_start;     /* [G+1] stream positions: seg_start[0] = 0, non-decreasing, seg_start[G] = P (empty segments are legal) */
+    const int32_t* n_variants;    /* [G], each >= 1, at most SIMON_MAX_ORDER_VARIANTS together */
+    const int32_t* variant_pods;  /* segment g's n_variants[g] rows of len_g = seg_start[g+1]-seg_start[g] pod ids, segments concatenated in order */
+    const int32_t* variant_live;  /* [sum_g n_variants[g]]: the variant's stream holds the first live entries of its row; NULL = all of every row */
+    const int32_t* choice;        /* [n_orders][G]: order o is the concatenation of variant choice[o][g] of every segment g */
+} simon_order_segments;
+int simon_load_scenarios_composed(simon_ctx* ctx, const simon_scenario* scen, int32_t S,
+                                  const simon_order_segments* seg, int32_t n_orders);
+int simon_fetch_orders(simon_ctx* ctx, int32_t first, int32_t n,
+                       int32_t* orders /* [n][P] */, uint32_t* present /* [n][(P+31)/32] by ORDER, or NULL */);
 
 /* Per-node usage and headroom of the last run's scenarios, reduced on the device from the placement matrix (which stays there).  Both
  * calls require what simon_fetch_group_counts requires: a run that stored placements (otherwise SIMON_ESTATE) and the pods, nodes and

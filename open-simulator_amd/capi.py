@@ -567,6 +567,79 @@ def gpu_ids_of(slices: int) -> List[int]:
     return out
 
 
+MAX_ORDER_SEGMENTS = 64     # SIMON_MAX_ORDER_SEGMENTS
+MAX_ORDER_VARIANTS = 1 << 24   # SIMON_MAX_ORDER_VARIANTS
+
+
+class OrderSegmentsC(C.Structure):       # simon_order_segments
+    _fields_ = [("struct_size", C.c_uint32), ("n_seg", C.c_int32), ("seg_start", _p32), ("n_variants", _p32), ("variant_pods", _p32),
+                ("variant_live", _p32), ("choice", _p32)]
+
+
+@dataclass
+class OrderSegments:
+    """Order rows as concatenations of per-segment variants (simon_load_scenarios_composed): order o = variants[g][choice[o][g]] for
+    g = 0 .. G-1, one after the other; with `live`, order o holds the first live[g][choice[o][g]] pods of each piece and no others."""
+    seg_start: np.ndarray                    # [G+1] stream positions, 0 .. P
+    variants: List[np.ndarray]               # per segment [V_g][len_g] pod ids: every row a permutation of the segment's set
+    live: Optional[List[np.ndarray]]         # per segment [V_g], or None = every pod of every row
+    choice: np.ndarray                       # [n_orders][G]
+
+    def __post_init__(self):
+        self.seg_start = np.ascontiguousarray(self.seg_start, dtype=np.int32).reshape(-1)
+        G = len(self.seg_start) - 1
+        lens = np.diff(self.seg_start)
+        # (an empty segment still has its variants: [V_g][0])
+        self.variants = [np.asarray(v, np.int32) if g >= G else np.zeros((len(v), 0), np.int32) if lens[g] <= 0 else
+                         np.ascontiguousarray(v, dtype=np.int32).reshape(-1, int(lens[g])) for g, v in enumerate(self.variants)]
+        if self.live is not None:
+            self.live = [np.ascontiguousarray(l, dtype=np.int32).reshape(-1) for l in self.live]
+        self.choice = np.ascontiguousarray(self.choice, dtype=np.int32).reshape(-1, max(G, 1))
+        if len(self.variants) != G or (self.live is not None and [len(l) for l in self.live] != [len(v) for v in self.variants]):
+            raise ValueError(f"{G} segments, {len(self.variants)} variant tables" + ("" if self.live is None else f", live rows {[len(l) for l in self.live]}"))
+
+    @property
+    def n_orders(self) -> int:
+        return len(self.choice)
+
+    @property
+    def n_pods(self) -> int:
+        return int(self.seg_start[-1])
+
+    def order(self, o: int) -> np.ndarray:
+        """Row o of compose()'s orders alone."""
+        return np.concatenate([rows[self.choice[o, g]] for g, rows in enumerate(self.variants)] + [np.zeros(0, np.int32)]).astype(np.int32)
+
+    def compose(self):
+        """The explicit rows: (orders int32 [n_orders][P], present bool [n_orders][P] by pod id) -- what the library composes on the device."""
+        P, n = self.n_pods, self.n_orders
+        orders = np.zeros((n, P), np.int32)
+        present = np.zeros((n, P), bool)
+        for g, rows in enumerate(self.variants):
+            lo, hi = int(self.seg_start[g]), int(self.seg_start[g + 1])
+            if hi == lo:
+                continue
+            pick = self.choice[:, g]
+            piece = rows[pick]                                         # [n][len_g]
+            orders[:, lo:hi] = piece
+            n_live = np.full(n, hi - lo) if self.live is None else self.live[g][pick]
+            keep = np.arange(hi - lo)[None, :] < n_live[:, None]
+            present[np.nonzero(keep)[0], piece[keep]] = True
+        return orders, present
+
+    def c_struct(self):
+        """(simon_order_segments, the arrays it points into)."""
+        G = len(self.seg_start) - 1
+        nv = np.array([len(v) for v in self.variants], np.int32)
+        pods = np.ascontiguousarray(np.concatenate([v.reshape(-1) for v in self.variants] + [np.zeros(0, np.int32)]), dtype=np.int32)
+        live = None if self.live is None else np.ascontiguousarray(np.concatenate(self.live + [np.zeros(0, np.int32)]), dtype=np.int32)
+        o = OrderSegmentsC()
+        o.struct_size, o.n_seg = C.sizeof(OrderSegmentsC), G
+        o.seg_start, o.n_variants, o.variant_pods = _ptr(self.seg_start, C.c_int32), _ptr(nv, C.c_int32), _ptr(pods, C.c_int32)
+        o.variant_live, o.choice = _ptr(live, C.c_int32), _ptr(self.choice, C.c_int32)
+        return o, (nv, pods, live)
+
+
 def scenarios_array(scen: Sequence) -> np.ndarray:
     a = np.ascontiguousarray(np.asarray(scen, dtype=np.int32).reshape(-1, 2))
     return a
@@ -596,6 +669,7 @@ EXPORTS = [
     "simon_set_own_nodes_all_feature",
     "simon_set_scenario_pods", "simon_fetch_group_counts", "simon_fetch_node_usage", "simon_fetch_headroom",
     "simon_fetch_gpu_usage", "simon_fetch_headroom_gpu", "simon_fetch_local_usage", "simon_fetch_headroom_local",
+    "simon_load_scenarios_composed", "simon_fetch_orders",
     "simon_group_create", "simon_group_destroy", "simon_group_last_error", "simon_group_size", "simon_group_member",
     "simon_group_load_nodes", "simon_group_load_pods", "simon_group_load_class_tables", "simon_group_load_scenarios",
     "simon_group_run_loaded", "simon_group_fetch_results", "simon_group_run_batch", "simon_group_fetch_placement", "simon_group_fetch_gpu_slices",
@@ -646,6 +720,10 @@ def load_library(path: Optional[str] = None):
     lib.simon_set_own_nodes_all_feature.restype = C.c_int
     lib.simon_set_scenario_pods.argtypes = [vp, C.POINTER(C.c_uint32)]
     lib.simon_set_scenario_pods.restype = C.c_int
+    lib.simon_load_scenarios_composed.argtypes = [vp, C.POINTER(Scenario), C.c_int32, C.POINTER(OrderSegmentsC), C.c_int32]
+    lib.simon_load_scenarios_composed.restype = C.c_int
+    lib.simon_fetch_orders.argtypes = [vp, C.c_int32, C.c_int32, _p32, C.POINTER(C.c_uint32)]
+    lib.simon_fetch_orders.restype = C.c_int
     lib.simon_fetch_group_counts.argtypes = [vp, _p32, C.c_int32, _p32, _p32]
     lib.simon_fetch_group_counts.restype = C.c_int
     lib.simon_fetch_node_usage.argtypes = [vp, _p32, C.c_int32, C.POINTER(NodeUsageC)]
@@ -816,6 +894,34 @@ class Context:
                                                   _ptr(orders, C.c_int32), orders.shape[0]), "simon_load_scenarios")
         self.S = len(scen)
         self.scen = scen
+
+    def load_scenarios_composed(self, scen, segments: OrderSegments):
+        """load_scenarios with the order rows -- and, with segments.live, the pod rows -- composed on the device from the segment table
+        (include/simon_hip.h: simon_load_scenarios_composed)."""
+        scen = scenarios_array(scen)
+        o, keep = segments.c_struct()
+        self._check(self.lib.simon_load_scenarios_composed(self.h, scen.ctypes.data_as(C.POINTER(Scenario)), len(scen), C.byref(o), segments.n_orders),
+                    "simon_load_scenarios_composed")
+        del keep
+        self.S = len(scen)
+        self.scen = scen
+
+    def fetch_orders(self, first: int = 0, n: Optional[int] = None, present: bool = False):
+        """Rows [first, first + n) of the loaded orders (simon_fetch_orders); present=True: the pair (orders, bool [n][P] by pod id);
+        present="words": the pair (orders, the packed uint32 words [n][ceil(P / 32)] as the library wrote them)."""
+        P = self.problem.n_pods
+        n = 1 if n is None else int(n)
+        orders = np.zeros((max(n, 0), P), np.int32)
+        words = np.zeros((max(n, 0), (P + 31) // 32), np.uint32) if present else None
+        self._check(self.lib.simon_fetch_orders(self.h, int(first), n, _ptr(orders, C.c_int32), _ptr(words, C.c_uint32)), "simon_fetch_orders")
+        if not present:
+            return orders
+        if present == "words":
+            return orders, words
+        bits = np.unpackbits(np.ascontiguousarray(words).view(np.uint8), axis=1, bitorder="little").astype(bool)
+        if bits[:, P:].any():
+            raise SimonError("simon_fetch_orders set presence bits beyond P")
+        return orders, bits[:, :P]
 
     def run_loaded(self, want_placement: bool = True, want_gpu_slices: bool = False):
         flags = (WANT_PLACEMENT if want_placement else 0) | (WANT_GPU_SLICES if want_gpu_slices else 0)

@@ -14,12 +14,14 @@
 #include "simon_table.h"
 #include "simon_subset.h"
 #include "simon_podsets.h"
+#include "simon_orders.h"
 
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <map>
 #include <numeric>
 #include <set>
@@ -214,6 +216,11 @@ struct simon_ctx : simon::HostInputs {
     int pod_W = 0;
     DevBuf<uint32_t> d_pod_words;
     DevBuf<int32_t> d_pod_group, d_grp_uns, d_grp_placed;
+    // simon_load_scenarios_composed: the presence words of the live entries of every ORDER [n_orders][pod_W], which the pod rows expand by
+    // scenario; order_rows_on while those rows are the installed ones (simon_fetch_orders reports them).  order_host: env
+    // SIMON_ORDER_STAGE=host -- orders, inverse orders and words from host loops (A/B + tests)
+    DevBuf<uint32_t> d_order_words;
+    bool order_rows_on = false, order_host = false;
     // simon_fetch_node_usage / simon_fetch_headroom: compact int64 copies of the pod requests and the node rows ([kUsageRows][P] / [N]),
     // uploaded on the first call after simon_load_pods / simon_load_nodes; usage_rows: bit r = some pod requests resource row r (cpu and
     // memory always), the rows the kernels accumulate.  usage_tile: env SIMON_USAGE_TILE (nodes per LDS tile; 0 = from the LDS budget)
@@ -1793,6 +1800,7 @@ simon_ctx* simon_ctx_create(int device_id) {
     c->no_shared_prologue = getenv("SIMON_NO_SHARED_PROLOGUE") != nullptr;
     c->no_size_dispatch = getenv("SIMON_NO_SIZE_DISPATCH") != nullptr;
     if (const char* e = getenv("SIMON_SUBSET_STAGE")) c->subset_host = strcmp(e, "host") == 0;   // A/B + tests: node-subset staging in host loops
+    if (const char* e = getenv("SIMON_ORDER_STAGE")) c->order_host = strcmp(e, "host") == 0;     // A/B + tests: composed order rows in host loops
     if (const char* e = getenv("SIMON_IMAGE_STAGE")) c->image_host = strcmp(e, "host") == 0;     // A/B + tests: image states of an own-nodes batch in a host loop
     if (const char* e = getenv("SIMON_IMAGE_STATE_MB")) c->img_state_cap = (size_t)std::max(atoll(e), 0ll) << 20;
     if (const char* e = getenv("SIMON_USAGE_TILE")) c->usage_tile = std::max(atoi(e), 0);        // tests: node tiles of simon_fetch_node_usage / _headroom
@@ -2233,15 +2241,17 @@ static int table_layout(simon_ctx* c) {
 // What a loaded batch derives from the staged problem next to its scenarios (simon_load_scenarios; again after an own-nodes image batch
 // has re-staged the tables): for the score-table kernel the inverse orders -- placements are recorded by scheduling step and gathered
 // back to pod ids through them, which takes every order to be a permutation of [0, P) -- and the layout of the batch.
+// orders == null: the rows were composed on the device (simon_load_scenarios_composed) -- permutations by construction, their inverse
+// already in d_inv_orders.
 static int batch_orders_stage(simon_ctx* c, const int32_t* orders, int n_orders, int S, int max_n) {
     const int P = c->P;
     c->scen_ni.assign(S, 0);
     c->orders_perm = false;
     c->table_perm_ok = false;
     if (c->variant == SIMON_KERNEL_NARROW && c->table_ok) {
-        std::vector<int32_t> inv((size_t)n_orders * P, -1);
+        std::vector<int32_t> inv(orders ? (size_t)n_orders * P : 0, -1);
         bool is_perm = true;
-        for (int o = 0; o < n_orders && is_perm; ++o)
+        for (int o = 0; orders && o < n_orders && is_perm; ++o)
             for (int i = 0; i < P; ++i) {
                 int32_t& slot = inv[(size_t)o * P + orders[(size_t)o * P + i]];
                 if (slot >= 0) { is_perm = false; break; }
@@ -2250,17 +2260,24 @@ static int batch_orders_stage(simon_ctx* c, const int32_t* orders, int n_orders,
         c->orders_perm = is_perm;
         c->S = S; c->max_n = max_n;
         if (is_perm) {
-            HIP_TRY(c, c->d_inv_orders.upload(inv, c->stream));
+            if (orders) HIP_TRY(c, c->d_inv_orders.upload(inv, c->stream));
             if (const int rc = table_layout(c)) return rc;           // (synchronises: inv may die)
         }
     }
     return SIMON_OK;
 }
 
-int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, const int32_t* orders, int32_t n_orders) {
-    if (!c || !scen || S <= 0 || !orders || n_orders <= 0) return c ? fail(c, SIMON_EINVAL, "load_scenarios: bad arguments") : SIMON_EINVAL;
+// Order rows that the device composes from a validated segment table (simon_load_scenarios_composed): `dev` points at the uploaded table.
+struct ComposedOrders {
+    OrderCompose dev;
+    bool live;                                           // the call installs pod rows: the live entries of every scenario's order
+};
+
+// The body of simon_load_scenarios and simon_load_scenarios_composed: the order rows are the caller's (orders) or composed on the device
+// (comp, orders == null); everything else is the same call.
+static int load_scenarios_body(simon_ctx* c, const simon_scenario* scen, int32_t S, const int32_t* orders, int32_t n_orders, const ComposedOrders* comp) {
     c->seg_n = 0; c->sub_on = false;                     // (segments and node subsets belong to the batch they were set for)
-    c->pods_on = false;                                  // (and so do pod rows)
+    c->pods_on = false; c->order_rows_on = false;        // (and so do pod rows)
     if (c->img_own_T > 0) { c->img_own_T = 0; c->staged = false; }   // (image states belong to the own-nodes batch they were built for)
     if (c->has_img) {                    // ImageLocality: one slot per distinct cluster size; another set of sizes re-stages the tables
         std::vector<int32_t> sizes(S);
@@ -2282,7 +2299,7 @@ int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, co
         max_n = std::max(max_n, scen[s].n_nodes);
     }
     // every order must be a sequence of valid pod ids; preset targets must exist in each scenario
-    for (size_t i = 0; i < (size_t)n_orders * P; ++i)
+    for (size_t i = 0; orders && i < (size_t)n_orders * P; ++i)
         if (orders[i] < 0 || orders[i] >= P) return fail(c, SIMON_EINVAL, "orders[%zu] = %d is not a pod id", i, orders[i]);
     int min_n = c->N;
     for (int s = 0; s < S; ++s) min_n = std::min(min_n, scen[s].n_nodes);
@@ -2302,7 +2319,17 @@ int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, co
     HIP_TRY(c, c->d_scen.upload(c->scen, c->stream));
     HIP_TRY(c, c->d_perm.upload(perm, c->stream));
     HIP_TRY(c, c->d_orders.ensure((size_t)n_orders * P));
-    HIP_TRY(c, hipMemcpyAsync(c->d_orders.p, orders, (size_t)n_orders * P * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    const size_t W = (size_t)pod_row_words(P);
+    if (orders) HIP_TRY(c, hipMemcpyAsync(c->d_orders.p, orders, (size_t)n_orders * P * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    else {
+        // composed rows: the orders by stream position; by pod id the inverse orders, where batch_orders_stage would derive them, and the
+        // presence words of every order
+        const bool inv = c->variant == SIMON_KERNEL_NARROW && c->table_ok;
+        if (inv) HIP_TRY(c, c->d_inv_orders.ensure((size_t)n_orders * P));
+        if (comp->live) HIP_TRY(c, c->d_order_words.ensure((size_t)n_orders * W));
+        HIP_TRY(c, launch_order_compose(comp->dev, c->d_orders.p, c->stream));
+        HIP_TRY(c, launch_order_by_pod(comp->dev, inv ? c->d_inv_orders.p : nullptr, comp->live ? c->d_order_words.p : nullptr, c->stream));
+    }
     HIP_TRY(c, c->d_unsched.ensure(S));
     HIP_TRY(c, c->d_used_cpu.ensure(S));
     HIP_TRY(c, c->d_used_mem.ensure(S));
@@ -2318,19 +2345,123 @@ int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, co
     c->h_perm = perm;
     rc = batch_orders_stage(c, orders, n_orders, S, max_n);
     if (rc) return rc;
-    if (c->has_img) c->img_orders.assign(orders, orders + (size_t)n_orders * P);   // (an own-nodes batch re-stages, whenever the sizes arrive: img_own_restage)
-    else c->img_orders.clear();
+    if (!c->has_img) c->img_orders.clear();
+    else if (orders) c->img_orders.assign(orders, orders + (size_t)n_orders * P);   // (an own-nodes batch re-stages, whenever the sizes arrive: img_own_restage)
+    else {                                               // (composed rows are read back once for the host-side readers)
+        c->img_orders.resize((size_t)n_orders * P);
+        HIP_TRY(c, hipMemcpyAsync(c->img_orders.data(), c->d_orders.p, (size_t)n_orders * P * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (!orders && c->has_local) {
+        c->h_orders.resize((size_t)n_orders * P);
+        HIP_TRY(c, hipMemcpyAsync(c->h_orders.data(), c->d_orders.p, (size_t)n_orders * P * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (comp && comp->live) {                            // the pod rows: scenario s holds the live entries of its order
+        static_assert(sizeof(ScenarioDesc) == 8, "order_rows_expand_kernel reads ScenarioDesc as int32 pairs");
+        HIP_TRY(c, c->d_pod_words.ensure((size_t)S * W));
+        HIP_TRY(c, launch_order_rows_expand(c->d_order_words.p, reinterpret_cast<const int32_t*>(c->d_scen.p), S, (int)W, c->d_pod_words.p, c->stream));
+    }
     HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // caller buffers may die after return
     float ms = 0;
     (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
     c->stats.h2d_ms = ms;
     c->S = S; c->n_orders = n_orders; c->max_n = max_n;
-    if (c->has_local) c->h_orders.assign(orders, orders + (size_t)n_orders * P);    // (only the storage calls read them: local_stage)
-    else c->h_orders.clear();
+    if (!c->has_local) c->h_orders.clear();
+    else if (orders) c->h_orders.assign(orders, orders + (size_t)n_orders * P);     // (only the storage calls read them: local_stage)
+    if (comp && comp->live) { c->pod_W = (int)W; c->pods_on = true; c->order_rows_on = true; }
     c->local_pods_staged = false;
     c->has_ranks = false;
     c->have_results = false;
+    return SIMON_OK;
+}
+
+int simon_load_scenarios(simon_ctx* c, const simon_scenario* scen, int32_t S, const int32_t* orders, int32_t n_orders) {
+    if (!c || !scen || S <= 0 || !orders || n_orders <= 0) return c ? fail(c, SIMON_EINVAL, "load_scenarios: bad arguments") : SIMON_EINVAL;
+    return load_scenarios_body(c, scen, S, orders, n_orders, nullptr);
+}
+
+// simon_load_scenarios with the order rows composed from segments: on the device (simon_orders.hip) from the uploaded table, or with
+// SIMON_ORDER_STAGE=host in the loops of order_segments_compose_host, whose rows then take simon_load_scenarios' and
+// simon_set_scenario_pods' own road.
+static int load_composed(simon_ctx* c, const simon_scenario* scen, int32_t S, const simon_order_segments* seg, int32_t n_orders) {
+    if (!scen || S <= 0 || !seg || n_orders <= 0) return fail(c, SIMON_EINVAL, "load_scenarios_composed: bad arguments");
+    if (seg->struct_size != sizeof(simon_order_segments)) return fail(c, SIMON_EINVAL, "load_scenarios_composed: simon_order_segments size mismatch");
+    if (!(c->have_nodes && c->have_pods && c->have_tables)) return fail(c, SIMON_ESTATE, "load nodes, pods and class tables before scenarios");
+    const int P = c->P;
+    OrderSegTable t;
+    long long at = 0;
+    const OrderSegView view{seg->n_seg, seg->seg_start, seg->n_variants, seg->variant_pods, seg->variant_live, seg->choice};
+    if (const OrderSegError e = order_segments_check(view, P, n_orders, t, &at))
+        return fail(c, SIMON_EINVAL, "load_scenarios_composed: %s (entry %lld)", order_segments_text(e), at);
+    if (c->debug_route) fprintf(stderr, "[orders] stage %s n_orders %d segments %d table ids %zu\n", c->order_host ? "host" : "device", n_orders, t.G, t.n_ids());
+    const size_t W = (size_t)pod_row_words(P);
+    if (c->order_host) {
+        std::vector<int32_t> orders((size_t)n_orders * P);
+        std::vector<uint32_t> words(seg->variant_live ? (size_t)n_orders * W : 0);
+        order_segments_compose_host(t, seg->variant_pods, seg->variant_live, seg->choice, n_orders, orders.data(), nullptr,
+                                    seg->variant_live ? words.data() : nullptr);
+        if (const int rc = load_scenarios_body(c, scen, S, orders.data(), n_orders, nullptr)) return rc;
+        if (!seg->variant_live) return SIMON_OK;
+        std::vector<uint32_t> rows((size_t)S * W);
+        for (int s = 0; s < S; ++s) std::copy_n(words.begin() + (size_t)scen[s].order_id * W, W, rows.begin() + (size_t)s * W);
+        if (const int rc = simon_set_scenario_pods(c, rows.data())) return rc;
+        HIP_TRY(c, c->d_order_words.upload(words, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->order_rows_on = true;
+        return SIMON_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the table on the device, for the length of this call: sum_g n_variants[g] x len_g ids twice, n_orders x G choices
+    DevBuf<int32_t> d_start, d_live_off, d_pods, d_pos, d_owner, d_local, d_live, d_choice;
+    DevBuf<int64_t> d_var_off;
+    const std::vector<int32_t> pods(seg->variant_pods, seg->variant_pods + t.n_ids()), choice(seg->choice, seg->choice + (size_t)n_orders * t.G);
+    std::vector<int32_t> live;
+    if (seg->variant_live) live.assign(seg->variant_live, seg->variant_live + t.n_var());
+    const auto staged = [&]() -> int {
+        HIP_TRY(c, d_start.upload(t.seg_start, c->stream));
+        HIP_TRY(c, d_var_off.upload(t.var_off, c->stream));
+        HIP_TRY(c, d_live_off.upload(t.live_off, c->stream));
+        HIP_TRY(c, d_pods.upload(pods, c->stream));
+        HIP_TRY(c, d_pos.upload(t.pos, c->stream));
+        HIP_TRY(c, d_owner.upload(t.owner, c->stream));
+        HIP_TRY(c, d_local.upload(t.local, c->stream));
+        HIP_TRY(c, d_choice.upload(choice, c->stream));
+        if (seg->variant_live) HIP_TRY(c, d_live.upload(live, c->stream));
+        ComposedOrders comp;
+        comp.dev = OrderCompose{d_start.p, d_var_off.p, d_live_off.p, d_pods.p, d_pos.p, d_owner.p, d_local.p, seg->variant_live ? d_live.p : nullptr,
+                                d_choice.p, t.G, P, n_orders};
+        comp.live = seg->variant_live != nullptr;
+        return load_scenarios_body(c, scen, S, nullptr, n_orders, &comp);
+    };
+    const int rc = staged();
+    (void)hipStreamSynchronize(c->stream);                       // (the table's buffers die here: whichever step failed, nothing of it is in flight)
+    return rc;
+}
+
+int simon_load_scenarios_composed(simon_ctx* c, const simon_scenario* scen, int32_t S, const simon_order_segments* seg, int32_t n_orders) {
+    if (!c) return SIMON_EINVAL;
+    int rc;
+    try {
+        rc = load_composed(c, scen, S, seg, n_orders);
+    } catch (const std::exception&) {                    // (no exception crosses the C ABI: a table the host cannot hold)
+        rc = fail(c, SIMON_ENOMEM, "load_scenarios_composed: out of host memory");
+    }
+    if (rc) { c->S = 0; c->pods_on = false; c->order_rows_on = false; }     // (a failing call leaves no batch loaded)
+    return rc;
+}
+
+int simon_fetch_orders(simon_ctx* c, int32_t first, int32_t n, int32_t* orders, uint32_t* present) {
+    if (!c) return SIMON_EINVAL;
+    if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "fetch_orders: load scenarios first");
+    if (!orders || first < 0 || n < 1 || first > c->n_orders - n) return fail(c, SIMON_EINVAL, "fetch_orders: rows [%d, %d + %d) outside the %d loaded orders", first, first, n, c->n_orders);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t P = c->P, W = (size_t)pod_row_words(c->P);
+    HIP_TRY(c, hipMemcpyAsync(orders, c->d_orders.p + (size_t)first * P, (size_t)n * P * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (present && c->order_rows_on)
+        HIP_TRY(c, hipMemcpyAsync(present, c->d_order_words.p + (size_t)first * W, (size_t)n * W * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    else if (present)                                            // (no rows of a composed batch: every order holds every pod)
+        for (size_t i = 0; i < (size_t)n * W; ++i) present[i] = (i % W == W - 1 && (P & 31)) ? ~(~0u << (P & 31)) : ~0u;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SIMON_OK;
 }
 
@@ -2725,7 +2856,7 @@ int simon_fetch_node_ranks(simon_ctx* c, int32_t* rank) {
 int simon_set_scenario_pods(simon_ctx* c, const uint32_t* present) {
     if (!c) return SIMON_EINVAL;
     if (!c->staged || c->S <= 0) return fail(c, SIMON_ESTATE, "set_scenario_pods: load scenarios first");
-    if (!present) { c->pods_on = false; c->have_results = false; return SIMON_OK; }
+    if (!present) { c->pods_on = false; c->order_rows_on = false; c->have_results = false; return SIMON_OK; }
     const int S = c->S, P = c->P, W = pod_row_words(P);
     int bit = 0;
     if (const int s = pod_rows_first_bad(present, S, P, &bit); s >= 0)
@@ -2738,6 +2869,7 @@ int simon_set_scenario_pods(simon_ctx* c, const uint32_t* present) {
     std::swap(c->d_pod_words.p, fresh.p); std::swap(c->d_pod_words.n, fresh.n);
     c->pod_W = W;
     c->pods_on = true;
+    c->order_rows_on = false;                                    // (the caller's rows replace a composed batch's)
     c->have_results = false;
     return SIMON_OK;
 }

@@ -29,6 +29,7 @@ class HipEngine:
     supports_scenario_subsets = True          # node subsets (simon_set_scenario_nodes): sweep_failures() batches the loss of every failure domain
     supports_pod_eviction = True              # ... and reschedules the pods of the lost nodes (simon_set_pod_eviction): sweep_failures(reschedule=...)
     supports_pod_subsets = True               # pod subsets (simon_set_scenario_pods): sweep_apps() batches the combinations of apps
+    supports_order_segments = True            # ... with per-scenario pod orders composed on the device (simon_load_scenarios_composed): sweep_scale() batches replica levels
     supports_node_usage = True                # per-node usage and headroom reduced on the device (simon_fetch_node_usage / simon_fetch_headroom)
     supports_gpu_usage = True                 # ... GPU-share devices and the device bound of headroom (simon_fetch_gpu_usage / simon_fetch_headroom_gpu)
     supports_local_usage = True               # ... Open-Local storage and the storage bound of headroom (simon_fetch_local_usage / simon_fetch_headroom_local)
@@ -50,8 +51,10 @@ class HipEngine:
 
     def run(self, prob: capi.Problem, scen, orders, want_placement=True, node_ranks=None, want_gpu_slices=False,
             segments=None, present=None, evict=None, pod_present=None, pod_groups=None, headroom_pods=None, usage_of=None,
-            gpu_usage_of=None, headroom_devices=False, local_usage_of=None, headroom_storage=False) -> capi.BatchResult:
-        """local_usage_of: scenario indices -- the result carries local_usage, the volume groups' requests and the allocated devices per
+            gpu_usage_of=None, headroom_devices=False, local_usage_of=None, headroom_storage=False, order_segments=None) -> capi.BatchResult:
+        """order_segments: capi.OrderSegments -- the order rows and, with its `live`, the pod rows are composed on the device from the
+        segment table (simon_load_scenarios_composed) instead of being passed: `orders` and `pod_present` must then be None.
+        local_usage_of: scenario indices -- the result carries local_usage, the volume groups' requests and the allocated devices per
         node at the end of those scenarios (simon_fetch_local_usage).  headroom_storage: headroom_pods are answered with the storage bound
         and, where the problem has GPUs, the device bound (simon_fetch_headroom_local: Open-Local probes become exact).
         gpu_usage_of: scenario indices -- the result carries gpu_usage, GPU memory and stream pods per device at the end of those
@@ -71,16 +74,17 @@ class HipEngine:
             raise ValueError("a batch has pool segments or node subsets, not both")
         if evict is not None and present is None:
             raise ValueError("evicted pods belong to a node-subset batch: pass present")
+        _segments_only(order_segments, orders, pod_present)
         with self._context() as ctx:
             ctx.load_problem(prob)
             if evict is not None:
                 ctx.set_pod_eviction(evict)
             usage = headroom_pods is not None or usage_of is not None or gpu_usage_of is not None or local_usage_of is not None
             record = want_gpu_slices or gpu_usage_of is not None or ((headroom_devices or headroom_storage) and headroom_pods is not None)
-            if node_ranks is None and segments is None and present is None and pod_present is None and pod_groups is None and not usage:
+            if node_ranks is None and segments is None and present is None and pod_present is None and pod_groups is None and not usage and order_segments is None:
                 res = ctx.run_batch(scen, orders, want_placement, want_gpu_slices)
             else:
-                ctx.load_scenarios(scen, orders)
+                _load(ctx, scen, orders, order_segments)
                 if pod_present is not None:
                     ctx.set_scenario_pods(pod_present)
                 if segments is not None:
@@ -115,18 +119,20 @@ class HipEngine:
             return nf, failed, codes, ctx.explain_local_detail(len(failed), n_nodes)
 
     def explain_batch(self, prob: capi.Problem, scen, orders, node_ranks, ids, max_failed: int, max_bins: int = 32, *,
-                      pod_present=None) -> List["ExplainedScenario"]:
-        """Why the pods of scenarios `ids` of the batch (scen, orders, node_ranks) fail, many scenarios per launch (simon_explain_batch):
+                      pod_present=None, order_segments=None) -> List["ExplainedScenario"]:
+        """order_segments: as run() takes it (orders and pod_present None).
+        Why the pods of scenarios `ids` of the batch (scen, orders, node_ranks) fail, many scenarios per launch (simon_explain_batch):
         per failed pod the (code, node count) histogram.  Scenarios with a pod whose histogram cannot be turned into text -- a code that
         names the node (fiterror.NODE_SPECIFIC_CODES) or more distinct codes than fit -- are listed once more for their full code rows,
         and those with Open-Local's size-carrying errors are replayed one by one for the sizes (simon_explain_local_detail).
         The output buffers of one call hold max_failed entries for EVERY listed scenario, so the list goes to the device in groups whose
         buffers stay within `buffer_bytes` (a group is one scenario at least: that one's buffers are explain_loaded's)."""
         ids = [int(s) for s in ids]
+        _segments_only(order_segments, orders, pod_present)
         per_bins = max_failed * (8 + 8 * max_bins)                           # failed_pods + n_bins + bins, per listed scenario
         with self._context() as ctx:
             ctx.load_problem(prob)
-            ctx.load_scenarios(scen, orders)
+            _load(ctx, scen, orders, order_segments)
             if pod_present is not None:              # (every listed scenario is replayed with its own pod row)
                 ctx.set_scenario_pods(pod_present)
             if node_ranks is not None:
@@ -152,8 +158,9 @@ class HipEngine:
             return out
 
     def explain_own_batch(self, prob: capi.Problem, scen, orders, node_ranks, ids, max_failed: int, max_bins: int = 32, *, present=None,
-                          segments=None, evict=None, pod_present=None) -> List["ExplainedScenario"]:
-        """explain_batch for a batch with pool segments or node subsets (simon_explain_own_batch), on the context shape run() gives such a
+                          segments=None, evict=None, pod_present=None, order_segments=None) -> List["ExplainedScenario"]:
+        """order_segments: as run() takes it (orders and pod_present None).
+        explain_batch for a batch with pool segments or node subsets (simon_explain_own_batch), on the context shape run() gives such a
         batch: `segments` / `present` / `evict` / `node_ranks` as run() takes them.  Bins count each scenario's own nodes; the rows of the
         second pass are [failed][N], indexed by POOL node, 0 on the nodes the scenario lacks.  capi.SimonError (ESTATE) where the
         library refuses: a problem whose route is the all-feature kernel."""
@@ -161,13 +168,14 @@ class HipEngine:
             raise ValueError("an own-nodes batch has pool segments or node subsets (exactly one of them)")
         if evict is not None and present is None:
             raise ValueError("evicted pods belong to a node-subset batch: pass present")
+        _segments_only(order_segments, orders, pod_present)
         ids = [int(s) for s in ids]
         per_bins = max_failed * (8 + 8 * max_bins)                           # failed_pods + n_bins + bins, per listed scenario
         with self._context() as ctx:
             ctx.load_problem(prob)
             if evict is not None:
                 ctx.set_pod_eviction(evict)
-            ctx.load_scenarios(scen, orders)
+            _load(ctx, scen, orders, order_segments)
             if segments is not None:
                 ctx.set_scenario_segments(*segments)
             if present is not None:
@@ -195,6 +203,19 @@ class HipEngine:
     supports_explain_batch = True             # sweep(..., reasons=True) explains every failing size in one launch
     supports_explain_own = True               # ... and sweep_failures / sweep_mix (reasons=True) every failing scenario of an own-nodes batch
     buffer_bytes = 256 << 20                  # explain_batch: host (and device) output buffers per simon_explain_batch call
+
+
+def _segments_only(order_segments, orders, pod_present):
+    if order_segments is not None and (orders is not None or pod_present is not None):
+        raise ValueError("order_segments compose the order rows and the pod rows: pass neither orders nor pod_present with them")
+
+
+def _load(ctx: capi.Context, scen, orders, order_segments):
+    """The scenarios of a batch onto the context: the caller's order rows, or the rows its segment table composes on the device."""
+    if order_segments is not None:
+        ctx.load_scenarios_composed(scen, order_segments)
+    else:
+        ctx.load_scenarios(scen, orders)
 
 
 def _groups(items: list, size: int):
@@ -953,7 +974,10 @@ def _reason_texts(flat: fl.Flat, failed, rows, detail, bins=None, node_names=Non
     return reasons
 
 
-def _unscheduled_list(flat: fl.Flat, placement: np.ndarray, reasons: Dict[int, str]) -> List[dict]:
+def _unscheduled_list(flat: fl.Flat, placement: np.ndarray, reasons: Dict[int, str], order=None) -> List[dict]:
+    """order: the pod ids in the order the scenario fed them (default: the problem's own)."""
+    if order is not None:
+        return [{"pod": _public(flat.pods[pid]), "reason": reasons.get(pid, "")} for pid in np.asarray(order).tolist() if placement[pid] == capi.UNSCHEDULED]
     return [{"pod": _public(flat.pods[pid]), "reason": reasons.get(pid, "")} for pid, j in enumerate(placement.tolist()) if j == capi.UNSCHEDULED]
 
 
@@ -1860,9 +1884,9 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
     else.  Where the argument does not hold the scenarios run one by one, each as its own simulate() (AppFallbackWarning, batched =
     False): an engine without supports_pod_subsets; an app with a DaemonSet whose pod list at some size is not the pool's restricted
     to that size (_same_stream's case); an app whose pods use a StorageClass that only another app defines (_storage_classes registers
-    them all up front); an engine that refuses the batch (SIMON_ESTATE).  Not covered: subsets of the replicas WITHIN one app --
+    them all up front); an engine that refuses the batch (SIMON_ESTATE).  Subsets of the replicas WITHIN one app are sweep_scale's:
     ScheduleApp's unstable sorts order an app's pods by the length of the list, so a shorter replica list is not a restriction of the
-    longer one's stream.
+    longer one's stream, and every replica level brings an order of its own there.
     headroom=[...] / node_table=True / devices=True / storage=True: as sweep() takes them, per scenario (u, k) (AppSweepResult.headroom[u][k] etc.); a probe may be a
     pod of an app the scenario lacks -- its request and class stand for "one more such pod"."""
     engine = engine or HipEngine()
@@ -1967,6 +1991,327 @@ def sweep_apps(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], subs
             by_app.append([int(g[a]) if a < len(g) else 0 for a in range(A)])
             lists.append(replayed[s] if s in replayed else _unscheduled_list(flat, out.placement[s], told.get(s, {})) if reasons else [])
     return usage.onto(_app_summary(apps, subs, counts, _nested(rows, K), _nested(by_app, K), caps, w, _nested(lists, K) if reasons else [], True, None), K)
+
+
+@dataclass
+class ScaleSweepResult:
+    """sweep_scale: how far the target workloads scale.  Scenario (c, k) = the cluster, the apps with the targets at combos[c] replicas and
+    counts[k] new nodes."""
+    targets: List[tuple]                  # (app name, kind, workload name, levels) as given
+    combos: List[tuple]                   # [C] replicas per target
+    counts: List[int]                     # new nodes per column
+    unscheduled: List[List[int]]          # [C][K]
+    unscheduled_by_target: List[List[List[int]]]   # [C][K][T] pods of target t left unscheduled
+    cpu_pct: List[List[int]]              # [C][K] occupancies (satisfyResourceSetting)
+    mem_pct: List[List[int]]
+    vg_pct: List[List[int]]
+    fits: List[List[bool]]                # [C][K] no unscheduled pod and the caps hold
+    min_count: List[Optional[int]]        # [C] the smallest count that fits, or None
+    max_level: List[List[Optional[int]]]  # [T][K] the largest level of target t such that it and every smaller level of the sweep fit with counts[k]
+                                          # (the other targets at their smallest level); None: not even the smallest
+    needs_reference: List[List[bool]]     # [C][K] DefaultPreemption could have acted there (simon_fetch_preempt_risk)
+    unscheduled_pods: List[List[List[dict]]] = field(default_factory=list)   # reasons=True: [C][K] simulate()'s list of that scenario
+    batched: bool = True                  # one problem, per-level orders and pod rows (False: every scenario ran as its own simulate())
+    fallback: Optional[str] = None        # why the scenarios ran one by one (None when batched); sweep_scale also warns
+    headroom: Optional[List[List[List[int]]]] = None    # as AppSweepResult carries them, [C][K]
+    headroom_exact: Optional[List[bool]] = None
+    node_table: Optional[List[List[List[dict]]]] = None
+    gpu_table: Optional[List[List[List[dict]]]] = None
+    storage_table: Optional[List[List[List[dict]]]] = None
+
+
+class ScaleFallbackWarning(UserWarning):
+    """sweep_scale could not batch the scenarios and runs each as its own problem: one flatten, upload and launch per (combo, count).
+    The reason names what refused: an engine without pod subsets, two pods of one name, an app whose DaemonSet makes some level's own
+    order differ from the batch's, ImageLocality / node ranks the engine lacks, or an engine that refused the batch."""
+
+
+SCALABLE_KINDS = {"Deployment": "replicas", "ReplicaSet": "replicas", "StatefulSet": "replicas", "Job": "completions"}
+
+
+def _scale_targets(apps, scale) -> List[tuple]:
+    """(app index, kind, workload name, levels) per target of `scale`, validated."""
+    names = {a.name: i for i, a in enumerate(apps)}
+    out, seen = [], set()
+    for target in scale:
+        app_name, kind, wname, levels = target
+        if kind not in SCALABLE_KINDS:
+            raise ValueError(f"a {kind} has no replica count to scale: the kinds are {sorted(SCALABLE_KINDS)}")
+        if app_name not in names:
+            raise ValueError(f"scale names app {app_name!r}: the apps are {sorted(names)}")
+        if not any(o["metadata"]["name"] == wname for o in apps[names[app_name]].resource.get(kind, [])):
+            raise ValueError(f"app {app_name} has no {kind} {wname!r}")
+        levels = [int(x) for x in levels]
+        if not levels or min(levels) < 0:
+            raise ValueError(f"the levels of {kind} {wname!r} are {levels}: one at least, none negative")
+        if (app_name, kind, wname) in seen:
+            raise ValueError(f"{kind} {wname!r} of app {app_name} is a target twice")
+        seen.add((app_name, kind, wname))
+        out.append((names[app_name], kind, wname, levels))
+    if not out:
+        raise ValueError("sweep_scale needs one target at least")
+    return out
+
+
+def scaled_app(app: AppResource, replicas: Dict[tuple, int]) -> AppResource:
+    """The app with the workloads (kind, name) of `replicas` set to that many replicas (completions for a Job); the objects are shared
+    but for the patched ones' top level and spec."""
+    res = dict(app.resource)
+    for kind in {k for k, _ in replicas}:
+        res[kind] = [dict(o, spec=dict(o["spec"], **{SCALABLE_KINDS[kind]: int(replicas[(kind, o["metadata"]["name"])])}))
+                     if (kind, o["metadata"]["name"]) in replicas else o for o in res.get(kind, [])]
+    return AppResource(app.name, res)
+
+
+def _scaled_apps(apps, targets, combo) -> List[AppResource]:
+    per: Dict[int, Dict[tuple, int]] = {}
+    for (a, kind, wname, _), r in zip(targets, combo):
+        per.setdefault(a, {})[(kind, wname)] = int(r)
+    return [scaled_app(app, per[a]) if a in per else app for a, app in enumerate(apps)]
+
+
+def _target_refs(apps, target, n: int) -> List[tuple]:
+    """(namespace, name) of the first n replicas of a target, as workloads names them: <workload>-<i>."""
+    a, kind, wname, _ = target
+    obj = next(o for o in apps[a].resource[kind] if o["metadata"]["name"] == wname)
+    return [(obj["metadata"].get("namespace") or "default", f"{wname}-{i}") for i in range(n)]
+
+
+def _scale_summary(targets, scale, combos, counts, rows, by_target, caps, why_lists, batched, fallback) -> ScaleSweepResult:
+    """rows[c][k] = (unscheduled, cpu_pct, mem_pct, vg_pct, needs_reference)."""
+    fits = [[_within(r, caps) for r in row] for row in rows]
+    min_count = [min((counts[k] for k in range(len(counts)) if f[k]), default=None) for f in fits]
+    index = {tuple(c): i for i, c in reversed(list(enumerate(combos)))}
+    low = [min(t[3]) for t in targets]
+    max_level = []
+    for t, target in enumerate(targets):
+        max_level.append([])
+        for k in range(len(counts)):
+            best = None
+            for level in sorted(set(target[3])):
+                c = index.get(tuple(level if u == t else low[u] for u in range(len(targets))))
+                if c is None or not fits[c][k]:
+                    break
+                best = level
+            max_level[-1].append(best)
+    return ScaleSweepResult([tuple(t) for t in scale], [tuple(c) for c in combos], list(counts), [[r[0] for r in row] for row in rows], by_target,
+                            [[r[1] for r in row] for row in rows], [[r[2] for r in row] for row in rows], [[r[3] for r in row] for row in rows],
+                            fits, min_count, max_level, [[bool(r[4]) for r in row] for row in rows], why_lists, batched, fallback)
+
+
+def _sweep_scale_each(cluster, apps, targets, scale, combos, new_node, counts, engine, caps, reasons, why: str, headroom=None,
+                      node_table: bool = False, devices: bool = False, storage: bool = False) -> ScaleSweepResult:
+    """Every scenario as its own Simulate(): the cluster, the apps at the combo's replicas and its new nodes."""
+    import warnings
+    warnings.warn(f"sweep_scale runs {len(combos) * len(counts)} scenarios one by one ({why})", ScaleFallbackWarning, stacklevel=3)   # (sweep_scale: always)
+    base = list(cluster.get("Node", []))
+    usage = _Usage(headroom, node_table, devices, storage)
+    rows, by_target, lists = [], [], []          # over the scenarios (c, k), k fastest
+    for combo in combos:
+        mine = _scaled_apps(apps, targets, combo)
+        refs = [set(_target_refs(apps, t, int(r))) for t, r in zip(targets, combo)]
+        for k in counts:
+            nodes = base + (wl.new_fake_nodes(new_node, k) if k > 0 else [])
+            a = _run_alone(cluster, mine, nodes, engine, want_slices=devices or storage, usage=usage, explain=reasons, explain_at_risk=False,
+                           skip_empty=True)
+            per = [0] * len(targets)
+            if a.out is None:
+                if usage.asked:
+                    raise ValueError("sweep_scale: headroom / node_table of a scenario without any pod, run on its own")
+                a.row, a.unscheduled_pods = (0, 0, 0, 0, False), []
+            else:
+                for pid in np.flatnonzero(a.out.placement[0] == capi.UNSCHEDULED).tolist():
+                    ref = _ns_name(a.flat.pods[pid])
+                    for t in range(len(targets)):
+                        per[t] += ref in refs[t]
+            rows.append(a.row)
+            by_target.append(per)
+            lists.append(a.unscheduled_pods)
+    K = len(counts)
+    return usage.onto(_scale_summary(targets, scale, combos, counts, _nested(rows, K), _nested(by_target, K), caps, _nested(lists, K) if reasons else [],
+                                     False, why), K)
+
+
+def scale_segments(apps, targets, combos, flat: fl.Flat, pool: List[dict]):
+    """The order segments of a sweep_scale batch over the pool problem `flat` (every target at its largest level): one segment for the
+    cluster's pods and one per app, in stream order; an app's variants are the distinct tuples of its own targets' levels among the
+    combos, each the level's OWN ScheduleApp order (workloads.app_pods of the patched app) with the absent pods appended in ascending
+    id order, live = the own list's length.  Returns (capi.OrderSegments with choice [C][1 + A], per app the list of its variants'
+    replica dicts), or a str: why the pool cannot carry the levels."""
+    ids: Dict[tuple, int] = {}
+    for pid, p in enumerate(flat.pods):
+        if ids.setdefault(_ns_name(p), pid) != pid:
+            return f"two pods are named {_ns_name(p)}"
+    tops = _scaled_apps(apps, targets, [max(t[3]) for t in targets])
+    lens = [len(wl.app_pods(a.name, a.resource, pool)) for a in tops]
+    P = len(flat.pods)
+    seg_start = np.concatenate([[0], np.cumsum([P - sum(lens)] + lens)]).astype(np.int32)
+    variants, live, patches = [np.arange(seg_start[1], dtype=np.int32)[None, :]], [np.array([seg_start[1]], np.int32)], []
+    choice = np.zeros((len(combos), 1 + len(apps)), np.int32)
+    for a, app in enumerate(apps):
+        mine = [t for t, target in enumerate(targets) if target[0] == a]
+        lo, hi = int(seg_start[1 + a]), int(seg_start[2 + a])
+        keys: Dict[tuple, int] = {}
+        for c, combo in enumerate(combos):
+            choice[c, 1 + a] = keys.setdefault(tuple(int(combo[t]) for t in mine), len(keys))
+        rows, lives, reps = [], [], []
+        for key in keys:
+            rep = {(targets[t][1], targets[t][2]): r for t, r in zip(mine, key)}
+            own = [ids.get(_ns_name(p), -1) for p in wl.app_pods(app.name, scaled_app(app, rep).resource if rep else app.resource, pool)]
+            if any(not lo <= pid < hi for pid in own):
+                return f"app {app.name} at {rep} has a pod that its largest level lacks"
+            absent = np.setdiff1d(np.arange(lo, hi), own)
+            rows.append(np.concatenate([np.asarray(own, np.int64), absent]).astype(np.int32))
+            lives.append(len(own))
+            reps.append(rep)
+        variants.append(np.asarray(rows, np.int32).reshape(len(rows), hi - lo))
+        live.append(np.asarray(lives, np.int32))
+        patches.append(reps)
+    return capi.OrderSegments(seg_start, variants, live, choice), patches
+
+
+@_gc_paused
+def sweep_scale(cluster: Dict[str, List[dict]], apps: Sequence[AppResource], scale, new_node: Optional[dict] = None,
+                counts: Sequence[int] = (0,), combos=None, engine=None, max_cpu: int = 100, max_mem: int = 100, max_vg: int = 100,
+                reasons: bool = False, batch_scenarios: int = 4096, headroom=None, node_table: bool = False, devices: bool = False,
+                storage: bool = False) -> ScaleSweepResult:
+    """How far can these workloads scale on this cluster, and how many new nodes does 2x, 3x, ... cost: scenario (c, k) is
+    simulate(cluster, apps with the target workloads set to combos[c] replicas, new_nodes = counts[k] clones of new_node).
+    scale: targets (app name, kind, workload name, levels), kind one of Deployment / ReplicaSet / StatefulSet (spec.replicas) or Job
+    (spec.completions); a DaemonSet, a CronJob, an unknown app or workload, a negative level or a duplicate target: ValueError.
+    combos: None = the cartesian product of the targets' levels, last target fastest; else [C][T] replica tuples, each value one of its
+    target's levels.
+
+    All scenarios run as batches of ONE problem -- the whole node pool and the apps with every target at its largest level
+    (sweep_batch).  Replicas are named <workload>-<i>, so level r is pods 0 .. r-1 of the top level, found by (namespace, name).  What
+    sweep_apps could not do is the order: ScheduleApp's two unstable sorts order an app's pods by the LENGTH of the list, so every level
+    has an order of its own.  The batch therefore carries one order per combo, cut into segments (scale_segments): the cluster's pods,
+    then one per app, whose variants are the app's pods in each level's own order with the absent pods appended -- and one pod row per
+    combo that holds the level's own pods only.  An engine with supports_order_segments composes both on the device from that table
+    (simon_load_scenarios_composed); one with pod subsets alone gets the same rows composed on the host (OrderSegments.compose).
+    Why that is exact: sweep_apps' argument -- the absent pods are never fed to the scheduler, every topology counter counts placed pods
+    only, the classes and signatures of absent pods cost table rows and nothing else -- and the order within the app is the level's
+    own, because it was computed from the level's own list.  Pod groups are the targets plus one per app for the rest
+    (simon_fetch_group_counts).
+    Where the argument does not hold every scenario runs as its own simulate() (ScaleFallbackWarning, batched = False, `fallback` names
+    the cause): an engine without supports_pod_subsets; two pods of one (namespace, name); an app with a DaemonSet where for some
+    (variant, count) the app's own list over that many nodes is not the variant's list without the pods gated at that size;
+    ImageLocality or node ranks the engine lacks; an engine that refuses the batch (SIMON_ESTATE).
+    reasons / headroom / node_table / devices / storage: as sweep_apps takes them, per scenario (c, k)."""
+    import itertools
+    engine = engine or HipEngine()
+    apps, counts, scale = list(apps), list(counts), [tuple(t) for t in scale]
+    if not counts:
+        raise ValueError("sweep_scale needs one count at least")
+    targets = _scale_targets(apps, scale)
+    T = len(targets)
+    if combos is None:
+        combos = list(itertools.product(*(t[3] for t in targets)))
+    else:
+        combos = [tuple(int(x) for x in row) for row in combos]
+        for row in combos:
+            if len(row) != T or any(r not in t[3] for r, t in zip(row, targets)):
+                raise ValueError(f"combo {row}: one level of each of the {T} targets")
+    if not combos:
+        raise ValueError("sweep_scale needs one combo at least")
+    caps = _caps(max_cpu, max_mem, max_vg)
+    base = list(cluster.get("Node", []))
+    if max(counts) > 0 and new_node is None:
+        raise ValueError("new node is nil when adding node to cluster")
+    each = lambda why: _sweep_scale_each(cluster, apps, targets, scale, combos, new_node, counts, engine, caps, reasons, why, headroom,   # noqa: E731
+                                         node_table, devices, storage)
+    if not getattr(engine, "supports_pod_subsets", False):
+        return each("the engine has no pod subsets")
+    tops = _scaled_apps(apps, targets, [max(t[3]) for t in targets])
+    try:
+        batch = sweep_batch(cluster, tops, new_node, counts, ranks_ok=getattr(engine, "supports_node_ranks", True),
+                            image_batch=getattr(engine, "supports_image_locality", False))
+    except fl.Unsupported as e:
+        if "ImageLocality" not in str(e) and "node ranks" not in str(e):
+            raise
+        return each(str(e))
+    flat, pr = batch.flat, batch.flat.problem
+    P, K, A = len(flat.pods), len(counts), len(apps)
+    if P == 0:
+        return each("no pods")
+    if 1 + A > capi.MAX_ORDER_SEGMENTS:
+        return each(f"{A} apps need more than {capi.MAX_ORDER_SEGMENTS} order segments")
+    made = scale_segments(apps, targets, combos, flat, batch.pool)
+    if isinstance(made, str):
+        return each(made)
+    segs, patches = made
+    gate = np.asarray(pr.gate_node) if pr.gate_node is not None else np.full(P, -1)
+    for a, app in enumerate(apps):
+        if not app.resource.get("DaemonSet"):
+            continue
+        # such an app makes one pod per pool node, and the sorts order its pods by the length of that list: the batch stands only if at
+        # every size every variant's own list is the variant's pool list without the pods gated at that size
+        for v, rep in enumerate(patches[a]):
+            own = segs.variants[1 + a][v][:int(segs.live[1 + a][v])]
+            res = scaled_app(app, rep).resource if rep else app.resource
+            for k in counts:
+                n = len(base) + k
+                if [_ns_name(flat.pods[pid]) for pid in own[gate[own] < n].tolist()] != [_ns_name(p) for p in wl.app_pods(app.name, res, batch.pool[:n])]:
+                    return each(f"app {app.name} holds a DaemonSet, and its pod order at {rep or 'its own size'} with {k} new nodes is not the pool's")
+    ids = {_ns_name(p): pid for pid, p in enumerate(flat.pods)}
+    group = np.full(P, -1, np.int32)
+    for a in range(A):
+        group[int(segs.seg_start[1 + a]):int(segs.seg_start[2 + a])] = T + a
+    for t, target in enumerate(targets):
+        group[[ids[ref] for ref in _target_refs(apps, target, max(target[3]))]] = t
+    composed_on_device = getattr(engine, "supports_order_segments", False)
+    rows, by_target, lists = [], [], []          # over the scenarios (c, k), k fastest: the launches hold whole combos, in order
+    usage = _Usage(headroom, node_table, devices, storage)
+    usage.bind(flat)
+    on_host = usage.asked and not _on_device(engine, devices, storage)     # (the host figures need the rows)
+    per_launch = max(1, int(batch_scenarios) // K)
+    for lo in range(0, len(combos), per_launch):
+        cs = np.arange(lo, min(lo + per_launch, len(combos)))
+        part = capi.OrderSegments(segs.seg_start, segs.variants, segs.live, segs.choice[cs])
+        scen = np.array([[len(base) + k, c] for c in range(len(cs)) for k in counts], np.int32)
+        kw = {}
+        if batch.node_ranks is not None:
+            kw["node_ranks"] = np.tile(batch.node_ranks, (len(cs), 1))
+        if (devices or storage) and on_host and pr.gpu_mem is not None:
+            kw["want_gpu_slices"] = True
+        orders = present = None
+        if not composed_on_device or on_host:
+            orders, by_order = part.compose()
+            present = by_order[scen[:, 1]]
+        rows_kw = {"order_segments": part} if composed_on_device else {"pod_present": present}
+        try:
+            out = engine.run(pr, scen, None if composed_on_device else orders, want_placement=reasons or on_host, pod_groups=group, **rows_kw, **kw,
+                             **usage.kw(engine, len(scen)))
+        except capi.SimonError as e:
+            if getattr(e, "code", None) != capi.ESTATE:
+                raise
+            return each(f"the engine refused the batch: {e}")
+        usage.add_launch(engine, out, batch.pool, pr, np.arange(len(batch.pool))[None, :] < scen[:, :1], ScaleFallbackWarning, "sweep_scale",
+                         orders, scen)
+        told: Dict[int, Dict[int, str]] = {}
+        replayed: Dict[int, List[dict]] = {}
+        # as sweep_apps: the failing scenarios that are not at preemption risk are explained
+        failing = [s for s in range(len(scen)) if out.unscheduled[s] > 0 and not _risk(out, s)] if reasons else []
+        if failing and not getattr(engine, "supports_explain_batch", False):
+            for s in failing:
+                c, k = int(cs[s // K]), s % K
+                try:
+                    replayed[s] = simulate(cluster, _scaled_apps(apps, targets, combos[c]), engine,
+                                           wl.new_fake_nodes(new_node, counts[k]) if counts[k] > 0 else ()).unscheduled_pods
+                except NeedsReference:
+                    replayed[s] = _unscheduled_list(flat, out.placement[s], {}, part.order(int(scen[s, 1])))
+        elif failing:
+            for e in engine.explain_batch(pr, scen, None if composed_on_device else orders, kw.get("node_ranks"), failing,
+                                          int(max(out.unscheduled[s] for s in failing)), **rows_kw):
+                told[e.scenario] = _reason_texts(flat, e.failed, e.rows, e.detail, [(e.n_nodes, b) for b in e.bins])
+        rows += _scenario_rows(out, *_alloc_of_prefixes(pr, out, scen[:, 0]))
+        for s in range(len(scen)):
+            g = out.group_unscheduled[s]
+            by_target.append([int(g[t]) if t < len(g) else 0 for t in range(T)])
+            # (simulate() lists the unscheduled pods in the order it fed them: the scenario's own order row)
+            lists.append(replayed[s] if s in replayed else _unscheduled_list(flat, out.placement[s], told.get(s, {}), part.order(int(scen[s, 1]))) if reasons else [])
+    return usage.onto(_scale_summary(targets, scale, combos, counts, _nested(rows, K), _nested(by_target, K), caps, _nested(lists, K) if reasons else [],
+                                     True, None), K)
 
 
 def _claimed_storage_classes(app: AppResource) -> set:
